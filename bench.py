@@ -7,6 +7,11 @@
 One "step" = forward + backward + gradient all-reduce (N > 1) + global-norm clip + fused Adam on one
 micro-batch of B synthetic 1024-token sequences per GPU (weak scaling: per-GPU work is fixed).  Inputs are
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the
+line can carry: box calibration, the per-kernel rooflines (HIP events in and after the timed region), the exposed
+communication of N > 1, the rl / mixture / ga16 / decode legs and the CPU baselines.  --dump-outputs DIR writes what
+the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -534,6 +539,33 @@ def rocprof_crosscheck(family_kernels_note: str):
         return None
 
 
+DUMP_SEED = 20240601
+DUMP_SAMPLE_EVERY = 256
+
+
+def dump_outputs(out_dir: str, model, engine, loss) -> None:
+    """What the last timed step computed, as DIR/<name>.npy: `loss` and `grad_norm` (float64, shape [1]), and float32 samples of the
+    parameter arena at fixed positions -- 1 in DUMP_SAMPLE_EVERY elements of every parameter, drawn per parameter (sorted by name) from a
+    generator seeded with DUMP_SEED, so two builds sample the same positions: `params_sample` (the parameters the optimizer step wrote) and
+    `grads_sample` (the gradient arena after the step: the weight gradients of the last backward; the small accumulators -- LayerNorm,
+    bias, u / v, embedding tables -- are cleared by the step and read 0).  About 38 MB at the 1.3B geometry."""
+    os.makedirs(out_dir, exist_ok=True)
+    ar = model.arena
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = []
+    for name in sorted(ar.offsets):
+        off, shape, _ = ar.offsets[name]
+        n = int(np.prod(shape))
+        idx.append(off + np.sort(rng.integers(0, n, max(1, n // DUMP_SAMPLE_EVERY))))
+    idx = torch.from_numpy(np.concatenate(idx)).to(ar.master.device)
+    arrays = {"loss": np.array([float(loss)], np.float64),
+              "grad_norm": np.array([engine.get_global_grad_norm()], np.float64),
+              "params_sample": ar.master[idx].float().cpu().numpy(),
+              "grads_sample": ar.grad[idx].float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` with no launcher around it: start N copies of this script, one rank per GPU, with the
     rendezvous environment torch.distributed.run would have set (127.0.0.1, a free port).  Rank 0's stdout is ours, so
@@ -633,7 +665,12 @@ def main():
     ap.add_argument("--flash-probs", choices=["forward", "scratch", "recompute"], default="forward",
                     help="A/B: what the flash backward recomputes (nothing: the forward keeps p~ per layer / the query side only / both sides)")
     ap.add_argument("--materialise-logits", action="store_true", help="A/B: head GEMM + CE on a full (tokens x vocabulary) logits buffer instead of the chunked sweep")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: box calibration, per-kernel rooflines, the exposed communication "
+                                                        "(N > 1), the rl / mixture / ga16 / decode legs and the CPU baselines (the --no-* options switch parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, time the steps, print the line
+        args.no_kernel_timing = args.no_box = args.no_mixture = args.no_ga16 = args.no_decode = args.no_cpu_baseline = True
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -716,7 +753,7 @@ def main():
     # families' rooflines (`kernels`) are taken on two extra, untimed steps after the timed region
     timer = None if args.no_kernel_timing else ops.KernelTimer(only=("gemm", "lmhead_ce"))
     ops.set_gemm_timer(timer)
-    engine.time_comm = world > 1          # event pairs around the wait for the bucket all-reduces (GradSync.finish): the exposed communication
+    engine.time_comm = world > 1 and args.full   # event pairs around the wait for the bucket all-reduces (GradSync.finish): the exposed communication
     ops.marker(1)                         # empty marker kernels: tools/prof_table.py cuts a rocprofv3 kernel trace to the timed steps
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -731,14 +768,17 @@ def main():
         dist.all_gather(ts, torch.tensor([dt_local], device=dev, dtype=torch.float64))
         per_rank = [float(t.item()) for t in ts]
         dt = max(per_rank)                                    # the job is as slow as its slowest rank
-        exposed = torch.tensor([engine.exposed_comm_ms()], device=dev, dtype=torch.float64)
-        dist.all_reduce(exposed, op=dist.ReduceOp.MAX)
         dp_info = {"ms_per_step_per_rank": [round(t / args.steps * 1e3, 3) for t in per_rank],
-                   "ms_per_step_min": round(min(per_rank) / args.steps * 1e3, 3), "ms_per_step_max": round(max(per_rank) / args.steps * 1e3, 3),
-                   "exposed_comm_ms_per_step_max": round(float(exposed.item()) / args.steps, 3),
-                   "note": "exposed communication = time the compute stream waits in GradSync.finish for bucket all-reduces that were launched from the "
-                           "backward (HIP events around the waits, max over ranks); gradients cross xGMI in bf16, 25 per-layer buckets + embeddings"}
+                   "ms_per_step_min": round(min(per_rank) / args.steps * 1e3, 3), "ms_per_step_max": round(max(per_rank) / args.steps * 1e3, 3)}
+        if args.full:
+            exposed = torch.tensor([engine.exposed_comm_ms()], device=dev, dtype=torch.float64)
+            dist.all_reduce(exposed, op=dist.ReduceOp.MAX)
+            dp_info.update({"exposed_comm_ms_per_step_max": round(float(exposed.item()) / args.steps, 3),
+                            "note": "exposed communication = time the compute stream waits in GradSync.finish for bucket all-reduces that were launched from "
+                                    "the backward (HIP events around the waits, max over ranks); gradients cross xGMI in bf16, 25 per-layer buckets + embeddings"})
     engine.time_comm = False
+    if args.dump_outputs and rank == 0:   # (before the untimed steps of --full change the parameters)
+        dump_outputs(args.dump_outputs, model, engine, loss)
     timer_rest, rest_steps = None, 2
     if timer is not None:
         timer_rest = ops.KernelTimer()

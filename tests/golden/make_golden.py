@@ -520,6 +520,36 @@ def gen_data_ingest():
     return out
 
 
+def gen_ref_helpers():
+    """The reference's native index builders (src/data/helpers.cpp compiled by oracle/Makefile into oracle/_ref/) on 20 random inputs
+    (seed 5): the inputs and what the builders returned, trial t under the prefix "t<t>/"."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref"))
+    import helpers as ref_helpers
+    rng = np.random.default_rng(5)
+    out = {}
+    for t in range(20):
+        ndoc = int(rng.integers(1, 60))
+        sizes = rng.integers(1, 300, ndoc).astype(np.int32)
+        epochs = int(rng.integers(1, 4))
+        doc_idx = np.concatenate([rng.permutation(ndoc) for _ in range(epochs)]).astype(np.int32)
+        seq = int(rng.integers(2, 128))
+        tpe = int(sizes.sum())
+        pl = rng.integers(2, 100, int(rng.integers(1, 50))).astype(np.int32)
+        tn = int(rng.integers(1, 60))
+        nd = int(rng.integers(1, 9))
+        w = rng.random(nd)
+        w /= w.sum()
+        size = int(rng.integers(1, 5000))
+        di, dsi = np.zeros(size, np.uint8), np.zeros(size, np.int64)
+        ref_helpers.build_blending_indices(di, dsi, w, nd, size, False)
+        p = f"t{t}/"
+        out.update({p + "sizes": sizes, p + "doc_idx": doc_idx, p + "sample_args": np.array([seq, epochs, tpe]),
+                    p + "sample_idx": np.array(ref_helpers.build_sample_idx(sizes, doc_idx, seq, epochs, tpe)),
+                    p + "path_lengths": pl, p + "tn": np.array(tn), p + "rl_idx": np.array(ref_helpers.build_rl_sample_idx(pl, tn)),
+                    p + "blend_weights": w, p + "blend_index": di, p + "blend_sample": dsi})
+    return out
+
+
 def gen_init_stats():
     """a14: moments of the reference's own initialisation (transformer_xl.py:444-468 + the nn.Conv2d / nn.GroupNorm defaults it leaves
     in the patch embedder), plain and DeepNorm: per parameter (mean, std, min, max, numel).  Pins the DISTRIBUTION (the values depend on
@@ -553,6 +583,10 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "data":
         np.savez_compressed(os.path.join(HERE, "data_ingest.npz"), **gen_data_ingest())
         print("wrote data_ingest + data_fixture.idx/.bin")
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "ref_helpers":
+        np.savez_compressed(os.path.join(HERE, "ref_helpers.npz"), **gen_ref_helpers())
+        print("wrote ref_helpers")
         return
     if len(sys.argv) > 1 and sys.argv[1] == "gpt":
         np.savez_compressed(os.path.join(HERE, "gpt_dataset.npz"), **gen_gpt_dataset())

@@ -225,7 +225,7 @@ def test_bench_launches_its_own_ranks():
     if torch.cuda.device_count() < 2:
         env["DB1_DIST_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--layers", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--layers", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -259,7 +259,7 @@ def test_bench_eight_ranks_on_this_box():
     if torch.cuda.device_count() < 8:
         env["DB1_DIST_BACKEND"] = "gloo"
     env["DB1_LAUNCH_TIMEOUT_S"] = "1200"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--batch", "2", "--full", "--no-cpu-baseline",
                         "--no-kernel-timing", "--leg-steps", "1"], env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -496,7 +496,7 @@ def test_bench_line_contract(workload):
     import json
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--layers", "2", "--batch", "4",
-                        "--no-cpu-baseline", "--workload", workload], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--workload", workload], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -518,6 +518,35 @@ def test_bench_line_contract(workload):
         assert "ga16" not in d
     else:
         assert "rl" not in d and "mixture" not in d
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain bench.py run prints the headline keys only (no box, roofline or legs: those need --full), and --dump-outputs writes the last
+    timed step's loss, gradient norm and parameter / gradient samples; two runs with the same arguments dump the same loss"""
+    import json
+    import subprocess
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--layers", "2", "--batch", "4",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 2 and d["warmup"] == 1 and abs(d["value"] - 4 * 1024 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+        for k in ("box", "roofline", "kernels", "rl", "mixture", "ga16", "decode", "cpu_baseline"):
+            assert k not in d, k
+        got = {n: np.load(out / f"{n}.npy") for n in ("loss", "grad_norm", "params_sample", "grads_sample")}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+        assert abs(float(got["loss"][0]) - d["final_loss"]) < 1e-3 and float(got["grad_norm"][0]) > 0
+        assert got["params_sample"].shape == got["grads_sample"].shape and got["params_sample"].size > 1000
+        assert sum(a.nbytes for a in got.values()) < 64 * 2**20
+        dumps.append(got)
+    assert dumps[0]["params_sample"].shape == dumps[1]["params_sample"].shape
+    assert abs(float(dumps[0]["loss"][0]) - float(dumps[1]["loss"][0])) < 1e-3 * abs(float(dumps[0]["loss"][0]))
 
 
 @pytest.mark.parametrize("tag", ["plain", "deepnorm"])

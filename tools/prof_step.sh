@@ -4,6 +4,7 @@
 #   gpurun_out/step_stats.csv   the whole-process kernel_stats summary (top kernels by total time), as before
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the per-kernel timing (`work_per_step`) the table divides into is part of the full line
 rm -rf $R/gpurun_out/prof_step
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_step -o s -- python $R/bench.py --steps ${PROF_STEPS:-6} --warmup 2 --no-cpu-baseline --no-decode --no-mixture --no-ga16 ${BENCH_ARGS} > $R/gpurun_out/prof_step.log 2>&1 </dev/null
 cd $R

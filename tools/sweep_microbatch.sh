@@ -7,7 +7,7 @@ mkdir -p $E
 cd $R
 for b in ${SWEEP_BATCHES:-4 8 16 32 64}; do
   ga=$((64 / b))
-  timeout 600 python bench.py --batch $b --ga $ga --steps 4 --warmup 2 --no-cpu-baseline --no-decode ${SWEEP_ARGS} > $E/${TAG}_bench_b${b}.json 2> $E/bench_b${b}.err </dev/null
+  timeout 600 python bench.py --full --batch $b --ga $ga --steps 4 --warmup 2 --no-cpu-baseline --no-decode ${SWEEP_ARGS} > $E/${TAG}_bench_b${b}.json 2> $E/bench_b${b}.err </dev/null
   python - <<P
 import json
 try:
