@@ -3,7 +3,8 @@
 Importing the package does not need a GPU; constructing a model or calling an op does, and raises
 if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
-__all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep"]
+__all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep",
+           "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos"]
 
 
 def __getattr__(name):
@@ -22,6 +23,9 @@ def __getattr__(name):
     if name == "GraphedTrainStep":
         from .graphed_train import GraphedTrainStep
         return GraphedTrainStep
+    if name in ("GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos"):
+        from . import generation
+        return getattr(generation, name)
     if name == "mpu":
         import importlib
         return importlib.import_module(".mpu", __name__)

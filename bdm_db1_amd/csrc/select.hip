@@ -1,0 +1,279 @@
+// Next-token selection on the device (db1_select_tokens, include/db1_hip.h): greedy / temperature / top-k / top-p sampling over a vocabulary
+// window, EOS bookkeeping and the hand-back of the chosen token into the next call's input ids -- so a generation loop is N graph replays with no
+// host round trip in between.  The reference picks tokens with torch (logits.argmax(-1) and a host copy per token, evaluate_rl.py:157-266); its
+// caption / VQA evaluation (train.py:146-170, text_decoder.py:42-62) keeps the tokens up to the first EOS.
+//
+// One workgroup of 1024 threads per row; the row lives in registers: thread `tid` owns the four consecutive columns 4 (j * 1024 + tid) + 0..3,
+// j < NG (NG * 4096 >= V).  Every logit becomes an order-preserving uint32 key (0 = not a candidate: outside the window, NaN or +-inf), so
+// max / arg-max are integer reductions (ties: lowest column) and the top-k / top-p thresholds are found by a bisection over the key range --
+// no sort, no histogram atomics.  All reductions run in a fixed order (wave butterflies, then the 16 wave results read in order from LDS):
+// the same inputs give the same bits.
+#include "db1_common.h"
+
+#define SEL_THREADS 1024
+#define SEL_WAVES (SEL_THREADS / 64)
+#define SEL_MAX_NG 9                       // V <= 36 864 (DB1-1.3B: 33 025)
+#define SEL_SITE_SAMPLE 0xE0000100u        // Philox site of the sampling draws (dropout sites: layer * 4 + {0, 1, 2}, 0xE0000000, 0xE0000001)
+
+__device__ __forceinline__ unsigned sel_key(float f) {
+    const unsigned b = __float_as_uint(f);
+    if ((b & 0x7f800000u) == 0x7f800000u) return 0u;          // NaN, +-inf: never a candidate
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // finite keys are > 0x007fffff
+}
+__device__ __forceinline__ float sel_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)x, o, 64), hi = __shfl_xor((unsigned)(x >> 32), o, 64);
+        const unsigned long long y = ((unsigned long long)hi << 32) | lo;
+        x = y > x ? y : x;
+    }
+    return x;
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = min(x, (unsigned)__shfl_xor(x, o, 64));
+    return x;
+}
+
+// Block reductions: every wave writes its result to one LDS slot, one barrier, every thread combines the 16 slots in order.  Consecutive
+// reductions alternate between two slot sets, so a slot is never rewritten while a slower wave may still read it (one barrier per reduction).
+struct SelShared {
+    unsigned long long u64[2][SEL_WAVES];
+    float f[2][SEL_WAVES];
+    int i[2][SEL_WAVES];
+    unsigned u[2][SEL_WAVES];
+};
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long x, SelShared& sh, int& ph) {
+    x = wave_max_u64(x);
+    if ((threadIdx.x & 63) == 0) sh.u64[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    unsigned long long r = sh.u64[ph][0];
+#pragma unroll
+    for (int w = 1; w < SEL_WAVES; w++) r = sh.u64[ph][w] > r ? sh.u64[ph][w] : r;
+    ph ^= 1;
+    return r;
+}
+__device__ __forceinline__ unsigned block_min_u32(unsigned x, SelShared& sh, int& ph) {
+    x = wave_min_u32(x);
+    if ((threadIdx.x & 63) == 0) sh.u[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    unsigned r = sh.u[ph][0];
+#pragma unroll
+    for (int w = 1; w < SEL_WAVES; w++) r = min(r, sh.u[ph][w]);
+    ph ^= 1;
+    return r;
+}
+__device__ __forceinline__ int block_sum_i(int x, SelShared& sh, int& ph) {   // x wave-uniform already
+    if ((threadIdx.x & 63) == 0) sh.i[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < SEL_WAVES; w++) r += sh.i[ph][w];
+    ph ^= 1;
+    return r;
+}
+__device__ __forceinline__ float block_sum_f(float x, SelShared& sh, int& ph) {
+    x = wave_sum(x);   // (butterfly: every lane ends with the same bits)
+    if ((threadIdx.x & 63) == 0) sh.f[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    float r = sh.f[ph][0];
+#pragma unroll
+    for (int w = 1; w < SEL_WAVES; w++) r += sh.f[ph][w];
+    ph ^= 1;
+    return r;
+}
+
+template <int NG>
+__device__ __forceinline__ int sel_count_ge(const unsigned (&key)[NG][4], unsigned thr, SelShared& sh, int& ph) {
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < NG; j++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) c += (int)__popcll(__ballot(key[j][q] >= thr));
+    return block_sum_i(c, sh, ph);
+}
+template <int NG>
+__device__ __forceinline__ float sel_mass_ge(const unsigned (&key)[NG][4], const float (&e)[NG][4], unsigned thr, SelShared& sh, int& ph) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NG; j++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) s += key[j][q] >= thr ? e[j][q] : 0.f;
+    return block_sum_f(s, sh, ph);
+}
+
+struct SelArgs {
+    const void* logits;
+    int64_t ld;
+    int V, vlo, vhi;
+    float inv_t;
+    int top_k;
+    float top_p;
+    int greedy;
+    unsigned k0, k1;
+    int eos, pad, step_base, max_new;
+    const int* t;
+    const int* stream_id;
+    int* finished;
+    int* lengths;
+    int* out;
+    long long* next_ids;
+    int64_t ids_stride;
+    int* status;
+};
+
+template <typename T, int NG>
+__global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
+    __shared__ SelShared sh;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const int t = *a.t;
+    const bool t_ok = t >= 0 && t < a.max_new;
+    if (a.finished[row]) {     // (block-uniform)
+        if (tid == 0) {
+            if (t_ok) a.out[(int64_t)row * a.max_new + t] = a.pad;
+            else a.status[row] |= 2;
+            a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+        }
+        return;
+    }
+    const T* lg = reinterpret_cast<const T*>(a.logits) + (int64_t)row * a.ld;
+    const int lo = max(a.vlo, 0), hi = min(a.vhi, a.V);
+    unsigned key[NG][4];
+    unsigned long long best = 0;   // (key << 32) | ~column: max = largest key, lowest column on ties
+    unsigned kmin = 0xffffffffu;
+#pragma unroll
+    for (int j = 0; j < NG; j++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int c = 4 * (j * SEL_THREADS + tid) + q;
+            const unsigned k = (c >= lo && c < hi) ? sel_key(ldf<T>(lg + c)) : 0u;
+            key[j][q] = k;
+            const unsigned long long p = ((unsigned long long)k << 32) | (unsigned)~c;
+            best = (k && p > best) ? p : best;
+            kmin = k ? min(kmin, k) : kmin;
+        }
+    int ph = 0;
+    best = block_max_u64(best, sh, ph);
+    int tok, bits = 0;
+    const unsigned kmax = (unsigned)(best >> 32);
+    if (kmax == 0) {                                  // nothing finite in the window
+        tok = a.pad;
+        bits = 1;
+    } else if (a.greedy || a.top_k == 1) {
+        tok = (int)~(unsigned)best;
+    } else {
+        // top-k: thr_k = the k-th largest key = the largest x with #{key >= x} >= k (bisection over [smallest key, largest key])
+        // (bf16 logits: the low 16 bits of every key are 0, the bisection runs over the high 16)
+        constexpr int S = sizeof(T) == 2 ? 16 : 0;
+        unsigned thr = block_min_u32(kmin, sh, ph);
+        if (a.top_k > 1) {
+            unsigned l = thr >> S, h = kmax >> S;
+            while (l < h) {
+                const unsigned mid = l + ((h - l) >> 1) + ((h - l) & 1);
+                if (sel_count_ge<NG>(key, mid << S, sh, ph) >= a.top_k) l = mid; else h = mid - 1;
+            }
+            thr = l << S;
+        }
+        // top-p: p = softmax(l / T) over {key >= thr_k}; thr_p = the largest key x with mass{key >= x} >= top_p (ties at x kept)
+        if (a.top_p < 1.f) {
+            const float m = sel_unkey(kmax);
+            float e[NG][4];
+            float z = 0.f;
+#pragma unroll
+            for (int j = 0; j < NG; j++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    e[j][q] = key[j][q] >= thr ? expf((sel_unkey(key[j][q]) - m) * a.inv_t) : 0.f;
+                    z += e[j][q];
+                }
+            z = block_sum_f(z, sh, ph);
+            const float target = a.top_p * z;
+            unsigned l = thr >> S, h = kmax >> S;
+            while (l < h) {
+                const unsigned mid = l + ((h - l) >> 1) + ((h - l) & 1);
+                if (sel_mass_ge<NG>(key, e, mid << S, sh, ph) >= target) l = mid; else h = mid - 1;
+            }
+            thr = l << S;
+        }
+        // Gumbel-max over the kept set: argmax l / T - log(-log u), u from Philox (column / 4, stream id, step, SITE_SAMPLE; seed)
+        const unsigned sid = a.stream_id ? (unsigned)a.stream_id[row] : (unsigned)row;
+        const unsigned step = (unsigned)(a.step_base + t);
+        unsigned long long sb = 0;
+#pragma unroll
+        for (int j = 0; j < NG; j++) {
+            const bool any = key[j][0] >= thr || key[j][1] >= thr || key[j][2] >= thr || key[j][3] >= thr;
+            if (any) {
+                const int g = j * SEL_THREADS + tid;
+                unsigned o[4];
+                db1_philox4x32_10((unsigned)g, sid, step, SEL_SITE_SAMPLE, a.k0, a.k1, o);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (key[j][q] < thr) continue;
+                    const float u = ((float)(o[q] >> 8) + 0.5f) * 5.9604644775390625e-8f;   // ((x >> 8) + 0.5) * 2^-24: exact in fp32
+                    const float s = sel_unkey(key[j][q]) * a.inv_t - logf(-logf(u));
+                    const unsigned sk = sel_key(s);
+                    const unsigned long long p = ((unsigned long long)sk << 32) | (unsigned)~(4 * g + q);
+                    sb = p > sb ? p : sb;
+                }
+            }
+        }
+        sb = block_max_u64(sb, sh, ph);
+        tok = (unsigned)(sb >> 32) ? (int)~(unsigned)sb : (int)~(unsigned)best;   // (a non-finite score cannot win: fall back to the arg-max)
+    }
+    if (tid == 0) {
+        int fin = 0;
+        if (bits & 1) fin = 1;
+        else if (tok == a.eos) fin = 1;
+        else a.lengths[row] += 1;
+        if (fin) a.finished[row] = 1;
+        if (t_ok) a.out[(int64_t)row * a.max_new + t] = tok;
+        else bits |= 2;
+        if (bits) a.status[row] |= bits;
+        a.next_ids[(int64_t)row * a.ids_stride] = tok;
+    }
+}
+
+static int sel_ng(int V) { return V <= 4096 ? 1 : (V <= 3 * 4096 ? 3 : (V <= SEL_MAX_NG * 4096 ? SEL_MAX_NG : 0)); }
+
+extern "C" int db1_select_tokens_supported(int V, int64_t ld, int dt) {
+    return db1_dt_ok(dt) && V > 0 && ld >= V && sel_ng(V) > 0;
+}
+
+extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
+    (void)M; (void)V; (void)dt;
+    return 0;
+}
+
+extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                                 float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
+                                 const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                                 int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "select_tokens: dtype %d", dt);
+    if (M <= 0 || M > 65535 || V <= 0 || ld < V || max_new <= 0 || ids_stride < 0)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld", M, V, (long long)ld, max_new, (long long)ids_stride);
+    if (!sel_ng(V)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "select_tokens: V=%d (at most %d)", V, SEL_MAX_NG * 4096);
+    if (!logits || !t || !finished || !lengths || !out || !next_ids || !status) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: null buffer");
+    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
+    if (!greedy && !(temperature > 0.f && temperature < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: temperature %g", (double)temperature);
+    if (!greedy && (top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: top_k %d top_p %g", top_k, (double)top_p);
+    SelArgs a;
+    a.logits = logits; a.ld = ld; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
+    a.inv_t = greedy ? 1.f : 1.f / temperature;
+    a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
+    a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
+    a.t = t; a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
+    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    const int ng = sel_ng(V);
+    DB1_DISPATCH_DT(dt, T, {
+        if (ng == 1) select_tokens_kernel<T, 1><<<M, SEL_THREADS, 0, st>>>(a);
+        else if (ng == 3) select_tokens_kernel<T, 3><<<M, SEL_THREADS, 0, st>>>(a);
+        else select_tokens_kernel<T, SEL_MAX_NG><<<M, SEL_THREADS, 0, st>>>(a);
+    });
+    DB1_CHECK_LAUNCH("select_tokens");
+    return DB1_OK;
+}

@@ -97,10 +97,18 @@ class RingMemory:
 
     def reset(self):
         """a new episode: the keys / values of the zero memory (init_mem), origin 0"""
+        self.load(self.model.init_mem(self.B))
+
+    def load(self, mems):
+        """fill the ring from a list-form memory (``model.init_mem`` layout: per layer the hidden states [B, mem_len, d] a call with
+        ``mems=`` returned, e.g. after a prompt longer than 64 tokens ran through the list-form path): the projection ``reset`` does for the
+        zero memory, applied to the given states; origin 0"""
         model, mlen = self.model, int(self.model.mem_len)
+        if len(mems) != model.n_layer or any(tuple(m.shape) != (self.B, mlen, model.n_embed) for m in mems):
+            raise ValueError(f"RingMemory.load: expected {model.n_layer} tensors of shape ({self.B}, {mlen}, {model.n_embed})")
         with torch.no_grad():
             saved, model._dec_state = model._dec_state, None
-            dec = model._decode_begin(model.init_mem(self.B), self.B, 1, mlen)
+            dec = model._decode_begin(list(mems), self.B, 1, mlen)
             model._dec_state = saved
             for ring, kv in zip(self.kv, dec.kv):
                 ring[:, :mlen].copy_(kv.reshape(self.B, mlen, 2, model.n_head, model.d_head))
@@ -110,9 +118,10 @@ class RingMemory:
 class GraphedRingStep:
     """One inference call with memory (batch ``batch_size``, ``n_new`` new tokens) as ONE hipGraph replay over a RingMemory: nothing is
     concatenated, copied or re-projected per call.  Several steps (e.g. the observation call and the 1-token calls of evaluate_rl) can
-    share one memory: ``GraphedRingStep(model, 1, 1, memory=obs_step.memory)``."""
+    share one memory: ``GraphedRingStep(model, 1, 1, memory=obs_step.memory)``.  ``epilogue(step, logits)`` (optional) is captured into the
+    same graph after the forward, e.g. a token sampler that writes the next ids into ``step.ids`` (generation.py); the warm-up does not run it."""
 
-    def __init__(self, model, batch_size: int, n_new: int, memory: RingMemory = None, make_input=None):
+    def __init__(self, model, batch_size: int, n_new: int, memory: RingMemory = None, make_input=None, epilogue=None):
         from .data import NLPTaskInput
         self.model, self.B, self.q = model, batch_size, n_new
         self.memory = memory if memory is not None else RingMemory(model, batch_size)
@@ -138,6 +147,8 @@ class GraphedRingStep:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     logits, _, _ = model([self.x], compute_loss=False, mems=self.memory)
+                    if epilogue is not None:
+                        epilogue(self, logits)
                 watch = model._chain_watch
         self.graph, self.logits = g, logits
         self._watch = watch            # the captured call's copy of the persistent launches' error flag (None: per-launch path)

@@ -1,0 +1,252 @@
+"""Text generation: captions (IC), answers (VQA) and text continuations, with the next token picked ON THE DEVICE.
+
+The reference trains these three workloads and evaluates IC / VQA by generating text (train.py:24-25,44,146-170: evaluate_ic /
+evaluate_vqa with a ``Decoder(max_length=30)`` that keeps the tokens before the first EOS, text_decoder.py:42-62); those evaluation modules
+are not part of its release.  Here a generation is
+
+  * one prefill call: the prompt (``[prompt, image patches, text]``, longer than the 64 new tokens a ring call takes) runs once through the
+    list-form memory path (``model.init_mem``);
+  * then one call per token.  bf16 models with the K/V-cached decode path (``model.use_decode``): the list-form memory is projected into a
+    ``RingMemory`` and every token is ONE hipGraph replay holding the one-token forward, ``db1_select_tokens`` (which writes the next token
+    straight into the step's static input ids) and the captured ``t += 1`` of the token counter -- no host round trip between tokens; the
+    host reads the ``finished`` flags every ``sync_every`` tokens to stop early.  Other models (fp32, no ring) run the same loop eagerly
+    over the list-form memory, with the same selection kernel.
+
+The selection rule (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox) is stated in include/db1_hip.h (db1_select_tokens)
+and restated in NumPy in tests/select_rule.py.
+"""
+from __future__ import annotations
+
+import dataclasses
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+
+@dataclass(frozen=True)
+class GenerationConfig:
+    """``greedy``: arg-max (``temperature`` / ``top_k`` / ``top_p`` / ``seed`` unused); else Gumbel-max sampling at ``temperature`` after
+    top-k (0 = off) and top-p (1 = off).  ``eos_id`` None: no end-of-sequence token.  Tokens are chosen in ``[vocab_lo, vocab_hi)``
+    (``vocab_hi`` None: the model's whole vocabulary for ``generate``, the text vocabulary for captions and answers).  The host checks
+    whether every row has finished each ``sync_every`` tokens."""
+    max_new_tokens: int = 30
+    greedy: bool = True
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+    eos_id: Optional[int] = None
+    pad_id: int = 0
+    vocab_lo: int = 0
+    vocab_hi: Optional[int] = None
+    sync_every: int = 8
+
+    def __post_init__(self):
+        if int(self.max_new_tokens) < 1:
+            raise ValueError(f"max_new_tokens {self.max_new_tokens} must be >= 1")
+        if not self.greedy and not (0.0 < float(self.temperature) < float("inf")):
+            raise ValueError(f"temperature {self.temperature} must be > 0 when sampling")
+        if not 0.0 < float(self.top_p) <= 1.0:
+            raise ValueError(f"top_p {self.top_p} must lie in (0, 1]")
+        if int(self.top_k) < 0:
+            raise ValueError(f"top_k {self.top_k} must be >= 0")
+        if int(self.vocab_lo) < 0 or (self.vocab_hi is not None and int(self.vocab_hi) <= int(self.vocab_lo)):
+            raise ValueError(f"vocabulary window [{self.vocab_lo}, {self.vocab_hi}) is empty")
+        if int(self.sync_every) < 1:
+            raise ValueError(f"sync_every {self.sync_every} must be >= 1")
+        if not 0 <= int(self.seed) < 2 ** 64:
+            raise ValueError(f"seed {self.seed} must be a 64-bit unsigned integer")
+
+
+def clip_at_eos(ids, lengths) -> List[List[int]]:
+    """the tokens ``Decoder.decode(..., clip_at_eos=True)`` keeps (text_decoder.py:53-58), as id lists: row r's first ``lengths[r]`` ids"""
+    ids = np.asarray(ids)
+    return [[int(v) for v in row[:int(n)]] for row, n in zip(ids, np.asarray(lengths))]
+
+
+class _State:
+    """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
+
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
+        dev = model.dev
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.M, self.cfg, self.V, self.hi = M, cfg, V, hi
+        self.t = torch.zeros(1, **i32)
+        self.finished = torch.zeros(M, **i32)
+        self.lengths = torch.zeros(M, **i32)
+        self.status = torch.zeros(M, **i32)
+        self.stream_id = torch.arange(M, **i32)
+        self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
+
+    def start(self, stream_ids):
+        self.t.zero_()
+        self.finished.zero_()
+        self.lengths.zero_()
+        self.status.zero_()
+        self.out.fill_(self.cfg.pad_id)
+        if stream_ids is None:
+            self.stream_id.copy_(torch.arange(self.M, dtype=torch.int32))
+        else:
+            s = torch.as_tensor(np.asarray(stream_ids, dtype=np.int64))
+            if s.shape != (self.M,):
+                raise ValueError(f"stream_ids: {self.M} values expected, got shape {tuple(s.shape)}")
+            self.stream_id.copy_(s.to(torch.int32))
+
+    def select(self, logits3d, next_ids):
+        """the token of every row from the last position of ``logits3d`` [M, L, V] into ``next_ids`` (int64 [M]), then t += 1"""
+        c = self.cfg
+        ops.select_tokens(logits3d[:, -1], self.t, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V, vocab_lo=c.vocab_lo,
+                          vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
+                          eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id)
+        self.t.add_(1)
+
+    def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        out, lengths, status = self.out.cpu(), self.lengths.cpu(), self.status.cpu()
+        if (status & 2).any():
+            raise RuntimeError("db1_select_tokens: the token counter left [0, max_new_tokens)")
+        return out, lengths
+
+
+class _RingGenerator:
+    """a RingMemory, the selection state and the captured per-token graph for one (model, batch size, config); reused across calls"""
+
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
+        from .decode import GraphedRingStep, RingMemory
+        self.key = (M, cfg, V, hi)
+        self.state = _State(model, M, cfg, V, hi)
+        self.ring = RingMemory(model, M)
+        self.step = GraphedRingStep(model, M, 1, memory=self.ring, epilogue=lambda step, logits: self.state.select(logits, step.ids[:, 0]))
+
+
+def _batch_size(prompt) -> int:
+    kind = type(prompt).__name__
+    if kind == "NLPTaskInput":
+        seq = prompt.text_seq
+        lens = getattr(prompt, "text_len", None)
+        if lens is not None and np.unique(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens)).size > 1:
+            raise ValueError("generate: the rows of a prompt batch must share one length (group prompts by length)")
+    elif kind in ("ICTaskInput", "VQATaskInput"):
+        seq = prompt.prompt_seq
+    else:
+        raise TypeError(f"generate: NLPTaskInput, ICTaskInput or VQATaskInput expected, got {kind}")
+    try:
+        arr = seq if torch.is_tensor(seq) else np.asarray(seq)
+    except ValueError as e:
+        raise ValueError("generate: the rows of a prompt batch must share one length (group prompts by length)") from e
+    if arr.ndim != 2 or arr.dtype == object:
+        raise ValueError("generate: the prompt ids must form a [batch, length] array (rows of one length)")
+    return int(arr.shape[0])
+
+
+def _ring_ok(model) -> bool:
+    return (model.compute_dtype == torch.bfloat16 and bool(model.use_decode) and int(model.mem_len or 0) > 0 and model.d_head == 128)
+
+
+@torch.no_grad()
+def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
+             stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
+    of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
+    after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
+    on its logits, its stream id, the seed and the token index, not on the other rows.  ``graphed`` None: the hipGraph ring path where the
+    model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
+    receives the path taken and the number of per-token calls."""
+    cfg = config or GenerationConfig()
+    if not int(model.mem_len or 0) > 0:
+        raise ValueError("generate needs a model with memory (mem_len > 0)")
+    M = _batch_size(prompt)
+    V = int(model.total_vocab_size)
+    hi = V if cfg.vocab_hi is None else int(cfg.vocab_hi)
+    if hi > V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {hi}) exceeds the model's vocabulary ({V})")
+    if not ops.select_tokens_supported(V, V, model.compute_dtype):
+        raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
+    ring = _ring_ok(model) if graphed is None else bool(graphed)
+    if ring and not _ring_ok(model):
+        raise ValueError("the graphed ring path needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
+    was_training = model.training
+    model.eval()
+    try:
+        if ring:
+            gen = getattr(model, "_generator", None)
+            if gen is None or gen.key != (M, cfg, V, hi) or gen.step._version != model._wversion:
+                model._generator = None        # (free the old ring before the new one is allocated)
+                gen = model._generator = _RingGenerator(model, M, cfg, V, hi)
+            st = gen.state
+            ids = gen.step.ids
+        else:
+            st = _State(model, M, cfg, V, hi)
+            ids = torch.zeros(M, 1, dtype=torch.long, device=model.dev)
+        st.start(stream_ids)
+        # prefill: the whole prompt through the list-form memory path; its last position picks token 0
+        model._dec_state = None
+        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(M))
+        st.select(logits, ids[:, 0])
+        calls = 0
+        if ring:
+            gen.ring.load(mems)
+            del mems, logits
+        for i in range(1, cfg.max_new_tokens):
+            if i % cfg.sync_every == 0 and bool(st.finished.all()):
+                break
+            if ring:
+                gen.step(ids)
+            else:
+                from .data import NLPTaskInput
+                x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+                logits, _, mems = model([x], compute_loss=False, mems=mems)
+                st.select(logits, ids[:, 0])
+            calls += 1
+        if ring:
+            gen.step.check(synchronize=True)
+        else:
+            chk = getattr(model, "check_decode_chain", None)
+            if chk is not None:
+                chk(True)
+        if stats is not None:
+            stats.update(path="ring" if ring else "eager", token_calls=calls)
+        return st.result()
+    finally:
+        model.train(was_training)
+
+
+def _text_window(model, cfg: Optional[GenerationConfig]) -> GenerationConfig:
+    cfg = cfg or GenerationConfig()
+    return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
+
+
+def generate_captions(model, ic_batch, cfg: Optional[GenerationConfig] = None, **kw):
+    """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
+    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``"""
+    from .data import ICTaskInput
+    M = _batch_size(ic_batch)
+    x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
+                    text_seq=torch.zeros(M, 0, dtype=torch.long))
+    for f in ("vision_row_ids", "vision_col_ids"):
+        if hasattr(ic_batch, f):
+            setattr(x, f, getattr(ic_batch, f))
+    return generate(model, x, _text_window(model, cfg), **kw)
+
+
+def answer_questions(model, vqa_batch, cfg: Optional[GenerationConfig] = None, **kw):
+    """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
+    ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
+    otherwise -> (ids, lengths) as ``generate``"""
+    from .data import VQATaskInput
+    q = vqa_batch.text_seq
+    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
+    if getattr(vqa_batch, "ques_len", None) is not None:
+        ql = np.unique(np.asarray(torch.as_tensor(vqa_batch.ques_len).cpu()).reshape(-1))
+        if ql.size != 1:
+            raise ValueError("answer_questions: the questions of a batch must share one length (group them by length)")
+        q = q[:, :int(ql[0])]
+    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=vqa_batch.prompt_seq, img_seq=vqa_batch.img_seq,
+                     text_seq=q)
+    for f in ("vision_row_ids", "vision_col_ids"):
+        if hasattr(vqa_batch, f):
+            setattr(x, f, getattr(vqa_batch, f))
+    return generate(model, x, _text_window(model, cfg), **kw)

@@ -883,7 +883,8 @@ class TransformerXL(nn.Module):
             # gather straight into the concatenated layout (row stride L*d per sample handled by per-sample calls)
             for b in range(B):
                 ops.embed_gather(E, prompt[b], emb[b, :P_])
-                ops.embed_gather(E, text[b], emb[b, P_ + nv:])
+                if Tt > 0:     # (an empty text -- a generation prompt [prompt, patches] -- gathers nothing)
+                    ops.embed_gather(E, text[b], emb[b, P_ + nv:])
             emb[:, P_:P_ + nv].copy_(v)  # placement of the patch embeddings (data movement only)
             c.prompt, c.text, c.nv = prompt, text, nv
         else:

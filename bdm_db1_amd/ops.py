@@ -529,6 +529,56 @@ def masked_ce_fwd_bwd(logits2d, labels, mask, lse, sums, norm, V, gscale=1.0):
     lib.call("db1_masked_ce_fwd_bwd", P(logits2d), P(labels), P(mask), P(lse), P(sums), P(norm), T, V, ld, float(gscale), dt_code(logits2d), ws, wsn, stream())
 
 
+DB1_ERR_BAD_SHAPE, DB1_ERR_UNSUPPORTED_DTYPE, DB1_ERR_UNSUPPORTED = -1, -3, -6
+
+
+def select_tokens_supported(V: int, ld: int, dtype) -> bool:
+    return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
+
+
+def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True, temperature=1.0,
+                  top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None):
+    """one token per row of ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) on the device (db1_select_tokens): greedy, or
+    Gumbel-max sampling at ``temperature`` after top-k / top-p, over the columns [vocab_lo, vocab_hi).  ``t`` (int32 [1], device): the token
+    index within the generation, READ only; ``finished`` / ``lengths`` / ``status`` (int32 [M]) updated; the token goes to ``out`` [M, max_new]
+    (int32) at column t and to ``next_ids`` (int64, [M] or a column of [M, q]: row stride taken from the tensor).  Capturable; raises
+    ValueError on bad arguments before anything is launched."""
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError("select_tokens: logits must be a 2-D tensor with unit column stride")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"select_tokens: logits dtype {logits2d.dtype} (float32 / bfloat16)")
+    M, ld = logits2d.shape[0], logits2d.stride(0)
+    V = logits2d.shape[1] if V is None else int(V)
+    vocab_hi = V if vocab_hi is None else int(vocab_hi)
+    vocab_lo = int(vocab_lo)
+    if not 0 < V <= logits2d.shape[1] or not select_tokens_supported(V, max(ld, V), logits2d.dtype):
+        raise ValueError(f"select_tokens: V={V} unsupported for logits of shape {tuple(logits2d.shape)}")
+    if not 0 <= vocab_lo < vocab_hi <= V:
+        raise ValueError(f"select_tokens: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
+    if not greedy:
+        if not (temperature > 0 and temperature < float("inf")):
+            raise ValueError(f"select_tokens: temperature {temperature} must be > 0 when sampling")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"select_tokens: top_p {top_p} must lie in (0, 1]")
+        if top_k < 0:
+            raise ValueError(f"select_tokens: top_k {top_k} must be >= 0")
+    i32 = torch.int32
+    for name, x, n in (("finished", finished, M), ("lengths", lengths, M), ("status", status, M), ("t", t, 1)):
+        if x.dtype != i32 or x.numel() != n or not x.is_contiguous() or x.device != logits2d.device:
+            raise ValueError(f"select_tokens: {name} must be a contiguous int32 tensor of {n} elements on {logits2d.device}")
+    if stream_id is not None and (stream_id.dtype != i32 or stream_id.numel() != M or not stream_id.is_contiguous()
+                                  or stream_id.device != logits2d.device):
+        raise ValueError(f"select_tokens: stream_id must be a contiguous int32 tensor of {M} elements on {logits2d.device}")
+    if out.dtype != i32 or out.dim() != 2 or out.shape[0] != M or not out.is_contiguous() or out.device != logits2d.device:
+        raise ValueError(f"select_tokens: out must be a contiguous int32 [{M}, max_new] tensor on {logits2d.device}")
+    if next_ids.dtype != torch.int64 or next_ids.shape[0] != M or next_ids.numel() != M or next_ids.device != logits2d.device:
+        raise ValueError(f"select_tokens: next_ids must be an int64 tensor of {M} rows (one element each) on {logits2d.device}")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lib.call("db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k), float(top_p),
+             int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(stream_id), P(finished),
+             P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), _vp(0), 0, stream())
+
+
 def lmhead_ce(h2d, W, labels, mask, lse, sums, V, dh=None, dW_acc=None, beta_dw=1.0, gscale=1.0, chunk_rows=0):
     """tied head + masked CE without the logits tensor (db1_lmhead_ce_fwd / _fwd_bwd): ``dh`` and ``dW_acc`` given -> the training sweep"""
     T, d = h2d.shape

@@ -527,6 +527,27 @@ int db1_patch_embed_fwd(const float* pixels, const void* const* weights, void* e
 int db1_patch_embed_bwd(const void* demb, const void* const* weights, const void* save, float* const* grads, int n_img, int C, int Himg,
                         int Wimg, int p, int d, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ next-token selection (generation; the reference picks tokens with
+ * logits.argmax(-1) in torch and a host copy per token, evaluate_rl.py:157-266; its caption / VQA evaluation keeps the tokens before the first EOS,
+ * text_decoder.py:42-62).  ONE launch picks one token for each of the M rows of logits [M, ld] (fp32 / bf16; columns >= V are padding):
+ *   - candidates: the FINITE logits of the columns in [vocab_lo, vocab_hi) (NaN and +-inf never chosen);
+ *   - greedy (or top_k == 1): the largest logit, lowest column on ties (torch.argmax);
+ *   - else top-k (0 = off): keep {l >= the k-th largest}; top-p (1 = off): p = softmax(l / T) in fp32 over what is left, keep {l >= tau},
+ *     tau = the largest kept logit with mass{l >= tau} >= top_p (sort-free: every token tied at a threshold is kept); then Gumbel-max:
+ *     argmax over the kept set of l / T - log(-log u), lowest column on ties, with u = ((x >> 8) + 0.5) * 2^-24 and x = output (col % 4) of
+ *     Philox4x32-10 on the counter (col / 4, stream_id[row] (NULL: row), step_base + *t, 0xE0000100) under the key (seed_lo, seed_hi);
+ *   - a row with finished[row] != 0 writes pad_id; a row that picks eos_id writes it and sets finished; a row with no candidate writes pad_id,
+ *     sets finished and status bit 0; otherwise lengths[row] += 1 (the tokens before EOS).  The token goes to out[row * max_new + *t] (status bit 1
+ *     and no write if *t is outside [0, max_new)) and to next_ids[row * ids_stride] (int64: the next call's input ids).  status[row] |= bits.
+ * *t is a device int32 the launch only READS (the caller advances it, e.g. with a captured t += 1): the call can be replayed from a hipGraph.
+ * V <= 36 864 (_supported); no workspace (the query returns 0). */
+int db1_select_tokens_supported(int V, int64_t ld, int dt);
+int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt);
+int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k, float top_p,
+                      int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
+                      const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
+                      int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
