@@ -4,7 +4,7 @@ Importing the package does not need a GPU; constructing a model or calling an op
 if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
 __all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep",
-           "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos"]
+           "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search"]
 
 
 def __getattr__(name):
@@ -23,7 +23,7 @@ def __getattr__(name):
     if name == "GraphedTrainStep":
         from .graphed_train import GraphedTrainStep
         return GraphedTrainStep
-    if name in ("GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos"):
+    if name in ("GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search"):
         from . import generation
         return getattr(generation, name)
     if name == "mpu":

@@ -8,82 +8,14 @@
 // max / arg-max are integer reductions (ties: lowest column) and the top-k / top-p thresholds are found by a bisection over the key range --
 // no sort, no histogram atomics.  All reductions run in a fixed order (wave butterflies, then the 16 wave results read in order from LDS):
 // the same inputs give the same bits.
-#include "db1_common.h"
+#include "select_common.h"
 
 #define SEL_THREADS 1024
 #define SEL_WAVES (SEL_THREADS / 64)
 #define SEL_MAX_NG 9                       // V <= 36 864 (DB1-1.3B: 33 025)
 #define SEL_SITE_SAMPLE 0xE0000100u        // Philox site of the sampling draws (dropout sites: layer * 4 + {0, 1, 2}, 0xE0000000, 0xE0000001)
 
-__device__ __forceinline__ unsigned sel_key(float f) {
-    const unsigned b = __float_as_uint(f);
-    if ((b & 0x7f800000u) == 0x7f800000u) return 0u;          // NaN, +-inf: never a candidate
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // finite keys are > 0x007fffff
-}
-__device__ __forceinline__ float sel_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)x, o, 64), hi = __shfl_xor((unsigned)(x >> 32), o, 64);
-        const unsigned long long y = ((unsigned long long)hi << 32) | lo;
-        x = y > x ? y : x;
-    }
-    return x;
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, (unsigned)__shfl_xor(x, o, 64));
-    return x;
-}
-
-// Block reductions: every wave writes its result to one LDS slot, one barrier, every thread combines the 16 slots in order.  Consecutive
-// reductions alternate between two slot sets, so a slot is never rewritten while a slower wave may still read it (one barrier per reduction).
-struct SelShared {
-    unsigned long long u64[2][SEL_WAVES];
-    float f[2][SEL_WAVES];
-    int i[2][SEL_WAVES];
-    unsigned u[2][SEL_WAVES];
-};
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long x, SelShared& sh, int& ph) {
-    x = wave_max_u64(x);
-    if ((threadIdx.x & 63) == 0) sh.u64[ph][threadIdx.x >> 6] = x;
-    __syncthreads();
-    unsigned long long r = sh.u64[ph][0];
-#pragma unroll
-    for (int w = 1; w < SEL_WAVES; w++) r = sh.u64[ph][w] > r ? sh.u64[ph][w] : r;
-    ph ^= 1;
-    return r;
-}
-__device__ __forceinline__ unsigned block_min_u32(unsigned x, SelShared& sh, int& ph) {
-    x = wave_min_u32(x);
-    if ((threadIdx.x & 63) == 0) sh.u[ph][threadIdx.x >> 6] = x;
-    __syncthreads();
-    unsigned r = sh.u[ph][0];
-#pragma unroll
-    for (int w = 1; w < SEL_WAVES; w++) r = min(r, sh.u[ph][w]);
-    ph ^= 1;
-    return r;
-}
-__device__ __forceinline__ int block_sum_i(int x, SelShared& sh, int& ph) {   // x wave-uniform already
-    if ((threadIdx.x & 63) == 0) sh.i[ph][threadIdx.x >> 6] = x;
-    __syncthreads();
-    int r = 0;
-#pragma unroll
-    for (int w = 0; w < SEL_WAVES; w++) r += sh.i[ph][w];
-    ph ^= 1;
-    return r;
-}
-__device__ __forceinline__ float block_sum_f(float x, SelShared& sh, int& ph) {
-    x = wave_sum(x);   // (butterfly: every lane ends with the same bits)
-    if ((threadIdx.x & 63) == 0) sh.f[ph][threadIdx.x >> 6] = x;
-    __syncthreads();
-    float r = sh.f[ph][0];
-#pragma unroll
-    for (int w = 1; w < SEL_WAVES; w++) r += sh.f[ph][w];
-    ph ^= 1;
-    return r;
-}
+typedef SelSharedT<SEL_WAVES> SelShared;
 
 template <int NG>
 __device__ __forceinline__ int sel_count_ge(const unsigned (&key)[NG][4], unsigned thr, SelShared& sh, int& ph) {

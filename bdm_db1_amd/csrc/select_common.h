@@ -1,0 +1,82 @@
+// Order-preserving logit keys and fixed-order block reductions shared by next-token selection (select.hip) and beam search (beam.hip).
+//
+// sel_key maps a float to a uint32 whose unsigned order is the float order (0 = not a candidate: NaN, +-inf), so max / arg-max are integer
+// reductions; packing (key << 32) | ~column into a uint64 makes the arg-max pick the lowest column on ties.  Block reductions: every wave
+// reduces by butterfly (every lane ends with the same bits), writes one LDS slot, one barrier, every thread combines the NW slots in order --
+// the same inputs give the same bits.  Consecutive reductions alternate between two slot sets, so a slot is never rewritten while a slower
+// wave may still read it (one barrier per reduction).
+#pragma once
+#include "db1_common.h"
+
+__device__ __forceinline__ unsigned sel_key(float f) {
+    const unsigned b = __float_as_uint(f);
+    if ((b & 0x7f800000u) == 0x7f800000u) return 0u;          // NaN, +-inf: never a candidate
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);          // finite keys are > 0x007fffff
+}
+__device__ __forceinline__ float sel_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)x, o, 64), hi = __shfl_xor((unsigned)(x >> 32), o, 64);
+        const unsigned long long y = ((unsigned long long)hi << 32) | lo;
+        x = y > x ? y : x;
+    }
+    return x;
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = min(x, (unsigned)__shfl_xor(x, o, 64));
+    return x;
+}
+
+template <int NW>
+struct SelSharedT {
+    unsigned long long u64[2][NW];
+    float f[2][NW];
+    int i[2][NW];
+    unsigned u[2][NW];
+};
+template <int NW>
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long x, SelSharedT<NW>& sh, int& ph) {
+    x = wave_max_u64(x);
+    if ((threadIdx.x & 63) == 0) sh.u64[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    unsigned long long r = sh.u64[ph][0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) r = sh.u64[ph][w] > r ? sh.u64[ph][w] : r;
+    ph ^= 1;
+    return r;
+}
+template <int NW>
+__device__ __forceinline__ unsigned block_min_u32(unsigned x, SelSharedT<NW>& sh, int& ph) {
+    x = wave_min_u32(x);
+    if ((threadIdx.x & 63) == 0) sh.u[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    unsigned r = sh.u[ph][0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) r = min(r, sh.u[ph][w]);
+    ph ^= 1;
+    return r;
+}
+template <int NW>
+__device__ __forceinline__ int block_sum_i(int x, SelSharedT<NW>& sh, int& ph) {   // x wave-uniform already
+    if ((threadIdx.x & 63) == 0) sh.i[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    int r = 0;
+#pragma unroll
+    for (int w = 0; w < NW; w++) r += sh.i[ph][w];
+    ph ^= 1;
+    return r;
+}
+template <int NW>
+__device__ __forceinline__ float block_sum_f(float x, SelSharedT<NW>& sh, int& ph) {
+    x = wave_sum(x);   // (butterfly: every lane ends with the same bits)
+    if ((threadIdx.x & 63) == 0) sh.f[ph][threadIdx.x >> 6] = x;
+    __syncthreads();
+    float r = sh.f[ph][0];
+#pragma unroll
+    for (int w = 1; w < NW; w++) r += sh.f[ph][w];
+    ph ^= 1;
+    return r;
+}

@@ -93,6 +93,8 @@ class RingMemory:
         dev = model.dev
         self.kv = [torch.zeros(batch_size, self.cap, 2, model.n_head, model.d_head, device=dev, dtype=torch.bfloat16) for _ in range(model.n_layer)]
         self.state = torch.zeros(1, dtype=torch.int32, device=dev)
+        from . import ops
+        self._ptrs = ops.ring_pointers(self.kv)   # (the layers' base pointers for reorder: made here, never under a capture)
         self.reset()
 
     def reset(self):
@@ -113,6 +115,16 @@ class RingMemory:
             for ring, kv in zip(self.kv, dec.kv):
                 ring[:, :mlen].copy_(kv.reshape(self.B, mlen, 2, model.n_head, model.d_head))
             self.state.zero_()
+
+    def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
+        """beam search: after the call that appended token t - 1, give row b the keys / values of the last ``t`` tokens of row
+        ``parent[b]`` in every layer (db1_ring_reorder; ``t`` a device int32 [1], read by the launch, so this can be captured).  The older
+        keys -- the prompt's, loaded from one prefill -- are the same across a group's rows and are not copied.  ``parent`` int32 [B];
+        ``group``: rows per group (a parent lies in its row's group); ``done`` (int32 [B / group]): groups left alone; ``max_t`` (default
+        mem_len): the largest t the call will see (sizes the staging workspace)."""
+        from . import ops
+        mlen = int(self.model.mem_len)
+        ops.ring_reorder(self.kv, self._ptrs, self.state, mlen, t, mlen if max_t is None else int(max_t), parent, W=group, done=done)
 
 
 class GraphedRingStep:

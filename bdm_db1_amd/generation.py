@@ -14,6 +14,11 @@ are not part of its release.  Here a generation is
 
 The selection rule (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox) is stated in include/db1_hip.h (db1_select_tokens)
 and restated in NumPy in tests/select_rule.py.
+
+Beam search (``beam_search``, or a ``BeamSearchConfig`` passed to ``generate_captions`` / ``answer_questions``) runs the same way: the
+prompt once per group, its memory and last logits expanded to the W beams of the group, then one call per token whose epilogue is
+``db1_beam_step`` (lse, per-row top-2W, the group walk, the hypothesis pool, the next ids) and ``db1_ring_reorder`` (the last t keys of
+every beam whose parent is another row).  The rule is stated in include/db1_hip.h and restated in NumPy in tests/beam_rule.py.
 """
 from __future__ import annotations
 
@@ -60,6 +65,39 @@ class GenerationConfig:
             raise ValueError(f"sync_every {self.sync_every} must be >= 1")
         if not 0 <= int(self.seed) < 2 ** 64:
             raise ValueError(f"seed {self.seed} must be a 64-bit unsigned integer")
+
+
+@dataclass(frozen=True)
+class BeamSearchConfig:
+    """Beam search with ``num_beams`` beams per prompt (1 .. 16), ``max_new_tokens`` new tokens (at most the model's ``mem_len``), scores
+    normalised by (length)^``length_penalty``; the best ``num_return_sequences`` (<= num_beams) hypotheses of each prompt come back.
+    ``eos_id`` None: no end-of-sequence token (every hypothesis runs ``max_new_tokens``).  Tokens are chosen in ``[vocab_lo, vocab_hi)``
+    (``vocab_hi`` None as in ``GenerationConfig``).  The host checks whether every prompt is done each ``sync_every`` tokens."""
+    num_beams: int = 4
+    max_new_tokens: int = 30
+    length_penalty: float = 1.0
+    num_return_sequences: int = 1
+    eos_id: Optional[int] = None
+    pad_id: int = 0
+    vocab_lo: int = 0
+    vocab_hi: Optional[int] = None
+    sync_every: int = 8
+
+    def __post_init__(self):
+        if not 1 <= int(self.num_beams) <= 16:
+            raise ValueError(f"num_beams {self.num_beams} must lie in [1, 16]")
+        if int(self.max_new_tokens) < 1:
+            raise ValueError(f"max_new_tokens {self.max_new_tokens} must be >= 1")
+        if not abs(float(self.length_penalty)) < float("inf"):
+            raise ValueError(f"length_penalty {self.length_penalty} must be finite")
+        if not 1 <= int(self.num_return_sequences) <= int(self.num_beams):
+            raise ValueError(f"num_return_sequences {self.num_return_sequences} must lie in [1, num_beams = {self.num_beams}]")
+        if int(self.vocab_lo) < 0 or (self.vocab_hi is not None and int(self.vocab_hi) <= int(self.vocab_lo)):
+            raise ValueError(f"vocabulary window [{self.vocab_lo}, {self.vocab_hi}) is empty")
+        if self.eos_id is not None and int(self.eos_id) < 0:
+            raise ValueError(f"eos_id {self.eos_id} must be >= 0 (or None)")
+        if int(self.sync_every) < 1:
+            raise ValueError(f"sync_every {self.sync_every} must be >= 1")
 
 
 def clip_at_eos(ids, lengths) -> List[List[int]]:
@@ -214,14 +252,19 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
         model.train(was_training)
 
 
-def _text_window(model, cfg: Optional[GenerationConfig]) -> GenerationConfig:
+def _text_window(model, cfg):
     cfg = cfg or GenerationConfig()
     return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
 
 
-def generate_captions(model, ic_batch, cfg: Optional[GenerationConfig] = None, **kw):
+def _run(model, x, cfg, **kw):
+    return beam_search(model, x, cfg, **kw) if isinstance(cfg, BeamSearchConfig) else generate(model, x, cfg, **kw)
+
+
+def generate_captions(model, ic_batch, cfg=None, **kw):
     """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
-    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``"""
+    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``:
+    (ids, lengths, scores) as ``beam_search``"""
     from .data import ICTaskInput
     M = _batch_size(ic_batch)
     x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
@@ -229,13 +272,13 @@ def generate_captions(model, ic_batch, cfg: Optional[GenerationConfig] = None, *
     for f in ("vision_row_ids", "vision_col_ids"):
         if hasattr(ic_batch, f):
             setattr(x, f, getattr(ic_batch, f))
-    return generate(model, x, _text_window(model, cfg), **kw)
+    return _run(model, x, _text_window(model, cfg), **kw)
 
 
-def answer_questions(model, vqa_batch, cfg: Optional[GenerationConfig] = None, **kw):
+def answer_questions(model, vqa_batch, cfg=None, **kw):
     """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
     ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
-    otherwise -> (ids, lengths) as ``generate``"""
+    otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``"""
     from .data import VQATaskInput
     q = vqa_batch.text_seq
     q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
@@ -249,4 +292,168 @@ def answer_questions(model, vqa_batch, cfg: Optional[GenerationConfig] = None, *
     for f in ("vision_row_ids", "vision_col_ids"):
         if hasattr(vqa_batch, f):
             setattr(x, f, getattr(vqa_batch, f))
-    return generate(model, x, _text_window(model, cfg), **kw)
+    return _run(model, x, _text_window(model, cfg), **kw)
+
+
+class _BeamState:
+    """the device state of one beam search over G groups of W beams (include/db1_hip.h, db1_beam_step)"""
+
+    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int):
+        dev = model.dev
+        W, mx = int(cfg.num_beams), int(cfg.max_new_tokens)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.G, self.W, self.M, self.cfg, self.V, self.hi = G, W, G * W, cfg, V, hi
+        self.t = torch.zeros(1, **i32)
+        self.beam_score = torch.zeros(G * W, dtype=torch.float32, device=dev)
+        self.parent = torch.zeros(G * W, **i32)
+        self.tokens = torch.zeros(G * W, mx, **i32)
+        self.pool_tokens = torch.zeros(G, W, mx, **i32)
+        self.pool_len = torch.zeros(G, W, **i32)
+        self.pool_score = torch.zeros(G, W, dtype=torch.float32, device=dev)
+        self.pool_slot = torch.zeros(G, W, **i32)
+        self.pool_count = torch.zeros(G, **i32)
+        self.done = torch.zeros(G, **i32)
+        self.switches = torch.zeros(G, **i32)
+        self.status = torch.zeros(G, **i32)
+
+    def start(self):
+        pad = self.cfg.pad_id
+        for x in (self.t, self.beam_score, self.pool_len, self.pool_count, self.done, self.switches, self.status):
+            x.zero_()
+        self.parent.copy_(torch.arange(self.M, dtype=torch.int32))
+        self.tokens.fill_(pad)
+        self.pool_tokens.fill_(pad)
+        self.pool_score.fill_(float("-inf"))
+        self.pool_slot.copy_(torch.arange(self.W, dtype=torch.int32).expand(self.G, self.W))
+
+    def select(self, logits2d, next_ids):
+        """db1_beam_step on the last-position logits [M, V] of step t; the next ids go to ``next_ids`` (int64 [M])"""
+        c = self.cfg
+        ops.beam_step(logits2d, self.t, self.beam_score, self.parent, self.tokens, self.pool_tokens, self.pool_len, self.pool_score, self.pool_slot,
+                      self.pool_count, self.done, self.switches, next_ids, self.status, W=self.W, V=self.V, vocab_lo=c.vocab_lo, vocab_hi=self.hi,
+                      eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, length_penalty=c.length_penalty)
+
+    def result(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        if (self.status.cpu() & 2).any():
+            raise RuntimeError("db1_beam_step: the token counter left [0, max_new_tokens)")
+        R, mx = int(self.cfg.num_return_sequences), int(self.cfg.max_new_tokens)
+        toks, slot, n, sc, count = (x.cpu() for x in (self.pool_tokens, self.pool_slot, self.pool_len, self.pool_score, self.pool_count))
+        ids = torch.full((self.G, R, mx), self.cfg.pad_id, dtype=torch.int32)
+        lengths = torch.zeros(self.G, R, dtype=torch.int32)
+        scores = torch.full((self.G, R), float("-inf"), dtype=torch.float32)
+        for g in range(self.G):
+            k = min(R, int(count[g]))           # (fewer hypotheses than R only when every beam of a group ran out of candidates)
+            ids[g, :k] = toks[g, slot[g, :k].long()]
+            lengths[g, :k] = n[g, :k]
+            scores[g, :k] = sc[g, :k]
+        return ids, lengths, scores
+
+
+class _BeamRingGenerator:
+    """a RingMemory of G * W rows, the beam state and the captured per-token graph (forward, db1_beam_step, db1_ring_reorder, t += 1) for
+    one (model, group count, config, vocabulary); reused across calls"""
+
+    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int):
+        from .decode import GraphedRingStep, RingMemory
+        self.key = (G, cfg, V, hi)
+        self.state = _BeamState(model, G, cfg, V, hi)
+        self.ring = RingMemory(model, self.state.M)
+        self.step = GraphedRingStep(model, self.state.M, 1, memory=self.ring, epilogue=self.epilogue)
+
+    def epilogue(self, step, logits):
+        st = self.state
+        st.select(logits[:, -1], step.ids[:, 0])
+        self.ring.reorder(st.parent, st.t, max_t=st.cfg.max_new_tokens, group=st.W, done=st.done)
+        st.t.add_(1)
+
+
+@torch.no_grad()
+def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
+                replay: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Beam search after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of G prompts of one shape ->
+    (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R = ``num_return_sequences``: each prompt's
+    best hypotheses, best first.  ``ids[g, r, :lengths[g, r]]`` are the tokens before EOS (then EOS, then ``pad_id``); the score is the sum of
+    the tokens' log-probabilities (EOS included) over length^``length_penalty``, length = the tokens before EOS + 1 for a hypothesis that
+    ended in EOS, max_new_tokens for one that ran to the end.  The prompt runs once per group; its memory is expanded to the W beams.
+    ``graphed`` None: the hipGraph ring path where the model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False
+    forces the eager loop (the list-form memory is reordered with index_select).  ``replay`` False (ring path): the same forward and epilogue
+    run eagerly over the same ring instead of as a graph replay.  ``stats`` (a dict): receives the path taken, the number of per-token calls
+    and ``parent_switches``, the number of (step, row) pairs (step > 0) whose parent was another row."""
+    cfg = config or BeamSearchConfig()
+    if not isinstance(cfg, BeamSearchConfig):
+        raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
+    mlen = int(model.mem_len or 0)
+    if not mlen > 0:
+        raise ValueError("beam_search needs a model with memory (mem_len > 0)")
+    if int(cfg.max_new_tokens) > mlen:
+        raise ValueError(f"beam_search: max_new_tokens {cfg.max_new_tokens} exceeds the model's mem_len {mlen}")
+    G = _batch_size(prompt)
+    W = int(cfg.num_beams)
+    V = int(model.total_vocab_size)
+    hi = V if cfg.vocab_hi is None else int(cfg.vocab_hi)
+    if hi > V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {hi}) exceeds the model's vocabulary ({V})")
+    if cfg.eos_id is not None and int(cfg.eos_id) >= V:
+        raise ValueError(f"eos_id {cfg.eos_id} lies outside the model's vocabulary ({V})")
+    if not ops.beam_step_supported(V, V, W, model.compute_dtype):
+        raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
+    ring = _ring_ok(model) if graphed is None else bool(graphed)
+    if ring and not _ring_ok(model):
+        raise ValueError("the graphed ring path needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
+    was_training = model.training
+    model.eval()
+    try:
+        if ring:
+            gen = getattr(model, "_beam_generator", None)
+            if gen is None or gen.key != (G, cfg, V, hi) or gen.step._version != model._wversion:
+                model._beam_generator = None        # (free the old ring before the new one is allocated)
+                gen = model._beam_generator = _BeamRingGenerator(model, G, cfg, V, hi)
+            st = gen.state
+            ids = gen.step.ids
+        else:
+            st = _BeamState(model, G, cfg, V, hi)
+            ids = torch.zeros(G * W, 1, dtype=torch.long, device=model.dev)
+        st.start()
+        # prefill: the prompt once per group through the list-form path; its last position and its memory expanded to the group's beams
+        model._dec_state = None
+        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(G))
+        st.select(logits[:, -1].repeat_interleave(W, 0), ids[:, 0])
+        st.t.add_(1)                              # (step 0: every beam descends from the same prefill, nothing to reorder)
+        mems = [m.repeat_interleave(W, 0) for m in mems]
+        del logits
+        calls = 0
+        if ring:
+            gen.ring.load(mems)
+            del mems
+        for i in range(1, cfg.max_new_tokens):
+            if i % cfg.sync_every == 0 and bool(st.done.all()):
+                break
+            if ring and replay:
+                gen.step(ids)
+            elif ring:
+                logits, _, _ = model([gen.step.x], compute_loss=False, mems=gen.ring)
+                gen.epilogue(gen.step, logits)
+            else:
+                from .data import NLPTaskInput
+                x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+                logits, _, mems = model([x], compute_loss=False, mems=mems)
+                st.select(logits[:, -1], ids[:, 0])
+                parent = st.parent.long()
+                mems = [m.index_select(0, parent) for m in mems]
+                st.t.add_(1)
+            calls += 1
+        if ring:
+            gen.step.check(synchronize=True)
+            if not replay:
+                chk = getattr(model, "check_decode_chain", None)
+                if chk is not None:
+                    chk(True)
+        else:
+            chk = getattr(model, "check_decode_chain", None)
+            if chk is not None:
+                chk(True)
+        if stats is not None:
+            stats.update(path="ring" if ring else "eager", token_calls=calls, parent_switches=int(st.switches.sum()))
+        return st.result()
+    finally:
+        model.train(was_training)

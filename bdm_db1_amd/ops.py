@@ -6,6 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import weakref
 from typing import Optional
 
 import torch
@@ -579,6 +580,93 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
              P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), _vp(0), 0, stream())
 
 
+def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:
+    return bool(lib.load().db1_beam_step_supported(int(V), int(ld), int(W), dt_code(dtype)))
+
+
+def beam_step(logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches, next_ids, status,
+              *, W, V=None, vocab_lo=0, vocab_hi=None, eos_id=-1, pad_id=0, length_penalty=1.0):
+    """one beam-search step over ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid, M = G * W rows) on the device
+    (db1_beam_step, rule in include/db1_hip.h): ``t`` (int32 [1]) READ only; beam_score (float32 [M]), parent (int32 [M]), tokens (int32
+    [M, max_new]), the pool (pool_tokens int32 [G, W, max_new], pool_len / pool_slot int32 [G, W], pool_score float32 [G, W]) and pool_count /
+    done / switches / status (int32 [G]) updated; the next ids go to ``next_ids`` (int64, [M] or a column of [M, q]).  Capturable; raises
+    ValueError on bad arguments before anything is launched."""
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError("beam_step: logits must be a 2-D tensor with unit column stride")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"beam_step: logits dtype {logits2d.dtype} (float32 / bfloat16)")
+    M, ld = logits2d.shape[0], logits2d.stride(0)
+    W = int(W)
+    if not 1 <= W <= 16 or M % W != 0 or M == 0:
+        raise ValueError(f"beam_step: W={W} must lie in [1, 16] and divide the {M} rows")
+    G = M // W
+    V = logits2d.shape[1] if V is None else int(V)
+    vocab_hi = V if vocab_hi is None else int(vocab_hi)
+    vocab_lo = int(vocab_lo)
+    if not 0 < V <= logits2d.shape[1] or not beam_step_supported(V, max(ld, V), W, logits2d.dtype):
+        raise ValueError(f"beam_step: V={V} unsupported for logits of shape {tuple(logits2d.shape)}")
+    if not 0 <= vocab_lo < vocab_hi <= V:
+        raise ValueError(f"beam_step: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
+    lp = float(length_penalty)
+    if not abs(lp) < float("inf"):
+        raise ValueError(f"beam_step: length_penalty {length_penalty} must be finite")
+    dev = logits2d.device
+    if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.shape[0] != M or not tokens.is_contiguous() or tokens.device != dev:
+        raise ValueError(f"beam_step: tokens must be a contiguous int32 [{M}, max_new] tensor on {dev}")
+    mx = tokens.shape[1]
+    if mx < 1:
+        raise ValueError("beam_step: max_new must be >= 1")
+    for name, x, shape, dt in (("t", t, (1,), torch.int32), ("beam_score", beam_score, (M,), torch.float32), ("parent", parent, (M,), torch.int32),
+                               ("pool_tokens", pool_tokens, (G, W, mx), torch.int32), ("pool_len", pool_len, (G, W), torch.int32),
+                               ("pool_score", pool_score, (G, W), torch.float32), ("pool_slot", pool_slot, (G, W), torch.int32),
+                               ("pool_count", pool_count, (G,), torch.int32), ("done", done, (G,), torch.int32),
+                               ("switches", switches, (G,), torch.int32), ("status", status, (G,), torch.int32)):
+        if x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"beam_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    if next_ids.dtype != torch.int64 or next_ids.shape[0] != M or next_ids.numel() != M or next_ids.device != dev:
+        raise ValueError(f"beam_step: next_ids must be an int64 tensor of {M} rows (one element each) on {dev}")
+    ws, wsn = _ws("db1_beam_step_workspace_bytes", (M, V, W, mx, dt_code(logits2d)), dev)
+    lib.call("db1_beam_step", P(logits2d), G, W, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, int(eos_id), int(pad_id), lp, P(t), mx,
+             P(beam_score), P(parent), P(tokens), P(pool_tokens), P(pool_len), P(pool_score), P(pool_slot), P(pool_count), P(done), P(switches),
+             P(next_ids), next_ids.stride(0), P(status), ws, wsn, stream())
+
+
+def ring_pointers(rings) -> torch.Tensor:
+    """the device array of ring base pointers db1_ring_reorder takes (int64 [n_layers])"""
+    return torch.tensor([r.data_ptr() for r in rings], dtype=torch.int64).to(rings[0].device)
+
+
+def ring_reorder(rings, ptrs, state, mlen, t, max_t, parent, W=1, done=None):
+    """copy the last t keys of every row from row parent[b] (same group of W rows) in every ring of ``rings`` (bf16 [M, cap, 2, H, D],
+    contiguous; ``ptrs`` = ring_pointers(rings)) -- db1_ring_reorder.  ``t`` (int32 [1]) READ only, at most ``max_t`` (<= mlen);
+    ``done`` (int32 [M / W] or None): groups left alone.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    if not rings:
+        raise ValueError("ring_reorder: no rings")
+    r0 = rings[0]
+    if r0.dim() < 3:
+        raise ValueError("ring_reorder: rings must be [M, cap, ...] tensors")
+    M, cap = r0.shape[0], r0.shape[1]
+    slot_bytes = r0[0, 0].numel() * r0.element_size()
+    for r in rings:
+        if r.shape != r0.shape or r.dtype != r0.dtype or not r.is_contiguous() or r.device != r0.device or r.data_ptr() % 16:
+            raise ValueError("ring_reorder: the rings must be contiguous 16-byte aligned tensors of one shape, dtype and device")
+    if not lib.load().db1_ring_reorder_supported(int(slot_bytes)):
+        raise ValueError(f"ring_reorder: a slot of {slot_bytes} bytes (a multiple of 16 expected)")
+    W, mlen, max_t = int(W), int(mlen), int(max_t)
+    if W < 1 or M % W:
+        raise ValueError(f"ring_reorder: W={W} must divide the {M} rows")
+    if not 1 <= max_t <= mlen < cap:
+        raise ValueError(f"ring_reorder: needs 1 <= max_t ({max_t}) <= mlen ({mlen}) < cap ({cap})")
+    dev = r0.device
+    if ptrs.dtype != torch.int64 or tuple(ptrs.shape) != (len(rings),) or ptrs.device != dev or not ptrs.is_contiguous():
+        raise ValueError(f"ring_reorder: ptrs must be a contiguous int64 [{len(rings)}] device tensor (ring_pointers)")
+    for name, x, n in (("state", state, 1), ("t", t, 1), ("parent", parent, M)) + ((("done", done, M // W),) if done is not None else ()):
+        if x.dtype != torch.int32 or x.numel() != n or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"ring_reorder: {name} must be a contiguous int32 tensor of {n} elements on {dev}")
+    ws, wsn = _ws("db1_ring_reorder_workspace_bytes", (len(rings), M, max_t, int(slot_bytes)), dev)
+    lib.call("db1_ring_reorder", P(ptrs), len(rings), M, W, cap, int(slot_bytes), P(state), mlen, P(t), max_t, P(parent), P(done), ws, wsn, stream())
+
+
 def lmhead_ce(h2d, W, labels, mask, lse, sums, V, dh=None, dW_acc=None, beta_dw=1.0, gscale=1.0, chunk_rows=0):
     """tied head + masked CE without the logits tensor (db1_lmhead_ce_fwd / _fwd_bwd): ``dh`` and ``dW_acc`` given -> the training sweep"""
     T, d = h2d.shape
@@ -703,12 +791,16 @@ def _chain_pinned_word():
     if _chain_flag_pool is None:
         if torch.cuda.is_current_stream_capturing():
             raise lib.Db1Error("db1_decode_chain: the first one-token call must run eagerly (GraphedRingStep warms up before it captures)")
-        _chain_flag_pool = [torch.zeros(256, dtype=torch.int32).pin_memory(), 0]
-    pool, used = _chain_flag_pool
-    if used >= pool.numel():
+        _chain_flag_pool = [torch.zeros(256, dtype=torch.int32).pin_memory(), list(range(255, -1, -1))]
+    pool, free = _chain_flag_pool
+    if not free:
         raise lib.Db1Error("db1_decode_chain: more than 256 scratch owners (device x stream pairs + captured steps) decode through the persistent launch")
-    _chain_flag_pool[1] = used + 1
-    return pool[used:used + 1]
+    i = free.pop()
+    word = pool[i:i + 1]
+    word.zero_()
+    # the word goes back to the free list when its owner (a GraphedRingStep, or whoever holds a new_chain_scratch result) is collected
+    weakref.finalize(word, free.append, i)
+    return word
 
 
 def new_chain_scratch(device):

@@ -548,6 +548,45 @@ int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int 
                       const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
                       int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ beam search (captions / answers / text; tests/beam_rule.py restates
+ * the rule in NumPy).  G groups (prompts) of W beams (1 <= W <= 16), M = G * W rows, row b = g * W + j; step t = 0 .. max_new - 1 chooses
+ * token t.  At every step (db1_beam_step, on logits [M, ld] of the step, fp32 / bf16 widened to fp32):
+ *   1. row candidates: the columns c in [vocab_lo, vocab_hi) with a finite logit; lse_b = fp32 log-sum-exp over them;
+ *      s(b, c) = beam_score[b] + (l[b, c] - lse_b);
+ *   2. live beams: at t = 0 only j = 0 of each group (beam_score is not read); later the rows with beam_score > -inf.  A dead row offers
+ *      nothing; a live row without a candidate sets status[g] bit 0;
+ *   3. the group's candidates sorted by s descending, ties by the lower (j, c); the first 2W are walked in order:
+ *   4. c == eos_id at rank < W: a finished hypothesis (the parent's tokens, then EOS; length n = t; score s / (t + 1)^length_penalty) is
+ *      offered to the pool; EOS at rank >= W is dropped; any other candidate becomes the next beam j' (parent b, token c, beam_score s) until
+ *      W beams are filled; unfilled beams get beam_score -inf (and parent = themselves).  The pool keeps the W best hypotheses sorted by
+ *      score descending; on equal scores the one offered first stays ahead;
+ *   5. the group is done when no beam was filled, or when the pool holds W hypotheses and its worst score >= (best new beam_score) /
+ *      (t + 1)^length_penalty.  A done group's rows write pad_id to next_ids and change no other state;
+ *   6. at t = max_new - 1, after the walk, every new beam is offered (in beam order) with n = t + 1 (no EOS) and score beam_score / (t + 1)^lp;
+ *   7. output: the first R pool entries of each group.
+ * State (device, int32 unless noted): beam_score float [M], parent [M], tokens [M, max_new] (the beams' histories, permuted in place),
+ * pool_tokens [G, W, max_new] (W slots per group, EOS then pad_id after a hypothesis' n tokens), pool_len / pool_score (float) / pool_slot
+ * [G, W] (sorted: entry k is slot pool_slot[g, k]), pool_count / done / switches / status [G].  Before step 0: pool_count, done, switches,
+ * status zero.  switches[g] += the number of new beams (t > 0) whose parent is another row.  The new beams' tokens go to
+ * next_ids[b * ids_stride] (int64).  status bit 1: *t outside [0, max_new) (nothing written but pad_id to next_ids).
+ * Two launches (rows x vocabulary chunks; one workgroup per group), fixed-order reductions: the same inputs give the same bits.  *t is only
+ * READ: the step can be captured into a graph.  V <= 65 536 (_supported). */
+int db1_beam_step_supported(int V, int64_t ld, int W, int dt);
+int64_t db1_beam_step_workspace_bytes(int M, int V, int W, int max_new, int dt);
+int db1_beam_step(const void* logits, int G, int W, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, int eos_id, int pad_id,
+                  float length_penalty, const int32_t* t, int max_new, float* beam_score, int32_t* parent, int32_t* tokens,
+                  int32_t* pool_tokens, int32_t* pool_len, float* pool_score, int32_t* pool_slot, int32_t* pool_count, int32_t* done,
+                  int32_t* switches, int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+/* Beam K/V history of a RingMemory: rings = a DEVICE array of n_layers pointers to rings [M, cap, slot] (slot = 2 * H * D bf16 =
+ * slot_bytes, a multiple of 16).  After the forward of step t (state = the ring origin after that call's advance) the last t logical keys
+ * of every row, slots (state + mlen - t + i) % cap for i < t, are copied from row parent[b] to row b in every layer; rows with parent[b] == b
+ * (or a parent outside b's group) and rows of groups with done[g] != 0 (done NULL: none) are left alone; *t outside [1, max_t] copies
+ * nothing.  Two launches (gather into the workspace, write back): an in-place permutation with duplicates.  Requires max_t <= mlen < cap. */
+int db1_ring_reorder_supported(int64_t slot_bytes);
+int64_t db1_ring_reorder_workspace_bytes(int n_layers, int M, int max_t, int64_t slot_bytes);
+int db1_ring_reorder(const void* const* rings, int n_layers, int M, int W, int cap, int64_t slot_bytes, const int32_t* state, int mlen,
+                     const int32_t* t, int max_t, const int32_t* parent, const int32_t* done, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
