@@ -4,7 +4,8 @@ Importing the package does not need a GPU; constructing a model or calling an op
 if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
 __all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep",
-           "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search"]
+           "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
+           "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers"]
 
 
 def __getattr__(name):
@@ -26,6 +27,9 @@ def __getattr__(name):
     if name in ("GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search"):
         from . import generation
         return getattr(generation, name)
+    if name in ("ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers"):
+        from . import scoring
+        return getattr(scoring, name)
     if name == "mpu":
         import importlib
         return importlib.import_module(".mpu", __name__)

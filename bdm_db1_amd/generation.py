@@ -265,6 +265,11 @@ def generate_captions(model, ic_batch, cfg=None, **kw):
     """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
     tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``:
     (ids, lengths, scores) as ``beam_search``"""
+    return _run(model, caption_prompt(ic_batch), _text_window(model, cfg), **kw)
+
+
+def caption_prompt(ic_batch):
+    """the generation prompt of an ``ICTaskInput`` batch: ``[prompt, image patches]`` and an empty caption"""
     from .data import ICTaskInput
     M = _batch_size(ic_batch)
     x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
@@ -272,13 +277,18 @@ def generate_captions(model, ic_batch, cfg=None, **kw):
     for f in ("vision_row_ids", "vision_col_ids"):
         if hasattr(ic_batch, f):
             setattr(x, f, getattr(ic_batch, f))
-    return _run(model, x, _text_window(model, cfg), **kw)
+    return x
 
 
 def answer_questions(model, vqa_batch, cfg=None, **kw):
     """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
     ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
     otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``"""
+    return _run(model, question_prompt(vqa_batch), _text_window(model, cfg), **kw)
+
+
+def question_prompt(vqa_batch):
+    """the generation prompt of a ``VQATaskInput`` batch: ``[prompt, image patches, question]`` without the answer"""
     from .data import VQATaskInput
     q = vqa_batch.text_seq
     q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
@@ -292,7 +302,7 @@ def answer_questions(model, vqa_batch, cfg=None, **kw):
     for f in ("vision_row_ids", "vision_col_ids"):
         if hasattr(vqa_batch, f):
             setattr(x, f, getattr(vqa_batch, f))
-    return _run(model, x, _text_window(model, cfg), **kw)
+    return x
 
 
 class _BeamState:

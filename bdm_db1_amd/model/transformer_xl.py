@@ -299,6 +299,7 @@ class TransformerXL(nn.Module):
         # training without a logits tensor: head GEMM, masked CE and the head's two gradient GEMMs in ONE sweep over 16 384-row chunks
         # (db1_lmhead_ce_fwd_bwd) during the forward; forward then returns (None, loss).  Set by the engine when keep_logits is False.
         self.fuse_head_loss = False
+        self._score_sink = None          # set by scoring.score for the duration of ITS eval-mode forwards: the head ends in ops.lmhead_score
         self.loss_grad_scale = 1.0       # d(loss * this) is what backward() accumulates: 1 / gradient-accumulation steps (set by the engine)
         self.use_flash = True            # fused attention when the shape is supported
         self.use_flash_bwd = True        # fused backward kernels (False: recompute through the materialised path)
@@ -1716,9 +1717,14 @@ class TransformerXL(nn.Module):
         if compute_loss:
             lab = (labels[0] if len(labels) == 1 else torch.cat(labels, dim=0)).reshape(-1).contiguous()
             msk = (masks[0] if len(masks) == 1 else torch.cat(masks, dim=0)).reshape(-1).contiguous()
+        sink = self._score_sink if (compute_loss and not self.training and not keep) else None
+        if compute_loss and sink is None:
             lse = self._new(T, dtype=torch.float32)
             sums = torch.zeros(2, device=self.dev, dtype=torch.float32)
-        if fused:
+        if sink is not None:
+            # scoring (scoring.score): per-token log-prob / arg-max / rank from the chunked sweep; no logits tensor, no gradient state touched
+            loss = sink.run(self, x, Wout, lab, msk, shapes, V)
+        elif fused:
             # loss, dh and the head's weight gradient in one sweep: the logits only ever exist 16 384 rows at a time (in the workspace)
             wname = "word_embedding.weight" if self.share_input_output_embedding else "lm_head.weight"
             gW = self.arena.view(self.arena.grad, wname, full=True).view(self.vocab_pad, d)

@@ -687,6 +687,83 @@ def lmhead_ce(h2d, W, labels, mask, lse, sums, V, dh=None, dW_acc=None, beta_dw=
     _timed("lmhead_ce", flops, run)   # (GEMM-dominated: reported as its own MFMA-bound family by bench.py)
 
 
+def score_rows_supported(V: int, ld: int, dtype) -> bool:
+    return bool(lib.load().db1_score_rows_supported(int(V), int(ld), dt_code(dtype)))
+
+
+def _score_window(who, V, vocab_lo, vocab_hi):
+    vocab_hi = V if vocab_hi is None else int(vocab_hi)
+    vocab_lo = int(vocab_lo)
+    if not 0 <= vocab_lo < vocab_hi <= V:
+        raise ValueError(f"{who}: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
+    return vocab_lo, vocab_hi
+
+
+def _score_outputs(who, T, dev, labels, lse, logprob, top1, rank, status):
+    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous() or labels.device != dev:
+        raise ValueError(f"{who}: labels must be a contiguous int64 tensor of {T} elements on {dev}")
+    for name, x, dt in (("lse", lse, torch.float32), ("logprob", logprob, torch.float32), ("top1", top1, torch.int32), ("rank", rank, torch.int32),
+                        ("status", status, torch.int32)):
+        if x.dtype != dt or x.numel() != T or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {T} elements on {dev}")
+
+
+def score_rows(logits2d, labels, lse, logprob, top1, rank, status, *, V=None, vocab_lo=0, vocab_hi=None):
+    """log-probability, arg-max and rank of ``labels`` (int64 [T]) under every row of ``logits2d`` [T, ld] (fp32 / bf16, the first V columns
+    valid) over the columns [vocab_lo, vocab_hi) (db1_score_rows, rule in include/db1_hip.h): lse / logprob (float32 [T]) and top1 / rank /
+    status (int32 [T]) are written, the logits are only read.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError("score_rows: logits must be a 2-D tensor with unit column stride")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"score_rows: logits dtype {logits2d.dtype} (float32 / bfloat16)")
+    T, ld = logits2d.shape[0], logits2d.stride(0)
+    V = logits2d.shape[1] if V is None else int(V)
+    if T < 1 or not 0 < V <= logits2d.shape[1] or not score_rows_supported(V, ld, logits2d.dtype) or logits2d.data_ptr() % 16:
+        raise ValueError(f"score_rows: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {ld} (16-byte aligned rows of at "
+                         "most 34 816 elements)")
+    vocab_lo, vocab_hi = _score_window("score_rows", V, vocab_lo, vocab_hi)
+    _score_outputs("score_rows", T, logits2d.device, labels, lse, logprob, top1, rank, status)
+    _timed("score_rows", float(T * V * logits2d.element_size()),
+           lambda: lib.call("db1_score_rows", P(logits2d), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, ld, dt_code(logits2d),
+                            vocab_lo, vocab_hi, stream()))
+
+
+def lmhead_score(h2d, W, labels, lse, logprob, top1, rank, status, *, V, vocab_lo=0, vocab_hi=None, chunk_rows=0):
+    """``score_rows`` on the logits ``h2d`` [T, d] x ``W`` [rows >= V, d]^T, ``chunk_rows`` rows of logits at a time (0: 16 384) in the workspace
+    (db1_lmhead_score): the logits tensor never exists.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    if h2d.dim() != 2 or W.dim() != 2 or not h2d.is_contiguous() or not W.is_contiguous() or W.shape[1] != h2d.shape[1]:
+        raise ValueError("lmhead_score: h [T, d] and W [rows, d] must be contiguous 2-D tensors of one width")
+    if h2d.dtype not in (torch.float32, torch.bfloat16) or W.dtype != h2d.dtype or W.device != h2d.device:
+        raise ValueError(f"lmhead_score: h and W must share one dtype (float32 / bfloat16) and device, got {h2d.dtype} / {W.dtype}")
+    (T, d), rows, V, chunk_rows = h2d.shape, W.shape[0], int(V), int(chunk_rows)
+    if T < 1 or not 0 < V <= rows or not score_rows_supported(V, rows, h2d.dtype):
+        raise ValueError(f"lmhead_score: V={V} unsupported for a head of {rows} rows (at most 34 816, a multiple of 16 bytes)")
+    if chunk_rows < 0:
+        raise ValueError(f"lmhead_score: chunk_rows {chunk_rows} must be >= 0")
+    vocab_lo, vocab_hi = _score_window("lmhead_score", V, vocab_lo, vocab_hi)
+    _score_outputs("lmhead_score", T, h2d.device, labels, lse, logprob, top1, rank, status)
+    ws, wsn = _ws("db1_lmhead_score_workspace_bytes", (T, rows, d, chunk_rows, dt_code(h2d)), h2d.device)
+    _timed("lmhead_score", 2.0 * T * V * d,
+           lambda: lib.call("db1_lmhead_score", P(h2d), P(W), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, rows, d, vocab_lo,
+                            vocab_hi, chunk_rows, dt_code(h2d), ws, wsn, stream()))
+
+
+def score_segments(logprob, rank, labels, mask, out, *, V):
+    """per-sequence sums of ``score_rows`` results (db1_score_segments): ``out`` float32 [n_seg, 3] = {sum(mask * logprob), sum(mask),
+    sum(mask * (rank == 0))} over segments of ``numel / n_seg`` consecutive rows; rows whose label lies outside [0, V) count as mask 0.
+    Capturable; raises ValueError on bad arguments before anything is launched."""
+    dev = logprob.device
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < 1 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"score_segments: out must be a contiguous float32 [n_seg, 3] tensor on {dev}")
+    n_seg, n = out.shape[0], logprob.numel()
+    if n < 1 or n % n_seg or int(V) < 1:
+        raise ValueError(f"score_segments: {n} rows do not split into {n_seg} segments (V={V})")
+    for name, x, dt in (("logprob", logprob, torch.float32), ("rank", rank, torch.int32), ("labels", labels, torch.int64), ("mask", mask, torch.float32)):
+        if x.dtype != dt or x.numel() != n or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"score_segments: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+    lib.call("db1_score_segments", P(logprob), P(rank), P(labels), P(mask), P(out), n_seg, n // n_seg, int(V), stream())
+
+
 def relattn_add_head_bias(qkv, u, vb, qu, qv, B, Lq, Lk, H, D):
     lib.call("db1_relattn_add_head_bias", P(qkv), P(u), P(vb), P(qu), P(qv), B, Lq, Lk, H, D, dt_code(qkv), dt_code(u), stream())
 

@@ -1,0 +1,283 @@
+"""Scoring text that somebody else wrote: token log-probabilities, per-task validation and candidate ranking.
+
+The reference's validation (``evaluate_and_print_results``, train.py:86-138) prints one mean loss and a ``sub_loss`` dictionary per task that it
+never fills; its caption / VQA evaluation can only generate.  Here
+
+  * ``score`` runs an eval-mode forward whose head ends in ``db1_lmhead_score`` (the chunked sweep of the tied head with ``db1_score_rows`` on
+    every chunk: the ``[tokens, padded vocabulary]`` logits tensor never exists) and ``db1_score_segments`` (the per-sequence sums);
+  * ``validation_report`` turns that into loss / perplexity / top-1 accuracy per task kind: the ``sub_loss`` breakdown;
+  * ``rank_candidates`` (``rank_captions``, ``rank_answers``) orders a closed set of continuations by likelihood: the prompt runs once per group
+    through the list-form memory path, as in ``beam_search``; its last logits score token 0 of every candidate, its memory is expanded K-fold and
+    ONE more call feeds tokens ``0 .. Lc-2`` and scores tokens ``1 .. Lc-1``.
+
+The rule (candidates, lse, logprob, top1, rank, ignored rows) is stated in include/db1_hip.h (db1_score_rows) and restated in NumPy in
+tests/score_rule.py.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+_KINDS = {"NLPTaskInput": "nlp", "ICTaskInput": "ic", "VQATaskInput": "vqa", "RLTaskInput": "rl"}
+IGNORE = -100     # a label outside the vocabulary: the row is ignored (torch's ignore_index)
+
+
+@dataclass(frozen=True)
+class ScoreConfig:
+    """Labels are scored over the columns ``[vocab_lo, vocab_hi)`` (``vocab_hi`` None: the model's whole vocabulary, so that the loss is the
+    training loss; ``rank_captions`` / ``rank_answers`` then take the text vocabulary).  ``length_penalty``: candidate scores are divided by
+    length^length_penalty.  ``chunk_rows``: rows of logits alive at a time in the sweep (None: the library's 16 384).  ``return_tokens``
+    False: only the per-sequence sums are copied to the host."""
+    vocab_lo: int = 0
+    vocab_hi: Optional[int] = None
+    length_penalty: float = 0.0
+    chunk_rows: Optional[int] = None
+    return_tokens: bool = True
+
+    def __post_init__(self):
+        if int(self.vocab_lo) < 0 or (self.vocab_hi is not None and int(self.vocab_hi) <= int(self.vocab_lo)):
+            raise ValueError(f"vocabulary window [{self.vocab_lo}, {self.vocab_hi}) is empty")
+        lp = float(self.length_penalty)
+        if not abs(lp) < float("inf"):     # (NaN fails the comparison too)
+            raise ValueError(f"length_penalty {self.length_penalty} must be finite")
+        if self.chunk_rows is not None and int(self.chunk_rows) < 1:
+            raise ValueError(f"chunk_rows {self.chunk_rows} must be >= 1")
+
+
+@dataclass
+class ScoreResult:
+    """Host-side results of ``score``.  Per task input i (``return_tokens``): ``logprob[i]`` float32, ``top1[i]`` / ``rank[i]`` int32, each
+    ``[B_i, L_i]``.  Per sequence, in the order of the task inputs: ``sum_logprob`` (the mask-weighted sum of the log-probabilities),
+    ``tokens`` (the sum of the mask), ``hits`` (the mask-weighted number of positions whose label is the arg-max or tied with it), all
+    float32, and ``task`` (int64: the index of the sequence's task input)."""
+    sum_logprob: np.ndarray
+    tokens: np.ndarray
+    hits: np.ndarray
+    task: np.ndarray
+    kinds: List[str]
+    logprob: Optional[List[np.ndarray]] = None
+    top1: Optional[List[np.ndarray]] = None
+    rank: Optional[List[np.ndarray]] = None
+    status: int = 0        # OR of the status bits of the rows with mask != 0 (1: the label is no candidate, 2: the row has no candidate)
+    stats: Dict[str, int] = field(default_factory=dict)
+
+    @property
+    def loss(self) -> float:
+        """-sum(sum_logprob) / sum(tokens): what ``model.forward`` returns as ``loss`` on the same input"""
+        return float(-np.sum(self.sum_logprob, dtype=np.float64) / np.sum(self.tokens, dtype=np.float64))
+
+
+class _ScoreSink:
+    """what ``TransformerXL._finish_forward`` hands the final hidden states to while ``score`` runs"""
+
+    def __init__(self, cfg: ScoreConfig):
+        self.cfg = cfg
+        self.sweeps = 0
+        self.out = None
+
+    def run(self, model, x, Wout, lab, msk, shapes, V):
+        cfg = self.cfg
+        T, dev = x.shape[0], x.device
+        lse, logprob, top1, rank, status = _score_buffers(T, dev)
+        ops.lmhead_score(x, Wout, lab, lse, logprob, top1, rank, status, V=V, vocab_lo=cfg.vocab_lo, vocab_hi=cfg.vocab_hi,
+                         chunk_rows=0 if cfg.chunk_rows is None else int(cfg.chunk_rows))
+        n_seq = sum(b for b, _ in shapes)
+        seg = torch.empty(n_seq, 3, dtype=torch.float32, device=dev)
+        ops.score_segments(logprob, rank, lab, msk, seg, V=V)
+        self.sweeps += 1
+        self.out = (logprob, top1, rank, status, seg, msk, lab, list(shapes))
+        tot = seg.sum(0)        # (n_seq values: the same order on every run)
+        return -tot[0] / tot[1]
+
+
+def _check_window(model, cfg: ScoreConfig) -> ScoreConfig:
+    V = int(model.total_vocab_size)
+    if cfg.vocab_hi is not None and int(cfg.vocab_hi) > V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) exceeds the model's vocabulary ({V})")
+    if int(cfg.vocab_lo) >= V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) is empty in a vocabulary of {V}")
+    if not ops.score_rows_supported(V, int(model.vocab_pad), model.compute_dtype):
+        raise ValueError(f"db1_score_rows does not support a padded vocabulary of {model.vocab_pad}")
+    return cfg
+
+
+@torch.no_grad()
+def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResult:
+    """Score the labels of ``tasks_input`` (what ``model.forward`` takes: ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` /
+    ``RLTaskInput`` with ``label`` and ``loss_mask``) under the model: ONE eval-mode forward without gradients whose head is the
+    ``db1_lmhead_score`` sweep.  The model's mode is restored; no gradient or optimizer state is touched."""
+    cfg = _check_window(model, config or ScoreConfig())
+    tasks_input = list(tasks_input)
+    if not tasks_input:
+        raise ValueError("score: no task input")
+    for t in tasks_input:
+        if type(t).__name__ not in _KINDS:
+            raise TypeError(f"score: NLPTaskInput, ICTaskInput, VQATaskInput or RLTaskInput expected, got {type(t).__name__}")
+        if t.label is None or t.loss_mask is None:
+            raise ValueError("score: every task input needs label and loss_mask")
+    sink = _ScoreSink(cfg)
+    was_training = model.training
+    model.eval()
+    model._score_sink = sink
+    try:
+        model(tasks_input, compute_loss=True)
+    finally:
+        model._score_sink = None
+        model.train(was_training)
+    if sink.sweeps != 1:
+        raise RuntimeError("score: the forward did not end in the scoring sweep")
+    logprob, top1, rank, status, seg, msk, _, shapes = sink.out
+    seg = seg.cpu().numpy()
+    kinds = [_KINDS[type(t).__name__] for t in tasks_input]
+    res = ScoreResult(sum_logprob=seg[:, 0].copy(), tokens=seg[:, 1].copy(), hits=seg[:, 2].copy(),
+                      task=np.repeat(np.arange(len(shapes), dtype=np.int64), [b for b, _ in shapes]), kinds=kinds,
+                      stats=dict(sweeps=sink.sweeps))
+    st = status.cpu().numpy()[msk.cpu().numpy() != 0]            # only rows that count: a masked-out label outside the window says nothing
+    res.status = int(np.bitwise_or.reduce(st)) if st.size else 0
+    if cfg.return_tokens:
+        lp, t1, rk = logprob.cpu().numpy(), top1.cpu().numpy(), rank.cpu().numpy()
+        res.logprob, res.top1, res.rank, r0 = [], [], [], 0
+        for b, l in shapes:
+            res.logprob.append(lp[r0:r0 + b * l].reshape(b, l))
+            res.top1.append(t1[r0:r0 + b * l].reshape(b, l))
+            res.rank.append(rk[r0:r0 + b * l].reshape(b, l))
+            r0 += b * l
+    return res
+
+
+def _summary(sum_logprob, tokens, hits) -> dict:
+    s, n, h = (float(np.sum(x, dtype=np.float64)) for x in (sum_logprob, tokens, hits))
+    loss = -s / n if n > 0 else float("nan")
+    return dict(loss=loss, ppl=math.exp(loss) if loss < 700 else float("inf"), top1_acc=h / n if n > 0 else float("nan"), tokens=n,
+                sequences=int(np.size(tokens)))
+
+
+def validation_report(model, tasks_input, config: Optional[ScoreConfig] = None) -> dict:
+    """``score`` summarised per task kind and overall: {"overall": {...}, "nlp": {...}, "ic": {...}, ...} with ``loss`` (the mask-weighted mean
+    negative log-probability), ``ppl`` = exp(loss), ``top1_acc`` (for RL batches: the action-token accuracy), ``tokens`` and ``sequences``.
+    The task losses, weighted by their tokens, recombine to the overall loss, which is the loss ``model.forward`` returns."""
+    cfg = config or ScoreConfig()
+    r = score(model, tasks_input, cfg if not cfg.return_tokens else dataclasses.replace(cfg, return_tokens=False))
+    out = {"overall": _summary(r.sum_logprob, r.tokens, r.hits)}
+    for kind in dict.fromkeys(r.kinds):
+        sel = np.isin(r.task, [i for i, k in enumerate(r.kinds) if k == kind])
+        out[kind] = _summary(r.sum_logprob[sel], r.tokens[sel], r.hits[sel])
+    return out
+
+
+def _padded_rows(model, logits3d: torch.Tensor) -> torch.Tensor:
+    """the [B * L, vocab_pad] buffer behind the ``[B, L, V]`` logits view a forward returned (rows of a 16-byte multiple, as db1_score_rows wants)"""
+    B, L, _ = logits3d.shape
+    vp = int(model.vocab_pad)
+    if logits3d.stride() != (L * vp, vp, 1):
+        raise RuntimeError("unexpected logits layout")
+    return torch.as_strided(logits3d, (B * L, vp), (vp, 1), logits3d.storage_offset())
+
+
+def _score_buffers(T, dev):
+    f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+    return torch.empty(T, **f32), torch.empty(T, **f32), torch.empty(T, **i32), torch.empty(T, **i32), torch.empty(T, **i32)
+
+
+@torch.no_grad()
+def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[ScoreConfig] = None,
+                    stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Rank K candidate continuations of every prompt by likelihood.  ``prompt``: ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch
+    of G rows of one shape, as for ``generate``; ``candidates``: ints ``[G, K, Lc]``, or ``[K, Lc]`` shared by all prompts; ``cand_len``: an int
+    or an array broadcastable to ``[G, K]`` with values in ``[1, Lc]`` (default ``Lc``) -> (scores float32 [G, K], order int64 [G, K], logprob
+    float32 [G, K, Lc]) on the host.  ``logprob[g, k, i]`` is the log-probability of token i of candidate k after the prompt g and the
+    candidate's tokens before i, over the window of ``config`` (0 at the positions at or after ``cand_len``, which cannot influence the earlier
+    ones: the attention is causal); ``scores[g, k] = sum_{i < len} logprob[g, k, i] / len^length_penalty``; ``order[g]`` sorts ``scores[g]``
+    descending, the lower k first on ties.  Tokens older than ``mem_len`` fall out of the memory, as in generation.  ``stats`` (a dict) receives
+    ``model_calls`` (1 when Lc == 1, else 2)."""
+    from .data import NLPTaskInput
+    from .generation import _batch_size
+    cfg = _check_window(model, config or ScoreConfig())
+    if not int(model.mem_len or 0) > 0:
+        raise ValueError("rank_candidates needs a model with memory (mem_len > 0)")
+    G = _batch_size(prompt)
+    V, dev = int(model.total_vocab_size), model.dev
+    cand = torch.as_tensor(np.asarray(candidates.cpu() if torch.is_tensor(candidates) else candidates))
+    if cand.dtype not in (torch.int64, torch.int32) or cand.dim() not in (2, 3):
+        raise ValueError("rank_candidates: candidates must be an integer [G, K, Lc] or [K, Lc] array")
+    cand = cand.long()
+    if cand.dim() == 2:
+        cand = cand.unsqueeze(0).expand(G, -1, -1)
+    if cand.shape[0] != G or cand.shape[1] < 1 or cand.shape[2] < 1:
+        raise ValueError(f"rank_candidates: candidates of shape {tuple(cand.shape)} for {G} prompts")
+    K, Lc = int(cand.shape[1]), int(cand.shape[2])
+    if bool(((cand < 0) | (cand >= V)).any()):
+        raise ValueError(f"rank_candidates: candidate tokens must lie in [0, {V})")
+    clen = np.full((G, K), Lc, np.int64) if cand_len is None else np.broadcast_to(np.asarray(cand_len, dtype=np.int64), (G, K)).copy()
+    if clen.min() < 1 or clen.max() > Lc:
+        raise ValueError(f"rank_candidates: cand_len must lie in [1, {Lc}]")
+    M = G * K
+    cand = cand.reshape(M, Lc).contiguous().to(dev)
+    valid = (torch.arange(Lc).unsqueeze(0) < torch.from_numpy(clen.reshape(M, 1))).to(dev)       # [M, Lc]
+    labels = torch.where(valid, cand, torch.full_like(cand, IGNORE))                              # masked-out positions: ignored rows
+    logprob, rank = torch.empty(M, Lc, dtype=torch.float32, device=dev), torch.empty(M, Lc, dtype=torch.int32, device=dev)
+    win = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=cfg.vocab_hi)
+    was_training = model.training
+    model.eval()
+    try:
+        # call 1: the prompt once per group; the logits of its last position, repeated K-fold, score token 0 of every candidate
+        model._dec_state = None
+        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(G))
+        L = logits.shape[1]
+        last = _padded_rows(model, logits)[L - 1::L].repeat_interleave(K, 0)          # [M, vocab_pad]
+        lse, lp, t1, rk, st = _score_buffers(M, dev)
+        ops.score_rows(last, labels[:, 0].contiguous(), lse, lp, t1, rk, st, **win)
+        logprob[:, 0], rank[:, 0] = lp, rk
+        calls = 1
+        del logits, last
+        if Lc > 1:
+            # call 2: the memory expanded K-fold, tokens 0 .. Lc-2 of every candidate in, tokens 1 .. Lc-1 scored
+            mems = [m.repeat_interleave(K, 0) for m in mems]
+            x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=cand[:, :Lc - 1].contiguous(), text_len=None)
+            logits, _, _ = model([x], compute_loss=False, mems=mems)
+            T = M * (Lc - 1)
+            lse, lp, t1, rk, st = _score_buffers(T, dev)
+            ops.score_rows(_padded_rows(model, logits), labels[:, 1:].reshape(-1).contiguous(), lse, lp, t1, rk, st, **win)
+            logprob[:, 1:], rank[:, 1:] = lp.view(M, Lc - 1), rk.view(M, Lc - 1)
+            calls = 2
+            del logits, mems
+        model._dec_state = None
+        chk = getattr(model, "check_decode_chain", None)
+        if chk is not None:
+            chk(True)
+        seg = torch.empty(M, 3, dtype=torch.float32, device=dev)
+        ops.score_segments(logprob.view(-1), rank.view(-1), labels.view(-1), valid.to(torch.float32).view(-1), seg, V=V)
+    finally:
+        model.train(was_training)
+    if stats is not None:
+        stats.update(model_calls=calls)
+    sums = seg[:, 0].cpu().numpy().reshape(G, K)
+    scores = (sums / np.power(clen.astype(np.float32), np.float32(cfg.length_penalty))).astype(np.float32)
+    order = np.argsort(-scores, axis=1, kind="stable")          # descending, the lower k first on ties
+    return torch.from_numpy(scores), torch.from_numpy(order.astype(np.int64)), logprob.view(G, K, Lc).cpu()
+
+
+def _text_window(model, cfg: Optional[ScoreConfig]) -> ScoreConfig:
+    cfg = cfg or ScoreConfig()
+    return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
+
+
+def rank_captions(model, ic_batch, candidates, cand_len=None, config: Optional[ScoreConfig] = None, stats: Optional[dict] = None):
+    """``rank_candidates`` after the prompt ``generate_captions`` builds (``[prompt, image patches]``, an empty caption), over the text
+    vocabulary unless ``config`` says otherwise"""
+    from .generation import caption_prompt
+    return rank_candidates(model, caption_prompt(ic_batch), candidates, cand_len, _text_window(model, config), stats)
+
+
+def rank_answers(model, vqa_batch, candidates, cand_len=None, config: Optional[ScoreConfig] = None, stats: Optional[dict] = None):
+    """``rank_candidates`` after the prompt ``answer_questions`` builds (``[prompt, image patches, question]``), over the text vocabulary
+    unless ``config`` says otherwise"""
+    from .generation import question_prompt
+    return rank_candidates(model, question_prompt(vqa_batch), candidates, cand_len, _text_window(model, config), stats)

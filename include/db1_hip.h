@@ -587,6 +587,37 @@ int64_t db1_ring_reorder_workspace_bytes(int n_layers, int M, int max_t, int64_t
 int db1_ring_reorder(const void* const* rings, int n_layers, int M, int W, int cap, int64_t slot_bytes, const int32_t* state, int mlen,
                      const int32_t* t, int max_t, const int32_t* parent, const int32_t* done, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
+ * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window
+ * [vocab_lo, vocab_hi) with 0 <= vocab_lo < vocab_hi <= V:
+ *   - candidates: the FINITE logits of the columns in the window (NaN and +-inf are never candidates: the rule of db1_select_tokens and
+ *     db1_beam_step);
+ *   - lse = fp32 log-sum-exp over the candidates, their maximum subtracted first (window [0, V), finite logits: the lse of db1_masked_ce_fwd);
+ *     -inf when there is no candidate;
+ *   - logprob = l[y] - lse when y is a candidate; y in [0, V) but not a candidate (outside the window or not finite): logprob = -inf,
+ *     rank = -1 and status bit 0; y outside [0, V) (torch's ignore_index, as db1_masked_ce_fwd treats it): the row is IGNORED,
+ *     logprob = 0, rank = -1, no status bit, and it counts as masked out in db1_score_segments;
+ *   - top1 = the candidate with the largest logit, the lowest column on ties; -1 (and status bit 1) when there is no candidate;
+ *   - rank = the number of candidates whose logit is strictly greater than l[y] (0: the label is the arg-max or tied with it).
+ * db1_score_rows: logits [T, ld] -> lse, logprob (float [T]), top1, rank, status (int32 [T]; every entry WRITTEN, status included).  One
+ * workgroup per row, the row stays in registers between the maximum and the sum / count pass (one read of the logits, nothing written to
+ * them); fixed-order reductions: the same inputs give the same bits.  Rows of at most 34 816 elements, ld a multiple of 16 bytes, logits
+ * 16-byte aligned (_supported).  No workspace, no device scalars written by the host: capturable.
+ * db1_lmhead_score: the rows of h [T, d] times the tied head W [n_w_rows, d] (n_w_rows >= V: the padded vocabulary), chunk_rows rows of logits at
+ * a time in the workspace (0: 16 384) with db1_score_rows on every chunk: the [T, n_w_rows] logits tensor never exists.
+ * db1_score_segments: n_seg segments of seg_len consecutive rows -> out [n_seg, 3] (float) = {sum(mask * logprob), sum(mask),
+ * sum(mask * (rank == 0))} over the rows with mask != 0 whose label lies in [0, V) (ignored rows count as mask 0), added in a fixed order.  A
+ * counted row with logprob = -inf makes its segment's first sum -inf; nothing becomes NaN. */
+int db1_score_rows_supported(int V, int64_t ld, int dt);
+int db1_score_rows(const void* logits, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank, int32_t* status,
+                   int64_t T, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, void* stream);
+int64_t db1_lmhead_score_workspace_bytes(int64_t T, int n_w_rows, int d, int chunk_rows, int dt);
+int db1_lmhead_score(const void* h, const void* W, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank,
+                     int32_t* status, int64_t T, int V, int n_w_rows, int d, int vocab_lo, int vocab_hi, int chunk_rows, int dt, void* ws,
+                     int64_t ws_bytes, void* stream);
+int db1_score_segments(const float* logprob, const int32_t* rank, const int64_t* labels, const float* mask, float* out, int64_t n_seg,
+                       int64_t seg_len, int V, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
