@@ -2,26 +2,26 @@
 
 The reference trains these three workloads and evaluates IC / VQA by generating text (train.py:24-25,44,146-170: evaluate_ic /
 evaluate_vqa with a ``Decoder(max_length=30)`` that keeps the tokens before the first EOS, text_decoder.py:42-62); those evaluation modules
-are not part of its release.  Here a generation is
+are not part of its release.  Here sampling (``generate``) and beam search (``beam_search``) are ONE driver, ``_decode``, over two kinds of
+device state (``_State``, ``_BeamState``), and a generation is
 
-  * one prefill call: the prompt (``[prompt, image patches, text]``, longer than the 64 new tokens a ring call takes) runs once through the
-    list-form memory path (``model.init_mem``);
+  * one prefill call (``_prefill``): the prompt (``[prompt, image patches, text]``, longer than the 64 new tokens a ring call takes) runs once
+    per prompt through the list-form memory path (``model.init_mem``); its last position picks token 0;
   * then one call per token.  bf16 models with the K/V-cached decode path (``model.use_decode``): the list-form memory is projected into a
-    ``RingMemory`` and every token is ONE hipGraph replay holding the one-token forward, ``db1_select_tokens`` (which writes the next token
-    straight into the step's static input ids) and the captured ``t += 1`` of the token counter -- no host round trip between tokens; the
-    host reads the ``finished`` flags every ``sync_every`` tokens to stop early.  Other models (fp32, no ring) run the same loop eagerly
-    over the list-form memory, with the same selection kernel.
+    ``RingMemory`` and every token is ONE hipGraph replay (``_RingGenerator``) holding the one-token forward and the state's epilogue: the
+    selection, which writes the next token straight into the step's static input ids, and the captured ``t += 1`` of the token counter -- no
+    host round trip between tokens; the host asks the state every ``sync_every`` tokens whether all rows have finished, to stop early.
+    Other models (fp32, no ring) run the same loop eagerly over the list-form memory, with the same epilogue.
 
-The selection rule (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox) is stated in include/db1_hip.h (db1_select_tokens)
-and restated in NumPy in tests/select_rule.py.
-
-Beam search (``beam_search``, or a ``BeamSearchConfig`` passed to ``generate_captions`` / ``answer_questions``) runs the same way: the
-prompt once per group, its memory and last logits expanded to the W beams of the group, then one call per token whose epilogue is
-``db1_beam_step`` (lse, per-row top-2W, the group walk, the hypothesis pool, the next ids) and ``db1_ring_reorder`` (the last t keys of
-every beam whose parent is another row).  The rule is stated in include/db1_hip.h and restated in NumPy in tests/beam_rule.py.
+Sampling's epilogue is ``db1_select_tokens`` (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox); beam search's is
+``db1_beam_step`` (lse, per-row top-2W, the group walk, the hypothesis pool, the next ids) and ``db1_ring_reorder`` (the last t keys of every
+beam whose parent is another row), after a prefill whose memory and last logits are expanded to the W beams of each prompt.  Both rules are
+stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py and tests/beam_rule.py.  scoring.py takes its prefill, its
+eval-mode switch and its vocabulary checks from here.
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -106,58 +106,39 @@ def clip_at_eos(ids, lengths) -> List[List[int]]:
     return [[int(v) for v in row[:int(n)]] for row, n in zip(ids, np.asarray(lengths))]
 
 
-class _State:
-    """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
-
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
-        dev = model.dev
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.M, self.cfg, self.V, self.hi = M, cfg, V, hi
-        self.t = torch.zeros(1, **i32)
-        self.finished = torch.zeros(M, **i32)
-        self.lengths = torch.zeros(M, **i32)
-        self.status = torch.zeros(M, **i32)
-        self.stream_id = torch.arange(M, **i32)
-        self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
-
-    def start(self, stream_ids):
-        self.t.zero_()
-        self.finished.zero_()
-        self.lengths.zero_()
-        self.status.zero_()
-        self.out.fill_(self.cfg.pad_id)
-        if stream_ids is None:
-            self.stream_id.copy_(torch.arange(self.M, dtype=torch.int32))
-        else:
-            s = torch.as_tensor(np.asarray(stream_ids, dtype=np.int64))
-            if s.shape != (self.M,):
-                raise ValueError(f"stream_ids: {self.M} values expected, got shape {tuple(s.shape)}")
-            self.stream_id.copy_(s.to(torch.int32))
-
-    def select(self, logits3d, next_ids):
-        """the token of every row from the last position of ``logits3d`` [M, L, V] into ``next_ids`` (int64 [M]), then t += 1"""
-        c = self.cfg
-        ops.select_tokens(logits3d[:, -1], self.t, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V, vocab_lo=c.vocab_lo,
-                          vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
-                          eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id)
-        self.t.add_(1)
-
-    def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        out, lengths, status = self.out.cpu(), self.lengths.cpu(), self.status.cpu()
-        if (status & 2).any():
-            raise RuntimeError("db1_select_tokens: the token counter left [0, max_new_tokens)")
-        return out, lengths
+# ------------------------------------------------------------------------------------ what generation and scoring share around a model call
+@contextlib.contextmanager
+def _eval_mode(model):
+    """the model in eval mode; its mode is restored on the way out"""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
 
 
-class _RingGenerator:
-    """a RingMemory, the selection state and the captured per-token graph for one (model, batch size, config); reused across calls"""
+def _need_memory(model, who: str) -> int:
+    mlen = int(model.mem_len or 0)
+    if not mlen > 0:
+        raise ValueError(f"{who} needs a model with memory (mem_len > 0)")
+    return mlen
 
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
-        from .decode import GraphedRingStep, RingMemory
-        self.key = (M, cfg, V, hi)
-        self.state = _State(model, M, cfg, V, hi)
-        self.ring = RingMemory(model, M)
-        self.step = GraphedRingStep(model, M, 1, memory=self.ring, epilogue=lambda step, logits: self.state.select(logits, step.ids[:, 0]))
+
+def _vocab_window(model, cfg) -> Tuple[int, int]:
+    """(V, hi): the model's vocabulary and the end of the window ``[cfg.vocab_lo, cfg.vocab_hi)`` inside it (``vocab_hi`` None: V)"""
+    V = int(model.total_vocab_size)
+    hi = V if cfg.vocab_hi is None else int(cfg.vocab_hi)
+    if hi > V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {hi}) exceeds the model's vocabulary ({V})")
+    if int(cfg.vocab_lo) >= V:
+        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) is empty in a vocabulary of {V}")
+    return V, hi
+
+
+def _text_window(model, cfg):
+    """``cfg`` (a GenerationConfig, BeamSearchConfig or ScoreConfig) with the text vocabulary as its window's end unless it names one"""
+    return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
 
 
 def _batch_size(prompt) -> int:
@@ -180,139 +161,101 @@ def _batch_size(prompt) -> int:
     return int(arr.shape[0])
 
 
+def _token_input(ids):
+    """the model input that feeds the token ids ``ids`` [rows, n] after what the memory holds"""
+    from .data import NLPTaskInput
+    return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+
+
+def _prefill(model, prompt, G: int, expand: Optional[int] = None):
+    """the prompt (G rows) once through the list-form memory path -> (logits [G, L, V], the new memory); ``expand`` given: every row of the
+    memory repeated ``expand``-fold (rows g * expand .. of the result descend from prompt g)"""
+    model._dec_state = None
+    logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(G))
+    if expand is not None:
+        mems = [m.repeat_interleave(expand, 0) for m in mems]
+    return logits, mems
+
+
+def _check_chain(model):
+    """raise what the hand-off chain of the eager decode launches recorded, if anything"""
+    chk = getattr(model, "check_decode_chain", None)
+    if chk is not None:
+        chk(True)
+
+
 def _ring_ok(model) -> bool:
     return (model.compute_dtype == torch.bfloat16 and bool(model.use_decode) and int(model.mem_len or 0) > 0 and model.d_head == 128)
 
 
-@torch.no_grad()
-def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
-             stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
-    of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
-    after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
-    on its logits, its stream id, the seed and the token index, not on the other rows.  ``graphed`` None: the hipGraph ring path where the
-    model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
-    receives the path taken and the number of per-token calls."""
-    cfg = config or GenerationConfig()
-    if not int(model.mem_len or 0) > 0:
-        raise ValueError("generate needs a model with memory (mem_len > 0)")
-    M = _batch_size(prompt)
-    V = int(model.total_vocab_size)
-    hi = V if cfg.vocab_hi is None else int(cfg.vocab_hi)
-    if hi > V:
-        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {hi}) exceeds the model's vocabulary ({V})")
-    if not ops.select_tokens_supported(V, V, model.compute_dtype):
-        raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
-    ring = _ring_ok(model) if graphed is None else bool(graphed)
-    if ring and not _ring_ok(model):
-        raise ValueError("the graphed ring path needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
-    was_training = model.training
-    model.eval()
-    try:
-        if ring:
-            gen = getattr(model, "_generator", None)
-            if gen is None or gen.key != (M, cfg, V, hi) or gen.step._version != model._wversion:
-                model._generator = None        # (free the old ring before the new one is allocated)
-                gen = model._generator = _RingGenerator(model, M, cfg, V, hi)
-            st = gen.state
-            ids = gen.step.ids
+# ------------------------------------------------------------------------------------------------------------------- the two device states
+# What ``_decode`` asks of a state: ``M`` rows, ``expand`` (None, or the rows per prompt), ``cache`` (the model attribute its ring generator
+# is kept under), ``start(...)``, ``epilogue(logits_last, next_ids, ring=None)`` -- select, reorder ``ring`` if beams, then t += 1 --,
+# ``reorder_list(mems)``, ``all_done()`` (a host read), ``result()`` and ``stats()``.
+class _State:
+    """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
+    cache, expand = "_generator", None
+
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
+        dev = model.dev
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.M, self.cfg, self.V, self.hi = M, cfg, V, hi
+        self.t = torch.zeros(1, **i32)
+        self.finished = torch.zeros(M, **i32)
+        self.lengths = torch.zeros(M, **i32)
+        self.status = torch.zeros(M, **i32)
+        self.stream_id = torch.arange(M, **i32)
+        self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
+
+    def start(self, stream_ids=None):
+        for x in (self.t, self.finished, self.lengths, self.status):
+            x.zero_()
+        self.out.fill_(self.cfg.pad_id)
+        if stream_ids is None:
+            self.stream_id.copy_(torch.arange(self.M, dtype=torch.int32))
         else:
-            st = _State(model, M, cfg, V, hi)
-            ids = torch.zeros(M, 1, dtype=torch.long, device=model.dev)
-        st.start(stream_ids)
-        # prefill: the whole prompt through the list-form memory path; its last position picks token 0
-        model._dec_state = None
-        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(M))
-        st.select(logits, ids[:, 0])
-        calls = 0
-        if ring:
-            gen.ring.load(mems)
-            del mems, logits
-        for i in range(1, cfg.max_new_tokens):
-            if i % cfg.sync_every == 0 and bool(st.finished.all()):
-                break
-            if ring:
-                gen.step(ids)
-            else:
-                from .data import NLPTaskInput
-                x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
-                logits, _, mems = model([x], compute_loss=False, mems=mems)
-                st.select(logits, ids[:, 0])
-            calls += 1
-        if ring:
-            gen.step.check(synchronize=True)
-        else:
-            chk = getattr(model, "check_decode_chain", None)
-            if chk is not None:
-                chk(True)
-        if stats is not None:
-            stats.update(path="ring" if ring else "eager", token_calls=calls)
-        return st.result()
-    finally:
-        model.train(was_training)
+            s = torch.as_tensor(np.asarray(stream_ids, dtype=np.int64))
+            if s.shape != (self.M,):
+                raise ValueError(f"stream_ids: {self.M} values expected, got shape {tuple(s.shape)}")
+            self.stream_id.copy_(s.to(torch.int32))
 
+    def select(self, logits2d, next_ids):
+        """db1_select_tokens on the last-position logits [M, V] of step t; the tokens go to ``next_ids`` (int64 [M])"""
+        c = self.cfg
+        ops.select_tokens(logits2d, self.t, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V, vocab_lo=c.vocab_lo,
+                          vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
+                          eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id)
 
-def _text_window(model, cfg):
-    cfg = cfg or GenerationConfig()
-    return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
+    def epilogue(self, logits2d, next_ids, ring=None):
+        self.select(logits2d, next_ids)
+        self.t.add_(1)
 
+    def reorder_list(self, mems):
+        return mems
 
-def _run(model, x, cfg, **kw):
-    return beam_search(model, x, cfg, **kw) if isinstance(cfg, BeamSearchConfig) else generate(model, x, cfg, **kw)
+    def all_done(self) -> bool:
+        return bool(self.finished.all())
 
+    def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        out, lengths, status = self.out.cpu(), self.lengths.cpu(), self.status.cpu()
+        if (status & 2).any():
+            raise RuntimeError("db1_select_tokens: the token counter left [0, max_new_tokens)")
+        return out, lengths
 
-def generate_captions(model, ic_batch, cfg=None, **kw):
-    """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
-    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``:
-    (ids, lengths, scores) as ``beam_search``"""
-    return _run(model, caption_prompt(ic_batch), _text_window(model, cfg), **kw)
-
-
-def caption_prompt(ic_batch):
-    """the generation prompt of an ``ICTaskInput`` batch: ``[prompt, image patches]`` and an empty caption"""
-    from .data import ICTaskInput
-    M = _batch_size(ic_batch)
-    x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
-                    text_seq=torch.zeros(M, 0, dtype=torch.long))
-    for f in ("vision_row_ids", "vision_col_ids"):
-        if hasattr(ic_batch, f):
-            setattr(x, f, getattr(ic_batch, f))
-    return x
-
-
-def answer_questions(model, vqa_batch, cfg=None, **kw):
-    """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
-    ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
-    otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``"""
-    return _run(model, question_prompt(vqa_batch), _text_window(model, cfg), **kw)
-
-
-def question_prompt(vqa_batch):
-    """the generation prompt of a ``VQATaskInput`` batch: ``[prompt, image patches, question]`` without the answer"""
-    from .data import VQATaskInput
-    q = vqa_batch.text_seq
-    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
-    if getattr(vqa_batch, "ques_len", None) is not None:
-        ql = np.unique(np.asarray(torch.as_tensor(vqa_batch.ques_len).cpu()).reshape(-1))
-        if ql.size != 1:
-            raise ValueError("answer_questions: the questions of a batch must share one length (group them by length)")
-        q = q[:, :int(ql[0])]
-    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=vqa_batch.prompt_seq, img_seq=vqa_batch.img_seq,
-                     text_seq=q)
-    for f in ("vision_row_ids", "vision_col_ids"):
-        if hasattr(vqa_batch, f):
-            setattr(x, f, getattr(vqa_batch, f))
-    return x
+    def stats(self) -> dict:
+        return {}
 
 
 class _BeamState:
     """the device state of one beam search over G groups of W beams (include/db1_hip.h, db1_beam_step)"""
+    cache = "_beam_generator"
 
     def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int):
         dev = model.dev
         W, mx = int(cfg.num_beams), int(cfg.max_new_tokens)
         i32 = dict(dtype=torch.int32, device=dev)
         self.G, self.W, self.M, self.cfg, self.V, self.hi = G, W, G * W, cfg, V, hi
+        self.expand = W
         self.t = torch.zeros(1, **i32)
         self.beam_score = torch.zeros(G * W, dtype=torch.float32, device=dev)
         self.parent = torch.zeros(G * W, **i32)
@@ -343,6 +286,20 @@ class _BeamState:
                       self.pool_count, self.done, self.switches, next_ids, self.status, W=self.W, V=self.V, vocab_lo=c.vocab_lo, vocab_hi=self.hi,
                       eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, length_penalty=c.length_penalty)
 
+    def epilogue(self, logits2d, next_ids, ring=None):
+        """``ring`` None: step 0 (every beam descends from the same prefill, nothing to reorder), or the list-form memory (``reorder_list``)"""
+        self.select(logits2d, next_ids)
+        if ring is not None:
+            ring.reorder(self.parent, self.t, max_t=self.cfg.max_new_tokens, group=self.W, done=self.done)
+        self.t.add_(1)
+
+    def reorder_list(self, mems):
+        parent = self.parent.long()
+        return [m.index_select(0, parent) for m in mems]
+
+    def all_done(self) -> bool:
+        return bool(self.done.all())
+
     def result(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         if (self.status.cpu() & 2).any():
             raise RuntimeError("db1_beam_step: the token counter left [0, max_new_tokens)")
@@ -358,23 +315,146 @@ class _BeamState:
             scores[g, :k] = sc[g, :k]
         return ids, lengths, scores
 
+    def stats(self) -> dict:
+        return dict(parent_switches=int(self.switches.sum()))
 
-class _BeamRingGenerator:
-    """a RingMemory of G * W rows, the beam state and the captured per-token graph (forward, db1_beam_step, db1_ring_reorder, t += 1) for
-    one (model, group count, config, vocabulary); reused across calls"""
 
-    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int):
+# ------------------------------------------------------------------------------------------------------------------------------ the driver
+class _RingGenerator:
+    """a RingMemory of ``state.M`` rows, the state and the captured per-token graph (the one-token forward and the state's epilogue) for one
+    (model, ``key`` = what the state was built from); reused across calls"""
+
+    def __init__(self, model, state, key):
         from .decode import GraphedRingStep, RingMemory
-        self.key = (G, cfg, V, hi)
-        self.state = _BeamState(model, G, cfg, V, hi)
-        self.ring = RingMemory(model, self.state.M)
-        self.step = GraphedRingStep(model, self.state.M, 1, memory=self.ring, epilogue=self.epilogue)
+        self.key, self.state = key, state
+        self.ring = RingMemory(model, state.M)
+        self.step = GraphedRingStep(model, state.M, 1, memory=self.ring, epilogue=self.epilogue)
 
     def epilogue(self, step, logits):
-        st = self.state
-        st.select(logits[:, -1], step.ids[:, 0])
-        self.ring.reorder(st.parent, st.t, max_t=st.cfg.max_new_tokens, group=st.W, done=st.done)
-        st.t.add_(1)
+        self.state.epilogue(logits[:, -1], step.ids[:, 0], self.ring)
+
+
+def _ring_generator(model, State, key) -> _RingGenerator:
+    """the generator kept on the model under ``State.cache`` if it was built from ``key`` and the weights it captured, else a new one"""
+    gen = getattr(model, State.cache, None)
+    if gen is None or gen.key != key or gen.step._version != model._wversion:
+        setattr(model, State.cache, None)        # (free the old ring before the new one is allocated)
+        gen = _RingGenerator(model, State(model, *key), key)
+        setattr(model, State.cache, gen)
+    return gen
+
+
+def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, stats: Optional[dict], start=()):
+    """``max_new_tokens`` steps of ``State(model, *key)`` after ``prompt`` (``key[0]`` rows) -> ``state.result()``.  On the ring path
+    (``graphed``, as ``generate`` documents it): over the cached ring generator, one graph replay per token (``replay`` False: the same forward
+    and epilogue launched eagerly over the same ring); else eagerly over the list-form memory.  The callers have validated everything else:
+    nothing is launched before that."""
+    ring = _ring_ok(model) if graphed is None else bool(graphed)
+    if ring and not _ring_ok(model):
+        raise ValueError("the graphed ring path needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
+    with _eval_mode(model):
+        if ring:
+            gen = _ring_generator(model, State, key)
+            st, ids = gen.state, gen.step.ids
+        else:
+            st = State(model, *key)
+            ids = torch.zeros(st.M, 1, dtype=torch.long, device=model.dev)
+        st.start(*start)
+        # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
+        logits, mems = _prefill(model, prompt, key[0], st.expand)
+        last = logits[:, -1]
+        st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids[:, 0])
+        del logits, last
+        calls = 0
+        if ring:
+            gen.ring.load(mems)
+            del mems
+        for i in range(1, st.cfg.max_new_tokens):
+            if i % st.cfg.sync_every == 0 and st.all_done():
+                break
+            if ring and replay:
+                gen.step(ids)
+            elif ring:
+                logits, _, _ = model([gen.step.x], compute_loss=False, mems=gen.ring)
+                gen.epilogue(gen.step, logits)
+            else:
+                logits, _, mems = model([_token_input(ids)], compute_loss=False, mems=mems)
+                st.epilogue(logits[:, -1], ids[:, 0])
+                mems = st.reorder_list(mems)
+            calls += 1
+        if ring:
+            gen.step.check(synchronize=True)
+        if not (ring and replay):
+            _check_chain(model)
+        if stats is not None:
+            stats.update(path="ring" if ring else "eager", token_calls=calls, **st.stats())
+        return st.result()
+
+
+@torch.no_grad()
+def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
+             stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
+    of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
+    after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
+    on its logits, its stream id, the seed and the token index, not on the other rows.  ``graphed`` None: the hipGraph ring path where the
+    model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
+    receives the path taken and the number of per-token calls."""
+    cfg = config or GenerationConfig()
+    _need_memory(model, "generate")
+    M = _batch_size(prompt)
+    V, hi = _vocab_window(model, cfg)
+    if not ops.select_tokens_supported(V, V, model.compute_dtype):
+        raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
+    return _decode(model, prompt, _State, (M, cfg, V, hi), graphed, True, stats, start=(stream_ids,))
+
+
+def _run(model, x, cfg, **kw):
+    return beam_search(model, x, cfg, **kw) if isinstance(cfg, BeamSearchConfig) else generate(model, x, cfg, **kw)
+
+
+def generate_captions(model, ic_batch, cfg=None, **kw):
+    """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
+    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``:
+    (ids, lengths, scores) as ``beam_search``"""
+    return _run(model, caption_prompt(ic_batch), _text_window(model, cfg or GenerationConfig()), **kw)
+
+
+def caption_prompt(ic_batch):
+    """the generation prompt of an ``ICTaskInput`` batch: ``[prompt, image patches]`` and an empty caption"""
+    from .data import ICTaskInput
+    M = _batch_size(ic_batch)
+    x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
+                    text_seq=torch.zeros(M, 0, dtype=torch.long))
+    for f in ("vision_row_ids", "vision_col_ids"):
+        if hasattr(ic_batch, f):
+            setattr(x, f, getattr(ic_batch, f))
+    return x
+
+
+def answer_questions(model, vqa_batch, cfg=None, **kw):
+    """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
+    ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
+    otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``"""
+    return _run(model, question_prompt(vqa_batch), _text_window(model, cfg or GenerationConfig()), **kw)
+
+
+def question_prompt(vqa_batch):
+    """the generation prompt of a ``VQATaskInput`` batch: ``[prompt, image patches, question]`` without the answer"""
+    from .data import VQATaskInput
+    q = vqa_batch.text_seq
+    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
+    if getattr(vqa_batch, "ques_len", None) is not None:
+        ql = np.unique(np.asarray(torch.as_tensor(vqa_batch.ques_len).cpu()).reshape(-1))
+        if ql.size != 1:
+            raise ValueError("answer_questions: the questions of a batch must share one length (group them by length)")
+        q = q[:, :int(ql[0])]
+    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=vqa_batch.prompt_seq, img_seq=vqa_batch.img_seq,
+                     text_seq=q)
+    for f in ("vision_row_ids", "vision_col_ids"):
+        if hasattr(vqa_batch, f):
+            setattr(x, f, getattr(vqa_batch, f))
+    return x
 
 
 @torch.no_grad()
@@ -392,78 +472,14 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     cfg = config or BeamSearchConfig()
     if not isinstance(cfg, BeamSearchConfig):
         raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
-    mlen = int(model.mem_len or 0)
-    if not mlen > 0:
-        raise ValueError("beam_search needs a model with memory (mem_len > 0)")
+    mlen = _need_memory(model, "beam_search")
     if int(cfg.max_new_tokens) > mlen:
         raise ValueError(f"beam_search: max_new_tokens {cfg.max_new_tokens} exceeds the model's mem_len {mlen}")
     G = _batch_size(prompt)
     W = int(cfg.num_beams)
-    V = int(model.total_vocab_size)
-    hi = V if cfg.vocab_hi is None else int(cfg.vocab_hi)
-    if hi > V:
-        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {hi}) exceeds the model's vocabulary ({V})")
+    V, hi = _vocab_window(model, cfg)
     if cfg.eos_id is not None and int(cfg.eos_id) >= V:
         raise ValueError(f"eos_id {cfg.eos_id} lies outside the model's vocabulary ({V})")
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
-    ring = _ring_ok(model) if graphed is None else bool(graphed)
-    if ring and not _ring_ok(model):
-        raise ValueError("the graphed ring path needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
-    was_training = model.training
-    model.eval()
-    try:
-        if ring:
-            gen = getattr(model, "_beam_generator", None)
-            if gen is None or gen.key != (G, cfg, V, hi) or gen.step._version != model._wversion:
-                model._beam_generator = None        # (free the old ring before the new one is allocated)
-                gen = model._beam_generator = _BeamRingGenerator(model, G, cfg, V, hi)
-            st = gen.state
-            ids = gen.step.ids
-        else:
-            st = _BeamState(model, G, cfg, V, hi)
-            ids = torch.zeros(G * W, 1, dtype=torch.long, device=model.dev)
-        st.start()
-        # prefill: the prompt once per group through the list-form path; its last position and its memory expanded to the group's beams
-        model._dec_state = None
-        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(G))
-        st.select(logits[:, -1].repeat_interleave(W, 0), ids[:, 0])
-        st.t.add_(1)                              # (step 0: every beam descends from the same prefill, nothing to reorder)
-        mems = [m.repeat_interleave(W, 0) for m in mems]
-        del logits
-        calls = 0
-        if ring:
-            gen.ring.load(mems)
-            del mems
-        for i in range(1, cfg.max_new_tokens):
-            if i % cfg.sync_every == 0 and bool(st.done.all()):
-                break
-            if ring and replay:
-                gen.step(ids)
-            elif ring:
-                logits, _, _ = model([gen.step.x], compute_loss=False, mems=gen.ring)
-                gen.epilogue(gen.step, logits)
-            else:
-                from .data import NLPTaskInput
-                x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
-                logits, _, mems = model([x], compute_loss=False, mems=mems)
-                st.select(logits[:, -1], ids[:, 0])
-                parent = st.parent.long()
-                mems = [m.index_select(0, parent) for m in mems]
-                st.t.add_(1)
-            calls += 1
-        if ring:
-            gen.step.check(synchronize=True)
-            if not replay:
-                chk = getattr(model, "check_decode_chain", None)
-                if chk is not None:
-                    chk(True)
-        else:
-            chk = getattr(model, "check_decode_chain", None)
-            if chk is not None:
-                chk(True)
-        if stats is not None:
-            stats.update(path="ring" if ring else "eager", token_calls=calls, parent_switches=int(st.switches.sum()))
-        return st.result()
-    finally:
-        model.train(was_training)
+    return _decode(model, prompt, _BeamState, (G, cfg, V, hi), graphed, replay, stats)

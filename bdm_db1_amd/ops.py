@@ -533,6 +533,47 @@ def masked_ce_fwd_bwd(logits2d, labels, mask, lse, sums, norm, V, gscale=1.0):
 DB1_ERR_BAD_SHAPE, DB1_ERR_UNSUPPORTED_DTYPE, DB1_ERR_UNSUPPORTED = -1, -3, -6
 
 
+# The argument checks of the capturable wrappers below (selection, beam step, ring reorder, scoring): each raises ValueError, naming the
+# function (``who``) and the argument, before anything is launched.
+def _check_window(who, V, vocab_lo, vocab_hi):
+    vocab_hi = V if vocab_hi is None else int(vocab_hi)
+    vocab_lo = int(vocab_lo)
+    if not 0 <= vocab_lo < vocab_hi <= V:
+        raise ValueError(f"{who}: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
+    return vocab_lo, vocab_hi
+
+
+def _check_logits(who, logits2d, V, vocab_lo, vocab_hi, supported):
+    """``logits2d`` [M, ld] fp32 / bf16 with unit column stride, its first V columns valid (``V`` None: all of them), ``supported(V, ld)`` (the
+    kernel's own predicate) and the window inside [0, V) -> (M, ld, V, vocab_lo, vocab_hi)"""
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise ValueError(f"{who}: logits must be a 2-D tensor with unit column stride")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: logits dtype {logits2d.dtype} (float32 / bfloat16)")
+    M, ld = logits2d.shape[0], logits2d.stride(0)
+    V = logits2d.shape[1] if V is None else int(V)
+    if not 0 < V <= logits2d.shape[1] or not supported(V, ld):
+        raise ValueError(f"{who}: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {ld}")
+    return (M, ld, V) + _check_window(who, V, vocab_lo, vocab_hi)
+
+
+def _check_tensor(who, name, x, dtype, shape, dev):
+    """``x``: a contiguous ``dtype`` tensor on ``dev`` of ``shape`` -- an int: that many elements; a tuple: that shape, -1 for any size"""
+    if isinstance(shape, int):
+        ok = x.numel() == shape
+    else:
+        xs = tuple(x.shape)
+        ok = xs == shape or (len(xs) == len(shape) and all(n in (-1, m) for n, m in zip(shape, xs)))
+    if not ok or x.dtype != dtype or not x.is_contiguous() or x.device != dev:
+        what = f"of {shape} elements" if isinstance(shape, int) else f"of shape {shape}"
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} tensor {what} on {dev}")
+
+
+def _check_next_ids(who, next_ids, M, dev):
+    if next_ids.dtype != torch.int64 or next_ids.shape[0] != M or next_ids.numel() != M or next_ids.device != dev:
+        raise ValueError(f"{who}: next_ids must be an int64 tensor of {M} rows (one element each) on {dev}")
+
+
 def select_tokens_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
 
@@ -544,18 +585,9 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
     index within the generation, READ only; ``finished`` / ``lengths`` / ``status`` (int32 [M]) updated; the token goes to ``out`` [M, max_new]
     (int32) at column t and to ``next_ids`` (int64, [M] or a column of [M, q]: row stride taken from the tensor).  Capturable; raises
     ValueError on bad arguments before anything is launched."""
-    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
-        raise ValueError("select_tokens: logits must be a 2-D tensor with unit column stride")
-    if logits2d.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"select_tokens: logits dtype {logits2d.dtype} (float32 / bfloat16)")
-    M, ld = logits2d.shape[0], logits2d.stride(0)
-    V = logits2d.shape[1] if V is None else int(V)
-    vocab_hi = V if vocab_hi is None else int(vocab_hi)
-    vocab_lo = int(vocab_lo)
-    if not 0 < V <= logits2d.shape[1] or not select_tokens_supported(V, max(ld, V), logits2d.dtype):
-        raise ValueError(f"select_tokens: V={V} unsupported for logits of shape {tuple(logits2d.shape)}")
-    if not 0 <= vocab_lo < vocab_hi <= V:
-        raise ValueError(f"select_tokens: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
+    who, dev, i32 = "select_tokens", logits2d.device, torch.int32
+    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
+                                                 lambda V, ld: select_tokens_supported(V, max(ld, V), logits2d.dtype))
     if not greedy:
         if not (temperature > 0 and temperature < float("inf")):
             raise ValueError(f"select_tokens: temperature {temperature} must be > 0 when sampling")
@@ -563,17 +595,11 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
             raise ValueError(f"select_tokens: top_p {top_p} must lie in (0, 1]")
         if top_k < 0:
             raise ValueError(f"select_tokens: top_k {top_k} must be >= 0")
-    i32 = torch.int32
-    for name, x, n in (("finished", finished, M), ("lengths", lengths, M), ("status", status, M), ("t", t, 1)):
-        if x.dtype != i32 or x.numel() != n or not x.is_contiguous() or x.device != logits2d.device:
-            raise ValueError(f"select_tokens: {name} must be a contiguous int32 tensor of {n} elements on {logits2d.device}")
-    if stream_id is not None and (stream_id.dtype != i32 or stream_id.numel() != M or not stream_id.is_contiguous()
-                                  or stream_id.device != logits2d.device):
-        raise ValueError(f"select_tokens: stream_id must be a contiguous int32 tensor of {M} elements on {logits2d.device}")
-    if out.dtype != i32 or out.dim() != 2 or out.shape[0] != M or not out.is_contiguous() or out.device != logits2d.device:
-        raise ValueError(f"select_tokens: out must be a contiguous int32 [{M}, max_new] tensor on {logits2d.device}")
-    if next_ids.dtype != torch.int64 or next_ids.shape[0] != M or next_ids.numel() != M or next_ids.device != logits2d.device:
-        raise ValueError(f"select_tokens: next_ids must be an int64 tensor of {M} rows (one element each) on {logits2d.device}")
+    for name, x, n in (("finished", finished, M), ("lengths", lengths, M), ("status", status, M), ("t", t, 1)) + \
+            ((("stream_id", stream_id, M),) if stream_id is not None else ()):
+        _check_tensor(who, name, x, i32, n, dev)
+    _check_tensor(who, "out", out, i32, (M, -1), dev)
+    _check_next_ids(who, next_ids, M, dev)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     lib.call("db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k), float(top_p),
              int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(stream_id), P(finished),
@@ -591,40 +617,28 @@ def beam_step(logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, po
     [M, max_new]), the pool (pool_tokens int32 [G, W, max_new], pool_len / pool_slot int32 [G, W], pool_score float32 [G, W]) and pool_count /
     done / switches / status (int32 [G]) updated; the next ids go to ``next_ids`` (int64, [M] or a column of [M, q]).  Capturable; raises
     ValueError on bad arguments before anything is launched."""
-    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
-        raise ValueError("beam_step: logits must be a 2-D tensor with unit column stride")
-    if logits2d.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"beam_step: logits dtype {logits2d.dtype} (float32 / bfloat16)")
-    M, ld = logits2d.shape[0], logits2d.stride(0)
-    W = int(W)
-    if not 1 <= W <= 16 or M % W != 0 or M == 0:
-        raise ValueError(f"beam_step: W={W} must lie in [1, 16] and divide the {M} rows")
+    who, dev, W, i32, f32 = "beam_step", logits2d.device, int(W), torch.int32, torch.float32
+    if not 1 <= W <= 16:
+        raise ValueError(f"beam_step: W={W} must lie in [1, 16]")
+    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
+                                                 lambda V, ld: beam_step_supported(V, max(ld, V), W, logits2d.dtype))
+    if M % W != 0 or M == 0:
+        raise ValueError(f"beam_step: W={W} must divide the {M} rows")
     G = M // W
-    V = logits2d.shape[1] if V is None else int(V)
-    vocab_hi = V if vocab_hi is None else int(vocab_hi)
-    vocab_lo = int(vocab_lo)
-    if not 0 < V <= logits2d.shape[1] or not beam_step_supported(V, max(ld, V), W, logits2d.dtype):
-        raise ValueError(f"beam_step: V={V} unsupported for logits of shape {tuple(logits2d.shape)}")
-    if not 0 <= vocab_lo < vocab_hi <= V:
-        raise ValueError(f"beam_step: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
     lp = float(length_penalty)
     if not abs(lp) < float("inf"):
         raise ValueError(f"beam_step: length_penalty {length_penalty} must be finite")
-    dev = logits2d.device
-    if tokens.dtype != torch.int32 or tokens.dim() != 2 or tokens.shape[0] != M or not tokens.is_contiguous() or tokens.device != dev:
-        raise ValueError(f"beam_step: tokens must be a contiguous int32 [{M}, max_new] tensor on {dev}")
+    _check_tensor(who, "tokens", tokens, i32, (M, -1), dev)
     mx = tokens.shape[1]
     if mx < 1:
         raise ValueError("beam_step: max_new must be >= 1")
-    for name, x, shape, dt in (("t", t, (1,), torch.int32), ("beam_score", beam_score, (M,), torch.float32), ("parent", parent, (M,), torch.int32),
-                               ("pool_tokens", pool_tokens, (G, W, mx), torch.int32), ("pool_len", pool_len, (G, W), torch.int32),
-                               ("pool_score", pool_score, (G, W), torch.float32), ("pool_slot", pool_slot, (G, W), torch.int32),
-                               ("pool_count", pool_count, (G,), torch.int32), ("done", done, (G,), torch.int32),
-                               ("switches", switches, (G,), torch.int32), ("status", status, (G,), torch.int32)):
-        if x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"beam_step: {name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
-    if next_ids.dtype != torch.int64 or next_ids.shape[0] != M or next_ids.numel() != M or next_ids.device != dev:
-        raise ValueError(f"beam_step: next_ids must be an int64 tensor of {M} rows (one element each) on {dev}")
+    for name, x, shape, dt in (("t", t, (1,), i32), ("beam_score", beam_score, (M,), f32), ("parent", parent, (M,), i32),
+                               ("pool_tokens", pool_tokens, (G, W, mx), i32), ("pool_len", pool_len, (G, W), i32),
+                               ("pool_score", pool_score, (G, W), f32), ("pool_slot", pool_slot, (G, W), i32),
+                               ("pool_count", pool_count, (G,), i32), ("done", done, (G,), i32), ("switches", switches, (G,), i32),
+                               ("status", status, (G,), i32)):
+        _check_tensor(who, name, x, dt, shape, dev)
+    _check_next_ids(who, next_ids, M, dev)
     ws, wsn = _ws("db1_beam_step_workspace_bytes", (M, V, W, mx, dt_code(logits2d)), dev)
     lib.call("db1_beam_step", P(logits2d), G, W, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, int(eos_id), int(pad_id), lp, P(t), mx,
              P(beam_score), P(parent), P(tokens), P(pool_tokens), P(pool_len), P(pool_score), P(pool_slot), P(pool_count), P(done), P(switches),
@@ -658,11 +672,9 @@ def ring_reorder(rings, ptrs, state, mlen, t, max_t, parent, W=1, done=None):
     if not 1 <= max_t <= mlen < cap:
         raise ValueError(f"ring_reorder: needs 1 <= max_t ({max_t}) <= mlen ({mlen}) < cap ({cap})")
     dev = r0.device
-    if ptrs.dtype != torch.int64 or tuple(ptrs.shape) != (len(rings),) or ptrs.device != dev or not ptrs.is_contiguous():
-        raise ValueError(f"ring_reorder: ptrs must be a contiguous int64 [{len(rings)}] device tensor (ring_pointers)")
+    _check_tensor("ring_reorder", "ptrs (ring_pointers)", ptrs, torch.int64, (len(rings),), dev)
     for name, x, n in (("state", state, 1), ("t", t, 1), ("parent", parent, M)) + ((("done", done, M // W),) if done is not None else ()):
-        if x.dtype != torch.int32 or x.numel() != n or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"ring_reorder: {name} must be a contiguous int32 tensor of {n} elements on {dev}")
+        _check_tensor("ring_reorder", name, x, torch.int32, n, dev)
     ws, wsn = _ws("db1_ring_reorder_workspace_bytes", (len(rings), M, max_t, int(slot_bytes)), dev)
     lib.call("db1_ring_reorder", P(ptrs), len(rings), M, W, cap, int(slot_bytes), P(state), mlen, P(t), max_t, P(parent), P(done), ws, wsn, stream())
 
@@ -691,38 +703,21 @@ def score_rows_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_score_rows_supported(int(V), int(ld), dt_code(dtype)))
 
 
-def _score_window(who, V, vocab_lo, vocab_hi):
-    vocab_hi = V if vocab_hi is None else int(vocab_hi)
-    vocab_lo = int(vocab_lo)
-    if not 0 <= vocab_lo < vocab_hi <= V:
-        raise ValueError(f"{who}: vocabulary window [{vocab_lo}, {vocab_hi}) is empty or outside [0, {V})")
-    return vocab_lo, vocab_hi
-
-
-def _score_outputs(who, T, dev, labels, lse, logprob, top1, rank, status):
-    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous() or labels.device != dev:
-        raise ValueError(f"{who}: labels must be a contiguous int64 tensor of {T} elements on {dev}")
-    for name, x, dt in (("lse", lse, torch.float32), ("logprob", logprob, torch.float32), ("top1", top1, torch.int32), ("rank", rank, torch.int32),
-                        ("status", status, torch.int32)):
-        if x.dtype != dt or x.numel() != T or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"{who}: {name} must be a contiguous {dt} tensor of {T} elements on {dev}")
+def _check_score_outputs(who, T, dev, labels, lse, logprob, top1, rank, status):
+    for name, x, dt in (("labels", labels, torch.int64), ("lse", lse, torch.float32), ("logprob", logprob, torch.float32),
+                        ("top1", top1, torch.int32), ("rank", rank, torch.int32), ("status", status, torch.int32)):
+        _check_tensor(who, name, x, dt, T, dev)
 
 
 def score_rows(logits2d, labels, lse, logprob, top1, rank, status, *, V=None, vocab_lo=0, vocab_hi=None):
     """log-probability, arg-max and rank of ``labels`` (int64 [T]) under every row of ``logits2d`` [T, ld] (fp32 / bf16, the first V columns
     valid) over the columns [vocab_lo, vocab_hi) (db1_score_rows, rule in include/db1_hip.h): lse / logprob (float32 [T]) and top1 / rank /
     status (int32 [T]) are written, the logits are only read.  Capturable; raises ValueError on bad arguments before anything is launched."""
-    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
-        raise ValueError("score_rows: logits must be a 2-D tensor with unit column stride")
-    if logits2d.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"score_rows: logits dtype {logits2d.dtype} (float32 / bfloat16)")
-    T, ld = logits2d.shape[0], logits2d.stride(0)
-    V = logits2d.shape[1] if V is None else int(V)
-    if T < 1 or not 0 < V <= logits2d.shape[1] or not score_rows_supported(V, ld, logits2d.dtype) or logits2d.data_ptr() % 16:
-        raise ValueError(f"score_rows: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {ld} (16-byte aligned rows of at "
-                         "most 34 816 elements)")
-    vocab_lo, vocab_hi = _score_window("score_rows", V, vocab_lo, vocab_hi)
-    _score_outputs("score_rows", T, logits2d.device, labels, lse, logprob, top1, rank, status)
+    T, ld, V, vocab_lo, vocab_hi = _check_logits("score_rows", logits2d, V, vocab_lo, vocab_hi,
+                                                 lambda V, ld: score_rows_supported(V, ld, logits2d.dtype))      # (ld itself, not max(ld, V))
+    if T < 1 or logits2d.data_ptr() % 16:
+        raise ValueError(f"score_rows: logits of shape {tuple(logits2d.shape)} at {logits2d.data_ptr():#x}: at least one row, 16-byte aligned")
+    _check_score_outputs("score_rows", T, logits2d.device, labels, lse, logprob, top1, rank, status)
     _timed("score_rows", float(T * V * logits2d.element_size()),
            lambda: lib.call("db1_score_rows", P(logits2d), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, ld, dt_code(logits2d),
                             vocab_lo, vocab_hi, stream()))
@@ -740,8 +735,8 @@ def lmhead_score(h2d, W, labels, lse, logprob, top1, rank, status, *, V, vocab_l
         raise ValueError(f"lmhead_score: V={V} unsupported for a head of {rows} rows (at most 34 816, a multiple of 16 bytes)")
     if chunk_rows < 0:
         raise ValueError(f"lmhead_score: chunk_rows {chunk_rows} must be >= 0")
-    vocab_lo, vocab_hi = _score_window("lmhead_score", V, vocab_lo, vocab_hi)
-    _score_outputs("lmhead_score", T, h2d.device, labels, lse, logprob, top1, rank, status)
+    vocab_lo, vocab_hi = _check_window("lmhead_score", V, vocab_lo, vocab_hi)
+    _check_score_outputs("lmhead_score", T, h2d.device, labels, lse, logprob, top1, rank, status)
     ws, wsn = _ws("db1_lmhead_score_workspace_bytes", (T, rows, d, chunk_rows, dt_code(h2d)), h2d.device)
     _timed("lmhead_score", 2.0 * T * V * d,
            lambda: lib.call("db1_lmhead_score", P(h2d), P(W), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, rows, d, vocab_lo,
@@ -753,14 +748,12 @@ def score_segments(logprob, rank, labels, mask, out, *, V):
     sum(mask * (rank == 0))} over segments of ``numel / n_seg`` consecutive rows; rows whose label lies outside [0, V) count as mask 0.
     Capturable; raises ValueError on bad arguments before anything is launched."""
     dev = logprob.device
-    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[1] != 3 or out.shape[0] < 1 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"score_segments: out must be a contiguous float32 [n_seg, 3] tensor on {dev}")
+    _check_tensor("score_segments", "out", out, torch.float32, (-1, 3), dev)
     n_seg, n = out.shape[0], logprob.numel()
-    if n < 1 or n % n_seg or int(V) < 1:
+    if n_seg < 1 or n < 1 or n % n_seg or int(V) < 1:
         raise ValueError(f"score_segments: {n} rows do not split into {n_seg} segments (V={V})")
     for name, x, dt in (("logprob", logprob, torch.float32), ("rank", rank, torch.int32), ("labels", labels, torch.int64), ("mask", mask, torch.float32)):
-        if x.dtype != dt or x.numel() != n or not x.is_contiguous() or x.device != dev:
-            raise ValueError(f"score_segments: {name} must be a contiguous {dt} tensor of {n} elements on {dev}")
+        _check_tensor("score_segments", name, x, dt, n, dev)
     lib.call("db1_score_segments", P(logprob), P(rank), P(labels), P(mask), P(out), n_seg, n // n_seg, int(V), stream())
 
 

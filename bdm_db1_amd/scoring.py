@@ -10,6 +10,9 @@ never fills; its caption / VQA evaluation can only generate.  Here
     through the list-form memory path, as in ``beam_search``; its last logits score token 0 of every candidate, its memory is expanded K-fold and
     ONE more call feeds tokens ``0 .. Lc-2`` and scores tokens ``1 .. Lc-1``.
 
+What a model call needs around it -- the eval-mode switch, the vocabulary checks, the prefill with its expanded memory, the check of the decode
+chain -- is generation.py's: the single decode driver there and the two entry points here share one copy of each.
+
 The rule (candidates, lse, logprob, top1, rank, ignored rows) is stated in include/db1_hip.h (db1_score_rows) and restated in NumPy in
 tests/score_rule.py.
 """
@@ -24,6 +27,8 @@ import numpy as np
 import torch
 
 from . import ops
+from .generation import (_batch_size, _check_chain, _eval_mode, _need_memory, _prefill, _text_window, _token_input, _vocab_window, caption_prompt,
+                         question_prompt)
 
 _KINDS = {"NLPTaskInput": "nlp", "ICTaskInput": "ic", "VQATaskInput": "vqa", "RLTaskInput": "rl"}
 IGNORE = -100     # a label outside the vocabulary: the row is ignored (torch's ignore_index)
@@ -98,11 +103,7 @@ class _ScoreSink:
 
 
 def _check_window(model, cfg: ScoreConfig) -> ScoreConfig:
-    V = int(model.total_vocab_size)
-    if cfg.vocab_hi is not None and int(cfg.vocab_hi) > V:
-        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) exceeds the model's vocabulary ({V})")
-    if int(cfg.vocab_lo) >= V:
-        raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) is empty in a vocabulary of {V}")
+    V, _ = _vocab_window(model, cfg)
     if not ops.score_rows_supported(V, int(model.vocab_pad), model.compute_dtype):
         raise ValueError(f"db1_score_rows does not support a padded vocabulary of {model.vocab_pad}")
     return cfg
@@ -123,14 +124,12 @@ def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResu
         if t.label is None or t.loss_mask is None:
             raise ValueError("score: every task input needs label and loss_mask")
     sink = _ScoreSink(cfg)
-    was_training = model.training
-    model.eval()
-    model._score_sink = sink
-    try:
-        model(tasks_input, compute_loss=True)
-    finally:
-        model._score_sink = None
-        model.train(was_training)
+    with _eval_mode(model):
+        model._score_sink = sink
+        try:
+            model(tasks_input, compute_loss=True)
+        finally:
+            model._score_sink = None
     if sink.sweeps != 1:
         raise RuntimeError("score: the forward did not end in the scoring sweep")
     logprob, top1, rank, status, seg, msk, _, shapes = sink.out
@@ -197,11 +196,8 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
     ones: the attention is causal); ``scores[g, k] = sum_{i < len} logprob[g, k, i] / len^length_penalty``; ``order[g]`` sorts ``scores[g]``
     descending, the lower k first on ties.  Tokens older than ``mem_len`` fall out of the memory, as in generation.  ``stats`` (a dict) receives
     ``model_calls`` (1 when Lc == 1, else 2)."""
-    from .data import NLPTaskInput
-    from .generation import _batch_size
     cfg = _check_window(model, config or ScoreConfig())
-    if not int(model.mem_len or 0) > 0:
-        raise ValueError("rank_candidates needs a model with memory (mem_len > 0)")
+    _need_memory(model, "rank_candidates")
     G = _batch_size(prompt)
     V, dev = int(model.total_vocab_size), model.dev
     cand = torch.as_tensor(np.asarray(candidates.cpu() if torch.is_tensor(candidates) else candidates))
@@ -224,12 +220,9 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
     labels = torch.where(valid, cand, torch.full_like(cand, IGNORE))                              # masked-out positions: ignored rows
     logprob, rank = torch.empty(M, Lc, dtype=torch.float32, device=dev), torch.empty(M, Lc, dtype=torch.int32, device=dev)
     win = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=cfg.vocab_hi)
-    was_training = model.training
-    model.eval()
-    try:
+    with _eval_mode(model):
         # call 1: the prompt once per group; the logits of its last position, repeated K-fold, score token 0 of every candidate
-        model._dec_state = None
-        logits, _, mems = model([prompt], compute_loss=False, mems=model.init_mem(G))
+        logits, mems = _prefill(model, prompt, G, K if Lc > 1 else None)
         L = logits.shape[1]
         last = _padded_rows(model, logits)[L - 1::L].repeat_interleave(K, 0)          # [M, vocab_pad]
         lse, lp, t1, rk, st = _score_buffers(M, dev)
@@ -239,9 +232,7 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
         del logits, last
         if Lc > 1:
             # call 2: the memory expanded K-fold, tokens 0 .. Lc-2 of every candidate in, tokens 1 .. Lc-1 scored
-            mems = [m.repeat_interleave(K, 0) for m in mems]
-            x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=cand[:, :Lc - 1].contiguous(), text_len=None)
-            logits, _, _ = model([x], compute_loss=False, mems=mems)
+            logits, _, _ = model([_token_input(cand[:, :Lc - 1].contiguous())], compute_loss=False, mems=mems)
             T = M * (Lc - 1)
             lse, lp, t1, rk, st = _score_buffers(T, dev)
             ops.score_rows(_padded_rows(model, logits), labels[:, 1:].reshape(-1).contiguous(), lse, lp, t1, rk, st, **win)
@@ -249,13 +240,9 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
             calls = 2
             del logits, mems
         model._dec_state = None
-        chk = getattr(model, "check_decode_chain", None)
-        if chk is not None:
-            chk(True)
+        _check_chain(model)
         seg = torch.empty(M, 3, dtype=torch.float32, device=dev)
         ops.score_segments(logprob.view(-1), rank.view(-1), labels.view(-1), valid.to(torch.float32).view(-1), seg, V=V)
-    finally:
-        model.train(was_training)
     if stats is not None:
         stats.update(model_calls=calls)
     sums = seg[:, 0].cpu().numpy().reshape(G, K)
@@ -264,20 +251,13 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
     return torch.from_numpy(scores), torch.from_numpy(order.astype(np.int64)), logprob.view(G, K, Lc).cpu()
 
 
-def _text_window(model, cfg: Optional[ScoreConfig]) -> ScoreConfig:
-    cfg = cfg or ScoreConfig()
-    return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
-
-
 def rank_captions(model, ic_batch, candidates, cand_len=None, config: Optional[ScoreConfig] = None, stats: Optional[dict] = None):
     """``rank_candidates`` after the prompt ``generate_captions`` builds (``[prompt, image patches]``, an empty caption), over the text
     vocabulary unless ``config`` says otherwise"""
-    from .generation import caption_prompt
-    return rank_candidates(model, caption_prompt(ic_batch), candidates, cand_len, _text_window(model, config), stats)
+    return rank_candidates(model, caption_prompt(ic_batch), candidates, cand_len, _text_window(model, config or ScoreConfig()), stats)
 
 
 def rank_answers(model, vqa_batch, candidates, cand_len=None, config: Optional[ScoreConfig] = None, stats: Optional[dict] = None):
     """``rank_candidates`` after the prompt ``answer_questions`` builds (``[prompt, image patches, question]``), over the text vocabulary
     unless ``config`` says otherwise"""
-    from .generation import question_prompt
-    return rank_candidates(model, question_prompt(vqa_batch), candidates, cand_len, _text_window(model, config), stats)
+    return rank_candidates(model, question_prompt(vqa_batch), candidates, cand_len, _text_window(model, config or ScoreConfig()), stats)

@@ -6,7 +6,6 @@ import dataclasses
 import gc
 import os
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -21,53 +20,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import beam_rule as B  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _tdev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _fp32_model():
-    from golden_util import case_cfg, make_params
-    from oracle import db1_oracle as O
-    from bdm_db1_amd import TransformerXL
-    cfg = case_cfg("small_vqa")
-    params = make_params(cfg, 321)
-    model = TransformerXL(SimpleNamespace(**cfg), device=DEV, compute_dtype=torch.float32)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=False)
-    params["pos_emb.inv_freq"] = model.pos_emb.inv_freq.cpu().numpy()
-    model.eval()
-    return cfg, model, O.OracleModel(O.OracleConfig(**cfg), params)
-
-
-def _bf16_model(seed=5, mem_len=40):
-    from bdm_db1_amd import TransformerXL, synth
-    cfg = synth.db1_config("tiny", n_embed=256, n_head=2, n_layer=2, n_position=128, mem_len=mem_len, fp16=True)
-    torch.manual_seed(seed)
-    model = TransformerXL(cfg, device=torch.device(DEV), compute_dtype=torch.bfloat16)
-    model.eval()
-    return cfg, model
+from gpu_common import _bf16_model, _fp32_model, _need_gpu, _prompt, _tdev  # noqa: E402,F401
 
 
 def _prompts(rng, kind, G, vocab):
     from oracle import db1_oracle as O
-    from bdm_db1_amd.data import ICTaskInput, NLPTaskInput
-    if kind == "nlp":
-        ids = rng.integers(0, vocab, (G, 6))
-        return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=_tdev(ids), text_len=None), \
-            [O.TaskBatch(kind="nlp", text_seq=ids[g:g + 1]) for g in range(G)]
-    prompt = rng.integers(0, vocab, (G, 3))
-    img = rng.standard_normal((G, 3, 32, 32)).astype(np.float32)
-    empty = np.zeros((G, 0), np.int64)
-    return ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_tdev(prompt), img_seq=_tdev(img),
-                       text_seq=_tdev(empty)), \
-        [O.TaskBatch(kind="ic", prompt_seq=prompt[g:g + 1], img_seq=img[g:g + 1], text_seq=empty[g:g + 1]) for g in range(G)]
+    x, fields = _prompt(rng, kind, G, vocab)
+    return x, [O.TaskBatch(kind=kind, **{k: v[g:g + 1] for k, v in fields.items()}) for g in range(G)]
 
 
 class _OracleLM:

@@ -14,14 +14,9 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import beam_rule as B  # noqa: E402
+from gpu_common import _need_gpu  # noqa: E402,F401
 
 DEV_KEYS = ("beam_score", "parent", "tokens", "pool_tokens", "pool_len", "pool_score", "pool_slot", "pool_count", "done", "switches", "status")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
 
 
 def _upload(S):

@@ -3,7 +3,6 @@ the eager bf16 loop, RingMemory.load, seeds / stream ids, EOS and the early stop
 import dataclasses
 import os
 import sys
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -18,44 +17,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import select_rule as R  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _tdev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    return t if dtype is None else t.to(dtype)
-
-
-def _fp32_model():
-    from golden_util import case_cfg, make_params
-    from oracle import db1_oracle as O
-    from bdm_db1_amd import TransformerXL
-    cfg = case_cfg("small_vqa")
-    params = make_params(cfg, 321)
-    model = TransformerXL(SimpleNamespace(**cfg), device=DEV, compute_dtype=torch.float32)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=False)
-    params["pos_emb.inv_freq"] = model.pos_emb.inv_freq.cpu().numpy()
-    model.eval()
-    return cfg, model, O.OracleModel(O.OracleConfig(**cfg), params)
+from gpu_common import _bf16_model, _fp32_model, _need_gpu, _prompt, _tdev  # noqa: E402,F401
 
 
 def _prompts(rng, kind, M, vocab):
     from oracle import db1_oracle as O
-    from bdm_db1_amd.data import ICTaskInput, NLPTaskInput
-    if kind == "nlp":
-        ids = rng.integers(0, vocab, (M, 6))
-        return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=_tdev(ids), text_len=None), \
-            O.TaskBatch(kind="nlp", text_seq=ids)
-    prompt = rng.integers(0, vocab, (M, 3))
-    img = rng.standard_normal((M, 3, 32, 32)).astype(np.float32)
-    empty = np.zeros((M, 0), np.int64)
-    return ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_tdev(prompt), img_seq=_tdev(img),
-                       text_seq=_tdev(empty)), O.TaskBatch(kind="ic", prompt_seq=prompt, img_seq=img, text_seq=empty)
+    x, fields = _prompt(rng, kind, M, vocab)
+    return x, O.TaskBatch(kind=kind, **fields)
 
 
 @pytest.mark.parametrize("kind", ["nlp", "ic"])
@@ -83,15 +51,6 @@ def test_fp32_greedy_generation_follows_the_oracle(kind):
                 assert srt[r, -1] - srt[r, -2] > 1e-4 * scale, (t, r)   # (a clear winner: the tokens must be equal)
                 assert ids[r, t] == np.argmax(l[r]), (t, r)
         logits, _, mems = oracle.forward([O.TaskBatch(kind="nlp", text_seq=ids[:, t:t + 1].astype(np.int64))], compute_loss=False, mems=mems)
-
-
-def _bf16_model(seed=5, mem_len=40):
-    from bdm_db1_amd import TransformerXL, synth
-    cfg = synth.db1_config("tiny", n_embed=256, n_head=2, n_layer=2, n_position=128, mem_len=mem_len, fp16=True)
-    torch.manual_seed(seed)
-    model = TransformerXL(cfg, device=torch.device(DEV), compute_dtype=torch.bfloat16)
-    model.eval()
-    return cfg, model
 
 
 def _teacher_forced(model, x, ids):

@@ -17,31 +17,9 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
+import gpu_common  # noqa: E402
 import score_rule as R  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-
-
-def _tdev(a, dtype=None):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-    return t if dtype is None else t.to(dtype)
-
-
-def _model(name, dtype=torch.float32, seed=321):
-    from golden_util import case_cfg, make_params
-    from oracle import db1_oracle as O
-    from bdm_db1_amd import TransformerXL
-    cfg = case_cfg(name)
-    params = make_params(cfg, seed)
-    model = TransformerXL(SimpleNamespace(**cfg), device=DEV, compute_dtype=dtype)
-    model.load_state_dict({k: torch.from_numpy(v) for k, v in params.items()}, strict=False)
-    params["pos_emb.inv_freq"] = model.pos_emb.inv_freq.cpu().numpy()
-    model.eval()
-    return cfg, model, O.OracleModel(O.OracleConfig(**cfg), params)
+from gpu_common import _model, _need_gpu, _prompt, _tdev  # noqa: E402,F401
 
 
 def _inputs(tasks):
@@ -219,23 +197,6 @@ def test_sweep_saves_the_logits_tensor(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------- candidate ranking
-def _prompt(rng, kind, G, vocab):
-    """(model input, the prompt's fields) of G rows: nlp 6 tokens; ic 3 + 4 patches; vqa 3 + 4 patches + 5 question tokens"""
-    from bdm_db1_amd.data import ICTaskInput, NLPTaskInput, VQATaskInput
-    if kind == "nlp":
-        ids = rng.integers(0, vocab, (G, 6))
-        return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=_tdev(ids), text_len=None), dict(text_seq=ids)
-    prompt = rng.integers(0, vocab, (G, 3))
-    img = rng.standard_normal((G, 3, 32, 32)).astype(np.float32)
-    if kind == "ic":
-        text = np.zeros((G, 0), np.int64)
-        return ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_tdev(prompt), img_seq=_tdev(img),
-                           text_seq=_tdev(text)), dict(prompt_seq=prompt, img_seq=img, text_seq=text)
-    q = rng.integers(1, vocab, (G, 5))
-    return VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_tdev(prompt), img_seq=_tdev(img),
-                        text_seq=_tdev(q), img_id_seq=None, ques_id_seq=None, ques_len=None), dict(prompt_seq=prompt, img_seq=img, text_seq=q)
-
-
 def _full_sequences(kind, fields, cand):
     """the G * K sequences prompt (+) candidate as oracle / model fields (rows g * K + k)"""
     G, K, Lc = cand.shape
@@ -342,12 +303,7 @@ def test_rank_candidates_shared_candidates_and_single_token():
 
 
 def _bf16_model(seed=5):
-    from bdm_db1_amd import TransformerXL, synth
-    cfg = synth.db1_config("tiny", n_embed=256, n_head=2, n_layer=2, n_position=128, mem_len=40, fp16=True)
-    torch.manual_seed(seed)
-    model = TransformerXL(cfg, device=torch.device(DEV), compute_dtype=torch.bfloat16)
-    model.eval()
-    return model
+    return gpu_common._bf16_model(seed)[1]
 
 
 @pytest.mark.parametrize("kind", ["nlp", "ic", "vqa"])

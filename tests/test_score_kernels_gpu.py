@@ -15,16 +15,11 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import score_rule as R  # noqa: E402
+from gpu_common import _need_gpu  # noqa: E402,F401
 
 # Both sides sum at most 2^16 positive fp32 terms after subtracting the same maximum, in different orders: a pairwise or blocked fp32 sum of
 # that many terms is good to about 16 ulp relative, 2e-6 absolute after the log.  The gate is 1e-5 absolute.
 TOL = 1e-5
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
 
 
 def _outs(T, nan=True):

@@ -15,12 +15,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import select_rule as R  # noqa: E402
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
+from gpu_common import _need_gpu  # noqa: E402,F401
 
 
 class State:
