@@ -5,7 +5,8 @@ if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
 __all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep",
            "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
-           "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers"]
+           "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers",
+           "generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler"]
 
 
 def __getattr__(name):
@@ -30,6 +31,9 @@ def __getattr__(name):
     if name in ("ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers"):
         from . import scoring
         return getattr(scoring, name)
+    if name in ("generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler"):
+        from . import serving
+        return getattr(serving, name)
     if name == "mpu":
         import importlib
         return importlib.import_module(".mpu", __name__)

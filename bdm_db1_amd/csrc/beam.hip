@@ -368,3 +368,78 @@ extern "C" int db1_ring_reorder(const void* const* rings, int n_layers, int M, i
     DB1_CHECK_LAUNCH("ring_reorder write-back");
     return DB1_OK;
 }
+
+// ------------------------------------------------------------------ ring load (continuous batching: a new request takes over a row)
+// db1_ring_load_rows, one launch: the mlen projected keys / values of n new requests (src [n, mlen, slot] per layer) go to rows rows[i] of
+// every ring, logical key j to slot (state + j) % cap.  A source row is contiguous and so is its target but for the one wrap at the ring's
+// end: workgroup (chunk, i, layer) streams LOAD_CHUNK 16-byte words, four loads in flight per thread before the four stores.
+#define LOAD_THREADS 256
+#define LOAD_UNROLL 4
+#define LOAD_CHUNK (LOAD_THREADS * LOAD_UNROLL * 4)
+
+struct LoadArgs {
+    const long long* rings;
+    const long long* src;
+    int M, cap, mlen;
+    int64_t slot16;
+    const int* rows;
+    const int* state;
+    int* status;
+};
+
+__global__ __launch_bounds__(LOAD_THREADS) void ring_load_rows_kernel(LoadArgs a) {
+    const int i = blockIdx.y, layer = blockIdx.z;
+    const int row = a.rows[i], s0 = *a.state;
+    const bool bad_row = row < 0 || row >= a.M, bad_origin = s0 < 0 || s0 >= a.cap;
+    if (bad_row || bad_origin) {     // (block-uniform) never written through: reported once per entry
+        if (blockIdx.x == 0 && layer == 0 && threadIdx.x == 0) atomicOr(a.status, (bad_row ? 1 : 0) | (bad_origin ? 2 : 0));
+        return;
+    }
+    const int64_t words = (int64_t)a.mlen * a.slot16, ring_words = (int64_t)a.cap * a.slot16;
+    const uint4* src = reinterpret_cast<const uint4*>(a.src[layer]) + (int64_t)i * words;
+    uint4* dst = reinterpret_cast<uint4*>(a.rings[layer]) + (int64_t)row * ring_words;
+    const int64_t first = (int64_t)s0 * a.slot16;          // (first + e < 2 * ring_words: one wrap at most)
+    const int64_t c0 = (int64_t)blockIdx.x * LOAD_CHUNK, c1 = min(c0 + LOAD_CHUNK, words);
+    for (int64_t e0 = c0 + threadIdx.x; e0 < c1; e0 += LOAD_THREADS * LOAD_UNROLL) {
+        uint4 v[LOAD_UNROLL];
+#pragma unroll
+        for (int q = 0; q < LOAD_UNROLL; q++) {
+            const int64_t e = e0 + q * LOAD_THREADS;
+            if (e < c1) v[q] = src[e];
+        }
+#pragma unroll
+        for (int q = 0; q < LOAD_UNROLL; q++) {
+            const int64_t e = e0 + q * LOAD_THREADS;
+            if (e < c1) {
+                int64_t o = first + e;
+                o = o >= ring_words ? o - ring_words : o;
+                dst[o] = v[q];
+            }
+        }
+    }
+}
+
+extern "C" int db1_ring_load_rows_supported(int64_t slot_bytes, int mlen, int cap) {
+    return slot_bytes > 0 && slot_bytes % 16 == 0 && mlen > 0 && mlen < cap;
+}
+
+extern "C" int db1_ring_load_rows(const void* const* rings, const void* const* src, int n_layers, int M, int n, int cap, int64_t slot_bytes,
+                                  const int32_t* state, int mlen, const int32_t* rows, int32_t* status, void* stream) {
+    if (!db1_ring_load_rows_supported(slot_bytes, mlen, cap))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "ring_load_rows: slot of %lld bytes, mlen=%d, cap=%d", (long long)slot_bytes, mlen, cap);
+    if (n_layers <= 0 || n_layers > 65535 || M <= 0 || n < 0 || n > 65535 || n > M)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "ring_load_rows: L=%d M=%d n=%d", n_layers, M, n);
+    if (n == 0) return DB1_OK;
+    if (!rings || !src || !state || !rows || !status) DB1_FAIL(DB1_ERR_BAD_SHAPE, "ring_load_rows: null buffer");
+    LoadArgs a;
+    a.rings = reinterpret_cast<const long long*>(rings);
+    a.src = reinterpret_cast<const long long*>(src);
+    a.M = M; a.cap = cap; a.mlen = mlen; a.slot16 = slot_bytes / 16;
+    a.rows = rows; a.state = state; a.status = status;
+    const int64_t words = (int64_t)mlen * a.slot16;
+    const int64_t chunks = (words + LOAD_CHUNK - 1) / LOAD_CHUNK;
+    if (chunks > 0x7fffffff) DB1_FAIL(DB1_ERR_BAD_SHAPE, "ring_load_rows: a row of %lld bytes", (long long)(words * 16));
+    ring_load_rows_kernel<<<dim3((unsigned)chunks, n, n_layers), LOAD_THREADS, 0, (hipStream_t)stream>>>(a);
+    DB1_CHECK_LAUNCH("ring_load_rows");
+    return DB1_OK;
+}

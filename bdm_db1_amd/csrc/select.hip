@@ -48,6 +48,10 @@ struct SelArgs {
     int eos, pad, step_base, max_new;
     const int* t;
     const int* stream_id;
+    int* t_slot;                // the slot form (db1_select_tokens_slots): per-slot counters (read and advanced), limits, the rows' slots
+    const int* limit;
+    const int* row_map;
+    int n_slots;
     int* finished;
     int* lengths;
     int* out;
@@ -56,21 +60,45 @@ struct SelArgs {
     int* status;
 };
 
-template <typename T, int NG>
+// SLOTS (db1_select_tokens_slots): logits row blockIdx.x belongs to slot `row` (row_map), which keeps its own counter t_slot[row] below
+// limit[row]; a vacant slot (finished) only hands pad_id on; the selection itself is the same code.
+template <typename T, int NG, bool SLOTS>
 __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
     __shared__ SelShared sh;
-    const int row = blockIdx.x, tid = threadIdx.x;
-    const int t = *a.t;
-    const bool t_ok = t >= 0 && t < a.max_new;
-    if (a.finished[row]) {     // (block-uniform)
-        if (tid == 0) {
-            if (t_ok) a.out[(int64_t)row * a.max_new + t] = a.pad;
-            else a.status[row] |= 2;
-            a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+    const int tid = threadIdx.x;
+    int row = blockIdx.x, t;
+    bool t_ok;
+    if constexpr (SLOTS) {
+        if (a.row_map) row = a.row_map[blockIdx.x];
+        if (row < 0 || row >= a.n_slots) return;     // (a slot that does not exist: nothing to write to)
+        if (a.finished[row]) {     // (block-uniform) vacant: out, t and lengths stay as they are
+            if (tid == 0) a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+            return;
         }
-        return;
+        t = a.t_slot[row];
+        const int lim = a.limit[row];
+        t_ok = t >= 0 && t < lim && lim <= a.max_new;
+        if (!t_ok) {
+            if (tid == 0) {
+                a.status[row] |= 2;
+                a.finished[row] = 1;
+                a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+            }
+            return;
+        }
+    } else {
+        t = *a.t;
+        t_ok = t >= 0 && t < a.max_new;
+        if (a.finished[row]) {     // (block-uniform)
+            if (tid == 0) {
+                if (t_ok) a.out[(int64_t)row * a.max_new + t] = a.pad;
+                else a.status[row] |= 2;
+                a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+            }
+            return;
+        }
     }
-    const T* lg = reinterpret_cast<const T*>(a.logits) + (int64_t)row * a.ld;
+    const T* lg = reinterpret_cast<const T*>(a.logits) + (int64_t)blockIdx.x * a.ld;
     const int lo = max(a.vlo, 0), hi = min(a.vhi, a.V);
     unsigned key[NG][4];
     unsigned long long best = 0;   // (key << 32) | ~column: max = largest key, lowest column on ties
@@ -159,6 +187,10 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
         if (bits & 1) fin = 1;
         else if (tok == a.eos) fin = 1;
         else a.lengths[row] += 1;
+        if constexpr (SLOTS) {      // this workgroup owns the slot: it advances the slot's counter itself and closes the slot at its limit
+            a.t_slot[row] = t + 1;
+            if (t + 1 == a.limit[row]) fin = 1;
+        }
         if (fin) a.finished[row] = 1;
         if (t_ok) a.out[(int64_t)row * a.max_new + t] = tok;
         else bits |= 2;
@@ -198,14 +230,61 @@ extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, i
     a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
     a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
     a.t = t; a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
+    a.t_slot = nullptr; a.limit = nullptr; a.row_map = nullptr; a.n_slots = M;
     a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
     hipStream_t st = (hipStream_t)stream;
     const int ng = sel_ng(V);
     DB1_DISPATCH_DT(dt, T, {
-        if (ng == 1) select_tokens_kernel<T, 1><<<M, SEL_THREADS, 0, st>>>(a);
-        else if (ng == 3) select_tokens_kernel<T, 3><<<M, SEL_THREADS, 0, st>>>(a);
-        else select_tokens_kernel<T, SEL_MAX_NG><<<M, SEL_THREADS, 0, st>>>(a);
+        if (ng == 1) select_tokens_kernel<T, 1, false><<<M, SEL_THREADS, 0, st>>>(a);
+        else if (ng == 3) select_tokens_kernel<T, 3, false><<<M, SEL_THREADS, 0, st>>>(a);
+        else select_tokens_kernel<T, SEL_MAX_NG, false><<<M, SEL_THREADS, 0, st>>>(a);
     });
     DB1_CHECK_LAUNCH("select_tokens");
+    return DB1_OK;
+}
+
+// ------------------------------------------------------------------ the slot form (continuous batching, serving.py)
+extern "C" int db1_select_tokens_slots_supported(int V, int64_t ld, int dt) { return db1_select_tokens_supported(V, ld, dt); }
+
+extern "C" int64_t db1_select_tokens_slots_workspace_bytes(int M, int V, int dt) {
+    (void)M; (void)V; (void)dt;
+    return 0;
+}
+
+extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                                       int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id,
+                                       int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished,
+                                       int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
+                                       const int32_t* row_map, int n_slots, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "select_tokens_slots: dtype %d", dt);
+    if (M <= 0 || M > 65535 || V <= 0 || ld < V || max_new <= 0 || ids_stride < 0 || n_slots <= 0 || (!row_map && n_slots != M))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", M, V, (long long)ld, max_new,
+                 (long long)ids_stride, n_slots, row_map ? "" : " (no row_map: n_slots must equal M)");
+    if (!sel_ng(V)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "select_tokens_slots: V=%d (at most %d)", V, SEL_MAX_NG * 4096);
+    if (!logits || !t || !limit || !finished || !lengths || !out || !next_ids || !status)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: null buffer");
+    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
+    if (!greedy && !(temperature > 0.f && temperature < INFINITY))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: temperature %g", (double)temperature);
+    if (!greedy && (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: top_k %d top_p %g", top_k, (double)top_p);
+    SelArgs a;
+    a.logits = logits; a.ld = ld; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
+    a.inv_t = greedy ? 1.f : 1.f / temperature;
+    a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
+    a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
+    a.t = nullptr; a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
+    a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots;
+    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
+    hipStream_t st = (hipStream_t)stream;
+    const int ng = sel_ng(V);
+    DB1_DISPATCH_DT(dt, T, {
+        if (ng == 1) select_tokens_kernel<T, 1, true><<<M, SEL_THREADS, 0, st>>>(a);
+        else if (ng == 3) select_tokens_kernel<T, 3, true><<<M, SEL_THREADS, 0, st>>>(a);
+        else select_tokens_kernel<T, SEL_MAX_NG, true><<<M, SEL_THREADS, 0, st>>>(a);
+    });
+    DB1_CHECK_LAUNCH("select_tokens_slots");
     return DB1_OK;
 }

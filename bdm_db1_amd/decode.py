@@ -93,6 +93,7 @@ class RingMemory:
         dev = model.dev
         self.kv = [torch.zeros(batch_size, self.cap, 2, model.n_head, model.d_head, device=dev, dtype=torch.bfloat16) for _ in range(model.n_layer)]
         self.state = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.load_status = torch.zeros(1, dtype=torch.int32, device=dev)   # (what load_rows skipped: db1_ring_load_rows' status word)
         from . import ops
         self._ptrs = ops.ring_pointers(self.kv)   # (the layers' base pointers for reorder: made here, never under a capture)
         self.reset()
@@ -115,6 +116,29 @@ class RingMemory:
             for ring, kv in zip(self.kv, dec.kv):
                 ring[:, :mlen].copy_(kv.reshape(self.B, mlen, 2, model.n_head, model.d_head))
             self.state.zero_()
+
+    def load_rows(self, mems, rows: torch.Tensor):
+        """continuous batching: the n requests of a list-form memory (per layer [n, mem_len, d], as ``load`` takes it for all B rows) take
+        over rows ``rows`` (int32 [n] on the device, distinct) of the ring: the projection ``load`` does, then db1_ring_load_rows writes the
+        keys / values relative to the CURRENT origin (read on the device, not zeroed), so the other rows go on undisturbed.  A row outside
+        [0, B) is skipped and recorded in ``self.load_status`` (int32 [1], bit 0)."""
+        from . import ops
+        model, mlen = self.model, int(self.model.mem_len)
+        n = int(rows.numel())
+        if len(mems) != model.n_layer or any(tuple(m.shape) != (n, mlen, model.n_embed) for m in mems):
+            raise ValueError(f"RingMemory.load_rows: expected {model.n_layer} tensors of shape ({n}, {mlen}, {model.n_embed})")
+        if n > self.B:
+            raise ValueError(f"RingMemory.load_rows: {n} rows for a ring of {self.B}")
+        if n == 0:
+            return
+        with torch.no_grad():
+            saved, model._dec_state = model._dec_state, None
+            try:
+                dec = model._decode_begin(list(mems), n, 1, mlen)
+            finally:      # (this runs in the middle of a stream: the model keeps its decode state whatever the projection does)
+                model._dec_state = saved
+            src = [kv.reshape(n, mlen, 2, model.n_head, model.d_head) for kv in dec.kv]
+            ops.ring_load_rows(self.kv, self._ptrs, src, self.state, mlen, rows, self.load_status)
 
     def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
         """beam search: after the call that appended token t - 1, give row b the keys / values of the last ``t`` tokens of row

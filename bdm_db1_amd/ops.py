@@ -606,6 +606,44 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
              P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), _vp(0), 0, stream())
 
 
+def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
+    return bool(lib.load().db1_select_tokens_slots_supported(int(V), int(ld), dt_code(dtype)))
+
+
+def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True,
+                        temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, row_map=None):
+    """``select_tokens`` over SLOTS (db1_select_tokens_slots): ``t`` and ``limit`` are int32 [S], one token counter and one token limit per
+    slot; a live slot's token goes to ``out`` [S, max_new] at column t[slot], then the launch sets t[slot] += 1 and, at t[slot] == limit[slot],
+    finished[slot].  A slot with finished != 0 is vacant: it only gets ``pad_id`` in ``next_ids``.  ``row_map`` (int32 [M], distinct slots) says
+    which slot each row of ``logits2d`` [M, ld] belongs to; None: row i is slot i and S = M.  ``finished`` / ``lengths`` / ``status`` /
+    ``stream_id`` are int32 [S], ``next_ids`` int64 ([S] or a column of [S, q]).  Capturable; raises ValueError on bad arguments before
+    anything is launched."""
+    who, dev, i32 = "select_tokens_slots", logits2d.device, torch.int32
+    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
+                                                 lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
+    if not greedy:
+        if not (temperature > 0 and temperature < float("inf")):
+            raise ValueError(f"{who}: temperature {temperature} must be > 0 when sampling")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"{who}: top_p {top_p} must lie in (0, 1]")
+        if top_k < 0:
+            raise ValueError(f"{who}: top_k {top_k} must be >= 0")
+    S = int(t.numel()) if row_map is not None else M
+    if row_map is not None:
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if S < M:
+            raise ValueError(f"{who}: {M} logits rows for {S} slots")
+    for name, x in (("t", t), ("limit", limit), ("finished", finished), ("lengths", lengths), ("status", status)) + \
+            ((("stream_id", stream_id),) if stream_id is not None else ()):
+        _check_tensor(who, name, x, i32, S, dev)
+    _check_tensor(who, "out", out, i32, (S, -1), dev)
+    _check_next_ids(who, next_ids, S, dev)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lib.call("db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k),
+             float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(limit), P(stream_id),
+             P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), P(row_map), S, _vp(0), 0, stream())
+
+
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:
     return bool(lib.load().db1_beam_step_supported(int(V), int(ld), int(W), dt_code(dtype)))
 
@@ -677,6 +715,42 @@ def ring_reorder(rings, ptrs, state, mlen, t, max_t, parent, W=1, done=None):
         _check_tensor("ring_reorder", name, x, torch.int32, n, dev)
     ws, wsn = _ws("db1_ring_reorder_workspace_bytes", (len(rings), M, max_t, int(slot_bytes)), dev)
     lib.call("db1_ring_reorder", P(ptrs), len(rings), M, W, cap, int(slot_bytes), P(state), mlen, P(t), max_t, P(parent), P(done), ws, wsn, stream())
+
+
+def ring_load_rows(rings, ptrs, src, state, mlen, rows, status):
+    """the projected keys / values ``src`` (per layer a contiguous tensor [n, mlen, ...] of the rings' dtype and slot) of n new requests go to
+    rows ``rows`` (int32 [n], distinct, on the device) of every ring of ``rings`` ([M, cap, ...], ``ptrs`` = ring_pointers(rings)), logical key
+    j to slot (state + j) % cap -- db1_ring_load_rows, one launch, nothing else written.  ``state`` (int32 [1]) READ only.  ``status`` (int32
+    [1]) |= 1 for a row outside [0, M) (skipped), |= 2 for an origin outside [0, cap).  Raises ValueError on bad arguments before anything is
+    launched."""
+    who = "ring_load_rows"
+    if not rings or len(src) != len(rings):
+        raise ValueError(f"{who}: one source tensor per ring expected")
+    r0, s0 = rings[0], src[0]
+    if r0.dim() < 3 or s0.dim() < 3:
+        raise ValueError(f"{who}: rings must be [M, cap, ...] and sources [n, mlen, ...] tensors")
+    M, cap, n, mlen = r0.shape[0], r0.shape[1], s0.shape[0], int(mlen)
+    slot_bytes = r0[0, 0].numel() * r0.element_size()
+    for r in rings:
+        if r.shape != r0.shape or r.dtype != r0.dtype or not r.is_contiguous() or r.device != r0.device or r.data_ptr() % 16:
+            raise ValueError(f"{who}: the rings must be contiguous 16-byte aligned tensors of one shape, dtype and device")
+    for x in src:
+        if tuple(x.shape) != (n, mlen) + tuple(r0.shape[2:]) or x.dtype != r0.dtype or not x.is_contiguous() or x.device != r0.device or \
+                (n and x.data_ptr() % 16):
+            raise ValueError(f"{who}: every source must be a contiguous 16-byte aligned {r0.dtype} tensor of shape "
+                             f"{(n, mlen) + tuple(r0.shape[2:])} on {r0.device}")
+    if not lib.load().db1_ring_load_rows_supported(int(slot_bytes), mlen, cap):
+        raise ValueError(f"{who}: a slot of {slot_bytes} bytes (a multiple of 16 expected) with 0 < mlen ({mlen}) < cap ({cap})")
+    if n > M:
+        raise ValueError(f"{who}: {n} source rows for a ring of {M} rows")
+    dev = r0.device
+    _check_tensor(who, "ptrs (ring_pointers)", ptrs, torch.int64, (len(rings),), dev)
+    for name, x, k in (("state", state, 1), ("rows", rows, n), ("status", status, 1)):
+        _check_tensor(who, name, x, torch.int32, k, dev)
+    if n == 0:
+        return
+    sp = ring_pointers(src)
+    lib.call("db1_ring_load_rows", P(ptrs), P(sp), len(rings), M, n, cap, int(slot_bytes), P(state), mlen, P(rows), P(status), stream())
 
 
 def lmhead_ce(h2d, W, labels, mask, lse, sums, V, dh=None, dW_acc=None, beta_dw=1.0, gscale=1.0, chunk_rows=0):

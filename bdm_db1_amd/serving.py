@@ -1,0 +1,447 @@
+"""Continuous batching for generation: the rows of ONE decode batch are SLOTS that requests pass through.
+
+``generate`` runs M rows in lockstep: they start together, the call lasts as long as its slowest row, and every row has the same prompt shape.
+Captioning or answering over a dataset is neither: most captions end long before ``max_new_tokens`` and real VQA batches hold questions of
+several lengths.  Here a request that ends (EOS, or its own token limit) frees its slot, and a waiting request takes the slot over while the
+other rows go on:
+
+  * the K/V ring advances all rows together from one device-side origin, so a new request moves in by writing its ``mem_len`` projected keys
+    and values relative to the current origin (``RingMemory.load_rows``, db1_ring_load_rows): nothing else in the ring moves;
+  * waiting requests of one prompt shape are prefilled together through the list-form path (``generation._prefill``), requests of other shapes
+    in calls of their own; after a prefill every row holds exactly ``mem_len`` memory entries, whatever its prompt was;
+  * the per-token graph (one ``GraphedRingStep`` of ``slots`` rows, kept on the model) ends in db1_select_tokens_slots: every slot has its own
+    token counter and limit, advanced by the launch itself, and a vacant slot only feeds ``pad_id`` forward.  The same kernel, given the
+    slots of the newly admitted rows (``row_map``), picks their token 0 from the prefill's last-position logits straight into their slots.
+
+A request's tokens depend on its prompt, its stream id, the seed and its token index: not on the slot it got or on when it was admitted.
+What the host decides -- which slot, which requests share a prefill, the order results come back in -- is ``SlotScheduler``, plain Python.
+"""
+from __future__ import annotations
+
+import contextlib
+import dataclasses
+from collections import OrderedDict
+from typing import Iterable, Iterator, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .generation import (GenerationConfig, _batch_size, _check_chain, _eval_mode, _need_memory, _prefill, _ring_ok, _text_window, _vocab_window,
+                         caption_prompt, question_prompt)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------- requests
+@dataclasses.dataclass
+class Request:
+    """one row of a prompt batch: ``index`` (its place in the results, and its default Philox stream), the batch and the row in it, its
+    token limit, and ``key``: requests with equal keys have one prompt shape and can share a prefill"""
+    index: int
+    limit: int
+    key: tuple
+    prompt: object = None
+    row: int = 0
+
+
+@dataclasses.dataclass
+class _Item:
+    """a prompt batch whose rows carry given result indices (``answer_stream``: the rows of one VQA batch, regrouped by question length)"""
+    prompt: object
+    indices: object
+    limit: Optional[int] = None
+
+
+_SEQ_FIELDS = ("text_seq", "prompt_seq", "img_seq")            # what makes a prompt's shape
+# the fields of a prompt batch that hold one entry per row (first dimension = the batch); every other field is handed on as it is
+_PER_ROW_FIELDS = ("position_id", "attention_mask", "loss_mask", "label", "text_seq", "text_len", "prompt_seq", "img_seq", "img_id_seq",
+                   "ques_id_seq", "ques_len")
+# attributes next to the dataclass fields (caption_prompt / question_prompt carry them over): one id per patch, image after image
+_PATCH_FIELDS = ("vision_row_ids", "vision_col_ids")
+
+
+def _shape_key(prompt) -> tuple:
+    key = [type(prompt).__name__]
+    for f in _SEQ_FIELDS:
+        v = getattr(prompt, f, None)
+        if v is not None:
+            v = v if torch.is_tensor(v) else np.asarray(v)
+            key.append((f,) + tuple(int(n) for n in v.shape[1:]))
+    return tuple(key)
+
+
+def _requests(items: Iterable, cfg: GenerationConfig) -> Iterator[Request]:
+    """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item) as Requests, numbered in order; raises ValueError for a limit outside
+    [1, cfg.max_new_tokens] and what ``generate`` raises for a prompt batch that is not one shape"""
+    nxt = 0
+    for item in items:
+        indices = None
+        if isinstance(item, _Item):
+            prompt, limit, indices = item.prompt, item.limit, item.indices
+        elif isinstance(item, tuple):
+            if len(item) != 2:
+                raise ValueError("generate_stream: a request is a prompt or (prompt, max_new_tokens)")
+            prompt, limit = item
+        else:
+            prompt, limit = item, None
+        limit = int(cfg.max_new_tokens if limit is None else limit)
+        if not 1 <= limit <= int(cfg.max_new_tokens):
+            raise ValueError(f"generate_stream: a request's max_new_tokens {limit} must lie in [1, config.max_new_tokens = {cfg.max_new_tokens}]")
+        G = _batch_size(prompt)
+        key = _shape_key(prompt)
+        if indices is None:
+            indices = range(nxt, nxt + G)
+        elif len(indices) != G:
+            raise ValueError(f"generate_stream: {len(indices)} indices for a prompt batch of {G} rows")
+        for r, i in enumerate(indices):
+            yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r)
+            nxt = max(nxt, int(i) + 1)
+
+
+def _take(prompt, name: str, G: int, rows):
+    """rows ``rows`` of field ``name`` of a prompt batch of G rows: a per-row field is index-selected, a per-patch field row block by row
+    block, anything else (and None) is handed on as it is"""
+    v = getattr(prompt, name, None)
+    if v is None or not (name in _PER_ROW_FIELDS or name in _PATCH_FIELDS):
+        return v
+    v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+    idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=v.device)
+    if name in _PATCH_FIELDS:
+        if G == 0 or v.numel() % G:
+            raise ValueError(f"generate_stream: {name} holds {v.numel()} ids for a batch of {G} rows")
+        return v.reshape(G, -1).index_select(0, idx).reshape(-1)
+    if v.dim() < 1 or v.shape[0] != G:
+        raise ValueError(f"generate_stream: {name} of shape {tuple(v.shape)} in a batch of {G} rows")
+    return v.index_select(0, idx)
+
+
+def _gather(reqs: List[Request]):
+    """ONE prompt batch holding the rows of ``reqs`` (one shape key), in order"""
+    first = reqs[0].prompt
+    if all(r.prompt is first for r in reqs) and [r.row for r in reqs] == list(range(_batch_size(first))):
+        return first
+    runs = []    # (consecutive requests of one batch are taken together)
+    for r in reqs:
+        if runs and runs[-1][0] is r.prompt:
+            runs[-1][1].append(r.row)
+        else:
+            runs.append((r.prompt, [r.row]))
+
+    def field(name):
+        parts = [_take(p, name, _batch_size(p), rows) for p, rows in runs]
+        if not torch.is_tensor(parts[0]) or not (name in _PER_ROW_FIELDS or name in _PATCH_FIELDS):
+            return parts[0]
+        return parts[0] if len(parts) == 1 else torch.cat([x.to(parts[0].device) for x in parts], 0)
+
+    x = type(first)(**{f.name: field(f.name) for f in dataclasses.fields(first)})
+    for n in _PATCH_FIELDS:
+        if hasattr(first, n):
+            setattr(x, n, field(n))
+    return x
+
+
+# ------------------------------------------------------------------------------------------------------------- the host's bookkeeping
+class SlotScheduler:
+    """Which request sits in which slot.  ``requests``: an iterable of objects with ``index``, ``limit`` and ``key``, consumed lazily and in
+    order (first come, first served).  The loop of ``generate_stream`` is
+
+        groups = admit()            # free slots -> waiting requests, grouped by key (one prefill each)
+        k = replays_due(every)      # how many token steps to run before looking at the device again
+        advance(k)
+        done = harvest(finished)    # the device's ``finished`` vector -> the (slot, request) pairs that ended, slots freed
+
+    until ``idle()``.  No device, no torch: tests drive it with scripted ``finished`` vectors."""
+
+    def __init__(self, slots: int, requests: Iterable):
+        if int(slots) < 1:
+            raise ValueError(f"slots {slots} must be >= 1")
+        self.slots = int(slots)
+        self.owner: List[Optional[object]] = [None] * self.slots
+        self.picked = [0] * self.slots       # tokens the slot's request has had picked so far, as far as the host can know (no EOS seen)
+        self._it = iter(requests)
+        self.admitted = 0
+
+    def free_slots(self) -> List[int]:
+        return [s for s in range(self.slots) if self.owner[s] is None]
+
+    def idle(self) -> bool:
+        return all(o is None for o in self.owner)
+
+    def admit(self) -> List[Tuple[tuple, List[Tuple[int, object]]]]:
+        """the next waiting requests, one per free slot (lowest slot first, in request order) -> [(key, [(slot, request), ...]), ...]: one
+        entry per prompt shape, in order of first appearance"""
+        groups: "OrderedDict[tuple, list]" = OrderedDict()
+        for s in self.free_slots():
+            req = next(self._it, None)
+            if req is None:
+                break
+            self.owner[s], self.picked[s] = req, 1     # (the prefill picks token 0)
+            self.admitted += 1
+            groups.setdefault(req.key, []).append((s, req))
+        return list(groups.items())
+
+    def replays_due(self, every: int) -> int:
+        """``every``, or fewer when every occupied slot reaches its limit sooner (0: nothing left to run)"""
+        left = [self.owner[s].limit - self.picked[s] for s in range(self.slots) if self.owner[s] is not None]
+        return max(0, min(int(every), max(left, default=0)))
+
+    def advance(self, k: int):
+        for s in range(self.slots):
+            if self.owner[s] is not None:
+                self.picked[s] = min(self.owner[s].limit, self.picked[s] + int(k))
+
+    def harvest(self, finished) -> List[Tuple[int, object]]:
+        """the occupied slots whose ``finished`` entry is set, freed -> [(slot, request)] by ascending request index (the yield order)"""
+        done = [(s, self.owner[s]) for s in range(self.slots) if self.owner[s] is not None and int(finished[s]) != 0]
+        for s, _ in done:
+            self.owner[s] = None
+        return sorted(done, key=lambda sr: sr[1].index)
+
+
+# ----------------------------------------------------------------------------------------------------------------------- the device state
+class _SlotState:
+    """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row"""
+
+    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int):
+        i32 = dict(dtype=torch.int32, device=model.dev)
+        self.M, self.cfg, self.V, self.hi, self.dev = slots, cfg, V, hi, model.dev
+        self.t = torch.zeros(slots, **i32)
+        self.limit = torch.ones(slots, **i32)
+        self.finished = torch.ones(slots, **i32)       # (vacant)
+        self.lengths = torch.zeros(slots, **i32)
+        self.status = torch.zeros(slots, **i32)
+        self.stream_id = torch.zeros(slots, **i32)
+        self.out = torch.full((slots, cfg.max_new_tokens), cfg.pad_id, **i32)
+
+    def start(self):
+        self.finished.fill_(1)
+        for x in (self.t, self.lengths, self.status):
+            x.zero_()
+
+    def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int]) -> torch.Tensor:
+        """fresh state for the requests moving into ``slots`` -> the slots as the int32 device vector ``select`` and ``load_rows`` take"""
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
+        for x in (self.t, self.lengths, self.status, self.finished):
+            x.index_fill_(0, idx, 0)
+        self.out.index_fill_(0, idx, self.cfg.pad_id)
+        self.limit.index_copy_(0, idx, torch.tensor(limits, dtype=torch.int32).to(self.dev))
+        self.stream_id.index_copy_(0, idx, torch.from_numpy(np.asarray(stream_ids, dtype=np.int64).astype(np.int32)).to(self.dev))
+        return idx.to(torch.int32)
+
+    def select(self, logits2d, next_ids, row_map=None):
+        c = self.cfg
+        ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V,
+                                vocab_lo=c.vocab_lo, vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p,
+                                seed=c.seed, eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id,
+                                row_map=row_map)
+
+    def read(self, slots: List[int]):
+        """(out rows, [t, length, status] rows) of ``slots`` on the host"""
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
+        meta = torch.stack((self.t, self.lengths, self.status), 1).index_select(0, idx).cpu()
+        return self.out.index_select(0, idx).cpu(), meta
+
+
+class _SlotGenerator:
+    """the ring of ``slots`` rows, the slot state and the captured per-token graph (forward + db1_select_tokens_slots) for one (model, key)"""
+
+    def __init__(self, model, key):
+        from .decode import GraphedRingStep, RingMemory
+        self.key = key
+        self.busy = False        # (a stream is running over this state: generate_stream refuses a second one)
+        self.state = _SlotState(model, *key)
+        self.ring = RingMemory(model, self.state.M)
+        self.step = GraphedRingStep(model, self.state.M, 1, memory=self.ring, epilogue=self.epilogue)
+
+    def epilogue(self, step, logits):
+        self.state.select(logits[:, -1], step.ids[:, 0])
+
+
+def _slot_generator(model, key) -> _SlotGenerator:
+    """the generator kept on the model if it was built from ``key`` and the weights it captured, else a new one (as ``_ring_generator``)"""
+    gen = getattr(model, "_slot_generator", None)
+    if gen is not None and gen.busy:
+        raise RuntimeError("generate_stream: another stream is still running on this model (one stream at a time: finish or close() it first)")
+    if gen is None or gen.key != key or gen.step._version != model._wversion:
+        model._slot_generator = None        # (free the old ring before the new one is allocated)
+        gen = _SlotGenerator(model, key)
+        model._slot_generator = gen
+    return gen
+
+
+@contextlib.contextmanager
+def _work(model):
+    """device work between two yields: eval mode and no autograd, both restored before the caller's code runs again"""
+    with torch.no_grad(), _eval_mode(model):
+        yield
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ the driver
+def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig] = None, slots: int = 8, stream_ids=None,
+                    stats: Optional[dict] = None, replay: bool = True) -> Iterator[Tuple[int, torch.Tensor, int]]:
+    """Generate for a stream of requests over ``slots`` recycled rows; yields ``(index, ids int32 [limit], length)`` on the host as requests
+    finish (requests that are found finished at the same look come in index order).  ``ids[:length]`` are the tokens before EOS, then EOS,
+    then ``pad_id``.
+
+    ``requests``: an iterable (consumed lazily) of prompts -- each ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of one or
+    more rows of one shape, every row a request -- or ``(prompt, max_new_tokens)`` with ``max_new_tokens <= config.max_new_tokens`` as the
+    rows' own limit.  Items may differ in shape and kind.  Requests are numbered in order; ``stream_ids`` (indexable by that number; default:
+    the number itself) gives every request its Philox stream.  Ring path only (bf16, ``use_decode``, d_head 128, mem_len > 0): anything else
+    raises ValueError here, before anything is launched, and so does a bad first request list when ``requests`` is a list or tuple.
+    The host looks at the device every ``config.sync_every`` token steps.  ``replay`` False: the same forward and epilogue launched eagerly
+    over the same ring instead of as a graph replay.  ``stats`` (a dict) receives ``replays`` (token steps), ``prefill_calls``,
+    ``admitted``, ``occupancy`` = live row-steps / (replays * slots) and ``no_candidate``: the requests that ended early because a step had no
+    finite logit in the window (``pad_id`` written, as ``generate`` does; they come back like any other request).  ONE stream at a time per
+    model: the slots, the ring and the graph are kept on the model, so a second ``generate_stream`` whose first result is asked for while
+    another is still running raises RuntimeError (run the first to its end or ``close()`` it)."""
+    cfg = config or GenerationConfig()
+    _need_memory(model, "generate_stream")
+    if not _ring_ok(model):
+        raise ValueError("generate_stream needs a bf16 model with the K/V-cached decode path (use_decode, d_head 128, mem_len > 0)")
+    slots = int(slots)
+    if not 1 <= slots <= 65535:
+        raise ValueError(f"slots {slots} must lie in [1, 65535]")
+    V, hi = _vocab_window(model, cfg)
+    if not ops.select_tokens_slots_supported(V, V, model.compute_dtype):
+        raise ValueError(f"db1_select_tokens_slots does not support a vocabulary of {V}")
+    if isinstance(requests, (list, tuple)):
+        for _ in _requests(requests, cfg):     # (a list can be checked as a whole before the first launch)
+            pass
+    return _stream(model, _requests(requests, cfg), cfg, slots, V, hi, stream_ids, stats, replay)
+
+
+def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
+    sched = SlotScheduler(slots, reqs)
+    counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
+    live_steps = 0
+
+    def report():
+        counts["admitted"] = sched.admitted
+        counts["occupancy"] = live_steps / (counts["replays"] * slots) if counts["replays"] else 0.0
+        if stats is not None:
+            stats.update(counts)
+
+    gen = None
+    try:
+        while True:
+            results = []
+            with _work(model):
+                if gen is None:
+                    gen = _slot_generator(model, (slots, cfg, V, hi))
+                    gen.busy = True
+                    gen.state.start()
+                    gen.ring.load_status.zero_()
+                st, step = gen.state, gen.step
+                for _, members in sched.admit():
+                    rows = [s for s, _ in members]
+                    rs = [r for _, r in members]
+                    # one prefill for the group; its last position picks token 0 of every request straight into its slot, its memory moves in
+                    logits, mems = _prefill(model, _gather(rs), len(rs))
+                    idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs])
+                    st.select(logits[:, -1], step.ids[:, 0], row_map=idx)
+                    gen.ring.load_rows(mems, idx)
+                    del logits, mems
+                    counts["prefill_calls"] += 1
+                k = sched.replays_due(cfg.sync_every)
+                for _ in range(k):
+                    if replay:
+                        step(step.ids)
+                    else:
+                        logits, _, _ = model([step.x], compute_loss=False, mems=gen.ring)
+                        gen.epilogue(step, logits)
+                sched.advance(k)
+                counts["replays"] += k
+                if not sched.idle():
+                    done = sched.harvest(st.finished.cpu())          # (the host's look at the device)
+                    if done:
+                        out, meta = st.read([s for s, _ in done])
+                        for j, (_, r) in enumerate(done):
+                            t, length, status = (int(v) for v in meta[j])
+                            if status & 2:
+                                raise RuntimeError("db1_select_tokens_slots: a slot's token counter left [0, limit)")
+                            counts["no_candidate"] += status & 1
+                            live_steps += t - 1
+                            results.append((r.index, out[j, :r.limit].clone(), length))
+                finish = sched.idle() and not results
+                if finish:     # nothing waits (admit found no request for the free slots) and every slot is vacant
+                    step.check(synchronize=True)
+                    if not replay:
+                        _check_chain(model)
+                    if int(gen.ring.load_status.cpu()) != 0:
+                        raise RuntimeError("db1_ring_load_rows: a request was given a row outside the ring")
+            report()
+            for r in results:
+                yield r
+            if finish:
+                return
+    finally:
+        if gen is not None:
+            gen.busy = False
+
+
+def generate_many(model, requests: Iterable, config: Optional[GenerationConfig] = None, **kw) -> Tuple[List[torch.Tensor], List[int]]:
+    """``generate_stream`` run to its end -> (ids, lengths) in request order: ``ids[i]`` int32 [request i's limit], ``lengths[i]`` an int"""
+    got = {i: (ids, n) for i, ids, n in generate_stream(model, requests, config, **kw)}
+    order = sorted(got)
+    return [got[i][0] for i in order], [got[i][1] for i in order]
+
+
+def _split(item):
+    return item if isinstance(item, tuple) else (item, None)
+
+
+def caption_stream(model, ic_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
+    """``generate_stream`` over ``ICTaskInput`` batches (or ``(batch, max_new_tokens)``): the prompts of ``caption_prompt``, tokens in the text
+    vocabulary unless ``cfg`` says otherwise; every image is one request"""
+    cfg = _text_window(model, cfg or GenerationConfig())
+
+    def items():
+        for it in ic_batches:
+            b, limit = _split(it)
+            yield caption_prompt(b), limit
+
+    return generate_stream(model, items(), cfg, **kw)
+
+
+def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
+    """``generate_stream`` over ``VQATaskInput`` batches (or ``(batch, max_new_tokens)``) whose questions may differ in length
+    (``question_prompts``), tokens in the text vocabulary unless ``cfg`` says otherwise; every question is one request, and the results'
+    indices number the batches' rows in their original order"""
+    cfg = _text_window(model, cfg or GenerationConfig())
+
+    def items():
+        base = 0
+        for it in vqa_batches:
+            b, limit = _split(it)
+            for prompt, rows in question_prompts(b):
+                yield _Item(prompt, [base + int(r) for r in rows], limit)
+            base += _batch_size(b)
+
+    return generate_stream(model, items(), cfg, **kw)
+
+
+def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
+    """the generation prompts of a ``VQATaskInput`` batch whose questions differ in length: one ``question_prompt`` per distinct ``ques_len``
+    (ascending) -> [(prompt, rows)]: ``rows`` (int64, ascending) are the batch rows the prompt's rows come from.  Every row of the batch is in
+    exactly one prompt.  ``ques_len`` None: one prompt, the whole ``text_seq`` as the question."""
+    from .data import VQATaskInput
+    G = _batch_size(vqa_batch)
+    ql = getattr(vqa_batch, "ques_len", None)
+    if ql is None:
+        return [(question_prompt(vqa_batch), np.arange(G, dtype=np.int64))]
+    ql = np.asarray(torch.as_tensor(ql).cpu()).reshape(-1).astype(np.int64)
+    if ql.size != G:
+        raise ValueError(f"question_prompts: {ql.size} question lengths for a batch of {G} rows")
+    q = vqa_batch.text_seq
+    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
+    if ql.min() < 0 or ql.max() > q.shape[1]:
+        raise ValueError(f"question_prompts: question lengths must lie in [0, {q.shape[1]}]")
+    out = []
+    for n in np.unique(ql):
+        rows = np.nonzero(ql == n)[0].astype(np.int64)
+        x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_take(vqa_batch, "prompt_seq", G, rows),
+                         img_seq=_take(vqa_batch, "img_seq", G, rows), text_seq=_take(vqa_batch, "text_seq", G, rows)[:, :int(n)])
+        for f in _PATCH_FIELDS:
+            if hasattr(vqa_batch, f):
+                setattr(x, f, _take(vqa_batch, f, G, rows))
+        out.append((x, rows))
+    return out

@@ -547,6 +547,25 @@ int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int 
                       int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
                       const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
                       int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+/* The slot form of db1_select_tokens (continuous batching: every row of a decode batch is a SLOT that requests pass through).  The
+ * selection rule is db1_select_tokens' own, unchanged; the bookkeeping is per slot:
+ *   - logits row i belongs to slot row_map[i] (int32 [M], distinct; NULL: slot i, and then n_slots == M).  t, limit, stream_id, finished,
+ *     lengths, status ([n_slots]), out ([n_slots, max_new]) and next_ids are indexed by the SLOT; a row_map entry outside [0, n_slots) is skipped;
+ *   - a slot with finished[slot] != 0 is vacant: pad_id goes to next_ids[slot * ids_stride] and nothing else is touched (not out, t, lengths);
+ *   - a live slot needs 0 <= t[slot] < limit[slot] <= max_new; otherwise status bit 1, finished[slot] = 1, pad_id to next_ids, nothing else;
+ *   - else the token is chosen as db1_select_tokens chooses it, the Philox counter being (col / 4, stream_id[slot] (NULL: slot),
+ *     step_base + t[slot], 0xE0000100): a request's draws depend on its logits, its stream id, the seed and its own token index only, not on
+ *     the slot it sits in or on when it was admitted.  The token goes to out[slot * max_new + t[slot]] and to next_ids[slot * ids_stride];
+ *     EOS / no candidate / lengths as there; then t[slot] += 1, WRITTEN by the launch (one workgroup owns a slot: no atomics, and a graph
+ *     replay needs no captured t += 1), and t[slot] == limit[slot] sets finished[slot].
+ * Same V limit and logits formats as db1_select_tokens (_supported); no workspace (the query returns 0). */
+int db1_select_tokens_slots_supported(int V, int64_t ld, int dt);
+int64_t db1_select_tokens_slots_workspace_bytes(int M, int V, int dt);
+int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                            float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, int32_t* t,
+                            const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                            int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, void* ws,
+                            int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ beam search (captions / answers / text; tests/beam_rule.py restates
  * the rule in NumPy).  G groups (prompts) of W beams (1 <= W <= 16), M = G * W rows, row b = g * W + j; step t = 0 .. max_new - 1 chooses
@@ -586,6 +605,17 @@ int db1_ring_reorder_supported(int64_t slot_bytes);
 int64_t db1_ring_reorder_workspace_bytes(int n_layers, int M, int max_t, int64_t slot_bytes);
 int db1_ring_reorder(const void* const* rings, int n_layers, int M, int W, int cap, int64_t slot_bytes, const int32_t* state, int mlen,
                      const int32_t* t, int max_t, const int32_t* parent, const int32_t* done, void* ws, int64_t ws_bytes, void* stream);
+/* A new request takes over rows of a RingMemory: rings as for db1_ring_reorder, src = a DEVICE array of n_layers pointers to the projected
+ * keys / values [n, mlen, slot] of n requests, rows = int32 [n], distinct target rows in [0, M).  Logical key j < mlen of source row i goes to
+ * slot (state[0] + j) % cap of row rows[i] in every layer (state = the ring origin, read on the device: no host synchronisation); nothing
+ * else is written: the other rows and the cap - mlen slots outside the window of the loaded rows stay as they are.  ONE launch, a pure copy in
+ * 16-byte words.  A rows[i] outside [0, M) is skipped and sets bit 0 of *status (int32 [1], |=); an origin outside [0, cap) copies nothing and
+ * sets bit 1.  n == 0 is a no-op.  Requires slot_bytes % 16 == 0 and 0 < mlen < cap (_supported; DB1_ERR_UNSUPPORTED otherwise).  Every ring and
+ * every source base pointer must be 16-byte aligned: they sit in device arrays the entry point cannot read, so this is the CALLER's to keep
+ * (as for db1_ring_reorder; ops.ring_load_rows checks it). */
+int db1_ring_load_rows_supported(int64_t slot_bytes, int mlen, int cap);
+int db1_ring_load_rows(const void* const* rings, const void* const* src, int n_layers, int M, int n, int cap, int64_t slot_bytes,
+                       const int32_t* state, int mlen, const int32_t* rows, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
  * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window

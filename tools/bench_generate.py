@@ -16,7 +16,17 @@ With --num-beams W the arguments are group counts G (default 1 16), and per G (M
   * db1_beam_step alone (bf16 logits [M, 33 025], the text window) and db1_ring_reorder alone at t = 29 (every row takes its neighbour's
     history: 2 x M x 29 x n_layer slots read and written), device time per call from events over 50 calls.
 
-    python tools/bench_generate.py --num-beams 4 [G ...]"""
+    python tools/bench_generate.py --num-beams 4 [G ...]
+
+With --stream: continuous batching (serving.caption_stream) against lockstep batches.  256 one-image requests, 64 slots, per-request token
+limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS); one JSON line with
+
+  * the per-replay cost of the slot graph (forward + db1_select_tokens_slots, every slot live) and of generate's graph at M = 64;
+  * the total time of the stream and of generate_captions over the same requests in batches of 64 in order, each run to its longest limit
+    (prefills included in both), the replay counts, the occupancy, and what the admissions cost (total - replays x per-replay cost);
+  * db1_ring_load_rows alone: 16 rows into a ring of 64, device time from events, bytes read + written.
+
+    python tools/bench_generate.py --stream [requests [slots]]"""
 import dataclasses
 import json
 import os
@@ -158,7 +168,124 @@ def beam_main(W, Gs):
         print(json.dumps(rec), flush=True)
 
 
+def stream_main(n_req=256, slots=64):
+    from bdm_db1_amd import caption_stream
+    from bdm_db1_amd.decode import RingMemory
+    from bdm_db1_amd.serving import _slot_generator
+    from bdm_db1_amd.generation import _text_window, _vocab_window
+    limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
+    cfg = GenerationConfig(max_new_tokens=N_NEW)
+    batches = [batch(slots + k) for k in range((n_req + slots - 1) // slots)]       # (another seed per batch)
+    rows = lambda b, r: ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=b.prompt_seq[r:r + 1],
+                                    img_seq=b.img_seq[r:r + 1], text_seq=None)
+    reqs = [(rows(batches[i // slots], i % slots), int(limits[i])) for i in range(n_req)]
+    rec = {"requests": n_req, "slots": slots, "limits": "uniform 5..30, seed 2024", "mean_limit": round(float(limits.mean()), 2)}
+
+    def timed(fn):
+        fn()                                   # capture + warm-up
+        t = 1e30
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            t = min(t, time.perf_counter() - t0)
+        return t * 1e3
+
+    # lockstep: batches of ``slots`` in order, each to its longest limit.  generate keeps ONE graph per (rows, config), so a batch with another
+    # longest limit re-captures it: every batch is timed after a warm-up call of its own (no capture inside a timed call) and the times add up;
+    # what the captures of a real pass over these batches would cost is reported next to it
+    longest = [int(limits[i:i + slots].max()) for i in range(0, n_req, slots)]
+    static_ms, capture_ms, prev = 0.0, 0.0, None
+    for b, n, i in zip(batches, longest, range(0, n_req, slots)):
+        k = min(slots, n_req - i)
+        bb = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=b.prompt_seq[:k], img_seq=b.img_seq[:k],
+                         text_seq=None)
+        c = dataclasses.replace(cfg, max_new_tokens=n)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        generate_captions(model, bb, c)                  # warm-up; captures when (k, n) differs from the batch before
+        torch.cuda.synchronize()
+        first = (time.perf_counter() - t0) * 1e3
+        best = 1e30
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            generate_captions(model, bb, c)
+            torch.cuda.synchronize()
+            best = min(best, (time.perf_counter() - t0) * 1e3)
+        static_ms += best
+        if (k, n) != prev:
+            capture_ms += first - best
+        prev = (k, n)
+    rec["static_longest_limits"] = longest
+    rec["static_total_ms"] = round(static_ms, 2)
+    rec["static_capture_ms_not_in_total"] = round(capture_ms, 2)
+    rec["static_replays"] = sum(n - 1 for n in longest)
+    gen = model._generator
+    gen.state.start()
+    for _ in range(3):
+        gen.step(gen.step.ids)
+    gen.state.start()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        gen.step(gen.step.ids)
+    torch.cuda.synchronize()
+    rec["generate_graph_replay_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
+    rec["generate_graph_M"] = gen.state.M
+    model._generator = None
+    del gen
+    torch.cuda.empty_cache()
+
+    stats = {}
+
+    def stream():
+        for _ in caption_stream(model, reqs, cfg, slots=slots, stats=stats):
+            pass
+    rec["stream_total_ms"] = round(timed(stream), 2)
+    rec.update(stream_replays=stats["replays"], prefill_calls=stats["prefill_calls"], occupancy=round(stats["occupancy"], 4))
+    tcfg = _text_window(model, cfg)
+    V, hi = _vocab_window(model, tcfg)
+    sg = _slot_generator(model, (slots, tcfg, V, hi))
+    st = sg.state
+
+    def live():
+        st.finished.zero_()
+        st.t.zero_()
+        st.limit.fill_(N_NEW)
+    live()
+    for _ in range(3):
+        sg.step(sg.step.ids)
+    live()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        sg.step(sg.step.ids)
+    torch.cuda.synchronize()
+    rec["slot_graph_replay_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
+    sg.step.check(synchronize=True)
+    st.start()
+    rec["slot_over_generate_replay"] = round(rec["slot_graph_replay_ms"] / rec["generate_graph_replay_ms"], 4)
+    rec["replay_count_ratio_static_over_stream"] = round(rec["static_replays"] / stats["replays"], 4)
+    rec["time_ratio_static_over_stream"] = round(rec["static_total_ms"] / rec["stream_total_ms"], 4)
+    rec["stream_admission_ms"] = round(rec["stream_total_ms"] - stats["replays"] * rec["slot_graph_replay_ms"], 2)
+    rec["static_prefill_ms"] = round(rec["static_total_ms"] - rec["static_replays"] * rec["generate_graph_replay_ms"], 2)
+    # db1_ring_load_rows alone
+    ring, n, mlen = sg.ring, min(16, slots), int(model.mem_len)
+    src = [torch.randn(n, mlen, 2, model.n_head, model.d_head, device=dev).to(torch.bfloat16) for _ in range(model.n_layer)]
+    idx = torch.arange(0, n, dtype=torch.int32, device=dev) * (slots // n)
+    us = device_us(lambda: ops.ring_load_rows(ring.kv, ring._ptrs, src, ring.state, mlen, idx, ring.load_status))
+    moved = 2 * n * mlen * model.n_layer * src[0][0, 0].numel() * 2
+    rec.update(ring_load_rows_us=round(us, 2), ring_load_rows_MB=round(moved / 1e6, 1), ring_load_rows_TBps=round(moved / (us * 1e-6) / 1e12, 3))
+    print(json.dumps(rec), flush=True)
+
+
 args = sys.argv[1:]
+if "--stream" in args:
+    rest = [int(a) for a in args if a != "--stream"]
+    stream_main(*rest[:2])
+    sys.exit(0)
 if "--num-beams" in args:
     i = args.index("--num-beams")
     W = int(args[i + 1])
