@@ -210,37 +210,61 @@ extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
     return 0;
 }
 
+template <typename T, bool SLOTS>
+static void sel_dispatch(int ng, const SelArgs& a, int M, hipStream_t st) {
+    if (ng == 1) select_tokens_kernel<T, 1, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
+    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
+    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
+}
+
+// The host side both entry points share: `a` arrives filled; validation (in one order for both, so an argument list that is wrong in two ways
+// fails with the same code as ever), 1 / temperature, the NG / SLOTS dispatch over M workgroups, the launch check.
+static int sel_launch(const char* who, bool slots, SelArgs& a, int M, int dt, float temperature, void* stream) {
+    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
+    if (M <= 0 || M > 65535 || a.V <= 0 || a.ld < a.V || a.max_new <= 0 || a.ids_stride < 0 || a.n_slots <= 0 || (!a.row_map && a.n_slots != M))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", who, M, a.V, (long long)a.ld, a.max_new,
+                 (long long)a.ids_stride, a.n_slots, slots && !a.row_map ? " (no row_map: n_slots must equal M)" : "");
+    const int ng = sel_ng(a.V);
+    if (!ng) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d (at most %d)", who, a.V, SEL_MAX_NG * 4096);
+    if (!a.logits || !(slots ? a.t_slot && a.limit : a.t != nullptr) || !a.finished || !a.lengths || !a.out || !a.next_ids || !a.status)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
+    if (a.vlo < 0 || a.vhi > a.V || a.vlo >= a.vhi)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, a.vlo, a.vhi, a.V);
+    if (!a.greedy && !(temperature > 0.f && temperature < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: temperature %g", who, (double)temperature);
+    if (!a.greedy && (a.top_k < 0 || !(a.top_p > 0.f && a.top_p <= 1.f)))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_k %d top_p %g", who, a.top_k, (double)a.top_p);
+    a.inv_t = a.greedy ? 1.f : 1.f / temperature;
+    hipStream_t st = (hipStream_t)stream;
+    DB1_DISPATCH_DT(dt, T, {
+        if (slots) sel_dispatch<T, true>(ng, a, M, st);
+        else sel_dispatch<T, false>(ng, a, M, st);
+    });
+    DB1_CHECK_LAUNCH(who);
+    return DB1_OK;
+}
+
+// every field but inv_t (sel_launch) and the counters (t | t_slot, limit, row_map, n_slots: the entry points)
+static SelArgs sel_args(const void* logits, int V, int64_t ld, int vocab_lo, int vocab_hi, int top_k, float top_p, int greedy, uint32_t seed_lo,
+                        uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* stream_id, int32_t* finished, int32_t* lengths,
+                        int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status) {
+    SelArgs a = {};
+    a.logits = logits; a.ld = ld; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
+    a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
+    a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
+    a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
+    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
+    return a;
+}
+
 extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
                                  float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
                                  const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                                  int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "select_tokens: dtype %d", dt);
-    if (M <= 0 || M > 65535 || V <= 0 || ld < V || max_new <= 0 || ids_stride < 0)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld", M, V, (long long)ld, max_new, (long long)ids_stride);
-    if (!sel_ng(V)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "select_tokens: V=%d (at most %d)", V, SEL_MAX_NG * 4096);
-    if (!logits || !t || !finished || !lengths || !out || !next_ids || !status) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: null buffer");
-    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
-    if (!greedy && !(temperature > 0.f && temperature < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: temperature %g", (double)temperature);
-    if (!greedy && (top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens: top_k %d top_p %g", top_k, (double)top_p);
-    SelArgs a;
-    a.logits = logits; a.ld = ld; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
-    a.inv_t = greedy ? 1.f : 1.f / temperature;
-    a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
-    a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
-    a.t = t; a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
-    a.t_slot = nullptr; a.limit = nullptr; a.row_map = nullptr; a.n_slots = M;
-    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
-    hipStream_t st = (hipStream_t)stream;
-    const int ng = sel_ng(V);
-    DB1_DISPATCH_DT(dt, T, {
-        if (ng == 1) select_tokens_kernel<T, 1, false><<<M, SEL_THREADS, 0, st>>>(a);
-        else if (ng == 3) select_tokens_kernel<T, 3, false><<<M, SEL_THREADS, 0, st>>>(a);
-        else select_tokens_kernel<T, SEL_MAX_NG, false><<<M, SEL_THREADS, 0, st>>>(a);
-    });
-    DB1_CHECK_LAUNCH("select_tokens");
-    return DB1_OK;
+    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
+                         lengths, out, max_new, next_ids, ids_stride, status);
+    a.t = t; a.n_slots = M;
+    return sel_launch("select_tokens", false, a, M, dt, temperature, stream);
 }
 
 // ------------------------------------------------------------------ the slot form (continuous batching, serving.py)
@@ -257,34 +281,8 @@ extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t
                                        int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
                                        const int32_t* row_map, int n_slots, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "select_tokens_slots: dtype %d", dt);
-    if (M <= 0 || M > 65535 || V <= 0 || ld < V || max_new <= 0 || ids_stride < 0 || n_slots <= 0 || (!row_map && n_slots != M))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", M, V, (long long)ld, max_new,
-                 (long long)ids_stride, n_slots, row_map ? "" : " (no row_map: n_slots must equal M)");
-    if (!sel_ng(V)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "select_tokens_slots: V=%d (at most %d)", V, SEL_MAX_NG * 4096);
-    if (!logits || !t || !limit || !finished || !lengths || !out || !next_ids || !status)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: null buffer");
-    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
-    if (!greedy && !(temperature > 0.f && temperature < INFINITY))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: temperature %g", (double)temperature);
-    if (!greedy && (top_k < 0 || !(top_p > 0.f && top_p <= 1.f)))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "select_tokens_slots: top_k %d top_p %g", top_k, (double)top_p);
-    SelArgs a;
-    a.logits = logits; a.ld = ld; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
-    a.inv_t = greedy ? 1.f : 1.f / temperature;
-    a.top_k = top_k; a.top_p = top_p; a.greedy = greedy;
-    a.k0 = seed_lo; a.k1 = seed_hi; a.eos = eos_id; a.pad = pad_id; a.step_base = step_base; a.max_new = max_new;
-    a.t = nullptr; a.stream_id = stream_id; a.finished = finished; a.lengths = lengths; a.out = out;
+    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
+                         lengths, out, max_new, next_ids, ids_stride, status);
     a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots;
-    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
-    hipStream_t st = (hipStream_t)stream;
-    const int ng = sel_ng(V);
-    DB1_DISPATCH_DT(dt, T, {
-        if (ng == 1) select_tokens_kernel<T, 1, true><<<M, SEL_THREADS, 0, st>>>(a);
-        else if (ng == 3) select_tokens_kernel<T, 3, true><<<M, SEL_THREADS, 0, st>>>(a);
-        else select_tokens_kernel<T, SEL_MAX_NG, true><<<M, SEL_THREADS, 0, st>>>(a);
-    });
-    DB1_CHECK_LAUNCH("select_tokens_slots");
-    return DB1_OK;
+    return sel_launch("select_tokens_slots", true, a, M, dt, temperature, stream);
 }

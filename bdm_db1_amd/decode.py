@@ -15,18 +15,21 @@ from typing import List
 import torch
 
 
+def _token_input(ids):
+    """the model input that feeds the token ids ``ids`` [rows, n] after what the memory holds"""
+    from .data import NLPTaskInput
+    return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+
+
 class GraphedMemoryStep:
     def __init__(self, model, batch_size: int, n_new: int, make_input=None):
         """``make_input(ids)`` builds the task input for static token ids [batch, n_new] (default: a text input)."""
-        from .data import NLPTaskInput
         if model.compute_dtype != torch.bfloat16 or not model.use_decode:
             raise ValueError("GraphedMemoryStep needs the bf16 K/V-cached decode path (model.use_decode)")
         self.model, self.B, self.q = model, batch_size, n_new
         dev = model.dev
         self.ids = torch.zeros(batch_size, n_new, dtype=torch.long, device=dev)
-        make_input = make_input or (lambda ids: NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None,
-                                                             text_seq=ids, text_len=None))
-        self.x = make_input(self.ids)
+        self.x = (make_input or _token_input)(self.ids)
         self.mems: List[torch.Tensor] = model.init_mem(batch_size)
         self.graph = None
         self.logits = None
@@ -110,12 +113,20 @@ class RingMemory:
         if len(mems) != model.n_layer or any(tuple(m.shape) != (self.B, mlen, model.n_embed) for m in mems):
             raise ValueError(f"RingMemory.load: expected {model.n_layer} tensors of shape ({self.B}, {mlen}, {model.n_embed})")
         with torch.no_grad():
-            saved, model._dec_state = model._dec_state, None
-            dec = model._decode_begin(list(mems), self.B, 1, mlen)
-            model._dec_state = saved
-            for ring, kv in zip(self.kv, dec.kv):
-                ring[:, :mlen].copy_(kv.reshape(self.B, mlen, 2, model.n_head, model.d_head))
+            for ring, kv in zip(self.kv, self._project(mems, self.B)):
+                ring[:, :mlen].copy_(kv)
             self.state.zero_()
+
+    def _project(self, mems, n: int):
+        """the projected keys / values of a list-form memory of n rows: per layer a [n, mem_len, 2, H, D] view.  The model keeps the decode
+        state it had, whatever the projection does (``load_rows`` runs in the middle of a stream)."""
+        model, mlen = self.model, int(self.model.mem_len)
+        saved, model._dec_state = model._dec_state, None
+        try:
+            dec = model._decode_begin(list(mems), n, 1, mlen)
+        finally:
+            model._dec_state = saved
+        return [kv.reshape(n, mlen, 2, model.n_head, model.d_head) for kv in dec.kv]
 
     def load_rows(self, mems, rows: torch.Tensor):
         """continuous batching: the n requests of a list-form memory (per layer [n, mem_len, d], as ``load`` takes it for all B rows) take
@@ -132,13 +143,7 @@ class RingMemory:
         if n == 0:
             return
         with torch.no_grad():
-            saved, model._dec_state = model._dec_state, None
-            try:
-                dec = model._decode_begin(list(mems), n, 1, mlen)
-            finally:      # (this runs in the middle of a stream: the model keeps its decode state whatever the projection does)
-                model._dec_state = saved
-            src = [kv.reshape(n, mlen, 2, model.n_head, model.d_head) for kv in dec.kv]
-            ops.ring_load_rows(self.kv, self._ptrs, src, self.state, mlen, rows, self.load_status)
+            ops.ring_load_rows(self.kv, self._ptrs, self._project(mems, n), self.state, mlen, rows, self.load_status)
 
     def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
         """beam search: after the call that appended token t - 1, give row b the keys / values of the last ``t`` tokens of row
@@ -158,14 +163,12 @@ class GraphedRingStep:
     same graph after the forward, e.g. a token sampler that writes the next ids into ``step.ids`` (generation.py); the warm-up does not run it."""
 
     def __init__(self, model, batch_size: int, n_new: int, memory: RingMemory = None, make_input=None, epilogue=None):
-        from .data import NLPTaskInput
         self.model, self.B, self.q = model, batch_size, n_new
         self.memory = memory if memory is not None else RingMemory(model, batch_size)
         assert self.memory.B == batch_size
         dev = model.dev
         self.ids = torch.zeros(batch_size, n_new, dtype=torch.long, device=dev)
-        make_input = make_input or (lambda ids: NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None))
-        self.x = make_input(self.ids)
+        self.x = (make_input or _token_input)(self.ids)
         from . import ops
         saved_state = self.memory.state.clone()
         saved_kv = None if memory is None else [k.clone() for k in self.memory.kv]

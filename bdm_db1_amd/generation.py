@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .decode import GraphedRingStep, RingMemory, _token_input  # noqa: F401  (scoring.py takes _token_input from here)
 
 
 @dataclass(frozen=True)
@@ -118,6 +119,13 @@ def _eval_mode(model):
         model.train(was_training)
 
 
+@contextlib.contextmanager
+def _work(model):
+    """device work between two yields of a stream: eval mode and no autograd, both restored before the caller's code runs again"""
+    with torch.no_grad(), _eval_mode(model):
+        yield
+
+
 def _need_memory(model, who: str) -> int:
     mlen = int(model.mem_len or 0)
     if not mlen > 0:
@@ -161,10 +169,57 @@ def _batch_size(prompt) -> int:
     return int(arr.shape[0])
 
 
-def _token_input(ids):
-    """the model input that feeds the token ids ``ids`` [rows, n] after what the memory holds"""
-    from .data import NLPTaskInput
-    return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+# the fields of a prompt batch that hold one entry per row (first dimension = the batch); every other field is handed on as it is
+_PER_ROW_FIELDS = ("position_id", "attention_mask", "loss_mask", "label", "text_seq", "text_len", "prompt_seq", "img_seq", "img_id_seq",
+                   "ques_id_seq", "ques_len")
+# attributes next to the dataclass fields: one id per patch, image after image
+_PATCH_FIELDS = ("vision_row_ids", "vision_col_ids")
+
+
+def _take(prompt, name: str, G: int, rows):
+    """rows ``rows`` of field ``name`` of a prompt batch of G rows: a per-row field is index-selected, a per-patch field row block by row
+    block, anything else (and None) is handed on as it is; ``rows`` None: the whole field, as it is"""
+    v = getattr(prompt, name, None)
+    if v is None or rows is None or not (name in _PER_ROW_FIELDS or name in _PATCH_FIELDS):
+        return v
+    v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
+    idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=v.device)
+    if name in _PATCH_FIELDS:
+        if G == 0 or v.numel() % G:
+            raise ValueError(f"generate_stream: {name} holds {v.numel()} ids for a batch of {G} rows")
+        return v.reshape(G, -1).index_select(0, idx).reshape(-1)
+    if v.dim() < 1 or v.shape[0] != G:
+        raise ValueError(f"generate_stream: {name} of shape {tuple(v.shape)} in a batch of {G} rows")
+    return v.index_select(0, idx)
+
+
+def _carry_patch_ids(src, dst, rows=None):
+    """the patch ids of the prompt batch ``src`` carried over to ``dst`` (returned): as they are, or those of ``src``'s rows ``rows``"""
+    G = None if rows is None else _batch_size(src)
+    for f in _PATCH_FIELDS:
+        if hasattr(src, f):
+            setattr(dst, f, _take(src, f, G, rows))
+    return dst
+
+
+def _questions(vqa_batch):
+    """(``text_seq`` as a tensor, ``ques_len`` as a flat int64 array or None) of a ``VQATaskInput`` batch"""
+    q = vqa_batch.text_seq
+    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
+    ql = getattr(vqa_batch, "ques_len", None)
+    return q, None if ql is None else np.asarray(torch.as_tensor(ql).cpu()).reshape(-1).astype(np.int64)
+
+
+def _question_rows(vqa_batch, q, n: Optional[int], rows=None):
+    """the prompt ``[prompt, image patches, question]`` of a ``VQATaskInput`` batch (of its rows ``rows``, if given): the question is the
+    first ``n`` tokens of ``q``, the batch's ``text_seq`` (``n`` None: all of it)"""
+    from .data import VQATaskInput
+    G = None if rows is None else _batch_size(vqa_batch)
+    take = lambda f: _take(vqa_batch, f, G, rows)
+    q = q if rows is None else take("text_seq")
+    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=take("prompt_seq"), img_seq=take("img_seq"),
+                     text_seq=q if n is None else q[:, :n])
+    return _carry_patch_ids(vqa_batch, x, rows)
 
 
 def _prefill(model, prompt, G: int, expand: Optional[int] = None):
@@ -188,24 +243,33 @@ def _ring_ok(model) -> bool:
     return (model.compute_dtype == torch.bfloat16 and bool(model.use_decode) and int(model.mem_len or 0) > 0 and model.d_head == 128)
 
 
-# ------------------------------------------------------------------------------------------------------------------- the two device states
+# ----------------------------------------------------------------------------------------------------------------------- the device states
 # What ``_decode`` asks of a state: ``M`` rows, ``expand`` (None, or the rows per prompt), ``cache`` (the model attribute its ring generator
 # is kept under), ``start(...)``, ``epilogue(logits_last, next_ids, ring=None)`` -- select, reorder ``ring`` if beams, then t += 1 --,
-# ``reorder_list(mems)``, ``all_done()`` (a host read), ``result()`` and ``stats()``.
-class _State:
-    """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
-    cache, expand = "_generator", None
+# ``reorder_list(mems)``, ``all_done()`` (a host read), ``result()`` and ``stats()``.  The stream (serving.py) asks its ``_SlotState`` for
+# ``M``, ``expand``, ``cache``, ``start()`` and ``epilogue``.
+class _SamplingState:
+    """what the two sampling states (``_State``, serving's ``_SlotState``) share: the per-row flags, stream ids and output, all zero / pad_id,
+    and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``"""
+    expand = None
 
     def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
-        dev = model.dev
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.M, self.cfg, self.V, self.hi = M, cfg, V, hi
-        self.t = torch.zeros(1, **i32)
-        self.finished = torch.zeros(M, **i32)
-        self.lengths = torch.zeros(M, **i32)
-        self.status = torch.zeros(M, **i32)
-        self.stream_id = torch.arange(M, **i32)
+        self.i32 = i32 = dict(dtype=torch.int32, device=model.dev)
+        self.M, self.cfg, self.V, self.hi, self.dev = M, cfg, V, hi, model.dev
+        self.finished, self.lengths, self.status, self.stream_id = (torch.zeros(M, **i32) for _ in range(4))
         self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
+        self.sel = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
+                        seed=cfg.seed, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, stream_id=self.stream_id)
+
+
+class _State(_SamplingState):
+    """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
+    cache = "_generator"
+
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
+        super().__init__(model, M, cfg, V, hi)
+        self.t = torch.zeros(1, **self.i32)
+        self.stream_id.copy_(torch.arange(M, dtype=torch.int32))
 
     def start(self, stream_ids=None):
         for x in (self.t, self.finished, self.lengths, self.status):
@@ -221,10 +285,7 @@ class _State:
 
     def select(self, logits2d, next_ids):
         """db1_select_tokens on the last-position logits [M, V] of step t; the tokens go to ``next_ids`` (int64 [M])"""
-        c = self.cfg
-        ops.select_tokens(logits2d, self.t, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V, vocab_lo=c.vocab_lo,
-                          vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p, seed=c.seed,
-                          eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id)
+        ops.select_tokens(logits2d, self.t, self.finished, self.lengths, self.out, next_ids, self.status, **self.sel)
 
     def epilogue(self, logits2d, next_ids, ring=None):
         self.select(logits2d, next_ids)
@@ -323,15 +384,30 @@ class _BeamState:
 class _RingGenerator:
     """a RingMemory of ``state.M`` rows, the state and the captured per-token graph (the one-token forward and the state's epilogue) for one
     (model, ``key`` = what the state was built from); reused across calls"""
+    busy = False        # (set while a stream runs over this state: generate_stream refuses a second one)
 
     def __init__(self, model, state, key):
-        from .decode import GraphedRingStep, RingMemory
-        self.key, self.state = key, state
+        self.model, self.key, self.state = model, key, state
         self.ring = RingMemory(model, state.M)
         self.step = GraphedRingStep(model, state.M, 1, memory=self.ring, epilogue=self.epilogue)
 
     def epilogue(self, step, logits):
         self.state.epilogue(logits[:, -1], step.ids[:, 0], self.ring)
+
+    def token(self, replay: bool):
+        """one token step on the ids the last one left in ``step.ids``: a graph replay, or the same forward and epilogue launched eagerly over
+        the same ring"""
+        if replay:
+            self.step(self.step.ids)
+        else:
+            logits, _, _ = self.model([self.step.x], compute_loss=False, mems=self.ring)
+            self.epilogue(self.step, logits)
+
+    def check(self, replay: bool):
+        """the end of a run: raise what the token steps recorded (the replays' hand-off flag; the eager launches' chain)"""
+        self.step.check(synchronize=True)
+        if not replay:
+            _check_chain(self.model)
 
 
 def _ring_generator(model, State, key) -> _RingGenerator:
@@ -372,19 +448,16 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
         for i in range(1, st.cfg.max_new_tokens):
             if i % st.cfg.sync_every == 0 and st.all_done():
                 break
-            if ring and replay:
-                gen.step(ids)
-            elif ring:
-                logits, _, _ = model([gen.step.x], compute_loss=False, mems=gen.ring)
-                gen.epilogue(gen.step, logits)
+            if ring:
+                gen.token(replay)
             else:
                 logits, _, mems = model([_token_input(ids)], compute_loss=False, mems=mems)
                 st.epilogue(logits[:, -1], ids[:, 0])
                 mems = st.reorder_list(mems)
             calls += 1
         if ring:
-            gen.step.check(synchronize=True)
-        if not (ring and replay):
+            gen.check(replay)
+        else:
             _check_chain(model)
         if stats is not None:
             stats.update(path="ring" if ring else "eager", token_calls=calls, **st.stats())
@@ -426,10 +499,7 @@ def caption_prompt(ic_batch):
     M = _batch_size(ic_batch)
     x = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=ic_batch.prompt_seq, img_seq=ic_batch.img_seq,
                     text_seq=torch.zeros(M, 0, dtype=torch.long))
-    for f in ("vision_row_ids", "vision_col_ids"):
-        if hasattr(ic_batch, f):
-            setattr(x, f, getattr(ic_batch, f))
-    return x
+    return _carry_patch_ids(ic_batch, x)
 
 
 def answer_questions(model, vqa_batch, cfg=None, **kw):
@@ -441,20 +511,29 @@ def answer_questions(model, vqa_batch, cfg=None, **kw):
 
 def question_prompt(vqa_batch):
     """the generation prompt of a ``VQATaskInput`` batch: ``[prompt, image patches, question]`` without the answer"""
-    from .data import VQATaskInput
-    q = vqa_batch.text_seq
-    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
-    if getattr(vqa_batch, "ques_len", None) is not None:
-        ql = np.unique(np.asarray(torch.as_tensor(vqa_batch.ques_len).cpu()).reshape(-1))
-        if ql.size != 1:
-            raise ValueError("answer_questions: the questions of a batch must share one length (group them by length)")
-        q = q[:, :int(ql[0])]
-    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=vqa_batch.prompt_seq, img_seq=vqa_batch.img_seq,
-                     text_seq=q)
-    for f in ("vision_row_ids", "vision_col_ids"):
-        if hasattr(vqa_batch, f):
-            setattr(x, f, getattr(vqa_batch, f))
-    return x
+    q, ql = _questions(vqa_batch)
+    if ql is None:
+        return _question_rows(vqa_batch, q, None)
+    ql = np.unique(ql)
+    if ql.size != 1:
+        raise ValueError("answer_questions: the questions of a batch must share one length (group them by length)")
+    return _question_rows(vqa_batch, q, int(ql[0]))
+
+
+def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
+    """the generation prompts of a ``VQATaskInput`` batch whose questions differ in length: one ``question_prompt`` per distinct ``ques_len``
+    (ascending) -> [(prompt, rows)]: ``rows`` (int64, ascending) are the batch rows the prompt's rows come from.  Every row of the batch is in
+    exactly one prompt.  ``ques_len`` None: one prompt, the whole ``text_seq`` as the question."""
+    G = _batch_size(vqa_batch)
+    q, ql = _questions(vqa_batch)
+    if ql is None:
+        return [(_question_rows(vqa_batch, q, None), np.arange(G, dtype=np.int64))]
+    if ql.size != G:
+        raise ValueError(f"question_prompts: {ql.size} question lengths for a batch of {G} rows")
+    if ql.min() < 0 or ql.max() > q.shape[1]:
+        raise ValueError(f"question_prompts: question lengths must lie in [0, {q.shape[1]}]")
+    groups = [(int(n), np.nonzero(ql == n)[0].astype(np.int64)) for n in np.unique(ql)]
+    return [(_question_rows(vqa_batch, q, n, rows), rows) for n, rows in groups]
 
 
 @torch.no_grad()

@@ -574,6 +574,29 @@ def _check_next_ids(who, next_ids, M, dev):
         raise ValueError(f"{who}: next_ids must be an int64 tensor of {M} rows (one element each) on {dev}")
 
 
+def _check_sampling(who, greedy, temperature, top_k, top_p):
+    if not greedy:
+        if not (temperature > 0 and temperature < float("inf")):
+            raise ValueError(f"{who}: temperature {temperature} must be > 0 when sampling")
+        if not 0 < top_p <= 1:
+            raise ValueError(f"{who}: top_p {top_p} must lie in (0, 1]")
+        if top_k < 0:
+            raise ValueError(f"{who}: top_k {top_k} must be >= 0")
+
+
+def _check_rings(who, rings):
+    """``rings``: contiguous 16-byte aligned [M, cap, ...] tensors of one shape, dtype and device -> (M, cap, the bytes of one slot, device)"""
+    if not rings:
+        raise ValueError(f"{who}: no rings")
+    r0 = rings[0]
+    if r0.dim() < 3:
+        raise ValueError(f"{who}: rings must be [M, cap, ...] tensors")
+    for r in rings:
+        if r.shape != r0.shape or r.dtype != r0.dtype or not r.is_contiguous() or r.device != r0.device or r.data_ptr() % 16:
+            raise ValueError(f"{who}: the rings must be contiguous 16-byte aligned tensors of one shape, dtype and device")
+    return r0.shape[0], r0.shape[1], int(r0[0, 0].numel() * r0.element_size()), r0.device
+
+
 def select_tokens_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
 
@@ -588,13 +611,7 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
     who, dev, i32 = "select_tokens", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_supported(V, max(ld, V), logits2d.dtype))
-    if not greedy:
-        if not (temperature > 0 and temperature < float("inf")):
-            raise ValueError(f"select_tokens: temperature {temperature} must be > 0 when sampling")
-        if not 0 < top_p <= 1:
-            raise ValueError(f"select_tokens: top_p {top_p} must lie in (0, 1]")
-        if top_k < 0:
-            raise ValueError(f"select_tokens: top_k {top_k} must be >= 0")
+    _check_sampling(who, greedy, temperature, top_k, top_p)
     for name, x, n in (("finished", finished, M), ("lengths", lengths, M), ("status", status, M), ("t", t, 1)) + \
             ((("stream_id", stream_id, M),) if stream_id is not None else ()):
         _check_tensor(who, name, x, i32, n, dev)
@@ -621,13 +638,7 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
     who, dev, i32 = "select_tokens_slots", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
-    if not greedy:
-        if not (temperature > 0 and temperature < float("inf")):
-            raise ValueError(f"{who}: temperature {temperature} must be > 0 when sampling")
-        if not 0 < top_p <= 1:
-            raise ValueError(f"{who}: top_p {top_p} must lie in (0, 1]")
-        if top_k < 0:
-            raise ValueError(f"{who}: top_k {top_k} must be >= 0")
+    _check_sampling(who, greedy, temperature, top_k, top_p)
     S = int(t.numel()) if row_map is not None else M
     if row_map is not None:
         _check_tensor(who, "row_map", row_map, i32, M, dev)
@@ -692,29 +703,19 @@ def ring_reorder(rings, ptrs, state, mlen, t, max_t, parent, W=1, done=None):
     """copy the last t keys of every row from row parent[b] (same group of W rows) in every ring of ``rings`` (bf16 [M, cap, 2, H, D],
     contiguous; ``ptrs`` = ring_pointers(rings)) -- db1_ring_reorder.  ``t`` (int32 [1]) READ only, at most ``max_t`` (<= mlen);
     ``done`` (int32 [M / W] or None): groups left alone.  Capturable; raises ValueError on bad arguments before anything is launched."""
-    if not rings:
-        raise ValueError("ring_reorder: no rings")
-    r0 = rings[0]
-    if r0.dim() < 3:
-        raise ValueError("ring_reorder: rings must be [M, cap, ...] tensors")
-    M, cap = r0.shape[0], r0.shape[1]
-    slot_bytes = r0[0, 0].numel() * r0.element_size()
-    for r in rings:
-        if r.shape != r0.shape or r.dtype != r0.dtype or not r.is_contiguous() or r.device != r0.device or r.data_ptr() % 16:
-            raise ValueError("ring_reorder: the rings must be contiguous 16-byte aligned tensors of one shape, dtype and device")
-    if not lib.load().db1_ring_reorder_supported(int(slot_bytes)):
+    M, cap, slot_bytes, dev = _check_rings("ring_reorder", rings)
+    if not lib.load().db1_ring_reorder_supported(slot_bytes):
         raise ValueError(f"ring_reorder: a slot of {slot_bytes} bytes (a multiple of 16 expected)")
     W, mlen, max_t = int(W), int(mlen), int(max_t)
     if W < 1 or M % W:
         raise ValueError(f"ring_reorder: W={W} must divide the {M} rows")
     if not 1 <= max_t <= mlen < cap:
         raise ValueError(f"ring_reorder: needs 1 <= max_t ({max_t}) <= mlen ({mlen}) < cap ({cap})")
-    dev = r0.device
     _check_tensor("ring_reorder", "ptrs (ring_pointers)", ptrs, torch.int64, (len(rings),), dev)
     for name, x, n in (("state", state, 1), ("t", t, 1), ("parent", parent, M)) + ((("done", done, M // W),) if done is not None else ()):
         _check_tensor("ring_reorder", name, x, torch.int32, n, dev)
-    ws, wsn = _ws("db1_ring_reorder_workspace_bytes", (len(rings), M, max_t, int(slot_bytes)), dev)
-    lib.call("db1_ring_reorder", P(ptrs), len(rings), M, W, cap, int(slot_bytes), P(state), mlen, P(t), max_t, P(parent), P(done), ws, wsn, stream())
+    ws, wsn = _ws("db1_ring_reorder_workspace_bytes", (len(rings), M, max_t, slot_bytes), dev)
+    lib.call("db1_ring_reorder", P(ptrs), len(rings), M, W, cap, slot_bytes, P(state), mlen, P(t), max_t, P(parent), P(done), ws, wsn, stream())
 
 
 def ring_load_rows(rings, ptrs, src, state, mlen, rows, status):
@@ -724,33 +725,26 @@ def ring_load_rows(rings, ptrs, src, state, mlen, rows, status):
     [1]) |= 1 for a row outside [0, M) (skipped), |= 2 for an origin outside [0, cap).  Raises ValueError on bad arguments before anything is
     launched."""
     who = "ring_load_rows"
-    if not rings or len(src) != len(rings):
-        raise ValueError(f"{who}: one source tensor per ring expected")
-    r0, s0 = rings[0], src[0]
-    if r0.dim() < 3 or s0.dim() < 3:
-        raise ValueError(f"{who}: rings must be [M, cap, ...] and sources [n, mlen, ...] tensors")
-    M, cap, n, mlen = r0.shape[0], r0.shape[1], s0.shape[0], int(mlen)
-    slot_bytes = r0[0, 0].numel() * r0.element_size()
-    for r in rings:
-        if r.shape != r0.shape or r.dtype != r0.dtype or not r.is_contiguous() or r.device != r0.device or r.data_ptr() % 16:
-            raise ValueError(f"{who}: the rings must be contiguous 16-byte aligned tensors of one shape, dtype and device")
+    M, cap, slot_bytes, dev = _check_rings(who, rings)
+    if len(src) != len(rings) or src[0].dim() < 3:
+        raise ValueError(f"{who}: one source tensor [n, mlen, ...] per ring expected")
+    r0, n, mlen = rings[0], src[0].shape[0], int(mlen)
     for x in src:
-        if tuple(x.shape) != (n, mlen) + tuple(r0.shape[2:]) or x.dtype != r0.dtype or not x.is_contiguous() or x.device != r0.device or \
+        if tuple(x.shape) != (n, mlen) + tuple(r0.shape[2:]) or x.dtype != r0.dtype or not x.is_contiguous() or x.device != dev or \
                 (n and x.data_ptr() % 16):
             raise ValueError(f"{who}: every source must be a contiguous 16-byte aligned {r0.dtype} tensor of shape "
-                             f"{(n, mlen) + tuple(r0.shape[2:])} on {r0.device}")
-    if not lib.load().db1_ring_load_rows_supported(int(slot_bytes), mlen, cap):
+                             f"{(n, mlen) + tuple(r0.shape[2:])} on {dev}")
+    if not lib.load().db1_ring_load_rows_supported(slot_bytes, mlen, cap):
         raise ValueError(f"{who}: a slot of {slot_bytes} bytes (a multiple of 16 expected) with 0 < mlen ({mlen}) < cap ({cap})")
     if n > M:
         raise ValueError(f"{who}: {n} source rows for a ring of {M} rows")
-    dev = r0.device
     _check_tensor(who, "ptrs (ring_pointers)", ptrs, torch.int64, (len(rings),), dev)
     for name, x, k in (("state", state, 1), ("rows", rows, n), ("status", status, 1)):
         _check_tensor(who, name, x, torch.int32, k, dev)
     if n == 0:
         return
     sp = ring_pointers(src)
-    lib.call("db1_ring_load_rows", P(ptrs), P(sp), len(rings), M, n, cap, int(slot_bytes), P(state), mlen, P(rows), P(status), stream())
+    lib.call("db1_ring_load_rows", P(ptrs), P(sp), len(rings), M, n, cap, slot_bytes, P(state), mlen, P(rows), P(status), stream())
 
 
 def lmhead_ce(h2d, W, labels, mask, lse, sums, V, dh=None, dW_acc=None, beta_dw=1.0, gscale=1.0, chunk_rows=0):

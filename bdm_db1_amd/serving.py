@@ -18,7 +18,6 @@ What the host decides -- which slot, which requests share a prefill, the order r
 """
 from __future__ import annotations
 
-import contextlib
 import dataclasses
 from collections import OrderedDict
 from typing import Iterable, Iterator, List, Optional, Tuple
@@ -27,8 +26,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .generation import (GenerationConfig, _batch_size, _check_chain, _eval_mode, _need_memory, _prefill, _ring_ok, _text_window, _vocab_window,
-                         caption_prompt, question_prompt)
+from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, GenerationConfig, _batch_size, _need_memory, _prefill, _ring_generator, _ring_ok,
+                         _SamplingState, _take, _text_window, _vocab_window, _work, caption_prompt, question_prompts)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- requests
@@ -52,11 +51,6 @@ class _Item:
 
 
 _SEQ_FIELDS = ("text_seq", "prompt_seq", "img_seq")            # what makes a prompt's shape
-# the fields of a prompt batch that hold one entry per row (first dimension = the batch); every other field is handed on as it is
-_PER_ROW_FIELDS = ("position_id", "attention_mask", "loss_mask", "label", "text_seq", "text_len", "prompt_seq", "img_seq", "img_id_seq",
-                   "ques_id_seq", "ques_len")
-# attributes next to the dataclass fields (caption_prompt / question_prompt carry them over): one id per patch, image after image
-_PATCH_FIELDS = ("vision_row_ids", "vision_col_ids")
 
 
 def _shape_key(prompt) -> tuple:
@@ -95,23 +89,6 @@ def _requests(items: Iterable, cfg: GenerationConfig) -> Iterator[Request]:
         for r, i in enumerate(indices):
             yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r)
             nxt = max(nxt, int(i) + 1)
-
-
-def _take(prompt, name: str, G: int, rows):
-    """rows ``rows`` of field ``name`` of a prompt batch of G rows: a per-row field is index-selected, a per-patch field row block by row
-    block, anything else (and None) is handed on as it is"""
-    v = getattr(prompt, name, None)
-    if v is None or not (name in _PER_ROW_FIELDS or name in _PATCH_FIELDS):
-        return v
-    v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v))
-    idx = torch.as_tensor(np.asarray(rows, dtype=np.int64), device=v.device)
-    if name in _PATCH_FIELDS:
-        if G == 0 or v.numel() % G:
-            raise ValueError(f"generate_stream: {name} holds {v.numel()} ids for a batch of {G} rows")
-        return v.reshape(G, -1).index_select(0, idx).reshape(-1)
-    if v.dim() < 1 or v.shape[0] != G:
-        raise ValueError(f"generate_stream: {name} of shape {tuple(v.shape)} in a batch of {G} rows")
-    return v.index_select(0, idx)
 
 
 def _gather(reqs: List[Request]):
@@ -198,19 +175,15 @@ class SlotScheduler:
 
 
 # ----------------------------------------------------------------------------------------------------------------------- the device state
-class _SlotState:
+class _SlotState(_SamplingState):
     """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row"""
+    cache = "_slot_generator"
 
     def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int):
-        i32 = dict(dtype=torch.int32, device=model.dev)
-        self.M, self.cfg, self.V, self.hi, self.dev = slots, cfg, V, hi, model.dev
-        self.t = torch.zeros(slots, **i32)
-        self.limit = torch.ones(slots, **i32)
-        self.finished = torch.ones(slots, **i32)       # (vacant)
-        self.lengths = torch.zeros(slots, **i32)
-        self.status = torch.zeros(slots, **i32)
-        self.stream_id = torch.zeros(slots, **i32)
-        self.out = torch.full((slots, cfg.max_new_tokens), cfg.pad_id, **i32)
+        super().__init__(model, slots, cfg, V, hi)
+        self.t = torch.zeros(slots, **self.i32)
+        self.limit = torch.ones(slots, **self.i32)
+        self.finished.fill_(1)       # (vacant)
 
     def start(self):
         self.finished.fill_(1)
@@ -228,51 +201,16 @@ class _SlotState:
         return idx.to(torch.int32)
 
     def select(self, logits2d, next_ids, row_map=None):
-        c = self.cfg
-        ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, V=self.V,
-                                vocab_lo=c.vocab_lo, vocab_hi=self.hi, greedy=c.greedy, temperature=c.temperature, top_k=c.top_k, top_p=c.top_p,
-                                seed=c.seed, eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, stream_id=self.stream_id,
-                                row_map=row_map)
+        ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map, **self.sel)
+
+    def epilogue(self, logits2d, next_ids, ring=None):
+        self.select(logits2d, next_ids)      # (the launch advances every live slot's t itself)
 
     def read(self, slots: List[int]):
         """(out rows, [t, length, status] rows) of ``slots`` on the host"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
         meta = torch.stack((self.t, self.lengths, self.status), 1).index_select(0, idx).cpu()
         return self.out.index_select(0, idx).cpu(), meta
-
-
-class _SlotGenerator:
-    """the ring of ``slots`` rows, the slot state and the captured per-token graph (forward + db1_select_tokens_slots) for one (model, key)"""
-
-    def __init__(self, model, key):
-        from .decode import GraphedRingStep, RingMemory
-        self.key = key
-        self.busy = False        # (a stream is running over this state: generate_stream refuses a second one)
-        self.state = _SlotState(model, *key)
-        self.ring = RingMemory(model, self.state.M)
-        self.step = GraphedRingStep(model, self.state.M, 1, memory=self.ring, epilogue=self.epilogue)
-
-    def epilogue(self, step, logits):
-        self.state.select(logits[:, -1], step.ids[:, 0])
-
-
-def _slot_generator(model, key) -> _SlotGenerator:
-    """the generator kept on the model if it was built from ``key`` and the weights it captured, else a new one (as ``_ring_generator``)"""
-    gen = getattr(model, "_slot_generator", None)
-    if gen is not None and gen.busy:
-        raise RuntimeError("generate_stream: another stream is still running on this model (one stream at a time: finish or close() it first)")
-    if gen is None or gen.key != key or gen.step._version != model._wversion:
-        model._slot_generator = None        # (free the old ring before the new one is allocated)
-        gen = _SlotGenerator(model, key)
-        model._slot_generator = gen
-    return gen
-
-
-@contextlib.contextmanager
-def _work(model):
-    """device work between two yields: eval mode and no autograd, both restored before the caller's code runs again"""
-    with torch.no_grad(), _eval_mode(model):
-        yield
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
@@ -326,7 +264,11 @@ def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
             results = []
             with _work(model):
                 if gen is None:
-                    gen = _slot_generator(model, (slots, cfg, V, hi))
+                    held = getattr(model, _SlotState.cache, None)
+                    if held is not None and held.busy:
+                        raise RuntimeError("generate_stream: another stream is still running on this model (one stream at a time: finish or "
+                                           "close() it first)")
+                    gen = _ring_generator(model, _SlotState, (slots, cfg, V, hi))
                     gen.busy = True
                     gen.state.start()
                     gen.ring.load_status.zero_()
@@ -343,11 +285,7 @@ def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
                     counts["prefill_calls"] += 1
                 k = sched.replays_due(cfg.sync_every)
                 for _ in range(k):
-                    if replay:
-                        step(step.ids)
-                    else:
-                        logits, _, _ = model([step.x], compute_loss=False, mems=gen.ring)
-                        gen.epilogue(step, logits)
+                    gen.token(replay)
                 sched.advance(k)
                 counts["replays"] += k
                 if not sched.idle():
@@ -363,9 +301,7 @@ def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
                             results.append((r.index, out[j, :r.limit].clone(), length))
                 finish = sched.idle() and not results
                 if finish:     # nothing waits (admit found no request for the free slots) and every slot is vacant
-                    step.check(synchronize=True)
-                    if not replay:
-                        _check_chain(model)
+                    gen.check(replay)
                     if int(gen.ring.load_status.cpu()) != 0:
                         raise RuntimeError("db1_ring_load_rows: a request was given a row outside the ring")
             report()
@@ -417,31 +353,3 @@ def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] 
             base += _batch_size(b)
 
     return generate_stream(model, items(), cfg, **kw)
-
-
-def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
-    """the generation prompts of a ``VQATaskInput`` batch whose questions differ in length: one ``question_prompt`` per distinct ``ques_len``
-    (ascending) -> [(prompt, rows)]: ``rows`` (int64, ascending) are the batch rows the prompt's rows come from.  Every row of the batch is in
-    exactly one prompt.  ``ques_len`` None: one prompt, the whole ``text_seq`` as the question."""
-    from .data import VQATaskInput
-    G = _batch_size(vqa_batch)
-    ql = getattr(vqa_batch, "ques_len", None)
-    if ql is None:
-        return [(question_prompt(vqa_batch), np.arange(G, dtype=np.int64))]
-    ql = np.asarray(torch.as_tensor(ql).cpu()).reshape(-1).astype(np.int64)
-    if ql.size != G:
-        raise ValueError(f"question_prompts: {ql.size} question lengths for a batch of {G} rows")
-    q = vqa_batch.text_seq
-    q = q if torch.is_tensor(q) else torch.as_tensor(np.asarray(q))
-    if ql.min() < 0 or ql.max() > q.shape[1]:
-        raise ValueError(f"question_prompts: question lengths must lie in [0, {q.shape[1]}]")
-    out = []
-    for n in np.unique(ql):
-        rows = np.nonzero(ql == n)[0].astype(np.int64)
-        x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=_take(vqa_batch, "prompt_seq", G, rows),
-                         img_seq=_take(vqa_batch, "img_seq", G, rows), text_seq=_take(vqa_batch, "text_seq", G, rows)[:, :int(n)])
-        for f in _PATCH_FIELDS:
-            if hasattr(vqa_batch, f):
-                setattr(x, f, _take(vqa_batch, f, G, rows))
-        out.append((x, rows))
-    return out

@@ -127,3 +127,31 @@ def test_ring_memory_load_rows_continues_a_prefill():
         ring.load_rows(mems[:1], _tdev(np.asarray(rows, np.int32)))
     with pytest.raises(ValueError):
         ring.load_rows(mems, _tdev(np.asarray([1], np.int32)))
+
+
+def test_load_and_load_rows_share_one_projection():
+    """RingMemory.load against load_rows of all rows at origin 0, bit for bit; the model's decode state survives both, and a refused load"""
+    from bdm_db1_amd import RingMemory
+    from bdm_db1_amd.data import NLPTaskInput
+    cfg, model = _bf16_model()
+    B, mlen = 3, int(model.mem_len)
+    ids = np.random.default_rng(11).integers(0, 32000, (B, 50))
+    x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=_tdev(ids), text_len=None)
+    with torch.no_grad():
+        model._dec_state = None
+        _, _, mems = model([x], compute_loss=False, mems=model.init_mem(B))
+    a, b = RingMemory(model, B), RingMemory(model, B)
+    state = model._dec_state = object()
+    a.load(mems)
+    assert model._dec_state is state
+    b.load_rows(mems, torch.arange(B, dtype=torch.int32, device=DEV))
+    assert model._dec_state is state
+    assert int(a.state[0]) == int(b.state[0]) == 0 and int(a.load_status[0]) == int(b.load_status[0]) == 0
+    assert len(a.kv) == len(b.kv) == 2
+    for u, v in zip(a.kv, b.kv):
+        assert torch.equal(u[:, :mlen].view(torch.int16), v[:, :mlen].view(torch.int16))
+        assert bool(u[:, :mlen].any())
+    with pytest.raises(ValueError):
+        a.load([m[:, :-1] for m in mems])
+    assert model._dec_state is state
+    model._dec_state = None

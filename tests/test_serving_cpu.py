@@ -189,3 +189,43 @@ def test_question_prompts_partition_a_ragged_batch():
     batch.ques_len = torch.as_tensor(ql)
     with pytest.raises(ValueError):
         question_prompt(batch)
+
+
+def _vqa(ques_len):
+    G = 4
+    x = VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=torch.arange(G * 3).reshape(G, 3),
+                     img_seq=torch.arange(G * 3 * 4).reshape(G, 3, 2, 2).float(), text_seq=torch.arange(100, 100 + G * 7).reshape(G, 7),
+                     img_id_seq=None, ques_id_seq=None, ques_len=None if ques_len is None else torch.as_tensor(ques_len))
+    x.vision_row_ids = torch.arange(G * 4)            # (one id per patch, image after image)
+    x.vision_col_ids = torch.arange(G * 4) + 50
+    return x
+
+
+def _same_prompt(a, b):
+    import dataclasses
+    assert type(a) is type(b)
+    for name in [f.name for f in dataclasses.fields(a)] + ["vision_row_ids", "vision_col_ids"]:
+        u, v = getattr(a, name), getattr(b, name)
+        assert (u is None and v is None) or torch.equal(torch.as_tensor(u), torch.as_tensor(v)), name
+
+
+def test_question_prompt_is_the_one_length_case_of_question_prompts():
+    from bdm_db1_amd.generation import question_prompt
+    b = _vqa([3, 3, 3, 3])
+    (p, rows), = question_prompts(b)
+    assert rows.tolist() == [0, 1, 2, 3] and tuple(p.text_seq.shape) == (4, 3)
+    _same_prompt(p, question_prompt(b))
+    assert torch.equal(p.text_seq, b.text_seq[:, :3]) and torch.equal(p.vision_col_ids, b.vision_col_ids)
+    b = _vqa([3, 5, 3, 5])
+    with pytest.raises(ValueError):
+        question_prompt(b)
+    parts = question_prompts(b)
+    assert [r.tolist() for _, r in parts] == [[0, 2], [1, 3]]
+    for (p, r), n in zip(parts, (3, 5)):
+        assert torch.equal(p.text_seq, b.text_seq[r, :n]) and torch.equal(p.prompt_seq, b.prompt_seq[r])
+        assert torch.equal(p.vision_row_ids, b.vision_row_ids.reshape(4, -1)[r].reshape(-1))
+        assert torch.equal(p.vision_col_ids, b.vision_col_ids.reshape(4, -1)[r].reshape(-1))
+    b = _vqa(None)
+    (p, rows), = question_prompts(b)
+    assert rows.tolist() == [0, 1, 2, 3] and torch.equal(p.text_seq, b.text_seq)
+    _same_prompt(p, question_prompt(b))

@@ -249,3 +249,22 @@ def test_refusals_come_before_any_launch(model, prompts):
         generate_many(model, iter([(_text(prompts[0]), 0)]), _cfg(True), slots=SLOTS)
     with pytest.raises(ValueError):
         generate_stream(model, [x], _cfg(True), slots=0)
+
+
+def test_one_generator_class_serves_the_stream_and_generate():
+    from bdm_db1_amd import GenerationConfig, generate, generate_many, generate_stream
+    model = _bf16_model()[1]
+    rng = np.random.default_rng(8)
+    cfg = GenerationConfig(max_new_tokens=4, vocab_hi=HI, pad_id=PAD, sync_every=2)
+    reqs = [_text(rng.integers(0, HI, (1, n))) for n in (5, 7, 5)]
+    ids, lengths = generate_many(model, reqs, cfg, slots=2)
+    assert len(ids) == 3 and lengths == [4, 4, 4]
+    generate(model, reqs[0], cfg)
+    assert type(model._slot_generator) is type(model._generator) and model._slot_generator is not model._generator
+    gen = model._slot_generator
+    first = generate_stream(model, reqs, cfg, slots=2)
+    next(first)
+    with pytest.raises(RuntimeError):
+        next(generate_stream(model, reqs, cfg, slots=2))
+    assert model._slot_generator is gen and gen.busy              # nothing was rebuilt, the first stream still holds the slots
+    assert len(list(first)) == 2 and not gen.busy

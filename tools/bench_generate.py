@@ -171,8 +171,8 @@ def beam_main(W, Gs):
 def stream_main(n_req=256, slots=64):
     from bdm_db1_amd import caption_stream
     from bdm_db1_amd.decode import RingMemory
-    from bdm_db1_amd.serving import _slot_generator
-    from bdm_db1_amd.generation import _text_window, _vocab_window
+    from bdm_db1_amd.serving import _SlotState
+    from bdm_db1_amd.generation import _ring_generator, _text_window, _vocab_window
     limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
     cfg = GenerationConfig(max_new_tokens=N_NEW)
     batches = [batch(slots + k) for k in range((n_req + slots - 1) // slots)]       # (another seed per batch)
@@ -247,7 +247,7 @@ def stream_main(n_req=256, slots=64):
     rec.update(stream_replays=stats["replays"], prefill_calls=stats["prefill_calls"], occupancy=round(stats["occupancy"], 4))
     tcfg = _text_window(model, cfg)
     V, hi = _vocab_window(model, tcfg)
-    sg = _slot_generator(model, (slots, tcfg, V, hi))
+    sg = _ring_generator(model, _SlotState, (slots, tcfg, V, hi))
     st = sg.state
 
     def live():
