@@ -16,8 +16,10 @@ device state (``_State``, ``_BeamState``), and a generation is
 Sampling's epilogue is ``db1_select_tokens`` (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox); beam search's is
 ``db1_beam_step`` (lse, per-row top-2W, the group walk, the hypothesis pool, the next ids) and ``db1_ring_reorder`` (the last t keys of every
 beam whose parent is another row), after a prefill whose memory and last logits are expanded to the W beams of each prompt.  Both rules are
-stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py and tests/beam_rule.py.  scoring.py takes its prefill, its
-eval-mode switch and its vocabulary checks from here.
+stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py and tests/beam_rule.py.  With ``constraints=`` (a
+``DecodingConstraints``) either epilogue is preceded by ``db1_constrain_logits``, which edits the step's logits in place over each row's own
+generated tokens (tests/constraint_rule.py); without, nothing is launched.  scoring.py takes its prefill, its eval-mode switch and its
+vocabulary checks from here.
 """
 from __future__ import annotations
 
@@ -101,6 +103,56 @@ class BeamSearchConfig:
             raise ValueError(f"sync_every {self.sync_every} must be >= 1")
 
 
+MAX_BAD_TOKEN_IDS = 1024
+
+
+def _is_count(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= int(v) < 2 ** 31
+
+
+@dataclass(frozen=True)
+class DecodingConstraints:
+    """Edits of every step's logits before the token (or the beams) are chosen, applied on the device by ``db1_constrain_logits`` (rule in
+    include/db1_hip.h) over the tokens a row has GENERATED so far (the prompt is not part of the history): ``repetition_penalty`` theta
+    (1 = off): the logit of every token already generated is divided by theta if positive, else multiplied; ``no_repeat_ngram_size`` n
+    (0 = off): no n-gram occurs twice; ``min_new_tokens``: EOS cannot be chosen before that many tokens (nothing without an ``eos_id``);
+    ``bad_token_ids``: never chosen.  Passed as ``constraints=`` to ``generate``, ``beam_search`` and the streams."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+    bad_token_ids: Tuple[int, ...] = ()
+
+    def __post_init__(self):
+        theta = float(self.repetition_penalty)
+        if not 0.0 < theta < float("inf"):
+            raise ValueError(f"repetition_penalty {self.repetition_penalty} must be finite and > 0")
+        for name in ("no_repeat_ngram_size", "min_new_tokens"):
+            v = getattr(self, name)
+            if not _is_count(v):
+                raise ValueError(f"{name} {v!r} must be an integer >= 0")
+        ids = tuple(self.bad_token_ids)
+        if len(ids) > MAX_BAD_TOKEN_IDS:
+            raise ValueError(f"bad_token_ids: {len(ids)} ids (at most {MAX_BAD_TOKEN_IDS})")
+        for v in ids:
+            if not _is_count(v):
+                raise ValueError(f"bad_token_ids: {v!r} must be an integer >= 0")
+        object.__setattr__(self, "repetition_penalty", theta)
+        object.__setattr__(self, "no_repeat_ngram_size", int(self.no_repeat_ngram_size))
+        object.__setattr__(self, "min_new_tokens", int(self.min_new_tokens))
+        object.__setattr__(self, "bad_token_ids", tuple(int(v) for v in ids))
+
+    def applies(self, eos_id: Optional[int] = 0) -> bool:
+        """whether anything is edited under a config with this ``eos_id`` (None: no EOS, so the minimum length holds nothing back).  THE
+        definition of a no-op: False means no launch, and the generator's cache key stays what it is without constraints"""
+        return bool(self.repetition_penalty != 1.0 or self.no_repeat_ngram_size or self.bad_token_ids or
+                    (self.min_new_tokens and eos_id is not None))
+
+    @property
+    def is_noop(self) -> bool:
+        """nothing to apply whatever the config (``applies`` also knows the config's ``eos_id``)"""
+        return not self.applies()
+
+
 def clip_at_eos(ids, lengths) -> List[List[int]]:
     """the tokens ``Decoder.decode(..., clip_at_eos=True)`` keeps (text_decoder.py:53-58), as id lists: row r's first ``lengths[r]`` ids"""
     ids = np.asarray(ids)
@@ -142,6 +194,36 @@ def _vocab_window(model, cfg) -> Tuple[int, int]:
     if int(cfg.vocab_lo) >= V:
         raise ValueError(f"vocabulary window [{cfg.vocab_lo}, {cfg.vocab_hi}) is empty in a vocabulary of {V}")
     return V, hi
+
+
+def _constrained(who: str, model, key: tuple, constraints, limit: int) -> tuple:
+    """the state key ``key`` = (rows, cfg, V, hi) with the constraints appended -- unless they are None or edit nothing under this config
+    (``DecodingConstraints.applies``): then the key, and with it the state, the launches and the cached generator, is exactly what it is
+    without them.  Raises before anything is launched."""
+    if constraints is None:
+        return key
+    if not isinstance(constraints, DecodingConstraints):
+        raise TypeError(f"{who}: DecodingConstraints expected, got {type(constraints).__name__}")
+    if constraints.min_new_tokens > int(limit):
+        raise ValueError(f"{who}: min_new_tokens {constraints.min_new_tokens} exceeds max_new_tokens {limit}")
+    if not constraints.applies(key[1].eos_id):
+        return key
+    V = key[2]
+    if not ops.constrain_logits_supported(V, V, key[1].max_new_tokens, len(constraints.bad_token_ids), model.compute_dtype):
+        raise ValueError(f"{who}: db1_constrain_logits does not support max_new_tokens {key[1].max_new_tokens}")
+    return key + (constraints,)
+
+
+def _constrain_args(cons: Optional[DecodingConstraints], cfg, V: int, dev) -> Optional[dict]:
+    """the keyword arguments a state's ``ops.constrain_logits`` call takes from its constraints (the banned ids as a device vector, made
+    once); None: no launch"""
+    if cons is None or not cons.applies(cfg.eos_id):
+        return None
+    eos = -1 if cfg.eos_id is None else int(cfg.eos_id)
+    min_new = cons.min_new_tokens if eos >= 0 else 0
+    bad = torch.tensor(cons.bad_token_ids, dtype=torch.int32).to(dev) if cons.bad_token_ids else None
+    return dict(V=V, repetition_penalty=cons.repetition_penalty, no_repeat_ngram_size=cons.no_repeat_ngram_size, bad=bad, eos_id=eos,
+                min_new=min_new)
 
 
 def _text_window(model, cfg):
@@ -253,21 +335,27 @@ class _SamplingState:
     and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``"""
     expand = None
 
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
         self.i32 = i32 = dict(dtype=torch.int32, device=model.dev)
         self.M, self.cfg, self.V, self.hi, self.dev = M, cfg, V, hi, model.dev
         self.finished, self.lengths, self.status, self.stream_id = (torch.zeros(M, **i32) for _ in range(4))
         self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
         self.sel = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                         seed=cfg.seed, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, stream_id=self.stream_id)
+        self.con = _constrain_args(cons, cfg, V, model.dev)
+
+    def constrain(self, logits2d, row_map=None):
+        """the decoding constraints, in place on the step's logits, over every row's own output so far (no constraints: no launch)"""
+        if self.con is not None:
+            ops.constrain_logits(logits2d, self.t, self.out, finished=self.finished, row_map=row_map, **self.con)
 
 
 class _State(_SamplingState):
     """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
     cache = "_generator"
 
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int):
-        super().__init__(model, M, cfg, V, hi)
+    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
+        super().__init__(model, M, cfg, V, hi, cons)
         self.t = torch.zeros(1, **self.i32)
         self.stream_id.copy_(torch.arange(M, dtype=torch.int32))
 
@@ -288,6 +376,7 @@ class _State(_SamplingState):
         ops.select_tokens(logits2d, self.t, self.finished, self.lengths, self.out, next_ids, self.status, **self.sel)
 
     def epilogue(self, logits2d, next_ids, ring=None):
+        self.constrain(logits2d)
         self.select(logits2d, next_ids)
         self.t.add_(1)
 
@@ -311,7 +400,7 @@ class _BeamState:
     """the device state of one beam search over G groups of W beams (include/db1_hip.h, db1_beam_step)"""
     cache = "_beam_generator"
 
-    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int):
+    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
         dev = model.dev
         W, mx = int(cfg.num_beams), int(cfg.max_new_tokens)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -329,6 +418,7 @@ class _BeamState:
         self.done = torch.zeros(G, **i32)
         self.switches = torch.zeros(G, **i32)
         self.status = torch.zeros(G, **i32)
+        self.con = _constrain_args(cons, cfg, V, dev)
 
     def start(self):
         pad = self.cfg.pad_id
@@ -343,6 +433,8 @@ class _BeamState:
     def select(self, logits2d, next_ids):
         """db1_beam_step on the last-position logits [M, V] of step t; the next ids go to ``next_ids`` (int64 [M])"""
         c = self.cfg
+        if self.con is not None:     # (``tokens``: db1_beam_step has reordered it into every new beam's own history)
+            ops.constrain_logits(logits2d, self.t, self.tokens, **self.con)
         ops.beam_step(logits2d, self.t, self.beam_score, self.parent, self.tokens, self.pool_tokens, self.pool_len, self.pool_score, self.pool_slot,
                       self.pool_count, self.done, self.switches, next_ids, self.status, W=self.W, V=self.V, vocab_lo=c.vocab_lo, vocab_hi=self.hi,
                       eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, length_penalty=c.length_penalty)
@@ -466,20 +558,24 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
 
 @torch.no_grad()
 def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
-             stats: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             stats: Optional[dict] = None, replay: bool = True,
+             constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
     of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
     after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
     on its logits, its stream id, the seed and the token index, not on the other rows.  ``graphed`` None: the hipGraph ring path where the
     model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
-    receives the path taken and the number of per-token calls."""
+    receives the path taken and the number of per-token calls.  ``replay`` False (ring path): the same forward and epilogue run eagerly over
+    the same ring instead of as a graph replay.  ``constraints`` (a ``DecodingConstraints``): applied to every step's logits
+    on the device, over the tokens generated so far, before the token is chosen."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate")
     M = _batch_size(prompt)
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
-    return _decode(model, prompt, _State, (M, cfg, V, hi), graphed, True, stats, start=(stream_ids,))
+    key = _constrained("generate", model, (M, cfg, V, hi), constraints, cfg.max_new_tokens)
+    return _decode(model, prompt, _State, key, graphed, replay, stats, start=(stream_ids,))
 
 
 def _run(model, x, cfg, **kw):
@@ -538,7 +634,7 @@ def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
 
 @torch.no_grad()
 def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
-                replay: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                replay: bool = True, constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Beam search after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of G prompts of one shape ->
     (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R = ``num_return_sequences``: each prompt's
     best hypotheses, best first.  ``ids[g, r, :lengths[g, r]]`` are the tokens before EOS (then EOS, then ``pad_id``); the score is the sum of
@@ -547,7 +643,8 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     ``graphed`` None: the hipGraph ring path where the model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False
     forces the eager loop (the list-form memory is reordered with index_select).  ``replay`` False (ring path): the same forward and epilogue
     run eagerly over the same ring instead of as a graph replay.  ``stats`` (a dict): receives the path taken, the number of per-token calls
-    and ``parent_switches``, the number of (step, row) pairs (step > 0) whose parent was another row."""
+    and ``parent_switches``, the number of (step, row) pairs (step > 0) whose parent was another row.  ``constraints`` (a
+    ``DecodingConstraints``): applied to every step's logits on the device, over each beam's own tokens so far, before the beam step."""
     cfg = config or BeamSearchConfig()
     if not isinstance(cfg, BeamSearchConfig):
         raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
@@ -561,4 +658,5 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
         raise ValueError(f"eos_id {cfg.eos_id} lies outside the model's vocabulary ({V})")
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
-    return _decode(model, prompt, _BeamState, (G, cfg, V, hi), graphed, replay, stats)
+    key = _constrained("beam_search", model, (G, cfg, V, hi), constraints, cfg.max_new_tokens)
+    return _decode(model, prompt, _BeamState, key, graphed, replay, stats)

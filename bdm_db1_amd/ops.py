@@ -9,6 +9,7 @@ import threading
 import weakref
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import lib
@@ -653,6 +654,58 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
     lib.call("db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k),
              float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(limit), P(stream_id),
              P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), P(row_map), S, _vp(0), 0, stream())
+
+
+def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype) -> bool:
+    return bool(lib.load().db1_constrain_logits_supported(int(V), int(ld), int(max_new), int(n_bad), dt_code(dtype)))
+
+
+def constrain_logits(logits2d, t, hist, *, V=None, finished=None, row_map=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad=None,
+                     eos_id=-1, min_new=0):
+    """the decoding constraints of one step, IN PLACE on ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) before a selection
+    or beam step reads it (db1_constrain_logits, rule in include/db1_hip.h): the repetition penalty over each row's history, the no-repeat
+    n-gram ban, the banned ids ``bad`` (int32, device; None: none) and EOS banned while t < ``min_new``; a ban is a -inf.  ``hist`` (int32
+    [S, max_new]): the tokens every slot has generated so far; ``t`` (int32, device, READ only): [1], one counter for all rows, or [S], one
+    per slot; ``finished`` (int32 [S] or None): rows left alone; ``row_map`` (int32 [M]) as ``select_tokens_slots`` takes it, None: row i is
+    slot i and S = M.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    who, dev, i32 = "constrain_logits", logits2d.device, torch.int32
+    if not torch.is_tensor(hist) or hist.dim() != 2:
+        raise ValueError(f"{who}: hist must be a contiguous {i32} tensor of shape (slots, max_new) on {dev}")
+    if not torch.is_tensor(t) or not (bad is None or torch.is_tensor(bad)):
+        raise ValueError(f"{who}: t and bad must be {i32} tensors on {dev} (bad: or None)")
+    S, mx = hist.shape
+    n_bad = 0 if bad is None else int(bad.numel())
+    if not 1 <= mx <= 4096:
+        raise ValueError(f"{who}: max_new {mx} (the columns of hist) must lie in [1, 4096]")
+    if n_bad > 1024:
+        raise ValueError(f"{who}: {n_bad} banned ids (at most 1024)")
+    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None,
+                                   lambda V, ld: constrain_logits_supported(V, max(ld, V), mx, n_bad, logits2d.dtype))
+    _check_tensor(who, "hist", hist, i32, (S, mx), dev)
+    if row_map is not None:
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if S < M:
+            raise ValueError(f"{who}: {M} logits rows for {S} slots")
+    elif S != M:
+        raise ValueError(f"{who}: hist holds {S} rows for {M} logits rows (no row_map)")
+    if t.numel() not in (1, S):
+        raise ValueError(f"{who}: t must hold 1 or {S} elements")
+    _check_tensor(who, "t", t, i32, int(t.numel()), dev)
+    if finished is not None:
+        _check_tensor(who, "finished", finished, i32, S, dev)
+    if bad is not None:
+        _check_tensor(who, "bad", bad, i32, n_bad, dev)
+    theta = float(repetition_penalty)
+    if not 0.0 < theta < float("inf"):
+        raise ValueError(f"{who}: repetition_penalty {repetition_penalty} must be finite and > 0")
+    theta32 = float(np.float32(theta))
+    if not 0.0 < theta32 < float("inf") or not 0.0 < float(np.float32(1.0 / theta32)) < float("inf"):
+        raise ValueError(f"{who}: repetition_penalty {repetition_penalty} and its inverse must be finite and > 0 in float32")
+    if int(no_repeat_ngram_size) < 0 or int(min_new) < 0:
+        raise ValueError(f"{who}: no_repeat_ngram_size {no_repeat_ngram_size} and min_new {min_new} must be >= 0")
+    lib.call("db1_constrain_logits", P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(t), int(t.numel() == S and S > 1), P(hist), mx,
+             P(finished), P(row_map), S, theta32, float(np.float32(1.0 / theta32)), min(int(no_repeat_ngram_size), 2 ** 31 - 1),
+             P(bad if n_bad else None), n_bad, max(int(eos_id), -1), min(int(min_new), 2 ** 31 - 1), _vp(0), 0, stream())
 
 
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:

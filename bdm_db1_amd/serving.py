@@ -26,8 +26,9 @@ import numpy as np
 import torch
 
 from . import ops
-from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, GenerationConfig, _batch_size, _need_memory, _prefill, _ring_generator, _ring_ok,
-                         _SamplingState, _take, _text_window, _vocab_window, _work, caption_prompt, question_prompts)
+from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, GenerationConfig, _batch_size, _constrained, _need_memory,
+                         _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _work, caption_prompt,
+                         question_prompts)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- requests
@@ -63,9 +64,10 @@ def _shape_key(prompt) -> tuple:
     return tuple(key)
 
 
-def _requests(items: Iterable, cfg: GenerationConfig) -> Iterator[Request]:
+def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0) -> Iterator[Request]:
     """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item) as Requests, numbered in order; raises ValueError for a limit outside
-    [1, cfg.max_new_tokens] and what ``generate`` raises for a prompt batch that is not one shape"""
+    [1, cfg.max_new_tokens] or below ``min_new`` (the constraints' minimum length) and what ``generate`` raises for a prompt batch that is
+    not one shape"""
     nxt = 0
     for item in items:
         indices = None
@@ -80,6 +82,8 @@ def _requests(items: Iterable, cfg: GenerationConfig) -> Iterator[Request]:
         limit = int(cfg.max_new_tokens if limit is None else limit)
         if not 1 <= limit <= int(cfg.max_new_tokens):
             raise ValueError(f"generate_stream: a request's max_new_tokens {limit} must lie in [1, config.max_new_tokens = {cfg.max_new_tokens}]")
+        if limit < min_new:
+            raise ValueError(f"generate_stream: min_new_tokens {min_new} exceeds a request's max_new_tokens {limit}")
         G = _batch_size(prompt)
         key = _shape_key(prompt)
         if indices is None:
@@ -179,8 +183,8 @@ class _SlotState(_SamplingState):
     """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row"""
     cache = "_slot_generator"
 
-    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int):
-        super().__init__(model, slots, cfg, V, hi)
+    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
+        super().__init__(model, slots, cfg, V, hi, cons)
         self.t = torch.zeros(slots, **self.i32)
         self.limit = torch.ones(slots, **self.i32)
         self.finished.fill_(1)       # (vacant)
@@ -201,6 +205,7 @@ class _SlotState(_SamplingState):
         return idx.to(torch.int32)
 
     def select(self, logits2d, next_ids, row_map=None):
+        self.constrain(logits2d, row_map)
         ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map, **self.sel)
 
     def epilogue(self, logits2d, next_ids, ring=None):
@@ -215,7 +220,8 @@ class _SlotState(_SamplingState):
 
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
 def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig] = None, slots: int = 8, stream_ids=None,
-                    stats: Optional[dict] = None, replay: bool = True) -> Iterator[Tuple[int, torch.Tensor, int]]:
+                    stats: Optional[dict] = None, replay: bool = True,
+                    constraints: Optional[DecodingConstraints] = None) -> Iterator[Tuple[int, torch.Tensor, int]]:
     """Generate for a stream of requests over ``slots`` recycled rows; yields ``(index, ids int32 [limit], length)`` on the host as requests
     finish (requests that are found finished at the same look come in index order).  ``ids[:length]`` are the tokens before EOS, then EOS,
     then ``pad_id``.
@@ -230,7 +236,9 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     ``admitted``, ``occupancy`` = live row-steps / (replays * slots) and ``no_candidate``: the requests that ended early because a step had no
     finite logit in the window (``pad_id`` written, as ``generate`` does; they come back like any other request).  ONE stream at a time per
     model: the slots, the ring and the graph are kept on the model, so a second ``generate_stream`` whose first result is asked for while
-    another is still running raises RuntimeError (run the first to its end or ``close()`` it)."""
+    another is still running raises RuntimeError (run the first to its end or ``close()`` it).  ``constraints`` (a ``DecodingConstraints``):
+    applied on the device to every step's logits over each request's own tokens so far, whatever slot it sits in; a request whose limit is
+    below ``min_new_tokens`` raises ValueError."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -241,13 +249,16 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_slots_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens_slots does not support a vocabulary of {V}")
+    key = _constrained("generate_stream", model, (slots, cfg, V, hi), constraints, cfg.max_new_tokens)
+    min_new = 0 if constraints is None else constraints.min_new_tokens
     if isinstance(requests, (list, tuple)):
-        for _ in _requests(requests, cfg):     # (a list can be checked as a whole before the first launch)
+        for _ in _requests(requests, cfg, min_new):     # (a list can be checked as a whole before the first launch)
             pass
-    return _stream(model, _requests(requests, cfg), cfg, slots, V, hi, stream_ids, stats, replay)
+    return _stream(model, _requests(requests, cfg, min_new), key, stream_ids, stats, replay)
 
 
-def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
+def _stream(model, reqs, key, stream_ids, stats, replay):
+    slots, cfg = key[0], key[1]
     sched = SlotScheduler(slots, reqs)
     counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
     live_steps = 0
@@ -268,7 +279,7 @@ def _stream(model, reqs, cfg, slots, V, hi, stream_ids, stats, replay):
                     if held is not None and held.busy:
                         raise RuntimeError("generate_stream: another stream is still running on this model (one stream at a time: finish or "
                                            "close() it first)")
-                    gen = _ring_generator(model, _SlotState, (slots, cfg, V, hi))
+                    gen = _ring_generator(model, _SlotState, key)
                     gen.busy = True
                     gen.state.start()
                     gen.ring.load_status.zero_()

@@ -617,6 +617,37 @@ int db1_ring_load_rows_supported(int64_t slot_bytes, int mlen, int cap);
 int db1_ring_load_rows(const void* const* rings, const void* const* src, int n_layers, int M, int n, int cap, int64_t slot_bytes,
                        const int32_t* state, int mlen, const int32_t* rows, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------ decoding constraints (tests/constraint_rule.py restates the rule in
+ * NumPy).  db1_constrain_logits edits the step's logits [M, ld] (fp32 / bf16; columns >= V are padding) IN PLACE, before
+ * db1_select_tokens / db1_select_tokens_slots / db1_beam_step read them: those take only FINITE logits as candidates and keep NaN and
+ * +-inf out of their log-sum-exp, so a banned column is a column set to -inf.  Logits row i belongs to slot row_map[i] (NULL: slot i, and
+ * then n_slots == M); its history H = hist[slot * max_new + 0 .. t) holds the tokens it has generated so far (the prompt is not part of
+ * it) and t = t[slot] (t_per_slot != 0) or t[0] is its token index.  For one row l[0 .. V):
+ *   1. guard: nothing in the row is touched when t is outside [0, max_new), when finished[slot] != 0 (finished NULL: no such test), or when
+ *      the row_map entry is outside [0, n_slots);
+ *   2. repetition penalty theta (> 0; 1 = off): every DISTINCT token c of H with 0 <= c < V and l[c] finite, once however often it occurs:
+ *      l[c] <- round(l32 * inv_theta) if l32 > 0 else round(l32 * theta), l32 = the stored value widened to fp32, inv_theta = the fp32
+ *      nearest to 1 / theta (computed by the caller in double), each product ONE fp32 multiplication, round = identity (fp32) or round to
+ *      nearest even (bf16).  History entries outside [0, V) (a pad_id) are skipped, non-finite logits are left as stored;
+ *   3. no-repeat n-gram of size ngram (0 = off): for every i in [ngram - 1, t) with H[i - ngram + 1 .. i - 1] == H[t - ngram + 1 .. t - 1],
+ *      column H[i] is banned (ngram = 1: every token of H; nothing while t < ngram - 1);
+ *   4. banned ids: every id of the device list bad[0 .. n_bad) inside [0, V) is banned at every step;
+ *   5. minimum length: eos_id (>= 0) is banned while t < min_new;
+ *   6. a banned column is WRITTEN as -inf, after the penalty (a ban overrides it); a ban outside [0, V) is ignored;
+ *   7. every other column of the row, the padding columns [V, ld) and every other row stay bit-identical.
+ * One workgroup per row, the row's history staged in LDS: O(t + n_bad) columns are touched, the vocabulary is never swept.  No atomics: only
+ * the first occurrence of a token computes and stores its penalised value, a workgroup barrier follows, then the bans store -inf
+ * (duplicates write the same bits): the same inputs give the same bits.  t, hist, finished, row_map and bad are only READ: the launch can be
+ * captured into a graph and replayed.  With nothing to do (theta == 1, ngram == 0, n_bad == 0, no minimum length) there is no launch.
+ * The first-occurrence test scans the history before each position: O(t^2 / 256) LDS reads per thread in the worst case (all tokens
+ * distinct), on top of the O(t + n_bad) columns touched.
+ * max_new <= 4096 and n_bad <= 1024 (_supported; DB1_ERR_UNSUPPORTED otherwise); no workspace (the query returns 0). */
+int db1_constrain_logits_supported(int V, int64_t ld, int max_new, int n_bad, int dt);
+int64_t db1_constrain_logits_workspace_bytes(int M, int V, int max_new, int n_bad, int dt);
+int db1_constrain_logits(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist, int max_new,
+                         const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
+                         const int32_t* bad, int n_bad, int eos_id, int min_new, void* ws, int64_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
  * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window
  * [vocab_lo, vocab_hi) with 0 <= vocab_lo < vocab_hi <= V:

@@ -26,7 +26,13 @@ limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS);
     (prefills included in both), the replay counts, the occupancy, and what the admissions cost (total - replays x per-replay cost);
   * db1_ring_load_rows alone: 16 rows into a ring of 64, device time from events, bytes read + written.
 
-    python tools/bench_generate.py --stream [requests [slots]]"""
+    python tools/bench_generate.py --stream [requests [slots]]
+
+With --constraints: the greedy caption measurement above, unconstrained and with DecodingConstraints(repetition_penalty=1.2,
+no_repeat_ngram_size=3, min_new_tokens=5) -- one db1_constrain_logits launch more in every replay (no EOS, as in every run here, so
+the minimum length bans nothing) --, one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel time of db1_constrain_logits.
+
+    python tools/bench_generate.py --constraints [M ...]"""
 import dataclasses
 import json
 import os
@@ -38,7 +44,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from bdm_db1_amd import BeamSearchConfig, GenerationConfig, GraphedRingStep, TransformerXL, generate_captions, lib, ops, synth  # noqa: E402
+from bdm_db1_amd import BeamSearchConfig, DecodingConstraints, GenerationConfig, GraphedRingStep, TransformerXL, generate_captions, lib, ops, synth  # noqa: E402
 from bdm_db1_amd.data import ICTaskInput, NLPTaskInput  # noqa: E402
 lib.apply_env_knobs()
 
@@ -56,18 +62,18 @@ def batch(M):
                        img_seq=torch.from_numpy(rng.standard_normal((M, 3, 224, 224)).astype(np.float32)).to(dev), text_seq=None)
 
 
-def gen_ms_per_token(M, cfg, short=10):
+def gen_ms_per_token(M, cfg, short=10, **kw):
     """the token loop of generate_captions: (time of N_NEW tokens - time of `short` tokens) / (N_NEW - short) -- the prefill, the ring load
-    and the first selection are the same in both and cancel"""
+    and the first selection are the same in both and cancel; ``kw``: handed to generate_captions (constraints=)"""
     b = batch(M)
 
     def best(c):
-        generate_captions(model, b, c)                  # capture + warm-up
+        generate_captions(model, b, c, **kw)            # capture + warm-up
         t = 1e30
         for _ in range(REPS):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            generate_captions(model, b, c)
+            generate_captions(model, b, c, **kw)
             t = min(t, time.perf_counter() - t0)
         return t
 
@@ -290,6 +296,15 @@ if "--num-beams" in args:
     i = args.index("--num-beams")
     W = int(args[i + 1])
     beam_main(W, [int(a) for a in args[:i] + args[i + 2:]] or [1, 16])
+    sys.exit(0)
+if "--constraints" in args:
+    cons = DecodingConstraints(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=5)
+    for M in [int(a) for a in args if a != "--constraints"] or [1, 16, 64]:
+        rec = {"M": M, "new_tokens": N_NEW, "constraints": dataclasses.asdict(cons)}
+        rec["greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW)), 4)
+        rec["constrained_greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW), constraints=cons), 4)
+        rec["constrained_minus_plain_us"] = round((rec["constrained_greedy_ms_per_token"] - rec["greedy_ms_per_token"]) * 1e3, 2)
+        print(json.dumps(rec), flush=True)
     sys.exit(0)
 Ms = [int(a) for a in args] or [1, 16, 64]
 for M in Ms:
