@@ -190,19 +190,16 @@ extern "C" int db1_gemm_would_use_fast(int M, int N, int K, int dtA, int dtB, in
     return fast_ok(M, N, K, dtA, dtB, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, &fa, &fb, &lda, &ldb) ? 1 : 0;
 }
 
-template <bool AK, bool BK_>
-static void launch_tile(const GemmTileArgs& t, int dtC, int dtBias, dim3 grid, hipStream_t st) {
-    const size_t sm = 4 * TILE_BYTES;
-    if (dtC == DB1_F32) {
-        if (dtBias == DB1_BF16) gemm_bf16_tile_kernel<AK, BK_, float, bf16_t><<<grid, 256, sm, st>>>(t);
-        else gemm_bf16_tile_kernel<AK, BK_, float, float><<<grid, 256, sm, st>>>(t);
-    } else {
-        if (dtBias == DB1_BF16) gemm_bf16_tile_kernel<AK, BK_, bf16_t, bf16_t><<<grid, 256, sm, st>>>(t);
-        else gemm_bf16_tile_kernel<AK, BK_, bf16_t, float><<<grid, 256, sm, st>>>(t);
-    }
+template <bool AK, bool BK_> struct Tile128Kernels {
+    template <typename TC, typename TB> static GemmKernelFn fn() { return gemm_bf16_tile_kernel<AK, BK_, TC, TB>; }
+};
+// t.ksplit > 1: the slices of k are the grid's z (partial sums at t.C + z * t.c_zs)
+static int tile128_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st) {
+    gemm_launch_forms<Tile128Kernels>(t, fa, fb, dtC, dtBias, dim3((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch, (unsigned)t.ksplit), 256, 4 * TILE_BYTES, st);
+    DB1_CHECK_LAUNCH("gemm_bf16_tile");
+    return DB1_OK;
 }
 
-static thread_local int g_tri_mode = 0, g_tri_period = 0;  // structural-zero hint of the current call (db1_gemm_strided_tri)
 // test-only steering (include/db1_hip_test.h), thread-local: never set by product code
 static thread_local int g_force_generic = 0;
 static thread_local int g_tile_pref = 0;      // 0: measured heuristics; 128 / 256 / 512 / 1024: pin that tile kernel
@@ -212,33 +209,67 @@ extern "C" void db1_test_gemm_tile_override(int tile) { g_tile_pref = tile; }
 struct GemmEnv { int tile, splitk; };
 static GemmEnv gemm_env() { return GemmEnv{db1_knob(DB1_KNOB_GEMM_TILE, 0), db1_knob(DB1_KNOB_GEMM_SPLITK, 1)}; }
 
-// ---- the dispatcher's decision, separated from the launch so that the workspace query, the kernel-choice query and the call agree
+// ---- the dispatcher's decision.  gemm_plan is the ONLY place that decides; gemm_run executes a plan verbatim and the two queries
+// (workspace, kernel choice) read its fields, so the three cannot disagree.
 enum { GK_GENERIC = 0, GK_TILE128 = 1, GK_TILE256 = 2, GK_PP = 3, GK_PP32 = 4, GK_W4 = 5, GK_SKINNY = 6, GK_W4N = 7, GK_SPLITK = 16, GK_TAIL = 32 };
-struct GemmPlan {
-    int kind = GK_GENERIC;   // GK_* of the kernel that runs the contraction (for GK_TAIL: of the main part)
-    int fa = 0, fb = 0;
-    int64_t lda = 0, ldb = 0;
-    int S = 0;               // GK_SPLITK: slices of k
-    int m_tail = 0;          // GK_TAIL: rows of the second call
-    int ksplit = 1;          // GK_TILE128 with atomic split-K (conv weight gradients)
-};
 struct GemmShape {
     int M, N, K, dtA, dtB, dtC, batch0, batch1;
     int64_t a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, a_bs0, a_bs1, b_bs0, b_bs1, c_bs0, c_bs1;
     float beta;
+    int tri_mode = 0, tri_period = 0;   // structural-zero hint for A (db1_gemm_strided_tri; GemmTileArgs::tri_mode).  The queries have none.
+};
+struct GemmPlan {
+    int kind = GK_GENERIC;   // GK_* of the kernel that runs the contraction -- the one that is launched, after the choice between the 4-wave and
+                             // the 8-wave kernels (for GK_TAIL: of the main part) -- | GK_SPLITK | GK_TAIL
+    int fa = 0, fb = 0;      // storage forms of A and B (operand_form) ...
+    int64_t lda = 0, ldb = 0;   // ... and their leading dimensions
+    int tri_mode = 0, tri_period = 0;   // the hint as the kernel gets it (mode 2 with a period that does not fit the tiling is no hint)
+    int S = 0;               // GK_SPLITK: slices of k
+    int m_tail = 0;          // GK_TAIL: rows of the second call
+    int ksplit = 1;          // GK_TILE128: slices of a long contraction into a small fp32 accumulator (conv weight gradients), through the workspace
+    int64_t ws_bytes = 0;    // workspace this plan needs (db1_gemm_workspace_bytes)
 };
 static GemmTileArgs tile_args(const GemmShape& g, const GemmPlan& pl) {
-    GemmTileArgs t;
-    t.A = nullptr; t.B = nullptr; t.C = nullptr; t.bias = nullptr;
-    t.M = g.M; t.N = g.N; t.K = g.K; t.lda = pl.lda; t.ldb = pl.ldb; t.ldc = g.c_rs;
+    GemmTileArgs t = gemm_tile_args_2d(nullptr, nullptr, nullptr, nullptr, g.M, g.N, g.K, pl.lda, pl.ldb, g.c_rs);
     t.batch1 = g.batch1; t.a_bs0 = g.a_bs0; t.a_bs1 = g.a_bs1; t.b_bs0 = g.b_bs0; t.b_bs1 = g.b_bs1; t.c_bs0 = g.c_bs0; t.c_bs1 = g.c_bs1;
-    t.alpha = 1.f; t.beta = g.beta; t.tiles_m = (g.M + TBM - 1) / TBM; t.tiles_n = (g.N + TBN - 1) / TBN; t.ksplit = 1;
-    t.tri_mode = g_tri_mode; t.tri_period = g_tri_period; t.tri_walk = db1_knob(DB1_KNOB_TRI_SPLIT, 1) != 0;
-    t.split_n = 0; t.Cu = nullptr; t.Cv = nullptr; t.bias_u = nullptr; t.bias_v = nullptr; t.ld_uv = 0;
-    if (t.tri_mode == 2 && (t.tri_period <= 0 || (t.tri_period % TBK) || (g.K % t.tri_period))) t.tri_mode = 0;
+    t.beta = g.beta; t.tiles_m = (g.M + TBM - 1) / TBM; t.tiles_n = (g.N + TBN - 1) / TBN;
+    t.tri_mode = pl.tri_mode; t.tri_period = pl.tri_period; t.tri_walk = db1_knob(DB1_KNOB_TRI_SPLIT, 1) != 0;
     return t;
 }
+// one launch of a split-K plan: the pl.S slices of k become the inner batch level of `t` (operand pointers advance by K / S per slice), each
+// writing its fp32 partial sum to ws [batch][S][M][N].  The plan calls this with ws = nullptr to ask which kernel takes the slices.
+static GemmTileArgs splitk_slice_args(const GemmTileArgs& t, const GemmPlan& pl, void* ws) {
+    GemmTileArgs u = t;
+    const int64_t kc = t.K / pl.S;
+    u.K = (int)kc; u.C = ws; u.bias = nullptr; u.beta = 0.f; u.ldc = t.N;
+    if (u.tri_mode == 1 || (u.tri_mode == 2 && (kc % u.tri_period))) u.tri_mode = 0;  // a slice of k no longer starts at k = 0 / on a period
+    u.batch1 = pl.S; u.a_bs1 = pl.fa == 0 ? kc : kc * pl.lda; u.b_bs1 = pl.fb == 0 ? kc : kc * pl.ldb;
+    u.c_bs0 = (int64_t)pl.S * t.M * t.N; u.c_bs1 = (int64_t)t.M * t.N;
+    return u;
+}
 static int64_t splitk_bytes(const GemmShape& g, int S, int M) { return (int64_t)g.batch0 * g.batch1 * S * M * g.N * (int64_t)sizeof(float); }
+// which 256 x 256 kernel runs `t`: the 4-wave one wherever it applies, else an 8-wave ping-pong kernel (k32: the 4-stage k32 ring)
+static int kind_256(const GemmTileArgs& t, int fa, int fb, int dtC, int batch, bool k32) {
+    return db1_gemm_w4_supported(t, 8, fa, fb, dtC, batch) ? GK_W4 : (k32 ? GK_PP32 : GK_PP);
+}
+// the last-wave rule: by the fill of the last wave of workgroups, with the 256 x 128 kernel priced at 0.85 of the 256 x 256 one per FLOP
+static bool last_wave_wants_128(int64_t wg256, int64_t wg128) {
+    if (wg256 < 160 || wg256 >= 1024) return false;
+    const double e256 = (double)wg256 / (256.0 * ((wg256 + 255) / 256)), e128 = (double)wg128 / (256.0 * ((wg128 + 255) / 256));
+    return 0.85 * e128 > e256;
+}
+// the launch function of a plan's kernel (the tile kernels with 256-row tiles; 128-row tiles: tile128_launch)
+static int launch_kind(int kind, const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st) {
+    switch (kind & 15) {
+        case GK_W4: return db1_gemm_w4_launch(t, 8, fa, fb, dtC, dtBias, batch, st);
+        case GK_W4N: return db1_gemm_w4_launch(t, 4, fa, fb, dtC, dtBias, batch, st);
+        case GK_PP: return db1_gemm_pp_launch(t, fa, fb, dtC, dtBias, batch, st);
+        case GK_PP32: return db1_gemm_pp32_launch(t, fa, fb, dtC, dtBias, batch, st);
+        case GK_TILE256: return db1_gemm_tile256_launch(t, fa, fb, dtC, dtBias, batch, st);
+        case GK_TILE128: return tile128_launch(t, fa, fb, dtC, dtBias, batch, st);
+    }
+    DB1_FAIL(DB1_ERR_UNSUPPORTED, "gemm: no tile kernel of kind %d", kind);
+}
 
 // `aligned`: the operand pointers are 16-byte aligned (the queries assume so); `ws_bytes`: workspace the caller offers (< 0: "whatever
 // the plan needs", used by the queries).  A split-K plan is only made when its partial sums fit the offered workspace.
@@ -257,25 +288,29 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
     }
     if (batch > 65535 || !fast_ok(M, N, K, g.dtA, g.dtB, g.a_rs, g.a_cs, g.b_rs, g.b_cs, g.c_rs, g.c_cs, &pl.fa, &pl.fb, &pl.lda, &pl.ldb)) return pl;
     const int fa = pl.fa, fb = pl.fb;
+    pl.tri_mode = g.tri_mode == 2 && (g.tri_period <= 0 || (g.tri_period % TBK) || (K % g.tri_period)) ? 0 : g.tri_mode;
+    pl.tri_period = g.tri_period;
     const bool splitk_on = gemm_env().splitk != 0;
     // measured on MI355X at the DB1-1.3B shapes (tools/bench_kernels.py gemm; table in DESIGN.md): the 256x256 kernels win by 15-35 %
     // wherever they have >= ~160 output tiles to spread over the 256 CUs; below that the 3-stage 256x128 kernel wins for the
     // transposed-operand forms and the 2-stage 128x128 kernel for NT / small outputs.
     const bool pp_shape = (M % 256) == 0 && (N % 256) == 0, t256_shape = (M % 256) == 0 && (N % TBN) == 0;
     const GemmTileArgs t = tile_args(g, pl);
-    auto big = [&](const GemmTileArgs& u, int nbatch, bool k32) {   // which 256x256 kernel db1_gemm_pp(32)_launch ends up running
-        return db1_gemm_w4_supported(u, fa, fb, u.C == (void*)1 ? DB1_F32 : g.dtC, nbatch) ? GK_W4 : (k32 ? GK_PP32 : GK_PP);
-    };
     // a short last wave of 256x256 tiles (head dW: 1040 tiles = 4 waves + 16 tiles, i.e. a fifth wave on 6 % of the CUs): the tile
     // rows of that remainder become a second call (9.3 -> 7.9 ms at T = 65 536)
-    if (tile_pref == 0 && splitk_on && pp_shape && batch == 1 && g.c_cs == 1 && g_tri_mode == 0) {
+    if (tile_pref == 0 && splitk_on && pp_shape && batch == 1 && g.c_cs == 1 && g.tri_mode == 0) {
         const int64_t tn_ = N / 256, wg_ = (int64_t)(M / 256) * tn_, rem = wg_ % 256;
         if (wg_ > 256 && rem > 0 && rem <= 48 && rem % tn_ == 0 && (K / TBK) >= 256) {
-            GemmShape mainp = g;                      // (the second call plans itself: split-K or the 256x128 kernel, as its size says)
-            mainp.M = M - (int)(rem / tn_) * 256;
-            pl = gemm_plan(mainp, true, ws_bytes);
+            GemmShape part = g;                       // (both calls plan themselves: the second takes split-K or a smaller tile, as its size says)
+            part.M = (int)(rem / tn_) * 256;
+            const GemmPlan tail = gemm_plan(part, true, ws_bytes);
+            part.M = M - part.M;
+            pl = gemm_plan(part, true, ws_bytes);
             pl.kind |= GK_TAIL;
-            pl.m_tail = (int)(rem / tn_) * 256;
+            pl.m_tail = M - part.M;
+            // (what the query has always asked for: the split-K partials of the second call.  Its 128-tile split is not asked for and so
+            //  only taken when the caller offers more than the query said)
+            pl.ws_bytes = (tail.kind & GK_SPLITK) ? tail.ws_bytes : 0;
             return pl;
         }
     }
@@ -284,7 +319,7 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
     // the half-wave split-K; 2 after it; 3 = 1 + the last-wave rule below: the default)
     const int w4n_mode = db1_knob(DB1_KNOB_W4N, 3);
     const bool w4n_shape = w4n_mode && tile_pref == 0 && (M % 256) == 0 && (N % 128) == 0 && g.c_cs == 1 &&
-                           db1_gemm_w4n_supported(t, fa, fb, g.dtC, (int)batch);   // (incl. its structural-zero rules)
+                           db1_gemm_w4_supported(t, 4, fa, fb, g.dtC, (int)batch);   // (incl. its structural-zero rules)
     const int64_t wg256 = (int64_t)(M / 256) * ((N + 255) / 256) * batch, wg128 = (int64_t)(M / 256) * (N / 128) * batch;
     // (a weight gradient over K = 65 536 rows keeps the two-slice split-K of the 256 x 256 kernel: ff2 dW 831 us against 918 us here; at
     //  K = 16 384 the 256 x 128 kernel wins, 244 against 260 us)
@@ -298,11 +333,11 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
         // one slice set that fills the chip (4 slices: 256 workgroups) waits for its heaviest row; with 8 slices and the heavy-first walk of the
         // 4-wave kernel the light rows run behind the heavy ones (knob "tri_split": 0 = the plain rule)
         const bool tri_shape = !pp_shape && (int64_t)(N / TBN) == 1 && db1_knob(DB1_KNOB_TRI_SPLIT, 1) == 1;   // (2: the walk alone)
-        const bool tri_rows = tri_shape && g_tri_mode == 2 && g_tri_period > 0;
+        const bool tri_rows = tri_shape && g.tri_mode == 2 && g.tri_period > 0;
         // (the workspace query does not know the hint: it prices the shape as if it came with one -- the larger slice count)
         const int64_t wg_cap = (tri_rows || (tri_shape && ws_bytes < 0)) ? 512 : 288;
         for (int cand = 8; cand >= 2; cand >>= 1)
-            if (wg * cand <= wg_cap && (K / TBK) % cand == 0 && (K / TBK) / cand >= 16 && (!tri_rows || (K / cand) % g_tri_period == 0) &&
+            if (wg * cand <= wg_cap && (K / TBK) % cand == 0 && (K / TBK) / cand >= 16 && (!tri_rows || (K / cand) % g.tri_period == 0) &&
                 (ws_bytes < 0 || splitk_bytes(g, cand, M) <= ws_bytes)) { S = cand; break; }   // (16: micro-batches of 4 sequences, K = 4096)
         // half a wave of 256x256 tiles (128 of them) in two slices.  Round 1 measured the weight gradients of 64-sequence batches (ff2 dW: nothing
         // at K = 16 384, 1184 -> 978 us at K = 65 536).  Round 4, micro-batches of 4 sequences (T = 4096, tools/bench_kernels.py gemm 4, 4-wave
@@ -317,29 +352,24 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
         const bool three_quarters = pp_shape && fb == 1 && wg == 192 && (K / TBK) % 4 == 0 && (K / TBK) / 4 >= 128;
         if (three_quarters) S = 4;
         if (S && (wg <= 96 || half_wave || three_quarters) && (!pp_shape || wg * S >= 160) && (ws_bytes < 0 || splitk_bytes(g, S, M) <= ws_bytes)) {
-            GemmTileArgs u = t;
-            u.K = K / S; u.ldc = N; u.C = (void*)1;   // (marker: fp32 partials)
-            if (u.tri_mode == 1 || (u.tri_mode == 2 && (u.K % u.tri_period))) u.tri_mode = 0;
-            u.batch1 = S;
             pl.S = S;
+            pl.ws_bytes = splitk_bytes(g, S, M);
+            const GemmTileArgs u = splitk_slice_args(t, pl, nullptr);   // (the slices' partials are fp32 whatever C is)
             // (!pp_shape: N is a multiple of 128 only -- the per-head dR contraction: the 256 x 128 form of the 4-wave kernel where it applies)
-            const bool n128 = !pp_shape && w4n_mode && tile_pref == 0 && db1_gemm_w4n_supported(u, fa, fb, DB1_F32, (int)batch * S);
-            pl.kind = (pp_shape ? big(u, (int)batch * S, fb == 1) : (n128 ? GK_W4N : GK_TILE256)) | GK_SPLITK;
+            const bool n128 = !pp_shape && w4n_mode && tile_pref == 0 && db1_gemm_w4_supported(u, 4, fa, fb, DB1_F32, (int)batch * S);
+            pl.kind = (pp_shape ? kind_256(u, fa, fb, DB1_F32, (int)batch * S, fb == 1) : (n128 ? GK_W4N : GK_TILE256)) | GK_SPLITK;
             return pl;
         }
     }
     if (w4n_half) { pl.kind = GK_W4N; return pl; }
     // ... and outputs whose LAST wave of 256 x 256 workgroups is mostly empty (qkv at 4 sequences: 384 tiles = 1.5 waves): by the fill of the
-    // last wave, with the 256 x 128 kernel priced at 0.85 of the 256 x 256 one per FLOP (knob "w4n" >= 3; measured below)
-    if (w4n_shape && w4n_mode >= 3 && wg256 >= 160 && wg256 < 1024) {
-        const double e256 = (double)wg256 / (256.0 * ((wg256 + 255) / 256)), e128 = (double)wg128 / (256.0 * ((wg128 + 255) / 256));
-        if (0.85 * e128 > e256) { pl.kind = GK_W4N; return pl; }
-    }
-    if (pp_shape && tile_pref == 1024) { pl.kind = big(t, (int)batch, true); return pl; }
+    // last wave, with the 256 x 128 kernel priced at 0.85 of the 256 x 256 one per FLOP (last_wave_wants_128; knob "w4n" >= 3; measured below)
+    if (w4n_shape && w4n_mode >= 3 && last_wave_wants_128(wg256, wg128)) { pl.kind = GK_W4N; return pl; }
+    if (pp_shape && tile_pref == 1024) { pl.kind = kind_256(t, fa, fb, g.dtC, (int)batch, true); return pl; }
     if (pp_shape && (tile_pref == 512 || (tile_pref == 0 && (int64_t)(M / 256) * (N / 256) * batch >= 160))) {
         // measured: the 4-stage k32 ring is 3-9 % faster when B is M-major (NN, TN); with both operands K-major
         // (NT) its 64-byte rows fetch half cache lines and the 2-stage k64 kernel is 4-9 % faster
-        pl.kind = big(t, (int)batch, tile_pref == 0 && fb == 1);
+        pl.kind = kind_256(t, fa, fb, g.dtC, (int)batch, tile_pref == 0 && fb == 1);
         return pl;
     }
     // (measured: routing the under-filled transposed-operand cases -- o_net dW on 128 workgroups, the per-head dR on 64 --
@@ -347,7 +377,7 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
     // N a multiple of 128 but not of 256 with at least three quarters of a wave of 256 x 128 tiles: the 4-wave kernel's 256 x 128 form instead of the
     // 3-stage tile kernel (the per-head dR of an accumulation window, two batch levels, 1024 tiles: 404-409 -> 377-380 us with the heavy-first walk, profiles/r06q_dr_window_w4n.txt)
     // (not under hint 1: only the tile kernel skips those k-tiles -- half the product -- so that form stays where it is)
-    if (w4n_shape && w4n_mode >= 3 && !pp_shape && wg128 >= 192 && g_tri_mode != 1) { pl.kind = GK_W4N; return pl; }
+    if (w4n_shape && w4n_mode >= 3 && !pp_shape && wg128 >= 192 && g.tri_mode != 1) { pl.kind = GK_W4N; return pl; }
     const bool want256 = tile_pref == 256 || (tile_pref == 0 && fb == 1);
     if (want256 && t256_shape) { pl.kind = GK_TILE256; return pl; }
     // split-K for small outputs with a very long contraction (weight gradients of the 64-channel patch convolutions: 64 x 576 outputs
@@ -358,7 +388,9 @@ static GemmPlan gemm_plan(const GemmShape& g, bool aligned, int64_t ws_bytes) {
     if (g.dtC == DB1_F32 && g.beta == 1.0f && ntiles < 128 && K >= 64 * TBK && batch == 1 && (N % 4) == 0 && g.c_cs == 1) {
         int ks = 512 / ntiles;
         while (ks > 1 && ((K / TBK) % ks || (K / TBK) / ks < 8)) ks--;
-        pl.ksplit = ks;
+        // Without the workspace the product runs unsplit on the same kernel (the header's contract for the GEMMs: slower, equally valid)
+        const int64_t need = (int64_t)ks * M * N * (int64_t)sizeof(float);
+        if (ks > 1 && (ws_bytes < 0 || need <= ws_bytes)) { pl.ksplit = ks; pl.ws_bytes = need; }
     }
     return pl;
 }
@@ -373,21 +405,13 @@ static GemmShape gemm_shape(int M, int N, int K, int dtA, int dtB, int dtC, int6
     return g;
 }
 
+// ---- the queries: fields of the plan of a call with aligned operands and no structural-zero hint
 extern "C" int64_t db1_gemm_workspace_bytes(int M, int N, int K, int dtA, int dtB, int dtC, int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs,
                                             int64_t c_rs, int64_t c_cs, int batch0, int batch1) {
     if (M <= 0 || N <= 0 || K <= 0 || batch0 <= 0 || batch1 <= 0) return 0;
     // (batch strides only enter through their alignment, which the model's operands satisfy; beta only matters for the 128-tile split of
     // small fp32 accumulators, which exists for beta = 1: asked for here, so that an accumulating call finds its partial-sum space)
-    GemmShape g = gemm_shape(M, N, K, dtA, dtB, dtC, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, 0, 0, 0, 0, 0, 0, 1.f);
-    const GemmPlan pl = gemm_plan(g, true, -1);
-    if (pl.kind & GK_TAIL) {
-        GemmShape tail = g;
-        tail.M = pl.m_tail;
-        const GemmPlan tp = gemm_plan(tail, true, -1);
-        return (tp.kind & GK_SPLITK) ? splitk_bytes(tail, tp.S, tail.M) : 0;
-    }
-    if (pl.ksplit > 1) return (int64_t)pl.ksplit * M * N * (int64_t)sizeof(float);   // 128-tile split-K: partial sums instead of atomics
-    return (pl.kind & GK_SPLITK) ? splitk_bytes(g, pl.S, M) : 0;
+    return gemm_plan(gemm_shape(M, N, K, dtA, dtB, dtC, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, 0, 0, 0, 0, 0, 0, 1.f), true, -1).ws_bytes;
 }
 
 extern "C" int db1_gemm_kernel_choice(int M, int N, int K, int dtA, int dtB, int dtC, int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs,
@@ -396,98 +420,61 @@ extern "C" int db1_gemm_kernel_choice(int M, int N, int K, int dtA, int dtB, int
     return gemm_plan(gemm_shape(M, N, K, dtA, dtB, dtC, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, 0, 0, 0, 0, 0, 0, beta), true, ws_bytes).kind;
 }
 
-extern "C" int db1_gemm_strided(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int dtA, int dtB,
-                                int dtC, int dtBias, int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs, int64_t c_rs,
-                                int64_t c_cs, int batch0, int batch1, int64_t a_bs0, int64_t a_bs1, int64_t b_bs0,
-                                int64_t b_bs1, int64_t c_bs0, int64_t c_bs1, float alpha, float beta, void* ws, int64_t ws_bytes, void* stream) {
-    if (!db1_dt_ok(dtA) || !db1_dt_ok(dtB) || !db1_dt_ok(dtC) || (bias && !db1_dt_ok(dtBias)))
-        DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "gemm: dtype codes %d %d %d", dtA, dtB, dtC);
-    if (M <= 0 || N <= 0 || K <= 0 || batch0 <= 0 || batch1 <= 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm: M=%d N=%d K=%d batch=%dx%d", M, N, K, batch0, batch1);
-    if (!A || !B || !C) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm: null operand");
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t batch = (int64_t)batch0 * batch1;
-    const GemmShape g = gemm_shape(M, N, K, dtA, dtB, dtC, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, a_bs0, a_bs1, b_bs0, b_bs1, c_bs0, c_bs1, beta);
-    if (ws && (((uintptr_t)ws) & 15)) ws_bytes = 0;   // an unusable workspace is no workspace: the plan then avoids the split-K paths
-    const GemmPlan pl = gemm_plan(g, db1_aligned16(A) && db1_aligned16(B) && db1_aligned16(C), ws ? ws_bytes : 0);
-    const int base = pl.kind & 15, fa = pl.fa, fb = pl.fb;
-    if (base == GK_SKINNY)
-        return db1_gemm_skinny_launch((const bf16_t*)A, (const bf16_t*)B, C, bias, M, N, K, a_rs, b_cs, c_rs, alpha, beta, dtC, dtBias, st);
-    if (base == GK_GENERIC) {
-        GemmStridedArgs a;
-        a.A = A; a.B = B; a.C = C; a.bias = bias; a.M = M; a.N = N; a.K = K;
-        a.a_rs = a_rs; a.a_cs = a_cs; a.b_rs = b_rs; a.b_cs = b_cs; a.c_rs = c_rs; a.c_cs = c_cs;
-        a.batch1 = batch1; a.a_bs0 = a_bs0; a.a_bs1 = a_bs1; a.b_bs0 = b_bs0; a.b_bs1 = b_bs1; a.c_bs0 = c_bs0; a.c_bs1 = c_bs1;
-        a.alpha = alpha; a.beta = beta;
-        return db1_gemm_strided_generic(a, dtA, dtB, dtC, dtBias, (int)batch, st);
-    }
-    if (pl.kind & GK_TAIL) {   // the last, short wave of tile rows as a second call (it takes the split-K path)
-        const int m_main = M - pl.m_tail;
-        const size_t esA = dtA == DB1_F32 ? 4 : 2, esC = dtC == DB1_F32 ? 4 : 2;
-        int rc = db1_gemm_strided(A, B, C, bias, m_main, N, K, dtA, dtB, dtC, dtBias, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, 1, 1, 0, 0, 0, 0, 0,
-                                  0, alpha, beta, ws, ws_bytes, stream);
+// ---- the executor: one plan per call, carried out as it stands
+struct GemmOperands {
+    const void* A; const void* B; void* C; const void* bias;
+    int dtBias;
+    float alpha;
+};
+// C = sum of the S partials of each batch member (+ bias + beta C), in slice order
+static int splitk_reduce(const float* ws, const GemmShape& g, const GemmOperands& op, int S, hipStream_t st) {
+    const dim3 rg((unsigned)(((int64_t)g.M * (g.N / 4) + 255) / 256), (unsigned)(g.batch0 * g.batch1));
+#define RED(TC, TB) splitk_reduce_kernel<TC, TB><<<rg, 256, 0, st>>>(ws, (TC*)op.C, (const TB*)op.bias, g.M, g.N, S, g.c_rs, g.c_bs0, g.beta)
+    if (g.dtC == DB1_F32) { if (op.dtBias == DB1_BF16) RED(float, bf16_t); else RED(float, float); }
+    else { if (op.dtBias == DB1_BF16) RED(bf16_t, bf16_t); else RED(bf16_t, float); }
+#undef RED
+    DB1_CHECK_LAUNCH("splitk_reduce");
+    return DB1_OK;
+}
+static int gemm_run(const GemmShape& g, const GemmOperands& op, void* ws, int64_t ws_bytes, hipStream_t st) {
+    if (!ws || (((uintptr_t)ws) & 15) || ws_bytes < 0) ws_bytes = 0;   // an unusable workspace is no workspace: the plan then avoids the split-K paths
+    const GemmPlan pl = gemm_plan(g, db1_aligned16(op.A) && db1_aligned16(op.B) && db1_aligned16(op.C), ws_bytes);
+    const int batch = g.batch0 * g.batch1, fa = pl.fa, fb = pl.fb;
+    if (pl.kind & GK_TAIL) {   // the last, short wave of tile rows as a second call (one product, no batch: see the rule)
+        const int64_t esA = db1_elt_size(g.dtA), esC = db1_elt_size(g.dtC);
+        GemmShape part = gemm_shape(g.M - pl.m_tail, g.N, g.K, g.dtA, g.dtB, g.dtC, g.a_rs, g.a_cs, g.b_rs, g.b_cs, g.c_rs, g.c_cs, 1, 1, 0, 0, 0, 0, 0, 0, g.beta);
+        const int rc = gemm_run(part, op, ws, ws_bytes, st);
         if (rc) return rc;
-        return db1_gemm_strided((const char*)A + (size_t)m_main * a_rs * esA, B, (char*)C + (size_t)m_main * c_rs * esC, bias, pl.m_tail, N, K, dtA,
-                                dtB, dtC, dtBias, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, 1, 1, 0, 0, 0, 0, 0, 0, alpha, beta, ws, ws_bytes, stream);
+        GemmOperands rest = op;
+        rest.A = (const char*)op.A + (int64_t)part.M * g.a_rs * esA;
+        rest.C = (char*)op.C + (int64_t)part.M * g.c_rs * esC;
+        part.M = pl.m_tail;
+        return gemm_run(part, rest, ws, ws_bytes, st);
+    }
+    if (pl.kind == GK_SKINNY)
+        return db1_gemm_skinny_launch((const bf16_t*)op.A, (const bf16_t*)op.B, op.C, op.bias, g.M, g.N, g.K, g.a_rs, g.b_cs, g.c_rs, op.alpha, g.beta, g.dtC, op.dtBias, st);
+    if (pl.kind == GK_GENERIC) {
+        GemmStridedArgs a;
+        a.A = op.A; a.B = op.B; a.C = op.C; a.bias = op.bias; a.M = g.M; a.N = g.N; a.K = g.K;
+        a.a_rs = g.a_rs; a.a_cs = g.a_cs; a.b_rs = g.b_rs; a.b_cs = g.b_cs; a.c_rs = g.c_rs; a.c_cs = g.c_cs;
+        a.batch1 = g.batch1; a.a_bs0 = g.a_bs0; a.a_bs1 = g.a_bs1; a.b_bs0 = g.b_bs0; a.b_bs1 = g.b_bs1; a.c_bs0 = g.c_bs0; a.c_bs1 = g.c_bs1;
+        a.alpha = op.alpha; a.beta = g.beta;
+        return db1_gemm_strided_generic(a, g.dtA, g.dtB, g.dtC, op.dtBias, batch, st);
     }
     GemmTileArgs t = tile_args(g, pl);
-    t.A = (const bf16_t*)A; t.B = (const bf16_t*)B; t.C = C; t.bias = bias; t.alpha = alpha;
-    if (pl.kind & GK_SPLITK) {
-        const int S = pl.S;
-        float* wsf = (float*)ws;
-        GemmTileArgs u = t;
-        const int64_t kc = K / S;
-        u.K = (int)kc; u.C = wsf; u.bias = nullptr; u.beta = 0.f; u.ldc = N;
-        if (u.tri_mode == 1 || (u.tri_mode == 2 && (kc % u.tri_period))) u.tri_mode = 0;  // a slice of k no longer starts at k = 0 / on a period
-        u.batch1 = S; u.a_bs1 = fa == 0 ? kc : kc * pl.lda; u.b_bs1 = fb == 0 ? kc : kc * pl.ldb;
-        u.c_bs0 = (int64_t)S * M * N; u.c_bs1 = (int64_t)M * N;
-        const bool pp_shape = (M % 256) == 0 && (N % 256) == 0;
-        int rc = pp_shape ? (fb == 1 ? db1_gemm_pp32_launch(u, fa, fb, DB1_F32, DB1_F32, (int)batch * S, st)
-                                     : db1_gemm_pp_launch(u, fa, fb, DB1_F32, DB1_F32, (int)batch * S, st))
-                          : (base == GK_W4N ? db1_gemm_w4n_launch(u, fa, fb, DB1_F32, DB1_F32, (int)batch * S, st)
-                                            : db1_gemm_tile256_launch(u, fa, fb, DB1_F32, DB1_F32, (int)batch * S, st));
-        if (rc) return rc;
-        dim3 rg((unsigned)(((int64_t)M * (N / 4) + 255) / 256), (unsigned)batch);
-#define RED(TC, TB) splitk_reduce_kernel<TC, TB><<<rg, 256, 0, st>>>(wsf, (TC*)C, (const TB*)bias, M, N, S, c_rs, c_bs0, beta)
-        if (dtC == DB1_F32) { if (dtBias == DB1_BF16) RED(float, bf16_t); else RED(float, float); }
-        else { if (dtBias == DB1_BF16) RED(bf16_t, bf16_t); else RED(bf16_t, float); }
-#undef RED
-        DB1_CHECK_LAUNCH("splitk_reduce");
-        return DB1_OK;
+    t.A = (const bf16_t*)op.A; t.B = (const bf16_t*)op.B; t.C = op.C; t.bias = op.bias; t.alpha = op.alpha;
+    if (pl.kind & GK_SPLITK) {   // deterministic split-K: the slices' partial sums through the workspace, then the fixed-order reduce
+        const int rc = launch_kind(pl.kind, splitk_slice_args(t, pl, ws), fa, fb, DB1_F32, DB1_F32, batch * pl.S, st);
+        return rc ? rc : splitk_reduce((const float*)ws, g, op, pl.S, st);
     }
-    if (base == GK_W4 || base == GK_PP || base == GK_PP32) {
-        const int tile_pref = g_tile_pref ? g_tile_pref : gemm_env().tile;
-        const bool k32 = tile_pref == 1024 || (tile_pref == 0 && fb == 1);
-        return k32 ? db1_gemm_pp32_launch(t, fa, fb, dtC, dtBias, (int)batch, st) : db1_gemm_pp_launch(t, fa, fb, dtC, dtBias, (int)batch, st);
+    if (pl.ksplit > 1) {
+        // long-contraction split of a small fp32 output (weight gradients of the patch convolutions): the slices' partial sums are stored in
+        // the caller's workspace and added in a fixed order (bit-reproducible) -- never with float atomics
+        t.ksplit = pl.ksplit; t.C = ws; t.ldc = g.N; t.c_zs = (int64_t)g.M * g.N; t.bias = nullptr; t.beta = 0.f;
+        const int rc = launch_kind(pl.kind, t, fa, fb, g.dtC, op.dtBias, batch, st);
+        return rc ? rc : splitk_reduce((const float*)ws, g, op, pl.ksplit, st);
     }
-    if (base == GK_W4N) return db1_gemm_w4n_launch(t, fa, fb, dtC, dtBias, (int)batch, st);
-    if (base == GK_TILE256) return db1_gemm_tile256_launch(t, fa, fb, dtC, dtBias, (int)batch, st);
-    // long-contraction split of a small fp32 output (weight gradients of the patch convolutions): the slices' partial sums are stored in
-    // the caller's workspace and added in a fixed order (bit-reproducible).  Without the workspace the product runs unsplit on the same
-    // kernel (the header's contract for the GEMMs: slower, equally valid) -- never with float atomics.
-    const bool ws_split = pl.ksplit > 1 && ws && db1_aligned16(ws) && ws_bytes >= (int64_t)pl.ksplit * M * N * (int64_t)sizeof(float);
-    t.ksplit = ws_split ? pl.ksplit : 1;
-    dim3 grid((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch, (unsigned)t.ksplit);
-    void* C_final = C;
-    if (ws_split) { t.C = ws; t.ldc = N; t.c_zs = (int64_t)M * N; t.bias = nullptr; t.beta = 0.f; }
-    static Db1PerDeviceOnce attr_once;   // 64 KiB of dynamic LDS needs the opt-in attribute: once per device, every instantiation
-    attr_once.run([] {
-#define SET_ATTR(AK, BK_, TC, TB) hipFuncSetAttribute((const void*)gemm_bf16_tile_kernel<AK, BK_, TC, TB>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES)
-#define SET_ALL(AK, BK_) SET_ATTR(AK, BK_, float, float); SET_ATTR(AK, BK_, float, bf16_t); SET_ATTR(AK, BK_, bf16_t, float); SET_ATTR(AK, BK_, bf16_t, bf16_t)
-        SET_ALL(true, true); SET_ALL(true, false); SET_ALL(false, false);
-#undef SET_ALL
-#undef SET_ATTR
-    });
-    if (fa == 0 && fb == 0) launch_tile<true, true>(t, dtC, dtBias, grid, st);
-    else if (fa == 0 && fb == 1) launch_tile<true, false>(t, dtC, dtBias, grid, st);
-    else launch_tile<false, false>(t, dtC, dtBias, grid, st);
-    DB1_CHECK_LAUNCH("gemm_bf16_tile");
-    if (ws_split) {
-        dim3 rg((unsigned)(((int64_t)M * (N / 4) + 255) / 256), 1u);
-        if (dtBias == DB1_BF16) splitk_reduce_kernel<float, bf16_t><<<rg, 256, 0, st>>>((const float*)ws, (float*)C_final, (const bf16_t*)bias, M, N, pl.ksplit, c_rs, 0, beta);
-        else splitk_reduce_kernel<float, float><<<rg, 256, 0, st>>>((const float*)ws, (float*)C_final, (const float*)bias, M, N, pl.ksplit, c_rs, 0, beta);
-        DB1_CHECK_LAUNCH("splitk_reduce (128-tile)");
-    }
-    return DB1_OK;
+    return launch_kind(pl.kind, t, fa, fb, g.dtC, op.dtBias, batch, st);
 }
 
 extern "C" int db1_gemm_strided_tri(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int dtA, int dtB,
@@ -496,13 +483,20 @@ extern "C" int db1_gemm_strided_tri(const void* A, const void* B, void* C, const
                                     int64_t b_bs1, int64_t c_bs0, int64_t c_bs1, float alpha, float beta, int tri_mode, int tri_period,
                                     void* ws, int64_t ws_bytes, void* stream) {
     if (tri_mode < 0 || tri_mode > 2) DB1_FAIL(DB1_ERR_UNSUPPORTED, "gemm_strided_tri: mode %d", tri_mode);
-    g_tri_mode = tri_mode;
-    g_tri_period = tri_period;
-    const int rc = db1_gemm_strided(A, B, C, bias, M, N, K, dtA, dtB, dtC, dtBias, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, a_bs0,
-                                    a_bs1, b_bs0, b_bs1, c_bs0, c_bs1, alpha, beta, ws, ws_bytes, stream);
-    g_tri_mode = 0;
-    g_tri_period = 0;
-    return rc;
+    if (!db1_dt_ok(dtA) || !db1_dt_ok(dtB) || !db1_dt_ok(dtC) || (bias && !db1_dt_ok(dtBias)))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "gemm: dtype codes %d %d %d", dtA, dtB, dtC);
+    if (M <= 0 || N <= 0 || K <= 0 || batch0 <= 0 || batch1 <= 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm: M=%d N=%d K=%d batch=%dx%d", M, N, K, batch0, batch1);
+    if (!A || !B || !C) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm: null operand");
+    GemmShape g = gemm_shape(M, N, K, dtA, dtB, dtC, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, a_bs0, a_bs1, b_bs0, b_bs1, c_bs0, c_bs1, beta);
+    g.tri_mode = tri_mode; g.tri_period = tri_period;
+    return gemm_run(g, GemmOperands{A, B, C, bias, dtBias, alpha}, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int db1_gemm_strided(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int dtA, int dtB,
+                                int dtC, int dtBias, int64_t a_rs, int64_t a_cs, int64_t b_rs, int64_t b_cs, int64_t c_rs,
+                                int64_t c_cs, int batch0, int batch1, int64_t a_bs0, int64_t a_bs1, int64_t b_bs0,
+                                int64_t b_bs1, int64_t c_bs0, int64_t c_bs1, float alpha, float beta, void* ws, int64_t ws_bytes, void* stream) {
+    return db1_gemm_strided_tri(A, B, C, bias, M, N, K, dtA, dtB, dtC, dtBias, a_rs, a_cs, b_rs, b_cs, c_rs, c_cs, batch0, batch1, a_bs0, a_bs1, b_bs0,
+                                b_bs1, c_bs0, c_bs1, alpha, beta, 0, 0, ws, ws_bytes, stream);
 }
 
 extern "C" int db1_gemm_nt(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb,
@@ -521,25 +515,15 @@ extern "C" int db1_gemm_nt_headbias(const void* A, const void* W, void* C, void*
     if (!db1_aligned16(A) || !db1_aligned16(W) || !db1_aligned16(C) || !db1_aligned16(Cu) || !db1_aligned16(Cv) || (lda % 8) || (ldw % 8) || (ldc % 4) ||
         (ld_uv % 4) || lda < K || ldw < K || ldc < N || ld_uv < split_n)
         DB1_FAIL(DB1_ERR_BAD_ALIGN, "gemm_nt_headbias: alignment / leading dimensions");
-    GemmTileArgs t;
-    t.A = (const bf16_t*)A; t.B = (const bf16_t*)W; t.C = C; t.bias = nullptr;
-    t.M = M; t.N = N; t.K = K; t.lda = lda; t.ldb = ldw; t.ldc = ldc;
-    t.batch1 = 1; t.a_bs0 = t.a_bs1 = t.b_bs0 = t.b_bs1 = t.c_bs0 = t.c_bs1 = 0;
-    t.alpha = 1.f; t.beta = 0.f; t.tiles_m = M / 256; t.tiles_n = N / 256; t.ksplit = 1;
-    t.tri_mode = 0; t.tri_period = 0;
+    GemmTileArgs t = gemm_tile_args_2d(A, W, C, nullptr, M, N, K, lda, ldw, ldc);
     t.split_n = split_n; t.Cu = Cu; t.Cv = Cv; t.bias_u = bias_u; t.bias_v = bias_v; t.ld_uv = ld_uv;
-    // the reference's micro-batch of 4 sequences: 384 tiles of 256 x 256 = 1.5 rounds of workgroups; 768 tiles of 256 x 128 fill three (the
-    // dispatcher's rule for plain products, gemm_plan: the 256 x 128 form priced at 0.85 of the 256 x 256 one per FLOP)
-    {
-        const int64_t wg256 = (int64_t)(M / 256) * (N / 256), wg128 = (int64_t)(M / 256) * (N / 128);
-        const double e256 = (double)wg256 / (256.0 * ((wg256 + 255) / 256)), e128 = (double)wg128 / (256.0 * ((wg128 + 255) / 256));
-        const int w4n_mode = db1_knob(DB1_KNOB_W4N, 3);
-        if (w4n_mode >= 3 && w4n_mode != 5 && wg256 < 1024 && 0.85 * e128 > e256 && db1_gemm_w4n_supported(t, 0, 0, DB1_BF16, 1)) {   // (knob value 5: everything but this routing, for the A/B)
-            t.tiles_n = N / 128;
-            return db1_gemm_w4n_launch(t, 0, 0, DB1_BF16, DB1_BF16, 1, (hipStream_t)stream);
-        }
-    }
-    return db1_gemm_pp_launch(t, 0, 0, DB1_BF16, DB1_BF16, 1, (hipStream_t)stream);
+    // the reference's micro-batch of 4 sequences: 384 tiles of 256 x 256 = 1.5 rounds of workgroups; 768 tiles of 256 x 128 fill three: the
+    // dispatcher's last-wave rule for plain products (gemm_plan), then its choice among the 256 x 256 kernels.  Of the pins and knobs only
+    // "w4" / "w4n" apply here; w4n = 5 is everything but this routing, for the A/B
+    const int w4n_mode = db1_knob(DB1_KNOB_W4N, 3);
+    const bool n128 = w4n_mode >= 3 && w4n_mode != 5 && last_wave_wants_128((int64_t)(M / 256) * (N / 256), (int64_t)(M / 256) * (N / 128)) &&
+                      db1_gemm_w4_supported(t, 4, 0, 0, DB1_BF16, 1);
+    return launch_kind(n128 ? GK_W4N : kind_256(t, 0, 0, DB1_BF16, 1, false), t, 0, 0, DB1_BF16, DB1_BF16, 1, (hipStream_t)stream);
 }
 extern "C" int db1_gemm_nn(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb,
                            int64_t ldc, int dtAB, int dtC, float alpha, float beta, void* ws, int64_t ws_bytes, void* stream) {

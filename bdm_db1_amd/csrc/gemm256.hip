@@ -157,32 +157,16 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_tile256_kernel(GemmTileArgs 
                                   p.alpha, p.beta, p.bias);
 }
 
-template <bool AK, bool BK_>
-static void launch256(const GemmTileArgs& t, int dtC, int dtBias, dim3 grid, hipStream_t st) {
-    static Db1PerDeviceOnce attr_once;   // dynamic LDS above 64 KiB needs the opt-in attribute: once per device, every instantiation
-    attr_once.run([] {
-#define SET_ATTR(TC, TB) hipFuncSetAttribute((const void*)gemm_bf16_tile256_kernel<AK, BK_, TC, TB>, hipFuncAttributeMaxDynamicSharedMemorySize, T256_LDS_BYTES)
-        SET_ATTR(float, float); SET_ATTR(float, bf16_t); SET_ATTR(bf16_t, float); SET_ATTR(bf16_t, bf16_t);
-#undef SET_ATTR
-    });
-    if (dtC == DB1_F32) {
-        if (dtBias == DB1_BF16) gemm_bf16_tile256_kernel<AK, BK_, float, bf16_t><<<grid, 512, T256_LDS_BYTES, st>>>(t);
-        else gemm_bf16_tile256_kernel<AK, BK_, float, float><<<grid, 512, T256_LDS_BYTES, st>>>(t);
-    } else {
-        if (dtBias == DB1_BF16) gemm_bf16_tile256_kernel<AK, BK_, bf16_t, bf16_t><<<grid, 512, T256_LDS_BYTES, st>>>(t);
-        else gemm_bf16_tile256_kernel<AK, BK_, bf16_t, float><<<grid, 512, T256_LDS_BYTES, st>>>(t);
-    }
-}
+template <bool AK, bool BK_> struct Tile256Kernels {
+    template <typename TC, typename TB> static GemmKernelFn fn() { return gemm_bf16_tile256_kernel<AK, BK_, TC, TB>; }
+};
 
 int db1_gemm_tile256_launch(const GemmTileArgs& t_in, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st) {
     GemmTileArgs t = t_in;
     t.tiles_m = t.M / 256;
     t.tiles_n = t.N / TBN;
     t.ksplit = 1;
-    dim3 grid((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch);
-    if (fa == 0 && fb == 0) launch256<true, true>(t, dtC, dtBias, grid, st);
-    else if (fa == 0 && fb == 1) launch256<true, false>(t, dtC, dtBias, grid, st);
-    else launch256<false, false>(t, dtC, dtBias, grid, st);
+    gemm_launch_forms<Tile256Kernels>(t, fa, fb, dtC, dtBias, dim3((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch), 512, T256_LDS_BYTES, st);
     DB1_CHECK_LAUNCH("gemm_bf16_tile256");
     return DB1_OK;
 }

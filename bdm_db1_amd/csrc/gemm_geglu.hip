@@ -33,13 +33,7 @@ extern "C" int db1_gemm_nt_geglu(const void* A, const void* W1, const void* bias
     if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "gemm_nt_geglu: dtype");
     if (M <= 0 || dff <= 0 || K <= 0 || !A || !W1 || !Z || !ACT) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm_nt_geglu: M=%d dff=%d K=%d / null operand", M, dff, K);
     if (geglu_fused_fwd(M, dff, K, dt, lda, ldw, ldz, ldact, A, W1, Z, ACT)) {
-        GemmTileArgs t;
-        t.A = (const bf16_t*)A; t.B = (const bf16_t*)W1; t.C = Z; t.bias = bias;
-        t.M = M; t.N = 2 * dff; t.K = K; t.lda = lda; t.ldb = ldw; t.ldc = ldz;
-        t.batch1 = 1; t.a_bs0 = t.a_bs1 = t.b_bs0 = t.b_bs1 = t.c_bs0 = t.c_bs1 = 0;
-        t.alpha = 1.f; t.beta = 0.f; t.tiles_m = M / 256; t.tiles_n = 2 * dff / 256; t.ksplit = 1;
-        t.tri_mode = 0; t.tri_period = 0;
-        t.split_n = 0; t.Cu = nullptr; t.Cv = nullptr; t.bias_u = nullptr; t.bias_v = nullptr; t.ld_uv = 0;
+        GemmTileArgs t = gemm_tile_args_2d(A, W1, Z, bias, M, 2 * dff, K, lda, ldw, ldz);
         t.geglu_dff = dff; t.Cact = ACT; t.ld_act = ldact;
         return db1_gemm_w4_geglu_fwd_launch(t, dt, (hipStream_t)stream);
     }
@@ -65,13 +59,7 @@ extern "C" int db1_gemm_nn_geglu_bwd_parts(const void* dY, const void* W2, const
     if (M <= 0 || dff <= 0 || K <= 0 || !dY || !W2 || !Z || !dZ || !parts) DB1_FAIL(DB1_ERR_BAD_SHAPE, "gemm_nn_geglu_bwd_parts: M=%d dff=%d K=%d / null operand", M, dff, K);
     if (!geglu_fused_bwd(M, dff, K, dt, lddy, ldw, ldz, lddz, dY, W2, Z, dZ) || !db1_aligned16(parts))
         DB1_FAIL(DB1_ERR_UNSUPPORTED, "gemm_nn_geglu_bwd_parts: only the shapes of the fused 4-wave kernel (db1_gemm_nn_geglu_bwd_fused)");
-    GemmTileArgs t;
-    t.A = (const bf16_t*)dY; t.B = (const bf16_t*)W2; t.C = dZ; t.bias = nullptr;
-    t.M = M; t.N = dff; t.K = K; t.lda = lddy; t.ldb = ldw; t.ldc = lddz;
-    t.batch1 = 1; t.a_bs0 = t.a_bs1 = t.b_bs0 = t.b_bs1 = t.c_bs0 = t.c_bs1 = 0;
-    t.alpha = 1.f; t.beta = 0.f; t.tiles_m = M / 256; t.tiles_n = dff / 256; t.ksplit = 1;
-    t.tri_mode = 0; t.tri_period = 0;
-    t.split_n = 0; t.Cu = nullptr; t.Cv = nullptr; t.bias_u = nullptr; t.bias_v = nullptr; t.ld_uv = 0;
+    GemmTileArgs t = gemm_tile_args_2d(dY, W2, dZ, nullptr, M, dff, K, lddy, ldw, lddz);
     t.geglu_dff = dff; t.Zin = (const bf16_t*)Z; t.ld_z = ldz; t.colpart = parts;
     return db1_gemm_w4_geglu_bwd_launch(t, (hipStream_t)stream);
 }
@@ -82,13 +70,7 @@ extern "C" int db1_gemm_nn_geglu_bwd(const void* dY, const void* W2, const void*
     DB1_NEED_WS(ws, ws_bytes, db1_gemm_nn_geglu_bwd_workspace_bytes(M, dff, K, dt, lddy, ldw, ldz, lddz), "gemm_nn_geglu_bwd");
     hipStream_t st = (hipStream_t)stream;
     if (geglu_fused_bwd(M, dff, K, dt, lddy, ldw, ldz, lddz, dY, W2, Z, dZ)) {
-        GemmTileArgs t;
-        t.A = (const bf16_t*)dY; t.B = (const bf16_t*)W2; t.C = dZ; t.bias = nullptr;
-        t.M = M; t.N = dff; t.K = K; t.lda = lddy; t.ldb = ldw; t.ldc = lddz;
-        t.batch1 = 1; t.a_bs0 = t.a_bs1 = t.b_bs0 = t.b_bs1 = t.c_bs0 = t.c_bs1 = 0;
-        t.alpha = 1.f; t.beta = 0.f; t.tiles_m = M / 256; t.tiles_n = dff / 256; t.ksplit = 1;
-        t.tri_mode = 0; t.tri_period = 0;
-        t.split_n = 0; t.Cu = nullptr; t.Cv = nullptr; t.bias_u = nullptr; t.bias_v = nullptr; t.ld_uv = 0;
+        GemmTileArgs t = gemm_tile_args_2d(dY, W2, dZ, nullptr, M, dff, K, lddy, ldw, lddz);
         t.geglu_dff = dff; t.Zin = (const bf16_t*)Z; t.ld_z = ldz; t.colpart = (float*)ws;
         int rc = db1_gemm_w4_geglu_bwd_launch(t, st);
         if (rc) return rc;

@@ -186,38 +186,21 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_pp32_kernel(GemmTileArgs p) 
             store_frag<TC, TBIAS>(acc[i][j], C, p.ldc, m0 + grp * 128 + i * 16 + (lane & 15), n0 + u * 64 + j * 16 + (lane >> 4) * 4, p.alpha, p.beta, p.bias);
 }
 
-template <bool AK, bool BK_, int NS>
-static void launch_pp32(const GemmTileArgs& t, int dtC, int dtBias, dim3 grid, hipStream_t st) {
-    constexpr int LDS = NS * P32_STAGE_BYTES;
-    static Db1PerDeviceOnce attr_once;   // dynamic LDS above 64 KiB needs the opt-in attribute: once per device, every instantiation
-    attr_once.run([] {
-#define SET_ATTR(TC, TB) hipFuncSetAttribute((const void*)gemm_bf16_pp32_kernel<AK, BK_, TC, TB, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS)
-        SET_ATTR(float, float); SET_ATTR(float, bf16_t); SET_ATTR(bf16_t, float); SET_ATTR(bf16_t, bf16_t);
-#undef SET_ATTR
-    });
-    if (dtC == DB1_F32) {
-        if (dtBias == DB1_BF16) gemm_bf16_pp32_kernel<AK, BK_, float, bf16_t, NS><<<grid, 512, LDS, st>>>(t);
-        else gemm_bf16_pp32_kernel<AK, BK_, float, float, NS><<<grid, 512, LDS, st>>>(t);
-    } else {
-        if (dtBias == DB1_BF16) gemm_bf16_pp32_kernel<AK, BK_, bf16_t, bf16_t, NS><<<grid, 512, LDS, st>>>(t);
-        else gemm_bf16_pp32_kernel<AK, BK_, bf16_t, float, NS><<<grid, 512, LDS, st>>>(t);
-    }
-}
+template <int NS> struct Pp32Stages {
+    template <bool AK, bool BK_> struct Kernels {
+        template <typename TC, typename TB> static GemmKernelFn fn() { return gemm_bf16_pp32_kernel<AK, BK_, TC, TB, NS>; }
+    };
+};
 
 int db1_gemm_pp32_launch(const GemmTileArgs& t_in, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st) {
-    if (db1_gemm_w4_supported(t_in, fa, fb, dtC, batch)) return db1_gemm_w4_launch(t_in, fa, fb, dtC, dtBias, batch, st);
     GemmTileArgs t = t_in;
     t.tiles_m = t.M / 256;
     t.tiles_n = t.N / 256;
     t.ksplit = 1;
-    dim3 grid((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch);
+    const dim3 grid((unsigned)(t.tiles_m * t.tiles_n), (unsigned)batch);
     const int ns = db1_knob(DB1_KNOB_PP32_STAGES, 4);   // A/B knob (4 | 5); measured: 4 stages (128 KiB) beat 5 (160 KiB) on every shape
-#define FORMS(NS_)                                                                            \
-    if (fa == 0 && fb == 0) launch_pp32<true, true, NS_>(t, dtC, dtBias, grid, st);           \
-    else if (fa == 0 && fb == 1) launch_pp32<true, false, NS_>(t, dtC, dtBias, grid, st);     \
-    else launch_pp32<false, false, NS_>(t, dtC, dtBias, grid, st);
-    if (ns == 5) { FORMS(5) } else { FORMS(4) }
-#undef FORMS
+    if (ns == 5) gemm_launch_forms<Pp32Stages<5>::Kernels>(t, fa, fb, dtC, dtBias, grid, 512, 5 * P32_STAGE_BYTES, st);
+    else gemm_launch_forms<Pp32Stages<4>::Kernels>(t, fa, fb, dtC, dtBias, grid, 512, 4 * P32_STAGE_BYTES, st);
     DB1_CHECK_LAUNCH("gemm_bf16_pp32");
     return DB1_OK;
 }

@@ -1,4 +1,6 @@
-// Shared pieces of the bf16 MFMA tile GEMMs (gemm.hip: 128x128 tile / 4 waves; gemm256.hip: 256x128 tile / 8 waves).
+// Shared pieces of the bf16 MFMA tile GEMMs: the kernel argument block, operand staging / fragments / epilogues, and the typed launcher.
+//   gemm.hip 128x128 / 4 waves (+ the dispatcher); gemm256.hip 256x128 / 8 waves; gemm_pp.hip, gemm_pp32.hip 256x256 / 8 waves ping-pong
+//   (k64 / k32 ring); gemm_w4.hip 256x256 and 256x128 / 4 waves, hand-scheduled (+ the GEGLU epilogues); gemm_skinny.hip few rows.
 #pragma once
 #include "db1_common.h"
 
@@ -14,26 +16,26 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define TILE_BYTES (128 * 64 * 2)  // 16 KiB: one 128-row operand (sub-)tile per stage
 
 struct GemmTileArgs {
-    const bf16_t* A; const bf16_t* B; void* C; const void* bias;
-    int M, N, K;
-    int64_t lda, ldb, ldc;  // leading dimensions in elements
-    int batch1;
-    int64_t a_bs0, a_bs1, b_bs0, b_bs1, c_bs0, c_bs1;
-    float alpha, beta;
-    int tiles_m, tiles_n;
-    int ksplit;  // > 1: blockIdx.z owns K / ksplit of the contraction and accumulates into fp32 C with atomics (beta must be 1) ...
-    int64_t c_zs = 0;   // ... or, when != 0, STORES its partial sum at C + blockIdx.z * c_zs (a workspace; splitk_reduce_kernel adds the slices in order)
+    const bf16_t* A = nullptr; const bf16_t* B = nullptr; void* C = nullptr; const void* bias = nullptr;
+    int M = 0, N = 0, K = 0;
+    int64_t lda = 0, ldb = 0, ldc = 0;  // leading dimensions in elements
+    int batch1 = 1;
+    int64_t a_bs0 = 0, a_bs1 = 0, b_bs0 = 0, b_bs1 = 0, c_bs0 = 0, c_bs1 = 0;
+    float alpha = 1.f, beta = 0.f;
+    int tiles_m = 0, tiles_n = 0;   // set by the launch function of the kernel family (its tile size)
+    int ksplit = 1;  // > 1 (128-tile kernel only): blockIdx.z owns K / ksplit of the contraction ...
+    int64_t c_zs = 0;   // ... and STORES its partial sum at C + blockIdx.z * c_zs (a workspace; splitk_reduce_kernel adds the slices in order)
     // structural-zero hint for A (256x128 kernel only; elsewhere ignored, the zeros are simply multiplied):
     //   1: A[m, k] == 0 for k > m                      -> k-tiles beyond the tile's last row are skipped (dq_r = dT . R)
     //   2: A[m, k] == 0 for (k mod tri_period) < m     -> per period only the k-tiles from the tile's first row on (dR = dT^T . qv)
-    int tri_mode, tri_period;
-    int tri_walk;   // mode 2 on one column of tiles: hand the tile rows out heaviest first (gemm_w4.hip; only read when tri_mode == 2)
+    int tri_mode = 0, tri_period = 0;
+    int tri_walk = 0;   // mode 2 on one column of tiles: hand the tile rows out heaviest first (gemm_w4.hip; only read when tri_mode == 2)
     // head-bias epilogue of the attention input projection (ping-pong NT kernel only): columns n < split_n are written TWICE, as
     // acc + bias_u[n] to Cu and acc + bias_v[n] to Cv (row stride ld_uv) instead of to C: q + r_w_bias and q + r_r_bias straight from
     // the accumulators (db1_gemm_nt_headbias); 0 = off
-    int split_n;
-    void* Cu; void* Cv; const void* bias_u; const void* bias_v;
-    int64_t ld_uv;
+    int split_n = 0;
+    void* Cu = nullptr; void* Cv = nullptr; const void* bias_u = nullptr; const void* bias_v = nullptr;
+    int64_t ld_uv = 0;
     // GEGLU epilogues of the 4-wave kernel (gemm_w4.hip; 0 = off).  Forward (NT, db1_gemm_nt_geglu): B = W1 [2 dff, K], C = z [M, 2 dff] and
     // Cact = z[:, :dff] * gelu(z[:, dff:]) [M, dff] leave the same accumulators.  Backward (NN, db1_gemm_nn_geglu_bwd): the product is
     // dact [M, dff] = dy W2; the epilogue reads Zin = z and writes C = dz [M, 2 dff] plus the column sums of dz per 128-row block to colpart.
@@ -44,6 +46,37 @@ struct GemmTileArgs {
     int rot = 1;        // NT: per-XCD rotation of the k-tile walk (measured without effect at the five forward shapes, profiles/r05_nt_vs_nn.txt)
     int band = 4;       // tile rows per band of the XCD-aware walk of the 4-wave kernels (3 .. 8 measured flat, profiles/r05_w4_band_sweep.txt)
 };
+// one plain product C[M, N] = A . B (+ bias): everything else keeps its default
+static inline GemmTileArgs gemm_tile_args_2d(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc) {
+    GemmTileArgs t;
+    t.A = (const bf16_t*)A; t.B = (const bf16_t*)B; t.C = C; t.bias = bias;
+    t.M = M; t.N = N; t.K = K; t.lda = lda; t.ldb = ldb; t.ldc = ldc;
+    return t;
+}
+
+// ---- the typed launch: KERNELS::fn<TC, TBIAS>() is the __global__ instantiation for an output / bias type pair.  All four get the opt-in to
+// `lds` bytes of dynamic LDS (64 KiB and more need it) once per device, then the pair named by (dtC, dtBias) is launched.
+typedef void (*GemmKernelFn)(GemmTileArgs);
+template <class KERNELS>
+static inline void gemm_launch_typed(const GemmTileArgs& t, int dtC, int dtBias, dim3 grid, unsigned threads, int lds, hipStream_t st) {
+    static Db1PerDeviceOnce attr_once;   // (one per KERNELS, i.e. per kernel family and operand layout)
+    attr_once.run([lds] {
+        for (GemmKernelFn k : {KERNELS::template fn<float, float>(), KERNELS::template fn<float, bf16_t>(), KERNELS::template fn<bf16_t, float>(),
+                               KERNELS::template fn<bf16_t, bf16_t>()})
+            hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    });
+    const GemmKernelFn k = dtC == DB1_F32 ? (dtBias == DB1_BF16 ? KERNELS::template fn<float, bf16_t>() : KERNELS::template fn<float, float>())
+                                          : (dtBias == DB1_BF16 ? KERNELS::template fn<bf16_t, bf16_t>() : KERNELS::template fn<bf16_t, float>());
+    k<<<grid, threads, lds, st>>>(t);
+}
+// the three operand layouts of the tile kernels: FAMILY<A K-major, B K-major> for (fa, fb) in {(0, 0) NT, (0, 1) NN, (1, 1) TN}
+template <template <bool, bool> class FAMILY>
+static inline void gemm_launch_forms(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, dim3 grid, unsigned threads, int lds, hipStream_t st) {
+    if (fa == 0 && fb == 0) gemm_launch_typed<FAMILY<true, true>>(t, dtC, dtBias, grid, threads, lds, st);
+    else if (fa == 0 && fb == 1) gemm_launch_typed<FAMILY<true, false>>(t, dtC, dtBias, grid, threads, lds, st);
+    else gemm_launch_typed<FAMILY<false, false>>(t, dtC, dtBias, grid, threads, lds, st);
+}
+
 
 // ---- staging of one 16 KiB operand (sub-)tile = 16 wave-instructions of 1 KiB, PIECES per wave (wave w takes w*PIECES ..)
 //   K-major : memory [row][k]   -> LDS image [128 rows][128 B];  piece q = rows [8q, 8q+8):   lane -> (r = lane/8,  cp = lane%8),  holds chunk cp ^ (r & 7)
@@ -221,13 +254,13 @@ __device__ __forceinline__ void tile_coords(int bid, int tiles_m, int tiles_n, i
     tn = rem / band_rows;
 }
 
+// launch functions of the kernel families: each launches ITS kernel (the choice between them is gemm_plan's, gemm.hip)
 int db1_gemm_tile256_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
 int db1_gemm_pp_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
-bool db1_gemm_w4_supported(const GemmTileArgs& t, int fa, int fb, int dtC, int batch);
-int db1_gemm_w4_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
-bool db1_gemm_w4n_supported(const GemmTileArgs& t, int fa, int fb, int dtC, int batch);
-int db1_gemm_w4n_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
 int db1_gemm_pp32_launch(const GemmTileArgs& t, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
+// the 4-wave kernel: nj = 8: 256 x 256 tiles, nj = 4: 256 x 128 tiles
+bool db1_gemm_w4_supported(const GemmTileArgs& t, int nj, int fa, int fb, int dtC, int batch);
+int db1_gemm_w4_launch(const GemmTileArgs& t, int nj, int fa, int fb, int dtC, int dtBias, int batch, hipStream_t st);
 bool db1_gemm_w4_geglu_supported(int M, int dff, int K, int64_t lda, int64_t ldw, int64_t ldz, int64_t ld_other, bool fwd);
 int db1_gemm_w4_geglu_fwd_launch(const GemmTileArgs& t, int dtBias, hipStream_t st);
 int db1_gemm_w4_geglu_bwd_launch(const GemmTileArgs& t, hipStream_t st);

@@ -434,3 +434,30 @@ def test_generated_flash_loops_are_in_sync_with_their_generators(tmp_path):
         assert committed.count("s_barrier") == 6 * 3 + 1          # steady / last / idle of the six unrolled instances + the first iteration
         body = committed.split("L_ns1_%=:")[0].split("L_inst1_%=:")[-1]  # instance 1: from its label to the end of its steady path
         assert body.count("v_mfma_f32_16x16x32_bf16") == n_mfma_steady
+
+
+def test_gemm_dispatch_plan_matches_the_recorded_table():
+    """the GEMM dispatcher's two plan queries (kernel choice, workspace need; host code, no GPU) over tools/gemm_dispatch_table.py's
+    sweep -- the step's products at micro-batches of 4 and 64 sequences and one shape per branch of gemm_plan, x layouts, output types,
+    beta, offered workspace, batch levels and one A/B knob at a time -- equal, row by row, tests/golden/gemm_dispatch.json: the table
+    recorded from this project's own library before the dispatcher was restructured around one plan"""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gemm_dispatch_table as gdt
+    from bdm_db1_amd import lib as db1lib
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_dispatch.json")))
+    assert "this project" in gold["header"].lower() and gold["knobs"] == [k for k, _ in gdt.KNOBS] and gold["code_chars"] == gdt.CODE_CHARS
+    assert gold["betas"] == list(gdt.BETAS) and gold["offers"] == list(gdt.OFFERS)
+    L = db1lib.load()
+    rows = gdt.table(L)
+    assert sorted(rows) == sorted(gold["rows"]) and len(rows) >= 600
+    per = len(gdt.BETAS) * len(gdt.OFFERS)
+    bad = []
+    for key, want in gold["rows"].items():
+        got = rows[key]
+        for i, knob in enumerate(gold["knobs"]):
+            if got["ws"][i] != want["ws"][i] or got["codes"][i * per:(i + 1) * per] != want["codes"][i * per:(i + 1) * per]:
+                bad.append((key, knob, want["ws"][i], got["ws"][i], want["codes"][i * per:(i + 1) * per], got["codes"][i * per:(i + 1) * per]))
+    assert not bad, f"{len(bad)} rows differ (row, knob, ws want / got, codes want / got): {bad[:8]}"
+    for case in gdt.BRANCH_CASES:   # and each branch of gemm_plan is reached by its case of the branch list
+        assert gdt.branch_choice(L, case)[0] == case[6], case
