@@ -11,6 +11,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -81,7 +82,13 @@ def test_flash_forward_matches_oracle(B, L, H, shift):
     S = np.where(masked_for(L, shift)[None, None].astype(bool), -np.inf, (AC + BD) * scale)
     mx = S.max(-1)
     lse_ref = mx + np.log(np.exp(S - mx[..., None]).sum(-1))
-    assert np.abs(lse.cpu().numpy() - lse_ref).max() < 0.15, np.abs(lse.cpu().numpy() - lse_ref).max()
+    # per element, under the bound derived from the rounded model (tests/attn_probe.py): 4 x what bf16 rounding of q+u, q+v and p~ moves lse
+    # plus a float32 last place -- a fifteenth to a hundredth of the 0.15 this check used to allow
+    import attn_probe as A
+    p = dict(q=qkv[:, :, 0], k=qkv[:, :, 1], v=qkv[:, :, 2], R=R, u=u, vb=vb, mlen=0, shift=shift, scale=scale)
+    tol_lse = A.tolerance(lse_ref, A.reference(p, rounded=True)["lse"], 24)
+    err_lse = np.abs(lse.cpu().numpy() - lse_ref).max()
+    assert tol_lse < 0.15 and err_lse <= tol_lse, (err_lse, tol_lse)
 
 
 def test_flash_forward_matches_materialised_path_full_size():
