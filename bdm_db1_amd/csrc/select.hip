@@ -58,11 +58,15 @@ struct SelArgs {
     long long* next_ids;
     int64_t ids_stride;
     int* status;
+    float* logprob;             // the _lp forms (LP): [rows | n_slots, max_new] and [rows | n_slots]; NULL otherwise
+    float* sum_logprob;
 };
 
 // SLOTS (db1_select_tokens_slots): logits row blockIdx.x belongs to slot `row` (row_map), which keeps its own counter t_slot[row] below
 // limit[row]; a vacant slot (finished) only hands pad_id on; the selection itself is the same code.
-template <typename T, int NG, bool SLOTS>
+// LP (db1_select_tokens_lp, db1_select_tokens_slots_lp): after the token is chosen, one more sweep over the keys forms the log-sum-exp of the
+// row's candidates (the raw logits: no temperature, no top-k / top-p) and the owner of the row writes the token's log-probability next to it.
+template <typename T, int NG, bool SLOTS, bool LP>
 __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
     __shared__ SelShared sh;
     const int tid = threadIdx.x;
@@ -91,8 +95,10 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
         t_ok = t >= 0 && t < a.max_new;
         if (a.finished[row]) {     // (block-uniform)
             if (tid == 0) {
-                if (t_ok) a.out[(int64_t)row * a.max_new + t] = a.pad;
-                else a.status[row] |= 2;
+                if (t_ok) {
+                    a.out[(int64_t)row * a.max_new + t] = a.pad;
+                    if constexpr (LP) a.logprob[(int64_t)row * a.max_new + t] = 0.f;
+                } else a.status[row] |= 2;
                 a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
             }
             return;
@@ -182,6 +188,20 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
         sb = block_max_u64(sb, sh, ph);
         tok = (unsigned)(sb >> 32) ? (int)~(unsigned)sb : (int)~(unsigned)best;   // (a non-finite score cannot win: fall back to the arg-max)
     }
+    // LP: lp = (l[tok] - max) - log(sum exp(l - max)) over the candidates (key != 0), the sum in the fixed order of every reduction here.  The e
+    // of the top-p branch is exp((l - max) / T) over the top-k set: another quantity, dead by now.
+    float lz = 0.f;
+    if constexpr (LP) {
+        if (kmax != 0 && t_ok) {                      // (block-uniform)
+            const float m = sel_unkey(kmax);
+            float z = 0.f;
+#pragma unroll
+            for (int j = 0; j < NG; j++)
+#pragma unroll
+                for (int q = 0; q < 4; q++) z += key[j][q] ? expf(sel_unkey(key[j][q]) - m) : 0.f;
+            lz = logf(block_sum_f(z, sh, ph));
+        }
+    }
     if (tid == 0) {
         int fin = 0;
         if (bits & 1) fin = 1;
@@ -192,8 +212,17 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             if (t + 1 == a.limit[row]) fin = 1;
         }
         if (fin) a.finished[row] = 1;
-        if (t_ok) a.out[(int64_t)row * a.max_new + t] = tok;
-        else bits |= 2;
+        if (t_ok) {
+            a.out[(int64_t)row * a.max_new + t] = tok;
+            if constexpr (LP) {
+                float lp = 0.f;
+                if (kmax != 0) {                      // (a row without a candidate: 0, and the sum stays)
+                    lp = (ldf<T>(lg + tok) - sel_unkey(kmax)) - lz;
+                    a.sum_logprob[row] += lp;
+                }
+                a.logprob[(int64_t)row * a.max_new + t] = lp;
+            }
+        } else bits |= 2;
         if (bits) a.status[row] |= bits;
         a.next_ids[(int64_t)row * a.ids_stride] = tok;
     }
@@ -210,23 +239,25 @@ extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
     return 0;
 }
 
-template <typename T, bool SLOTS>
+template <typename T, bool SLOTS, bool LP>
 static void sel_dispatch(int ng, const SelArgs& a, int M, hipStream_t st) {
-    if (ng == 1) select_tokens_kernel<T, 1, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
-    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
-    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS><<<M, SEL_THREADS, 0, st>>>(a);
+    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
+    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
+    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
 }
 
 // The host side both entry points share: `a` arrives filled; validation (in one order for both, so an argument list that is wrong in two ways
-// fails with the same code as ever), 1 / temperature, the NG / SLOTS dispatch over M workgroups, the launch check.
-static int sel_launch(const char* who, bool slots, SelArgs& a, int M, int dt, float temperature, void* stream) {
+// fails with the same code as ever), 1 / temperature, the NG / SLOTS / LP dispatch over M workgroups, the launch check.  `lp`: the _lp
+// forms, which need both log-prob buffers; the others leave them NULL and launch the instantiations without that code.
+static int sel_launch(const char* who, bool slots, bool lp, SelArgs& a, int M, int dt, float temperature, void* stream) {
     if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
     if (M <= 0 || M > 65535 || a.V <= 0 || a.ld < a.V || a.max_new <= 0 || a.ids_stride < 0 || a.n_slots <= 0 || (!a.row_map && a.n_slots != M))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", who, M, a.V, (long long)a.ld, a.max_new,
                  (long long)a.ids_stride, a.n_slots, slots && !a.row_map ? " (no row_map: n_slots must equal M)" : "");
     const int ng = sel_ng(a.V);
     if (!ng) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d (at most %d)", who, a.V, SEL_MAX_NG * 4096);
-    if (!a.logits || !(slots ? a.t_slot && a.limit : a.t != nullptr) || !a.finished || !a.lengths || !a.out || !a.next_ids || !a.status)
+    if (!a.logits || !(slots ? a.t_slot && a.limit : a.t != nullptr) || !a.finished || !a.lengths || !a.out || !a.next_ids || !a.status ||
+        (lp && (!a.logprob || !a.sum_logprob)))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
     if (a.vlo < 0 || a.vhi > a.V || a.vlo >= a.vhi)
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, a.vlo, a.vhi, a.V);
@@ -236,8 +267,8 @@ static int sel_launch(const char* who, bool slots, SelArgs& a, int M, int dt, fl
     a.inv_t = a.greedy ? 1.f : 1.f / temperature;
     hipStream_t st = (hipStream_t)stream;
     DB1_DISPATCH_DT(dt, T, {
-        if (slots) sel_dispatch<T, true>(ng, a, M, st);
-        else sel_dispatch<T, false>(ng, a, M, st);
+        if (slots) { if (lp) sel_dispatch<T, true, true>(ng, a, M, st); else sel_dispatch<T, true, false>(ng, a, M, st); }
+        else { if (lp) sel_dispatch<T, false, true>(ng, a, M, st); else sel_dispatch<T, false, false>(ng, a, M, st); }
     });
     DB1_CHECK_LAUNCH(who);
     return DB1_OK;
@@ -256,15 +287,35 @@ static SelArgs sel_args(const void* logits, int V, int64_t ld, int vocab_lo, int
     return a;
 }
 
+// db1_select_tokens (logprob == NULL) and db1_select_tokens_lp
+static int sel_tokens(const char* who, bool lp, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                      int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
+                      const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                      int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* stream) {
+    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
+                         lengths, out, max_new, next_ids, ids_stride, status);
+    a.t = t; a.n_slots = M; a.logprob = logprob; a.sum_logprob = sum_logprob;
+    return sel_launch(who, false, lp, a, M, dt, temperature, stream);
+}
+
 extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
                                  float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
                                  const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                                  int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
-                         lengths, out, max_new, next_ids, ids_stride, status);
-    a.t = t; a.n_slots = M;
-    return sel_launch("select_tokens", false, a, M, dt, temperature, stream);
+    return sel_tokens("select_tokens", false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi, eos_id,
+                      pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, nullptr, nullptr, stream);
+}
+
+extern "C" int db1_select_tokens_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                                    float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
+                                    const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                                    int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* ws,
+                                    int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    return sel_tokens("select_tokens_lp", true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
+                      eos_id, pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, logprob, sum_logprob,
+                      stream);
 }
 
 // ------------------------------------------------------------------ the slot form (continuous batching, serving.py)
@@ -275,14 +326,37 @@ extern "C" int64_t db1_select_tokens_slots_workspace_bytes(int M, int V, int dt)
     return 0;
 }
 
+// db1_select_tokens_slots (logprob == NULL) and db1_select_tokens_slots_lp
+static int sel_slots(const char* who, bool lp, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                     int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, int32_t* t,
+                     const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                     int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
+                     float* sum_logprob, void* stream) {
+    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
+                         lengths, out, max_new, next_ids, ids_stride, status);
+    a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots; a.logprob = logprob; a.sum_logprob = sum_logprob;
+    return sel_launch(who, true, lp, a, M, dt, temperature, stream);
+}
+
 extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
                                        int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id,
                                        int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished,
                                        int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
                                        const int32_t* row_map, int n_slots, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
-                         lengths, out, max_new, next_ids, ids_stride, status);
-    a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots;
-    return sel_launch("select_tokens_slots", true, a, M, dt, temperature, stream);
+    return sel_slots("select_tokens_slots", false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
+                     eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map, n_slots,
+                     nullptr, nullptr, stream);
+}
+
+extern "C" int db1_select_tokens_slots_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                                          int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id,
+                                          int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished,
+                                          int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
+                                          const int32_t* row_map, int n_slots, float* logprob, float* sum_logprob, void* ws, int64_t ws_bytes,
+                                          void* stream) {
+    (void)ws; (void)ws_bytes;
+    return sel_slots("select_tokens_slots_lp", true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
+                     eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map, n_slots,
+                     logprob, sum_logprob, stream);
 }

@@ -40,7 +40,9 @@ class GenerationConfig:
     """``greedy``: arg-max (``temperature`` / ``top_k`` / ``top_p`` / ``seed`` unused); else Gumbel-max sampling at ``temperature`` after
     top-k (0 = off) and top-p (1 = off).  ``eos_id`` None: no end-of-sequence token.  Tokens are chosen in ``[vocab_lo, vocab_hi)``
     (``vocab_hi`` None: the model's whole vocabulary for ``generate``, the text vocabulary for captions and answers).  The host checks
-    whether every row has finished each ``sync_every`` tokens."""
+    whether every row has finished each ``sync_every`` tokens.  ``logprobs``: the selection also returns every chosen token's log-probability
+    over the window (``db1_select_tokens_lp``; the model's distribution, before temperature / top-k / top-p) and the row's sum; the tokens
+    are the same either way."""
     max_new_tokens: int = 30
     greedy: bool = True
     temperature: float = 1.0
@@ -52,6 +54,7 @@ class GenerationConfig:
     vocab_lo: int = 0
     vocab_hi: Optional[int] = None
     sync_every: int = 8
+    logprobs: bool = False
 
     def __post_init__(self):
         if int(self.max_new_tokens) < 1:
@@ -332,7 +335,8 @@ def _ring_ok(model) -> bool:
 # ``M``, ``expand``, ``cache``, ``start()`` and ``epilogue``.
 class _SamplingState:
     """what the two sampling states (``_State``, serving's ``_SlotState``) share: the per-row flags, stream ids and output, all zero / pad_id,
-    and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``"""
+    and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``; with ``cfg.logprobs`` also the tokens'
+    log-probs ``logprob`` [M, max_new_tokens] and their per-row sum ``sum_logprob`` (None otherwise: the plain entry point is called)"""
     expand = None
 
     def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
@@ -343,6 +347,11 @@ class _SamplingState:
         self.sel = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
                         seed=cfg.seed, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, stream_id=self.stream_id)
         self.con = _constrain_args(cons, cfg, V, model.dev)
+        self.logprob = self.sum_logprob = None
+        if cfg.logprobs:
+            self.logprob = torch.zeros(M, cfg.max_new_tokens, dtype=torch.float32, device=model.dev)
+            self.sum_logprob = torch.zeros(M, dtype=torch.float32, device=model.dev)
+            self.sel.update(logprob=self.logprob, sum_logprob=self.sum_logprob)
 
     def constrain(self, logits2d, row_map=None):
         """the decoding constraints, in place on the step's logits, over every row's own output so far (no constraints: no launch)"""
@@ -363,6 +372,9 @@ class _State(_SamplingState):
         for x in (self.t, self.finished, self.lengths, self.status):
             x.zero_()
         self.out.fill_(self.cfg.pad_id)
+        if self.logprob is not None:
+            self.logprob.zero_()
+            self.sum_logprob.zero_()
         if stream_ids is None:
             self.stream_id.copy_(torch.arange(self.M, dtype=torch.int32))
         else:
@@ -386,14 +398,29 @@ class _State(_SamplingState):
     def all_done(self) -> bool:
         return bool(self.finished.all())
 
-    def result(self) -> Tuple[torch.Tensor, torch.Tensor]:
+    def result(self):
         out, lengths, status = self.out.cpu(), self.lengths.cpu(), self.status.cpu()
         if (status & 2).any():
             raise RuntimeError("db1_select_tokens: the token counter left [0, max_new_tokens)")
+        if self.logprob is not None:
+            return out, lengths, self.logprob.cpu(), self.sum_logprob.cpu()
         return out, lengths
 
     def stats(self) -> dict:
         return {}
+
+
+class _BestOfState(_State):
+    """``_State`` over the G * n rows of a best-of-n sampling: every prompt's prefill expanded n-fold (rows g * n .. g * n + n - 1), the
+    log-probs always on; ``result`` adds the status, which the ranking needs"""
+    cache = "_best_of_generator"
+
+    def __init__(self, model, G: int, cfg: GenerationConfig, V: int, hi: int, n: int, cons: Optional[DecodingConstraints] = None):
+        super().__init__(model, G * n, cfg, V, hi, cons)
+        self.G, self.expand = G, n
+
+    def result(self):
+        return super().result() + (self.status.cpu(),)
 
 
 class _BeamState:
@@ -559,7 +586,7 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
 @torch.no_grad()
 def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
              stats: Optional[dict] = None, replay: bool = True,
-             constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             constraints: Optional[DecodingConstraints] = None):
     """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
     of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
     after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
@@ -567,7 +594,10 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
     receives the path taken and the number of per-token calls.  ``replay`` False (ring path): the same forward and epilogue run eagerly over
     the same ring instead of as a graph replay.  ``constraints`` (a ``DecodingConstraints``): applied to every step's logits
-    on the device, over the tokens generated so far, before the token is chosen."""
+    on the device, over the tokens generated so far, before the token is chosen.  With ``config.logprobs``: (ids, lengths, logprobs float32
+    [M, max_new_tokens], sum_logprob float32 [M]) -- ``logprobs[r, t]`` is the log-probability of ``ids[r, t]`` under the model's
+    distribution over the window (after the constraints, before temperature / top-k / top-p), EOS included, 0 after it; ``sum_logprob[r]``
+    their fp32 sum in token order."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate")
     M = _batch_size(prompt)
@@ -578,14 +608,19 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     return _decode(model, prompt, _State, key, graphed, replay, stats, start=(stream_ids,))
 
 
-def _run(model, x, cfg, **kw):
-    return beam_search(model, x, cfg, **kw) if isinstance(cfg, BeamSearchConfig) else generate(model, x, cfg, **kw)
+def _run(model, x, cfg, n=None, **kw):
+    if isinstance(cfg, BeamSearchConfig):
+        if n is not None:
+            raise ValueError("n= (best-of-n sampling) takes a GenerationConfig, not a BeamSearchConfig")
+        return beam_search(model, x, cfg, **kw)
+    return generate(model, x, cfg, **kw) if n is None else sample_best_of(model, x, cfg, n, **kw)
 
 
 def generate_captions(model, ic_batch, cfg=None, **kw):
     """captions for an ``ICTaskInput`` batch: the prompt ``[prompt, image patches]`` with an empty caption (coco_token_dataset.py layout),
-    tokens in the text vocabulary unless ``cfg`` says otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``:
-    (ids, lengths, scores) as ``beam_search``"""
+    tokens in the text vocabulary unless ``cfg`` says otherwise -> what ``generate`` returns (with ``cfg.logprobs`` the log-probs too); with
+    a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``; with ``n=`` (and ``sample_best_of``'s other keywords): the best of n
+    sampled captions per image, as ``sample_best_of`` returns them"""
     return _run(model, caption_prompt(ic_batch), _text_window(model, cfg or GenerationConfig()), **kw)
 
 
@@ -601,7 +636,8 @@ def caption_prompt(ic_batch):
 def answer_questions(model, vqa_batch, cfg=None, **kw):
     """answers for a ``VQATaskInput`` batch: the prompt ``[prompt, image patches, question]`` without the answer (the question is the first
     ``ques_len`` text tokens when ``ques_len`` is given, else the whole ``text_seq``), tokens in the text vocabulary unless ``cfg`` says
-    otherwise -> (ids, lengths) as ``generate``; with a ``BeamSearchConfig``: (ids, lengths, scores) as ``beam_search``"""
+    otherwise -> what ``generate`` returns (with ``cfg.logprobs`` the log-probs too); with a ``BeamSearchConfig``: (ids, lengths, scores) as
+    ``beam_search``; with ``n=``: the best of n sampled answers per question, as ``sample_best_of`` returns them"""
     return _run(model, question_prompt(vqa_batch), _text_window(model, cfg or GenerationConfig()), **kw)
 
 
@@ -660,3 +696,77 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
     key = _constrained("beam_search", model, (G, cfg, V, hi), constraints, cfg.max_new_tokens)
     return _decode(model, prompt, _BeamState, key, graphed, replay, stats)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- best-of-n sampling
+MAX_BEST_OF = 64
+
+
+def best_of_scores(sum_logprob, lengths, ended, no_candidate, length_penalty: float = 1.0) -> np.ndarray:
+    """float32 scores of sampled rows: ``sum_logprob / L^length_penalty``, L = ``lengths`` + 1 where the row ``ended`` with EOS (the EOS is
+    part of the sum) and ``lengths`` otherwise; -inf where ``no_candidate`` (status bit 0).  The normalisation of ``beam_search``'s scores."""
+    s = np.asarray(sum_logprob, np.float32)
+    L = np.asarray(lengths, np.int64) + np.asarray(ended, bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sc = (s / np.power(np.maximum(L, 1).astype(np.float32), np.float32(length_penalty))).astype(np.float32)
+    return np.where(np.asarray(no_candidate, bool), np.float32("-inf"), sc).astype(np.float32)
+
+
+def best_of_order(scores, R: int) -> np.ndarray:
+    """[G, n] scores -> int64 [G, R]: every group's R best columns, best first, ties to the lower column (a stable sort of the negated
+    scores)"""
+    return np.argsort(-np.asarray(scores, np.float32), axis=1, kind="stable")[:, :int(R)]
+
+
+def _check_best_of(cfg, n, num_return_sequences, length_penalty):
+    if not isinstance(cfg, GenerationConfig):
+        raise TypeError(f"sample_best_of: GenerationConfig expected, got {type(cfg).__name__}")
+    if cfg.greedy:
+        raise ValueError("sample_best_of: a sampling config is needed (greedy=True gives n copies of one sequence)")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_BEST_OF:
+        raise ValueError(f"sample_best_of: n {n!r} must be an integer in [1, {MAX_BEST_OF}]")
+    R = num_return_sequences
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= int(R) <= int(n):
+        raise ValueError(f"sample_best_of: num_return_sequences {R!r} must lie in [1, n = {n}]")
+    if not abs(float(length_penalty)) < float("inf"):
+        raise ValueError(f"sample_best_of: length_penalty {length_penalty} must be finite")
+    return int(n), int(R)
+
+
+@torch.no_grad()
+def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, length_penalty: float = 1.0, num_return_sequences: int = 1,
+                   stream_ids=None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
+                   constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Best-of-n sampling after ``prompt`` (G prompts of one shape): n sampled continuations of every prompt, ranked by their normalised
+    log-probability -> (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R =
+    ``num_return_sequences``, best first: the triple ``beam_search`` returns.  ``config``: a sampling ``GenerationConfig`` (``greedy`` raises);
+    its ``logprobs`` field is set here.  ``1 <= num_return_sequences <= n <= 64``.  The prompt runs ONCE per prompt; its memory and last
+    logits are expanded n-fold, as ``beam_search`` expands them to its beams, and row g * n + j samples from Philox stream g * n + j
+    (``stream_ids`` of shape [G, n]: the streams to use instead).  score = sum_logprob / L^``length_penalty``, L = the tokens before EOS + 1
+    for a row that ended with EOS, else its length; a row that met a step without a candidate scores -inf; ties go to the lower j.  The
+    ranking is NumPy on the host over [G, n].  ``graphed``, ``stats`` and ``constraints`` as ``generate`` takes them."""
+    cfg = config or GenerationConfig(greedy=False)
+    n, R = _check_best_of(cfg, n, num_return_sequences, length_penalty)
+    cfg = dataclasses.replace(cfg, logprobs=True)
+    _need_memory(model, "sample_best_of")
+    G = _batch_size(prompt)
+    V, hi = _vocab_window(model, cfg)
+    if not ops.select_tokens_supported(V, V, model.compute_dtype):
+        raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
+    if stream_ids is not None:
+        stream_ids = np.asarray(stream_ids, dtype=np.int64)
+        if stream_ids.shape != (G, n):
+            raise ValueError(f"sample_best_of: stream_ids of shape [{G}, {n}] expected, got {tuple(stream_ids.shape)}")
+        stream_ids = stream_ids.reshape(-1)
+    key = _constrained("sample_best_of", model, (G, cfg, V, hi, n), constraints, cfg.max_new_tokens)
+    out, lengths, _, sums, status = _decode(model, prompt, _BestOfState, key, graphed, True, stats, start=(stream_ids,))
+    out, lengths = out.numpy().reshape(G, n, -1), lengths.numpy().reshape(G, n)
+    mx = out.shape[2]
+    # a row ended with EOS when the token after its ``lengths`` tokens is the EOS (a row cut off at max_new_tokens has none)
+    at = np.take_along_axis(out, np.minimum(lengths, mx - 1)[..., None].astype(np.int64), 2)[..., 0]
+    no_cand = (status.numpy().reshape(G, n) & 1) != 0
+    ended = np.zeros_like(no_cand) if cfg.eos_id is None else (lengths < mx) & (at == int(cfg.eos_id)) & ~no_cand
+    scores = best_of_scores(sums.numpy().reshape(G, n), lengths, ended, no_cand, length_penalty)
+    order = best_of_order(scores, R)
+    pick = lambda a: torch.from_numpy(np.ascontiguousarray(np.take_along_axis(a, order.reshape(order.shape + (1,) * (a.ndim - 2)), 1)))
+    return pick(out), pick(lengths), pick(scores)

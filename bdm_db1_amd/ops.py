@@ -598,17 +598,31 @@ def _check_rings(who, rings):
     return r0.shape[0], r0.shape[1], int(r0[0, 0].numel() * r0.element_size()), r0.device
 
 
+def _check_logprobs(who, logprob, sum_logprob, rows, max_new, dev) -> bool:
+    """the optional log-prob outputs of the selection wrappers: both None (False: the plain entry point) or both given (True: the ``_lp`` one),
+    float32, contiguous, on ``dev``, ``logprob`` [rows, max_new] and ``sum_logprob`` [rows]"""
+    if logprob is None and sum_logprob is None:
+        return False
+    if logprob is None or sum_logprob is None:
+        raise ValueError(f"{who}: logprob and sum_logprob go together (one of them is None)")
+    _check_tensor(who, "logprob", logprob, torch.float32, (rows, max_new), dev)
+    _check_tensor(who, "sum_logprob", sum_logprob, torch.float32, (rows,), dev)
+    return True
+
+
 def select_tokens_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
 
 
 def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True, temperature=1.0,
-                  top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None):
+                  top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, logprob=None, sum_logprob=None):
     """one token per row of ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) on the device (db1_select_tokens): greedy, or
     Gumbel-max sampling at ``temperature`` after top-k / top-p, over the columns [vocab_lo, vocab_hi).  ``t`` (int32 [1], device): the token
     index within the generation, READ only; ``finished`` / ``lengths`` / ``status`` (int32 [M]) updated; the token goes to ``out`` [M, max_new]
-    (int32) at column t and to ``next_ids`` (int64, [M] or a column of [M, q]: row stride taken from the tensor).  Capturable; raises
-    ValueError on bad arguments before anything is launched."""
+    (int32) at column t and to ``next_ids`` (int64, [M] or a column of [M, q]: row stride taken from the tensor).  ``logprob`` (float32
+    [M, max_new]) and ``sum_logprob`` (float32 [M]), both or neither: the chosen token's log-probability over the window goes to column t and is
+    added to the row's sum (db1_select_tokens_lp; the choice itself is bit-identical).  Capturable; raises ValueError on bad arguments before
+    anything is launched."""
     who, dev, i32 = "select_tokens", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_supported(V, max(ld, V), logits2d.dtype))
@@ -618,10 +632,12 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
         _check_tensor(who, name, x, i32, n, dev)
     _check_tensor(who, "out", out, i32, (M, -1), dev)
     _check_next_ids(who, next_ids, M, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, M, out.shape[1], dev)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lib.call("db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k), float(top_p),
-             int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(stream_id), P(finished),
-             P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), _vp(0), 0, stream())
+    lib.call("db1_select_tokens_lp" if lp else "db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi,
+             float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
+             int(step_base), P(t), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status),
+             *((P(logprob), P(sum_logprob)) if lp else ()), _vp(0), 0, stream())
 
 
 def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
@@ -629,13 +645,15 @@ def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
 
 
 def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True,
-                        temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, row_map=None):
+                        temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, row_map=None, logprob=None,
+                        sum_logprob=None):
     """``select_tokens`` over SLOTS (db1_select_tokens_slots): ``t`` and ``limit`` are int32 [S], one token counter and one token limit per
     slot; a live slot's token goes to ``out`` [S, max_new] at column t[slot], then the launch sets t[slot] += 1 and, at t[slot] == limit[slot],
     finished[slot].  A slot with finished != 0 is vacant: it only gets ``pad_id`` in ``next_ids``.  ``row_map`` (int32 [M], distinct slots) says
     which slot each row of ``logits2d`` [M, ld] belongs to; None: row i is slot i and S = M.  ``finished`` / ``lengths`` / ``status`` /
-    ``stream_id`` are int32 [S], ``next_ids`` int64 ([S] or a column of [S, q]).  Capturable; raises ValueError on bad arguments before
-    anything is launched."""
+    ``stream_id`` are int32 [S], ``next_ids`` int64 ([S] or a column of [S, q]).  ``logprob`` (float32 [S, max_new]) and ``sum_logprob``
+    (float32 [S]), both or neither, as ``select_tokens`` takes them, indexed by the slot (db1_select_tokens_slots_lp).  Capturable; raises
+    ValueError on bad arguments before anything is launched."""
     who, dev, i32 = "select_tokens_slots", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
@@ -650,10 +668,12 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
         _check_tensor(who, name, x, i32, S, dev)
     _check_tensor(who, "out", out, i32, (S, -1), dev)
     _check_next_ids(who, next_ids, S, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, S, out.shape[1], dev)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lib.call("db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k),
-             float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id), int(step_base), P(t), P(limit), P(stream_id),
-             P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status), P(row_map), S, _vp(0), 0, stream())
+    lib.call("db1_select_tokens_slots_lp" if lp else "db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo,
+             vocab_hi, float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
+             int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0),
+             P(status), P(row_map), S, *((P(logprob), P(sum_logprob)) if lp else ()), _vp(0), 0, stream())
 
 
 def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype) -> bool:

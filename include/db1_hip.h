@@ -547,6 +547,25 @@ int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int 
                       int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
                       const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
                       int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+/* The _lp forms (db1_select_tokens_lp, db1_select_tokens_slots_lp) choose exactly as the forms above -- out, lengths, finished, status,
+ * next_ids and t come out bit-identical on the same inputs -- and also say how likely the chosen token was (tests/logprob_rule.py restates
+ * the rule in NumPy).  logprob [rows | n_slots, max_new] and sum_logprob [rows | n_slots] (float32, both required: a NULL one is
+ * DB1_ERR_BAD_SHAPE before any launch):
+ *   - lse = the fp32 log-sum-exp over the row's candidates, the FINITE logits of the columns in [vocab_lo, vocab_hi) as the launch reads them
+ *     (a row edited by db1_constrain_logits is scored on the edited values); temperature, top-k and top-p are NOT applied: lp is the model's
+ *     log-probability of the token over the window, the quantity of db1_score_rows' logprob and db1_beam_step's l - lse;
+ *   - lp = (l[tok] - max) - log(sum exp(l - max)), the sum in a fixed order (the wave butterflies, then the 16 wave results in order): the
+ *     same inputs give the same bits;
+ *   - wherever the launch writes a chosen token to out[row, t] it writes lp to logprob[row, t] and does sum_logprob[row] += lp (one fp32 add
+ *     per launch by the thread that owns the row; the EOS token is included, as in the beam rule);
+ *   - a finished row of the lockstep form (out gets pad_id) writes 0.0f to logprob[row, t] and leaves the sum alone; so does a row with no
+ *     candidate;
+ *   - t out of range: neither is touched; a vacant slot, or a row_map entry outside [0, n_slots): neither is touched.
+ * No atomics, no workspace; the _supported and _workspace_bytes queries of the forms above hold for these too. */
+int db1_select_tokens_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                         float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
+                         const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
+                         int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* ws, int64_t ws_bytes, void* stream);
 /* The slot form of db1_select_tokens (continuous batching: every row of a decode batch is a SLOT that requests pass through).  The
  * selection rule is db1_select_tokens' own, unchanged; the bookkeeping is per slot:
  *   - logits row i belongs to slot row_map[i] (int32 [M], distinct; NULL: slot i, and then n_slots == M).  t, limit, stream_id, finished,
@@ -566,6 +585,13 @@ int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt
                             const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                             int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, void* ws,
                             int64_t ws_bytes, void* stream);
+/* db1_select_tokens_slots with the token log-probs of db1_select_tokens_lp (the rule is stated there): logprob [n_slots, max_new] at
+ * column t[slot], sum_logprob [n_slots], both indexed by the SLOT. */
+int db1_select_tokens_slots_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                               float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, int32_t* t,
+                               const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                               int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
+                               float* sum_logprob, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ beam search (captions / answers / text; tests/beam_rule.py restates
  * the rule in NumPy).  G groups (prompts) of W beams (1 <= W <= 16), M = G * W rows, row b = g * W + j; step t = 0 .. max_new - 1 chooses

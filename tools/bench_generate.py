@@ -32,7 +32,20 @@ With --constraints: the greedy caption measurement above, unconstrained and with
 no_repeat_ngram_size=3, min_new_tokens=5) -- one db1_constrain_logits launch more in every replay (no EOS, as in every run here, so
 the minimum length bans nothing) --, one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel time of db1_constrain_logits.
 
-    python tools/bench_generate.py --constraints [M ...]"""
+    python tools/bench_generate.py --constraints [M ...]
+
+With --logprobs: the greedy and top-p 0.9 caption measurements above with ``GenerationConfig(logprobs=False)`` and ``logprobs=True`` (the
+replay ends in db1_select_tokens_lp instead of db1_select_tokens), and the two kernels alone on random bf16 logits [M, 33 025] over the text
+window (device time per call from events over 50 calls), one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel times of
+the LP and the plain instantiation of select_tokens_kernel.
+
+    python tools/bench_generate.py --logprobs [M ...]
+    python tools/bench_generate.py --select-kernels greedy|top_p_0.9 [M]   (the two kernels alone in ONE mode: the run to trace)
+
+With --best-of N the arguments are group counts G (default 16): sample_best_of (N samples per image, top-p 0.9, M = G * N rows) next to
+beam search with N beams over the same images, ms per token as above.
+
+    python tools/bench_generate.py --best-of 4 [G ...]"""
 import dataclasses
 import json
 import os
@@ -287,7 +300,68 @@ def stream_main(n_req=256, slots=64):
     print(json.dumps(rec), flush=True)
 
 
+SELECT_MODES = {"greedy": dict(), "top_p_0.9": dict(greedy=False, top_p=0.9, seed=1)}
+
+
+def select_kernels_us(M, modes=tuple(SELECT_MODES)):
+    """db1_select_tokens and db1_select_tokens_lp alone on random bf16 logits [M, V] over the text window, greedy and top-p 0.9"""
+    V, hi = int(model.total_vocab_size), int(model.text_vocab_size)
+    logits = (torch.randn(M, V, device=dev) * 3).to(torch.bfloat16)
+    i32 = dict(dtype=torch.int32, device=dev)
+    t, fin, n, status = torch.zeros(1, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32)
+    out = torch.zeros(M, N_NEW, **i32)
+    ids = torch.zeros(M, dtype=torch.long, device=dev)
+    lp, sums = torch.zeros(M, N_NEW, device=dev), torch.zeros(M, device=dev)
+    rec = {}
+    for name in modes:
+        kw = SELECT_MODES[name]
+        run = lambda **more: ops.select_tokens(logits, t, fin, n, out, ids, status, V=V, vocab_hi=hi, **kw, **more)
+        rec[f"select_{name}_us"] = round(device_us(run), 2)
+        rec[f"select_lp_{name}_us"] = round(device_us(lambda: run(logprob=lp, sum_logprob=sums)), 2)
+    return rec
+
+
+def logprobs_main(Ms):
+    for M in Ms:
+        rec = {"M": M, "new_tokens": N_NEW}
+        for name, cfg in (("greedy", GenerationConfig(max_new_tokens=N_NEW)),
+                          ("top_p_0.9", GenerationConfig(max_new_tokens=N_NEW, greedy=False, top_p=0.9, seed=1))):
+            rec[f"{name}_ms_per_token"] = round(gen_ms_per_token(M, cfg), 4)
+            rec[f"{name}_logprobs_ms_per_token"] = round(gen_ms_per_token(M, dataclasses.replace(cfg, logprobs=True)), 4)
+            rec[f"{name}_logprobs_minus_plain_us"] = round((rec[f"{name}_logprobs_ms_per_token"] - rec[f"{name}_ms_per_token"]) * 1e3, 2)
+        model._generator = None
+        torch.cuda.empty_cache()
+        rec.update(select_kernels_us(M))
+        print(json.dumps(rec), flush=True)
+
+
+def best_of_main(N, Gs):
+    for G in Gs:
+        rec = {"G": G, "n": N, "M": G * N, "new_tokens": N_NEW}
+        cfg = GenerationConfig(max_new_tokens=N_NEW, greedy=False, top_p=0.9, seed=1)
+        rec["best_of_ms_per_token"] = round(gen_ms_per_token(G, cfg, n=N), 4)
+        model._best_of_generator = None
+        torch.cuda.empty_cache()
+        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=N, max_new_tokens=N_NEW)), 4)
+        model._beam_generator = None
+        torch.cuda.empty_cache()
+        rec["best_of_over_beam"] = round(rec["best_of_ms_per_token"] / rec["beam_ms_per_token"], 4)
+        print(json.dumps(rec), flush=True)
+
+
 args = sys.argv[1:]
+if "--select-kernels" in args:
+    i = args.index("--select-kernels")
+    M = int((args[:i] + args[i + 2:] or [64])[0])
+    print(json.dumps({"M": M, **select_kernels_us(M, (args[i + 1],))}), flush=True)
+    sys.exit(0)
+if "--logprobs" in args:
+    logprobs_main([int(a) for a in args if a != "--logprobs"] or [1, 16, 64])
+    sys.exit(0)
+if "--best-of" in args:
+    i = args.index("--best-of")
+    best_of_main(int(args[i + 1]), [int(a) for a in args[:i] + args[i + 2:]] or [16])
+    sys.exit(0)
 if "--stream" in args:
     rest = [int(a) for a in args if a != "--stream"]
     stream_main(*rest[:2])
