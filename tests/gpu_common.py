@@ -9,13 +9,57 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stream_rule as S  # noqa: E402
+
 DEV = "cuda"
+TD = {"f32": torch.float32, "bf16": torch.bfloat16}
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
+
+
+def dev(a, dt):
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(DEV).to(TD[dt])
+
+
+def host(t):
+    return t.detach().float().cpu().numpy().copy()      # bf16 -> float32 is exact
+
+
+class Guarded:
+    """a [rows, cols] tensor (row stride ld) in the middle of one allocation filled with the sentinel: margins of at least one row and 64
+    elements before and after; ``off`` shifts the start by that many elements (an unaligned base)"""
+
+    def __init__(self, rows, cols, dt, ld=None, fill=None, off=0):
+        self.rows, self.cols, self.ld = rows, cols, ld or cols
+        self.start = 64 * -(-max(self.ld, 64) // 64) + off
+        self.buf = torch.full((2 * self.start + rows * self.ld,), S.SENT, device=DEV, dtype=TD[dt])
+        self.t = self._body(self.buf)
+        if fill is not None:
+            self.t.copy_(dev(np.reshape(fill, (rows, cols)), dt))
+
+    def _body(self, buf):
+        return buf[self.start:self.start + self.rows * self.ld].view(self.rows, self.ld)[:, :self.cols]
+
+    @property
+    def flat(self):
+        assert self.ld == self.cols
+        return self.buf[self.start:self.start + self.rows * self.cols]
+
+    def np(self, flat=False):
+        a = host(self.t)
+        return a.reshape(-1) if flat else a
+
+    def intact(self, name):
+        chk = self.buf.clone()
+        self._body(chk).fill_(S.SENT)
+        bits = torch.int16 if chk.dtype == torch.bfloat16 else torch.int32
+        bad = (chk.view(bits) != torch.full((1,), S.SENT, device=DEV, dtype=chk.dtype).view(bits)).nonzero()
+        assert bad.numel() == 0, f"{name}: {bad.shape[0]} guard elements changed, the first at offset {int(bad[0]) - self.start} from the output's start"
 
 
 def _tdev(a, dtype=None):

@@ -63,6 +63,7 @@ SENT = -7680.0            # what outputs and guard margins hold before a call (e
 EPS = 1e-5
 BFMAX = 3.3895313892515355e38   # largest finite bf16
 SPECIALS = np.array([0.0, -0.0, 1e-30, -1e-30, 6.0, -6.0, 12.0, -12.0, 40.0, -40.0, BFMAX], np.float32)
+GELU_C = {"f32": 8, "bf16": 12}   # c of gelu (fp32 erff path) and gelu (bf16 storage path) in the table above
 ADAM_HP = dict(lr=3e-3, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01)
 MUTANTS = ("drop_last_row", "tail_reads_past", "last_colvec_unwritten", "geglu_half_at_c", "swap_dgdb_group", "stale_waves", "acc_assign",
            "skip_tail", "swap_bf16_pair", "gscale_once", "no_s_round")
@@ -579,7 +580,7 @@ def _act_terms(case, inp):
     """float64 references and A of (out, dz halves)"""
     n, act, dt = case["n"], case["act"], case["dt"]
     z, g = _d(inp["z"]), _d(inp["dout"])
-    cg = 8 if dt == "f32" else 12
+    cg = GELU_C[dt]
     if act == "relu":
         return (np.maximum(z, 0.0), None, 0), [(g * (z > 0), None, 0)]
     x = z[:, n:] if act == "geglu" else z

@@ -1011,7 +1011,9 @@ def test_patch_resident_convolution_equals_the_tile_form(ops, N):
             ops.conv3x3_implicit_fwd(x, w_op, bias, y0, N, sign=1)
             ops.conv3x3_implicit_fwd(x, w_op, bias, y1, N, sign=1, res=res)
             ops.conv3x3_implicit_fwd(x, w_t, None, y2, N, sign=-1)
-            ops.conv3x3_implicit_fwd(x, w_op, bias.float(), y0.clone(), N, sign=1)     # (fp32 bias instantiation runs)
+            y0f = torch.full_like(y0, float("nan"))
+            ops.conv3x3_implicit_fwd(x, w_op, bias.float(), y0f, N, sign=1)            # the fp32-bias instantiation: the same (bf16-representable) values
+            assert torch.equal(y0f.view(torch.int16), y0.view(torch.int16)), f"fp32 bias differs from bf16 bias (conv_patch = {knob}, N = {N})"
             gp, gb = torch.full((64, 576), 0.5, device=DEV), torch.full((64,), -0.25, device=DEV)
             ops.conv3x3_implicit_wgrad(res, x, gp, N, gbias_acc=gb)                    # (res plays dY)
             gp2, gb2 = torch.full((64, 576), 0.5, device=DEV), torch.full((64,), -0.25, device=DEV)
