@@ -13,6 +13,7 @@
 #define SEL_THREADS 1024
 #define SEL_WAVES (SEL_THREADS / 64)
 #define SEL_MAX_NG 9                       // V <= 36 864 (DB1-1.3B: 33 025)
+#define SEL_MAX_TOP 16                     // alternatives per token of the _top forms
 #define SEL_SITE_SAMPLE 0xE0000100u        // Philox site of the sampling draws (dropout sites: layer * 4 + {0, 1, 2}, 0xE0000000, 0xE0000001)
 
 typedef SelSharedT<SEL_WAVES> SelShared;
@@ -60,13 +61,26 @@ struct SelArgs {
     int* status;
     float* logprob;             // the _lp forms (LP): [rows | n_slots, max_new] and [rows | n_slots]; NULL otherwise
     float* sum_logprob;
+    int top_n;                  // the _top forms (TOP): [rows | n_slots, max_new, top_n] each; 0 and NULL otherwise
+    int* top_ids;
+    float* top_logprob;
 };
+
+// the unused entries [from, top_n) of one (row, t) of the _top buffers: -1 / -inf
+__device__ __forceinline__ void sel_top_fill(const SelArgs& a, int64_t at, int from) {
+    for (int i = from; i < a.top_n; i++) {
+        a.top_ids[at * a.top_n + i] = -1;
+        a.top_logprob[at * a.top_n + i] = -INFINITY;
+    }
+}
 
 // SLOTS (db1_select_tokens_slots): logits row blockIdx.x belongs to slot `row` (row_map), which keeps its own counter t_slot[row] below
 // limit[row]; a vacant slot (finished) only hands pad_id on; the selection itself is the same code.
 // LP (db1_select_tokens_lp, db1_select_tokens_slots_lp): after the token is chosen, one more sweep over the keys forms the log-sum-exp of the
 // row's candidates (the raw logits: no temperature, no top-k / top-p) and the owner of the row writes the token's log-probability next to it.
-template <typename T, int NG, bool SLOTS, bool LP>
+// TOP (db1_select_tokens_top, db1_select_tokens_slots_top; LP as well): after that, top_n rounds over the same keys (sel_top_rounds) give the
+// row's best candidates in the arg-max's own order, and the owner of the row writes their columns and (l - max) - lz, the token's expression.
+template <typename T, int NG, bool SLOTS, bool LP, bool TOP>
 __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
     __shared__ SelShared sh;
     const int tid = threadIdx.x;
@@ -98,6 +112,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
                 if (t_ok) {
                     a.out[(int64_t)row * a.max_new + t] = a.pad;
                     if constexpr (LP) a.logprob[(int64_t)row * a.max_new + t] = 0.f;
+                    if constexpr (TOP) sel_top_fill(a, (int64_t)row * a.max_new + t, 0);
                 } else a.status[row] |= 2;
                 a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
             }
@@ -202,6 +217,32 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             lz = logf(block_sum_f(z, sh, ph));
         }
     }
+    if constexpr (TOP) {
+        if (t_ok) {                                   // (block-uniform)
+            const int64_t at = (int64_t)row * a.max_new + t;
+            const float m = sel_unkey(kmax);
+            auto scan = [&](unsigned long long below) {
+                const unsigned wk = (unsigned)(below >> 32);
+                const int d = (int)~(unsigned)below - 4 * tid;
+                const int z = sel_opaque_zero();
+                unsigned bk = 0;
+                int bo = 0;
+#pragma unroll
+                for (int j = 0; j < NG; j++)
+#pragma unroll
+                    for (int q = 0; q < 4; q++) sel_scan_step(key[j][q], z + (4 * j * SEL_THREADS + q), wk, d, bk, bo);
+                return sel_pair(bk, 4 * tid + bo);
+            };
+            auto emit = [&](int i, unsigned long long w, bool) {
+                if (tid == 0) {
+                    a.top_ids[at * a.top_n + i] = (int)~(unsigned)w;
+                    a.top_logprob[at * a.top_n + i] = (sel_unkey((unsigned)(w >> 32)) - m) - lz;   // (the key gives the logit back bit for bit)
+                }
+            };
+            const int got = kmax ? sel_top_rounds(a.top_n, best, scan, emit, sh, ph) : 0;
+            if (tid == 0) sel_top_fill(a, at, got);
+        }
+    }
     if (tid == 0) {
         int fin = 0;
         if (bits & 1) fin = 1;
@@ -239,25 +280,27 @@ extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
     return 0;
 }
 
-template <typename T, bool SLOTS, bool LP>
+template <typename T, bool SLOTS, bool LP, bool TOP>
 static void sel_dispatch(int ng, const SelArgs& a, int M, hipStream_t st) {
-    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
-    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
-    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP><<<M, SEL_THREADS, 0, st>>>(a);
+    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
+    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
+    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
 }
 
 // The host side both entry points share: `a` arrives filled; validation (in one order for both, so an argument list that is wrong in two ways
 // fails with the same code as ever), 1 / temperature, the NG / SLOTS / LP dispatch over M workgroups, the launch check.  `lp`: the _lp
-// forms, which need both log-prob buffers; the others leave them NULL and launch the instantiations without that code.
-static int sel_launch(const char* who, bool slots, bool lp, SelArgs& a, int M, int dt, float temperature, void* stream) {
+// forms, which need both log-prob buffers; the others leave them NULL and launch the instantiations without that code.  `top`: the _top
+// forms (lp as well), which need 1 <= top_n <= SEL_MAX_TOP and both of their buffers; a.top_n == 0 otherwise.
+static int sel_launch(const char* who, bool slots, bool lp, bool top, SelArgs& a, int M, int dt, float temperature, void* stream) {
     if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
     if (M <= 0 || M > 65535 || a.V <= 0 || a.ld < a.V || a.max_new <= 0 || a.ids_stride < 0 || a.n_slots <= 0 || (!a.row_map && a.n_slots != M))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", who, M, a.V, (long long)a.ld, a.max_new,
                  (long long)a.ids_stride, a.n_slots, slots && !a.row_map ? " (no row_map: n_slots must equal M)" : "");
+    if (top && (a.top_n < 1 || a.top_n > SEL_MAX_TOP)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_n %d (1 .. %d)", who, a.top_n, SEL_MAX_TOP);
     const int ng = sel_ng(a.V);
     if (!ng) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d (at most %d)", who, a.V, SEL_MAX_NG * 4096);
     if (!a.logits || !(slots ? a.t_slot && a.limit : a.t != nullptr) || !a.finished || !a.lengths || !a.out || !a.next_ids || !a.status ||
-        (lp && (!a.logprob || !a.sum_logprob)))
+        (lp && (!a.logprob || !a.sum_logprob)) || (top && (!a.top_ids || !a.top_logprob)))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
     if (a.vlo < 0 || a.vhi > a.V || a.vlo >= a.vhi)
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, a.vlo, a.vhi, a.V);
@@ -267,8 +310,15 @@ static int sel_launch(const char* who, bool slots, bool lp, SelArgs& a, int M, i
     a.inv_t = a.greedy ? 1.f : 1.f / temperature;
     hipStream_t st = (hipStream_t)stream;
     DB1_DISPATCH_DT(dt, T, {
-        if (slots) { if (lp) sel_dispatch<T, true, true>(ng, a, M, st); else sel_dispatch<T, true, false>(ng, a, M, st); }
-        else { if (lp) sel_dispatch<T, false, true>(ng, a, M, st); else sel_dispatch<T, false, false>(ng, a, M, st); }
+        if (slots) {
+            if (top) sel_dispatch<T, true, true, true>(ng, a, M, st);
+            else if (lp) sel_dispatch<T, true, true, false>(ng, a, M, st);
+            else sel_dispatch<T, true, false, false>(ng, a, M, st);
+        } else {
+            if (top) sel_dispatch<T, false, true, true>(ng, a, M, st);
+            else if (lp) sel_dispatch<T, false, true, false>(ng, a, M, st);
+            else sel_dispatch<T, false, false, false>(ng, a, M, st);
+        }
     });
     DB1_CHECK_LAUNCH(who);
     return DB1_OK;
@@ -287,15 +337,17 @@ static SelArgs sel_args(const void* logits, int V, int64_t ld, int vocab_lo, int
     return a;
 }
 
-// db1_select_tokens (logprob == NULL) and db1_select_tokens_lp
-static int sel_tokens(const char* who, bool lp, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+// db1_select_tokens (logprob == NULL), db1_select_tokens_lp (top_ids == NULL, top_n 0) and db1_select_tokens_top
+static int sel_tokens(const char* who, bool lp, bool top, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
                       int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
                       const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
-                      int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* stream) {
+                      int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                      float* top_logprob, void* stream) {
     SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
                          lengths, out, max_new, next_ids, ids_stride, status);
     a.t = t; a.n_slots = M; a.logprob = logprob; a.sum_logprob = sum_logprob;
-    return sel_launch(who, false, lp, a, M, dt, temperature, stream);
+    a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob;
+    return sel_launch(who, false, lp, top, a, M, dt, temperature, stream);
 }
 
 extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
@@ -303,8 +355,9 @@ extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, i
                                  const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                                  int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    return sel_tokens("select_tokens", false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi, eos_id,
-                      pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, nullptr, nullptr, stream);
+    return sel_tokens("select_tokens", false, false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi, eos_id,
+                      pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, nullptr, nullptr, 0, nullptr,
+                      nullptr, stream);
 }
 
 extern "C" int db1_select_tokens_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
@@ -313,9 +366,20 @@ extern "C" int db1_select_tokens_lp(const void* logits, int M, int V, int64_t ld
                                     int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* ws,
                                     int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    return sel_tokens("select_tokens_lp", true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
-                      eos_id, pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, logprob, sum_logprob,
-                      stream);
+    return sel_tokens("select_tokens_lp", true, false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo,
+                      seed_hi, eos_id, pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, logprob,
+                      sum_logprob, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int db1_select_tokens_top(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                                     float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base,
+                                     const int32_t* t, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                                     int64_t* next_ids, int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, int top_n,
+                                     int32_t* top_ids, float* top_logprob, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    return sel_tokens("select_tokens_top", true, true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo,
+                      seed_hi, eos_id, pad_id, step_base, t, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, logprob,
+                      sum_logprob, top_n, top_ids, top_logprob, stream);
 }
 
 // ------------------------------------------------------------------ the slot form (continuous batching, serving.py)
@@ -326,16 +390,17 @@ extern "C" int64_t db1_select_tokens_slots_workspace_bytes(int M, int V, int dt)
     return 0;
 }
 
-// db1_select_tokens_slots (logprob == NULL) and db1_select_tokens_slots_lp
-static int sel_slots(const char* who, bool lp, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+// db1_select_tokens_slots (logprob == NULL), db1_select_tokens_slots_lp (top_ids == NULL, top_n 0) and db1_select_tokens_slots_top
+static int sel_slots(const char* who, bool lp, bool top, const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
                      int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, int32_t* t,
                      const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                      int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
-                     float* sum_logprob, void* stream) {
+                     float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* stream) {
     SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, eos_id, pad_id, step_base, stream_id, finished,
                          lengths, out, max_new, next_ids, ids_stride, status);
     a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots; a.logprob = logprob; a.sum_logprob = sum_logprob;
-    return sel_launch(who, true, lp, a, M, dt, temperature, stream);
+    a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob;
+    return sel_launch(who, true, lp, top, a, M, dt, temperature, stream);
 }
 
 extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
@@ -344,9 +409,9 @@ extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t
                                        int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
                                        const int32_t* row_map, int n_slots, void* ws, int64_t ws_bytes, void* stream) {
     (void)ws; (void)ws_bytes;
-    return sel_slots("select_tokens_slots", false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
+    return sel_slots("select_tokens_slots", false, false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
                      eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map, n_slots,
-                     nullptr, nullptr, stream);
+                     nullptr, nullptr, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int db1_select_tokens_slots_lp(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
@@ -356,7 +421,19 @@ extern "C" int db1_select_tokens_slots_lp(const void* logits, int M, int V, int6
                                           const int32_t* row_map, int n_slots, float* logprob, float* sum_logprob, void* ws, int64_t ws_bytes,
                                           void* stream) {
     (void)ws; (void)ws_bytes;
-    return sel_slots("select_tokens_slots_lp", true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo, seed_hi,
-                     eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map, n_slots,
-                     logprob, sum_logprob, stream);
+    return sel_slots("select_tokens_slots_lp", true, false, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo,
+                     seed_hi, eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map,
+                     n_slots, logprob, sum_logprob, 0, nullptr, nullptr, stream);
+}
+
+extern "C" int db1_select_tokens_slots_top(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                                           int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id,
+                                           int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished,
+                                           int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
+                                           const int32_t* row_map, int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                                           float* top_logprob, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    return sel_slots("select_tokens_slots_top", true, true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo,
+                     seed_hi, eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map,
+                     n_slots, logprob, sum_logprob, top_n, top_ids, top_logprob, stream);
 }

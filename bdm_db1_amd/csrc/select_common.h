@@ -5,6 +5,11 @@
 // reduces by butterfly (every lane ends with the same bits), writes one LDS slot, one barrier, every thread combines the NW slots in order --
 // the same inputs give the same bits.  Consecutive reductions alternate between two slot sets, so a slot is never rewritten while a slower
 // wave may still read it (one barrier per reduction).
+//
+// sel_top_rounds: the n best candidates of a row in the order of those packed pairs (logit descending, ties by the lower column), one
+// block_max_u64 per round (db1_select_tokens_top, db1_score_rows_top).  A pair holds its column, so no two candidates share one and the
+// winner of a round belongs to exactly one thread: only that thread looks for its next best pair, below the winner; every other thread's
+// best pair is still its best.
 #pragma once
 #include "db1_common.h"
 
@@ -79,4 +84,45 @@ __device__ __forceinline__ float block_sum_f(float x, SelSharedT<NW>& sh, int& p
     for (int w = 1; w < NW; w++) r += sh.f[ph][w];
     ph ^= 1;
     return r;
+}
+
+// the packed pair of a candidate (0: not a candidate)
+__device__ __forceinline__ unsigned long long sel_pair(unsigned key, int col) {
+    return key ? ((unsigned long long)key << 32) | (unsigned)~col : 0ull;
+}
+// A zero the compiler cannot see through (no instruction).  The scans below add it to the literal column offsets of their unrolled elements: a
+// bare literal cannot be an operand of the select that keeps the best offset, so the compiler would load one register per element of the row
+// with its literal and keep all of them alive across the rounds.
+__device__ __forceinline__ int sel_opaque_zero() {
+    int z = 0;
+    asm volatile("" : "+v"(z));
+    return z;
+}
+// One element of a thread's scan for its best pair strictly below a winner (key wk, column wc; ~0ull: below nothing).  The thread's elements are
+// visited by ascending column; `off` = the element's column minus the thread's first one (sel_opaque_zero() + a literal) and d = wc minus that
+// first column.  (bk, bo): the best key so far and its `off`.
+__device__ __forceinline__ void sel_scan_step(unsigned k, int off, unsigned wk, int d, unsigned& bk, int& bo) {
+    // (k > bk: among equal keys the first, the lowest column, stays; | and &, not || and &&: no branch per element)
+    const bool up = ((k < wk) | ((k == wk) & (off > d))) & (k > bk);
+    bk = up ? k : bk;
+    bo = up ? off : bo;
+}
+// scan(below) -> the thread's best pair strictly below `below` (~0ull: its best pair; 0: it holds no such candidate); `first`: the block's best
+// pair when the caller has reduced it already (round 0 then costs no reduction), else 0; emit(i, winner, own): round i's winner, `own` on the
+// one thread that holds it.  Rounds end at n or when no pair is left -> the number of rounds that found one (block-uniform).  Every thread
+// scans once, before round 0; after that only the owner of the last winner does.
+template <int NW, typename Scan, typename Emit>
+__device__ __forceinline__ int sel_top_rounds(int n, unsigned long long first, Scan scan, Emit emit, SelSharedT<NW>& sh, int& ph) {
+    unsigned long long mine = 0, below = ~0ull;
+    bool own = true;
+    int i = 0;
+#pragma nounroll
+    for (; i < n; i++) {
+        if (own) mine = scan(below);
+        below = (i == 0 && first) ? first : block_max_u64(mine, sh, ph);
+        if (!(unsigned)(below >> 32)) break;
+        own = mine == below;
+        emit(i, below, own);
+    }
+    return i;
 }

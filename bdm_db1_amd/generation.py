@@ -25,7 +25,7 @@ from __future__ import annotations
 
 import contextlib
 import dataclasses
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -42,7 +42,8 @@ class GenerationConfig:
     (``vocab_hi`` None: the model's whole vocabulary for ``generate``, the text vocabulary for captions and answers).  The host checks
     whether every row has finished each ``sync_every`` tokens.  ``logprobs``: the selection also returns every chosen token's log-probability
     over the window (``db1_select_tokens_lp``; the model's distribution, before temperature / top-k / top-p) and the row's sum; the tokens
-    are the same either way."""
+    are the same either way.  ``top_logprobs`` n (keyword-only; 1 .. 16, with ``logprobs``; 0 = off): also the n most likely tokens of every step and their
+    log-probabilities under that same distribution (``db1_select_tokens_top``), the most likely first, ties to the lower id."""
     max_new_tokens: int = 30
     greedy: bool = True
     temperature: float = 1.0
@@ -54,9 +55,17 @@ class GenerationConfig:
     vocab_lo: int = 0
     vocab_hi: Optional[int] = None
     sync_every: int = 8
+    # keyword-only: it comes last in the constructor, after every argument a caller could pass by position before it existed; ``logprobs``
+    # stays the last of ``dataclasses.fields``
+    top_logprobs: int = field(default=0, kw_only=True)
     logprobs: bool = False
 
     def __post_init__(self):
+        n = self.top_logprobs
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= ops.MAX_TOP_N:
+            raise ValueError(f"top_logprobs {n!r} must be an integer in [0, {ops.MAX_TOP_N}]")
+        if int(n) and not self.logprobs:
+            raise ValueError(f"top_logprobs {n} needs logprobs=True")
         if int(self.max_new_tokens) < 1:
             raise ValueError(f"max_new_tokens {self.max_new_tokens} must be >= 1")
         if not self.greedy and not (0.0 < float(self.temperature) < float("inf")):
@@ -336,7 +345,8 @@ def _ring_ok(model) -> bool:
 class _SamplingState:
     """what the two sampling states (``_State``, serving's ``_SlotState``) share: the per-row flags, stream ids and output, all zero / pad_id,
     and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``; with ``cfg.logprobs`` also the tokens'
-    log-probs ``logprob`` [M, max_new_tokens] and their per-row sum ``sum_logprob`` (None otherwise: the plain entry point is called)"""
+    log-probs ``logprob`` [M, max_new_tokens] and their per-row sum ``sum_logprob`` (None otherwise: the plain entry point is called); with
+    ``cfg.top_logprobs`` n also the alternatives ``top_ids`` / ``top_logprob`` [M, max_new_tokens, n], -1 / -inf where nothing was written"""
     expand = None
 
     def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
@@ -352,6 +362,22 @@ class _SamplingState:
             self.logprob = torch.zeros(M, cfg.max_new_tokens, dtype=torch.float32, device=model.dev)
             self.sum_logprob = torch.zeros(M, dtype=torch.float32, device=model.dev)
             self.sel.update(logprob=self.logprob, sum_logprob=self.sum_logprob)
+        self.top_ids = self.top_logprob = None
+        if cfg.top_logprobs:
+            n = int(cfg.top_logprobs)
+            self.top_ids = torch.full((M, cfg.max_new_tokens, n), -1, **i32)
+            self.top_logprob = torch.full((M, cfg.max_new_tokens, n), float("-inf"), dtype=torch.float32, device=model.dev)
+            self.sel.update(top_n=n, top_ids=self.top_ids, top_logprob=self.top_logprob)
+
+    def clear_top(self, idx=None):
+        """-1 / -inf into the alternatives of every row (``idx``: int64 device vector, of those rows): nothing written yet"""
+        if self.top_ids is not None:
+            if idx is None:
+                self.top_ids.fill_(-1)
+                self.top_logprob.fill_(float("-inf"))
+            else:
+                self.top_ids.index_fill_(0, idx, -1)
+                self.top_logprob.index_fill_(0, idx, float("-inf"))
 
     def constrain(self, logits2d, row_map=None):
         """the decoding constraints, in place on the step's logits, over every row's own output so far (no constraints: no launch)"""
@@ -375,6 +401,7 @@ class _State(_SamplingState):
         if self.logprob is not None:
             self.logprob.zero_()
             self.sum_logprob.zero_()
+        self.clear_top()
         if stream_ids is None:
             self.stream_id.copy_(torch.arange(self.M, dtype=torch.int32))
         else:
@@ -403,7 +430,8 @@ class _State(_SamplingState):
         if (status & 2).any():
             raise RuntimeError("db1_select_tokens: the token counter left [0, max_new_tokens)")
         if self.logprob is not None:
-            return out, lengths, self.logprob.cpu(), self.sum_logprob.cpu()
+            top = () if self.top_ids is None else (self.top_ids.cpu(), self.top_logprob.cpu())
+            return (out, lengths, self.logprob.cpu(), self.sum_logprob.cpu()) + top
         return out, lengths
 
     def stats(self) -> dict:
@@ -597,7 +625,10 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     on the device, over the tokens generated so far, before the token is chosen.  With ``config.logprobs``: (ids, lengths, logprobs float32
     [M, max_new_tokens], sum_logprob float32 [M]) -- ``logprobs[r, t]`` is the log-probability of ``ids[r, t]`` under the model's
     distribution over the window (after the constraints, before temperature / top-k / top-p), EOS included, 0 after it; ``sum_logprob[r]``
-    their fp32 sum in token order."""
+    their fp32 sum in token order.  With ``config.top_logprobs`` n two more: top_ids int32 and top_logprobs float32, both
+    [M, max_new_tokens, n] -- the n most likely tokens of step t under that same distribution, the most likely first (ties: the lower id),
+    and their log-probabilities; -1 / -inf where the step had fewer candidates and at every position after a row's last written token
+    (where ``logprobs`` holds 0).  Greedy: ``top_ids[r, t, 0] == ids[r, t]``."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate")
     M = _batch_size(prompt)
@@ -723,6 +754,8 @@ def _check_best_of(cfg, n, num_return_sequences, length_penalty):
         raise TypeError(f"sample_best_of: GenerationConfig expected, got {type(cfg).__name__}")
     if cfg.greedy:
         raise ValueError("sample_best_of: a sampling config is needed (greedy=True gives n copies of one sequence)")
+    if cfg.top_logprobs:
+        raise ValueError("sample_best_of: top_logprobs is not supported (the ranking does not use the alternatives; use generate)")
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= MAX_BEST_OF:
         raise ValueError(f"sample_best_of: n {n!r} must be an integer in [1, {MAX_BEST_OF}]")
     R = num_return_sequences

@@ -610,19 +610,39 @@ def _check_logprobs(who, logprob, sum_logprob, rows, max_new, dev) -> bool:
     return True
 
 
+MAX_TOP_N = 16
+
+
+def _check_top(who, top_n, top_ids, top_logprob, shape, dev) -> int:
+    """the optional top-n outputs: all of ``top_n`` / ``top_ids`` / ``top_logprob`` unset (0: the entry point without them) or all given
+    (``top_n``, 1 .. 16): int32 and float32, contiguous, on ``dev``, of ``shape + (top_n,)``"""
+    if top_n is None and top_ids is None and top_logprob is None:
+        return 0
+    if top_n is None or top_ids is None or top_logprob is None:
+        raise ValueError(f"{who}: top_n, top_ids and top_logprob go together (one of them is None)")
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or not 1 <= int(top_n) <= MAX_TOP_N:
+        raise ValueError(f"{who}: top_n {top_n!r} must be an integer in [1, {MAX_TOP_N}]")
+    _check_tensor(who, "top_ids", top_ids, torch.int32, tuple(shape) + (int(top_n),), dev)
+    _check_tensor(who, "top_logprob", top_logprob, torch.float32, tuple(shape) + (int(top_n),), dev)
+    return int(top_n)
+
+
 def select_tokens_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
 
 
 def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True, temperature=1.0,
-                  top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, logprob=None, sum_logprob=None):
+                  top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, logprob=None, sum_logprob=None, top_n=None,
+                  top_ids=None, top_logprob=None):
     """one token per row of ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) on the device (db1_select_tokens): greedy, or
     Gumbel-max sampling at ``temperature`` after top-k / top-p, over the columns [vocab_lo, vocab_hi).  ``t`` (int32 [1], device): the token
     index within the generation, READ only; ``finished`` / ``lengths`` / ``status`` (int32 [M]) updated; the token goes to ``out`` [M, max_new]
     (int32) at column t and to ``next_ids`` (int64, [M] or a column of [M, q]: row stride taken from the tensor).  ``logprob`` (float32
     [M, max_new]) and ``sum_logprob`` (float32 [M]), both or neither: the chosen token's log-probability over the window goes to column t and is
-    added to the row's sum (db1_select_tokens_lp; the choice itself is bit-identical).  Capturable; raises ValueError on bad arguments before
-    anything is launched."""
+    added to the row's sum (db1_select_tokens_lp; the choice itself is bit-identical).  ``top_n`` (1 .. 16), ``top_ids`` (int32) and
+    ``top_logprob`` (float32), both [M, max_new, top_n], all or none and only with the log-prob outputs: the row's ``top_n`` most likely
+    tokens and their log-probabilities go to [row, t, :] (db1_select_tokens_top, rule in include/db1_hip.h; everything else is
+    bit-identical).  Capturable; raises ValueError on bad arguments before anything is launched."""
     who, dev, i32 = "select_tokens", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_supported(V, max(ld, V), logits2d.dtype))
@@ -633,11 +653,14 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
     _check_tensor(who, "out", out, i32, (M, -1), dev)
     _check_next_ids(who, next_ids, M, dev)
     lp = _check_logprobs(who, logprob, sum_logprob, M, out.shape[1], dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (M, out.shape[1]), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lib.call("db1_select_tokens_lp" if lp else "db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi,
+    lib.call("db1_select_tokens_top" if top else "db1_select_tokens_lp" if lp else "db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi,
              float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
              int(step_base), P(t), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status),
-             *((P(logprob), P(sum_logprob)) if lp else ()), _vp(0), 0, stream())
+             *((P(logprob), P(sum_logprob)) if lp else ()), *((top, P(top_ids), P(top_logprob)) if top else ()), _vp(0), 0, stream())
 
 
 def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
@@ -646,14 +669,15 @@ def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
 
 def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, status, *, V=None, vocab_lo=0, vocab_hi=None, greedy=True,
                         temperature=1.0, top_k=0, top_p=1.0, seed=0, eos_id=-1, pad_id=0, step_base=0, stream_id=None, row_map=None, logprob=None,
-                        sum_logprob=None):
+                        sum_logprob=None, top_n=None, top_ids=None, top_logprob=None):
     """``select_tokens`` over SLOTS (db1_select_tokens_slots): ``t`` and ``limit`` are int32 [S], one token counter and one token limit per
     slot; a live slot's token goes to ``out`` [S, max_new] at column t[slot], then the launch sets t[slot] += 1 and, at t[slot] == limit[slot],
     finished[slot].  A slot with finished != 0 is vacant: it only gets ``pad_id`` in ``next_ids``.  ``row_map`` (int32 [M], distinct slots) says
     which slot each row of ``logits2d`` [M, ld] belongs to; None: row i is slot i and S = M.  ``finished`` / ``lengths`` / ``status`` /
     ``stream_id`` are int32 [S], ``next_ids`` int64 ([S] or a column of [S, q]).  ``logprob`` (float32 [S, max_new]) and ``sum_logprob``
-    (float32 [S]), both or neither, as ``select_tokens`` takes them, indexed by the slot (db1_select_tokens_slots_lp).  Capturable; raises
-    ValueError on bad arguments before anything is launched."""
+    (float32 [S]), both or neither, as ``select_tokens`` takes them, indexed by the slot (db1_select_tokens_slots_lp); ``top_n``, ``top_ids``
+    and ``top_logprob`` ([S, max_new, top_n]) likewise (db1_select_tokens_slots_top).  Capturable; raises ValueError on bad arguments
+    before anything is launched."""
     who, dev, i32 = "select_tokens_slots", logits2d.device, torch.int32
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
@@ -669,11 +693,15 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
     _check_tensor(who, "out", out, i32, (S, -1), dev)
     _check_next_ids(who, next_ids, S, dev)
     lp = _check_logprobs(who, logprob, sum_logprob, S, out.shape[1], dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (S, out.shape[1]), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lib.call("db1_select_tokens_slots_lp" if lp else "db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo,
+    lib.call("db1_select_tokens_slots_top" if top else "db1_select_tokens_slots_lp" if lp else "db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo,
              vocab_hi, float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
              int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0),
-             P(status), P(row_map), S, *((P(logprob), P(sum_logprob)) if lp else ()), _vp(0), 0, stream())
+             P(status), P(row_map), S, *((P(logprob), P(sum_logprob)) if lp else ()), *((top, P(top_ids), P(top_logprob)) if top else ()), _vp(0), 0,
+             stream())
 
 
 def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype) -> bool:
@@ -850,23 +878,30 @@ def _check_score_outputs(who, T, dev, labels, lse, logprob, top1, rank, status):
         _check_tensor(who, name, x, dt, T, dev)
 
 
-def score_rows(logits2d, labels, lse, logprob, top1, rank, status, *, V=None, vocab_lo=0, vocab_hi=None):
+def score_rows(logits2d, labels, lse, logprob, top1, rank, status, *, V=None, vocab_lo=0, vocab_hi=None, top_n=None, top_ids=None,
+               top_logprob=None):
     """log-probability, arg-max and rank of ``labels`` (int64 [T]) under every row of ``logits2d`` [T, ld] (fp32 / bf16, the first V columns
     valid) over the columns [vocab_lo, vocab_hi) (db1_score_rows, rule in include/db1_hip.h): lse / logprob (float32 [T]) and top1 / rank /
-    status (int32 [T]) are written, the logits are only read.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    status (int32 [T]) are written, the logits are only read.  ``top_n`` (1 .. 16), ``top_ids`` (int32 [T, top_n]) and ``top_logprob``
+    (float32 [T, top_n]), all or none: every row's ``top_n`` best candidates and their log-probabilities (db1_score_rows_top; the other
+    outputs are bit-identical).  Capturable; raises ValueError on bad arguments before anything is launched."""
     T, ld, V, vocab_lo, vocab_hi = _check_logits("score_rows", logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: score_rows_supported(V, ld, logits2d.dtype))      # (ld itself, not max(ld, V))
     if T < 1 or logits2d.data_ptr() % 16:
         raise ValueError(f"score_rows: logits of shape {tuple(logits2d.shape)} at {logits2d.data_ptr():#x}: at least one row, 16-byte aligned")
     _check_score_outputs("score_rows", T, logits2d.device, labels, lse, logprob, top1, rank, status)
+    top = _check_top("score_rows", top_n, top_ids, top_logprob, (T,), logits2d.device)
     _timed("score_rows", float(T * V * logits2d.element_size()),
-           lambda: lib.call("db1_score_rows", P(logits2d), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, ld, dt_code(logits2d),
-                            vocab_lo, vocab_hi, stream()))
+           lambda: lib.call("db1_score_rows_top" if top else "db1_score_rows", P(logits2d), P(labels), P(lse), P(logprob), P(top1), P(rank),
+                            P(status), T, V, ld, dt_code(logits2d), *((top, P(top_ids), P(top_logprob)) if top else ()), vocab_lo, vocab_hi,
+                            stream()))
 
 
-def lmhead_score(h2d, W, labels, lse, logprob, top1, rank, status, *, V, vocab_lo=0, vocab_hi=None, chunk_rows=0):
+def lmhead_score(h2d, W, labels, lse, logprob, top1, rank, status, *, V, vocab_lo=0, vocab_hi=None, chunk_rows=0, top_n=None, top_ids=None,
+                 top_logprob=None):
     """``score_rows`` on the logits ``h2d`` [T, d] x ``W`` [rows >= V, d]^T, ``chunk_rows`` rows of logits at a time (0: 16 384) in the workspace
-    (db1_lmhead_score): the logits tensor never exists.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    (db1_lmhead_score): the logits tensor never exists.  ``top_n``, ``top_ids`` and ``top_logprob`` as ``score_rows`` takes them
+    (db1_lmhead_score_top).  Capturable; raises ValueError on bad arguments before anything is launched."""
     if h2d.dim() != 2 or W.dim() != 2 or not h2d.is_contiguous() or not W.is_contiguous() or W.shape[1] != h2d.shape[1]:
         raise ValueError("lmhead_score: h [T, d] and W [rows, d] must be contiguous 2-D tensors of one width")
     if h2d.dtype not in (torch.float32, torch.bfloat16) or W.dtype != h2d.dtype or W.device != h2d.device:
@@ -878,10 +913,12 @@ def lmhead_score(h2d, W, labels, lse, logprob, top1, rank, status, *, V, vocab_l
         raise ValueError(f"lmhead_score: chunk_rows {chunk_rows} must be >= 0")
     vocab_lo, vocab_hi = _check_window("lmhead_score", V, vocab_lo, vocab_hi)
     _check_score_outputs("lmhead_score", T, h2d.device, labels, lse, logprob, top1, rank, status)
+    top = _check_top("lmhead_score", top_n, top_ids, top_logprob, (T,), h2d.device)
     ws, wsn = _ws("db1_lmhead_score_workspace_bytes", (T, rows, d, chunk_rows, dt_code(h2d)), h2d.device)
     _timed("lmhead_score", 2.0 * T * V * d,
-           lambda: lib.call("db1_lmhead_score", P(h2d), P(W), P(labels), P(lse), P(logprob), P(top1), P(rank), P(status), T, V, rows, d, vocab_lo,
-                            vocab_hi, chunk_rows, dt_code(h2d), ws, wsn, stream()))
+           lambda: lib.call("db1_lmhead_score_top" if top else "db1_lmhead_score", P(h2d), P(W), P(labels), P(lse), P(logprob), P(top1), P(rank),
+                            P(status), T, V, rows, d, vocab_lo, vocab_hi, chunk_rows, dt_code(h2d),
+                            *((top, P(top_ids), P(top_logprob)) if top else ()), ws, wsn, stream()))
 
 
 def score_segments(logprob, rank, labels, mask, out, *, V):

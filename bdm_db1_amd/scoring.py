@@ -39,14 +39,19 @@ class ScoreConfig:
     """Labels are scored over the columns ``[vocab_lo, vocab_hi)`` (``vocab_hi`` None: the model's whole vocabulary, so that the loss is the
     training loss; ``rank_captions`` / ``rank_answers`` then take the text vocabulary).  ``length_penalty``: candidate scores are divided by
     length^length_penalty.  ``chunk_rows``: rows of logits alive at a time in the sweep (None: the library's 16 384).  ``return_tokens``
-    False: only the per-sequence sums are copied to the host."""
+    False: only the per-sequence sums are copied to the host.  ``top_n`` (1 .. 16; 0 = off, and nothing without ``return_tokens``): every
+    position's n most likely tokens and their log-probabilities come back too (``db1_lmhead_score_top``)."""
     vocab_lo: int = 0
     vocab_hi: Optional[int] = None
     length_penalty: float = 0.0
     chunk_rows: Optional[int] = None
     return_tokens: bool = True
+    top_n: int = 0
 
     def __post_init__(self):
+        n = self.top_n
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= ops.MAX_TOP_N:
+            raise ValueError(f"top_n {n!r} must be an integer in [0, {ops.MAX_TOP_N}]")
         if int(self.vocab_lo) < 0 or (self.vocab_hi is not None and int(self.vocab_hi) <= int(self.vocab_lo)):
             raise ValueError(f"vocabulary window [{self.vocab_lo}, {self.vocab_hi}) is empty")
         lp = float(self.length_penalty)
@@ -61,7 +66,9 @@ class ScoreResult:
     """Host-side results of ``score``.  Per task input i (``return_tokens``): ``logprob[i]`` float32, ``top1[i]`` / ``rank[i]`` int32, each
     ``[B_i, L_i]``.  Per sequence, in the order of the task inputs: ``sum_logprob`` (the mask-weighted sum of the log-probabilities),
     ``tokens`` (the sum of the mask), ``hits`` (the mask-weighted number of positions whose label is the arg-max or tied with it), all
-    float32, and ``task`` (int64: the index of the sequence's task input)."""
+    float32, and ``task`` (int64: the index of the sequence's task input).  With ``ScoreConfig.top_n`` n: ``top_ids[i]`` int32 and
+    ``top_logprob[i]`` float32, each ``[B_i, L_i, n]`` -- every position's n most likely tokens over the window, the most likely first
+    (ties: the lower id; -1 / -inf where the window has fewer candidates), whatever the label (ignored positions included); None when off."""
     sum_logprob: np.ndarray
     tokens: np.ndarray
     hits: np.ndarray
@@ -70,6 +77,8 @@ class ScoreResult:
     logprob: Optional[List[np.ndarray]] = None
     top1: Optional[List[np.ndarray]] = None
     rank: Optional[List[np.ndarray]] = None
+    top_ids: Optional[List[np.ndarray]] = None
+    top_logprob: Optional[List[np.ndarray]] = None
     status: int = 0        # OR of the status bits of the rows with mask != 0 (1: the label is no candidate, 2: the row has no candidate)
     stats: Dict[str, int] = field(default_factory=dict)
 
@@ -86,13 +95,20 @@ class _ScoreSink:
         self.cfg = cfg
         self.sweeps = 0
         self.out = None
+        self.top = None
 
     def run(self, model, x, Wout, lab, msk, shapes, V):
         cfg = self.cfg
         T, dev = x.shape[0], x.device
         lse, logprob, top1, rank, status = _score_buffers(T, dev)
+        top = {}
+        if cfg.top_n and cfg.return_tokens:
+            n = int(cfg.top_n)
+            top = dict(top_n=n, top_ids=torch.empty(T, n, dtype=torch.int32, device=dev),
+                       top_logprob=torch.empty(T, n, dtype=torch.float32, device=dev))
         ops.lmhead_score(x, Wout, lab, lse, logprob, top1, rank, status, V=V, vocab_lo=cfg.vocab_lo, vocab_hi=cfg.vocab_hi,
-                         chunk_rows=0 if cfg.chunk_rows is None else int(cfg.chunk_rows))
+                         chunk_rows=0 if cfg.chunk_rows is None else int(cfg.chunk_rows), **top)
+        self.top = (top["top_ids"], top["top_logprob"]) if top else None
         n_seq = sum(b for b, _ in shapes)
         seg = torch.empty(n_seq, 3, dtype=torch.float32, device=dev)
         ops.score_segments(logprob, rank, lab, msk, seg, V=V)
@@ -148,6 +164,13 @@ def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResu
             res.top1.append(t1[r0:r0 + b * l].reshape(b, l))
             res.rank.append(rk[r0:r0 + b * l].reshape(b, l))
             r0 += b * l
+        if sink.top is not None:
+            ti, tl = (x.cpu().numpy() for x in sink.top)
+            res.top_ids, res.top_logprob, r0 = [], [], 0
+            for b, l in shapes:
+                res.top_ids.append(ti[r0:r0 + b * l].reshape(b, l, -1))
+                res.top_logprob.append(tl[r0:r0 + b * l].reshape(b, l, -1))
+                r0 += b * l
     return res
 
 

@@ -203,6 +203,7 @@ class _SlotState(_SamplingState):
         if self.logprob is not None:         # (a new tenant does not inherit the last one's log-probs or their sum)
             self.logprob.index_fill_(0, idx, 0.0)
             self.sum_logprob.index_fill_(0, idx, 0.0)
+        self.clear_top(idx)
         self.limit.index_copy_(0, idx, torch.tensor(limits, dtype=torch.int32).to(self.dev))
         self.stream_id.index_copy_(0, idx, torch.from_numpy(np.asarray(stream_ids, dtype=np.int64).astype(np.int32)).to(self.dev))
         return idx.to(torch.int32)
@@ -215,11 +216,12 @@ class _SlotState(_SamplingState):
         self.select(logits2d, next_ids)      # (the launch advances every live slot's t itself)
 
     def read(self, slots: List[int]):
-        """(out rows, [t, length, status] rows, logprob rows or None) of ``slots`` on the host"""
+        """(out rows, [t, length, status] rows, logprob rows or None, (top_ids rows, top_logprob rows) or None) of ``slots`` on the host"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
         meta = torch.stack((self.t, self.lengths, self.status), 1).index_select(0, idx).cpu()
         lp = None if self.logprob is None else self.logprob.index_select(0, idx).cpu()
-        return self.out.index_select(0, idx).cpu(), meta, lp
+        top = None if self.top_ids is None else (self.top_ids.index_select(0, idx).cpu(), self.top_logprob.index_select(0, idx).cpu())
+        return self.out.index_select(0, idx).cpu(), meta, lp, top
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
@@ -243,7 +245,9 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     another is still running raises RuntimeError (run the first to its end or ``close()`` it).  ``constraints`` (a ``DecodingConstraints``):
     applied on the device to every step's logits over each request's own tokens so far, whatever slot it sits in; a request whose limit is
     below ``min_new_tokens`` raises ValueError.  With ``config.logprobs`` the stream yields ``(index, ids, length, logprobs float32 [limit])``:
-    every token's log-probability as ``generate`` returns it (EOS included, 0 after it)."""
+    every token's log-probability as ``generate`` returns it (EOS included, 0 after it); with ``config.top_logprobs`` n two more fields,
+    ``top_ids int32 [limit, n]`` and ``top_logprobs float32 [limit, n]``, as ``generate`` returns them (-1 / -inf after the request's last
+    token)."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -307,14 +311,15 @@ def _stream(model, reqs, key, stream_ids, stats, replay):
                 if not sched.idle():
                     done = sched.harvest(st.finished.cpu())          # (the host's look at the device)
                     if done:
-                        out, meta, lp = st.read([s for s, _ in done])
+                        out, meta, lp, top = st.read([s for s, _ in done])
                         for j, (_, r) in enumerate(done):
                             t, length, status = (int(v) for v in meta[j])
                             if status & 2:
                                 raise RuntimeError("db1_select_tokens_slots: a slot's token counter left [0, limit)")
                             counts["no_candidate"] += status & 1
                             live_steps += t - 1
-                            results.append((r.index, out[j, :r.limit].clone(), length) + (() if lp is None else (lp[j, :r.limit].clone(),)))
+                            results.append((r.index, out[j, :r.limit].clone(), length) + (() if lp is None else (lp[j, :r.limit].clone(),)) +
+                                           (() if top is None else (top[0][j, :r.limit].clone(), top[1][j, :r.limit].clone())))
                 finish = sched.idle() and not results
                 if finish:     # nothing waits (admit found no request for the free slots) and every slot is vacant
                     gen.check(replay)
@@ -332,11 +337,12 @@ def _stream(model, reqs, key, stream_ids, stats, replay):
 
 def generate_many(model, requests: Iterable, config: Optional[GenerationConfig] = None, **kw):
     """``generate_stream`` run to its end -> (ids, lengths) in request order: ``ids[i]`` int32 [request i's limit], ``lengths[i]`` an int;
-    with ``config.logprobs`` a third list: ``logprobs[i]`` float32 [request i's limit]"""
+    with ``config.logprobs`` a third list: ``logprobs[i]`` float32 [request i's limit]; with ``config.top_logprobs`` n two more:
+    ``top_ids[i]`` int32 and ``top_logprobs[i]`` float32, both [request i's limit, n]"""
     got = {r[0]: r[1:] for r in generate_stream(model, requests, config, **kw)}
     order = sorted(got)
     # as many lists as the stream's tuples have fields after the index; no request at all: what the config says they would have had
-    width = len(got[order[0]]) if order else (3 if config is not None and config.logprobs else 2)
+    width = len(got[order[0]]) if order else (2 if config is None or not config.logprobs else 5 if config.top_logprobs else 3)
     return tuple([got[i][k] for i in order] for k in range(width))
 
 

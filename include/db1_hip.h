@@ -566,6 +566,28 @@ int db1_select_tokens_lp(const void* logits, int M, int V, int64_t ld, int dt, i
                          float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
                          const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
                          int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, void* ws, int64_t ws_bytes, void* stream);
+/* The _top forms (db1_select_tokens_top, db1_select_tokens_slots_top) are the _lp forms -- every output of those comes out bit-identical
+ * on the same inputs -- and also say which tokens the model ranked highest at the step (tests/topn_rule.py restates the rule in NumPy).
+ * 1 <= top_n <= 16; top_ids (int32) and top_logprob (float32) are [rows | n_slots, max_new, top_n] (both required: a NULL one, or a top_n
+ * outside 1 .. 16, is DB1_ERR_BAD_SHAPE before any launch).  For a row that writes a token to out[row, t]:
+ *   - the candidates are those of lse above: the FINITE logits of the columns in [vocab_lo, vocab_hi) as the launch reads them (after
+ *     db1_constrain_logits: a banned token is never an alternative); temperature, top-k and top-p are NOT applied;
+ *   - the alternatives are the candidates sorted by logit descending, ties by the lower column -- the order of the greedy arg-max, whose
+ *     keys tell -0.0 (lower) from +0.0; entry i < k = min(top_n, #candidates) is top_ids[row, t, i] = the column c of the i-th and
+ *     top_logprob[row, t, i] = (l[c] - max) - log(sum exp(l - max)), the expression of lp with the same max and sum: the chosen token, when it
+ *     is among the alternatives, carries the bits of logprob[row, t]; top_logprob[row, t, 0 .. k) never increases; greedy: top_ids[row, t, 0]
+ *     is the token;
+ *   - the entries [k, top_n) are top_ids = -1 and top_logprob = -inf: fewer candidates than top_n, a row with no candidate (k = 0), and a
+ *     finished row of the lockstep form (the write that puts pad_id into out and 0 into logprob);
+ *   - t out of range, a vacant slot, a row_map entry outside [0, n_slots): neither buffer is touched, as for logprob.
+ * top_n rounds of one block-wide maximum over (key, ~column) pairs strictly below the last winner, on the keys the selection already holds in
+ * registers (round 0 is the arg-max the selection has reduced anyway); only the thread that held the last winner looks for its next pair.  No
+ * LDS beyond the selection's, no workspace, no atomics; the _supported and _workspace_bytes queries of the plain forms hold for these too. */
+int db1_select_tokens_top(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                          float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, const int32_t* t,
+                          const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids,
+                          int64_t ids_stride, int32_t* status, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                          float* top_logprob, void* ws, int64_t ws_bytes, void* stream);
 /* The slot form of db1_select_tokens (continuous batching: every row of a decode batch is a SLOT that requests pass through).  The
  * selection rule is db1_select_tokens' own, unchanged; the bookkeeping is per slot:
  *   - logits row i belongs to slot row_map[i] (int32 [M], distinct; NULL: slot i, and then n_slots == M).  t, limit, stream_id, finished,
@@ -592,6 +614,13 @@ int db1_select_tokens_slots_lp(const void* logits, int M, int V, int64_t ld, int
                                const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                                int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
                                float* sum_logprob, void* ws, int64_t ws_bytes, void* stream);
+/* db1_select_tokens_slots_lp with the alternatives of db1_select_tokens_top (the rule is stated there): top_ids and top_logprob
+ * [n_slots, max_new, top_n] at [slot, t[slot]], indexed by the SLOT. */
+int db1_select_tokens_slots_top(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                                float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int eos_id, int pad_id, int step_base, int32_t* t,
+                                const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
+                                int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
+                                float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ beam search (captions / answers / text; tests/beam_rule.py restates
  * the rule in NumPy).  G groups (prompts) of W beams (1 <= W <= 16), M = G * W rows, row b = g * W + j; step t = 0 .. max_new - 1 chooses
@@ -694,14 +723,30 @@ int db1_constrain_logits(void* logits, int M, int V, int64_t ld, int dt, const i
  * a time in the workspace (0: 16 384) with db1_score_rows on every chunk: the [T, n_w_rows] logits tensor never exists.
  * db1_score_segments: n_seg segments of seg_len consecutive rows -> out [n_seg, 3] (float) = {sum(mask * logprob), sum(mask),
  * sum(mask * (rank == 0))} over the rows with mask != 0 whose label lies in [0, V) (ignored rows count as mask 0), added in a fixed order.  A
- * counted row with logprob = -inf makes its segment's first sum -inf; nothing becomes NaN. */
+ * counted row with logprob = -inf makes its segment's first sum -inf; nothing becomes NaN.
+ * db1_score_rows_top / db1_lmhead_score_top: db1_score_rows / db1_lmhead_score -- lse, logprob, top1, rank and status come out bit-identical
+ * -- and the row's top_n best candidates (1 <= top_n <= 16; tests/topn_rule.py): top_ids (int32) and top_logprob (float32) are [T, top_n], both
+ * required.  The alternatives of a row are its candidates sorted by logit descending, ties by the lower column, -0.0 and +0.0 being one
+ * value as they are for top1 and rank; entry i < k = min(top_n, #candidates) holds the column c and l[c] - lse, the expression of logprob
+ * with the same lse; the entries [k, top_n) hold -1 and -inf (a row with no candidate: all of them).  They do not depend on the label: an
+ * ignored row gets what its logits give.  So top_ids[., 0] == top1; a label that is among the alternatives carries the bits of logprob; for
+ * a candidate label whose logit no other candidate shares, rank < top_n implies top_ids[., rank] == label; top_logprob[., 0 .. k) never
+ * increases.  A separate instantiation of the row kernel: after the sum pass the row's registers are rewritten as order-preserving keys
+ * and top_n rounds of one block-wide maximum each run over them (the rounds of db1_select_tokens_top); one launch per chunk as before, no
+ * workspace beyond db1_lmhead_score's (its _workspace_bytes and _supported queries hold), no atomics. */
 int db1_score_rows_supported(int V, int64_t ld, int dt);
 int db1_score_rows(const void* logits, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank, int32_t* status,
                    int64_t T, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, void* stream);
+int db1_score_rows_top(const void* logits, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank, int32_t* status,
+                       int64_t T, int V, int64_t ld, int dt, int top_n, int32_t* top_ids, float* top_logprob, int vocab_lo, int vocab_hi,
+                       void* stream);
 int64_t db1_lmhead_score_workspace_bytes(int64_t T, int n_w_rows, int d, int chunk_rows, int dt);
 int db1_lmhead_score(const void* h, const void* W, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank,
                      int32_t* status, int64_t T, int V, int n_w_rows, int d, int vocab_lo, int vocab_hi, int chunk_rows, int dt, void* ws,
                      int64_t ws_bytes, void* stream);
+int db1_lmhead_score_top(const void* h, const void* W, const int64_t* labels, float* lse, float* logprob, int32_t* top1, int32_t* rank,
+                         int32_t* status, int64_t T, int V, int n_w_rows, int d, int vocab_lo, int vocab_hi, int chunk_rows, int dt, int top_n,
+                         int32_t* top_ids, float* top_logprob, void* ws, int64_t ws_bytes, void* stream);
 int db1_score_segments(const float* logprob, const int32_t* rank, const int64_t* labels, const float* mask, float* out, int64_t n_seg,
                        int64_t seg_len, int V, void* stream);
 

@@ -41,6 +41,8 @@ the LP and the plain instantiation of select_tokens_kernel.
 
     python tools/bench_generate.py --logprobs [M ...]
     python tools/bench_generate.py --select-kernels greedy|top_p_0.9 [M]   (the two kernels alone in ONE mode: the run to trace)
+    python tools/bench_generate.py --logprobs --top-logprobs N [M ...]     (also ``top_logprobs=N``: the loop, its delta over logprobs=True,
+                                                                            and db1_select_tokens_top alone)
 
 With --best-of N the arguments are group counts G (default 16): sample_best_of (N samples per image, top-p 0.9, M = G * N rows) next to
 beam search with N beams over the same images, ms per token as above.
@@ -318,6 +320,10 @@ def select_kernels_us(M, modes=tuple(SELECT_MODES)):
         run = lambda **more: ops.select_tokens(logits, t, fin, n, out, ids, status, V=V, vocab_hi=hi, **kw, **more)
         rec[f"select_{name}_us"] = round(device_us(run), 2)
         rec[f"select_lp_{name}_us"] = round(device_us(lambda: run(logprob=lp, sum_logprob=sums)), 2)
+        if TOP_N:
+            ti, tl = torch.zeros(M, N_NEW, TOP_N, **i32), torch.zeros(M, N_NEW, TOP_N, device=dev)
+            rec[f"select_top{TOP_N}_{name}_us"] = round(device_us(lambda: run(logprob=lp, sum_logprob=sums, top_n=TOP_N, top_ids=ti,
+                                                                               top_logprob=tl)), 2)
     return rec
 
 
@@ -329,6 +335,10 @@ def logprobs_main(Ms):
             rec[f"{name}_ms_per_token"] = round(gen_ms_per_token(M, cfg), 4)
             rec[f"{name}_logprobs_ms_per_token"] = round(gen_ms_per_token(M, dataclasses.replace(cfg, logprobs=True)), 4)
             rec[f"{name}_logprobs_minus_plain_us"] = round((rec[f"{name}_logprobs_ms_per_token"] - rec[f"{name}_ms_per_token"]) * 1e3, 2)
+            if TOP_N:
+                key = f"{name}_top{TOP_N}_ms_per_token"
+                rec[key] = round(gen_ms_per_token(M, dataclasses.replace(cfg, logprobs=True, top_logprobs=TOP_N)), 4)
+                rec[f"{name}_top{TOP_N}_minus_logprobs_us"] = round((rec[key] - rec[f"{name}_logprobs_ms_per_token"]) * 1e3, 2)
         model._generator = None
         torch.cuda.empty_cache()
         rec.update(select_kernels_us(M))
@@ -350,6 +360,11 @@ def best_of_main(N, Gs):
 
 
 args = sys.argv[1:]
+TOP_N = None
+if "--top-logprobs" in args:
+    i = args.index("--top-logprobs")
+    TOP_N = int(args[i + 1])
+    args = args[:i] + args[i + 2:]
 if "--select-kernels" in args:
     i = args.index("--select-kernels")
     M = int((args[:i] + args[i + 2:] or [64])[0])
