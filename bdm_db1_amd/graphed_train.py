@@ -58,7 +58,7 @@ class GraphedTrainStep:
         for st in self.static:
             geo = self._vision_geometry(st)
             if geo is not None and getattr(st, "vision_row_ids", None) is None:
-                r, c = model._vision_position_ids(geo[1], geo[2], geo[0])
+                r, c = model.patch_embedder.position_ids(geo[1], geo[2], geo[0])
                 st.vision_row_ids, st.vision_col_ids = r.to(dev), c.to(dev)
                 self._vis.append((st, geo))
         self._fields = [_tensor_fields(t) for t in self.static]
@@ -155,7 +155,7 @@ class GraphedTrainStep:
                     dst.copy_(src, non_blocking=True)
         for st, geo in self._vis:
             if not any(getattr(t, "vision_row_ids", None) is not None for t in batch if self._vision_geometry(t) == geo):
-                r, c = model._vision_position_ids(geo[1], geo[2], geo[0])
+                r, c = model.patch_embedder.position_ids(geo[1], geo[2], geo[0])
                 st.vision_row_ids.copy_(r, non_blocking=True)
                 st.vision_col_ids.copy_(c, non_blocking=True)
         boundary = eng.is_gradient_accumulation_boundary()

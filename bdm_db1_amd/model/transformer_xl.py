@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from .. import lib, ops
+from .patch_embedder import PatchEmbedder, _round_up
 
 
 def print_with_rank(message):
@@ -42,10 +43,6 @@ class _Node(nn.Module):
 
     def forward(self, *a, **k):  # pragma: no cover
         raise RuntimeError("container module")
-
-
-def _round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
 
 
 class ParamArena:
@@ -326,10 +323,7 @@ class TransformerXL(nn.Module):
         self.use_geglu_epilogue = os.environ.get("DB1_GEGLU_EPI", "1") != "0"   # GEGLU and its backward inside the feed-forward GEMMs' epilogues (large bf16 batches)
         self.use_channels_last = True    # bf16 image-patch embedder in channels-last layout (False: the NCHW kernels of the fp32 path)
         self.use_implicit_conv = True    # 64 -> 64 channel convolutions without a column matrix (conv_implicit.hip)
-        self._conv_ops = {}              # (weight name, weight version) -> tap-major GEMM operand
-        self.use_conv1_fused = os.environ.get("DB1_CONV1_FUSED", "1") != "0"      # 3 -> 64 channel convolution as one streaming kernel
-        self.use_conv_res_epilogue = os.environ.get("DB1_CONV_RES", "1") != "0"   # residual sum of the patch block in the last convolution's epilogue
-        self.use_proj_cl = os.environ.get("DB1_PROJ_CL", "1") != "0"   # channels-last patch embedder: projection against a column-permuted weight copy (no activation shuffles)
+        self.patch_embedder = PatchEmbedder(self)   # the image-patch embedder of the vision encoder (reads the two switches above at call time)
         self.use_decode = True           # inference with memory: K/V-cached path + fused decode attention when the shape allows
         self.use_decode_fused = True     # ... and, for <= 64 new tokens, linear maps as W streams that finish with GEGLU (post-LN)
         self.use_decode_ln_prologue = True   # ... <= 16 tokens: the residual LayerNorms ride on the way IN to the next linear map
@@ -533,315 +527,9 @@ class TransformerXL(nn.Module):
             r = r.clone()    # (deferred backward: the ids are read at the window's boundary -- the caller may have refilled its tensor by then)
         return r
 
-    # ------------------------------------------------------------------ vision encoder (vision_embedding.py:65-180)
     def _vision_position_ids(self, h0: int, w0: int, n_img: int):
-        """eval: midpoint rule; train: uniform pick in [low, high) per (image, position) (vision_embedding.py:134-172)."""
-        vocab = self.vision_position_vocab_size
-        seq = torch.arange(h0 * w0)
-        row = torch.div(seq, w0, rounding_mode="trunc")
-        col = seq % w0
-        col_hi = ((col + 1) / w0 * vocab).to(torch.int32)
-        col_lo = (col / w0 * vocab).to(torch.int32)
-        row_hi = ((row + 1) / h0 * vocab).to(torch.int32)
-        row_lo = (row / h0 * vocab).to(torch.int32)
-        if self.training:
-            r = (torch.rand(n_img, h0 * w0) * (row_hi - row_lo) + row_lo).floor().to(torch.int64)
-            c = (torch.rand(n_img, h0 * w0) * (col_hi - col_lo) + col_lo).floor().to(torch.int64)
-        else:
-            r = ((row_lo + row_hi) / 2).int().to(torch.int64).unsqueeze(0).expand(n_img, -1)
-            c = ((col_lo + col_hi) / 2).int().to(torch.int64).unsqueeze(0).expand(n_img, -1)
-        return r.contiguous(), c.contiguous()
-
-    def _conv3x3_fwd(self, x_nchw, wname, bname, N, Cin):
-        """per-patch 3x3 conv as im2col + GEMM; returns NHWC output [N*256, 64] and the column matrix"""
-        hw = self.patch_size * self.patch_size
-        K = Cin * 9
-        Kp = _round_up(K, 8)  # conv1: 27 -> 32 zero-padded columns so its weight gradient can use the MFMA tile kernel (split-K)
-        cols = self._new(N * hw, Kp)
-        ops.im2col3x3(x_nchw, cols, N, Cin, self.patch_size)
-        out = self._new(N * hw, 64)
-        ops.gemm(cols, self._conv_weight(wname, K, Kp).t(), out, bias=self.W(bname))
-        return out, cols
-
-    def _conv_weight(self, wname, K, Kp):
-        """[64, Kp] view of a 3x3 conv weight in the compute dtype (zero-padded copy when Cin*9 is not a multiple of 8)"""
-        w = self.W(wname).view(64, K)
-        if Kp == K:
-            return w
-        wp = torch.zeros(64, Kp, device=self.dev, dtype=self.compute_dtype)
-        ops.add2d(w, wp[:, :K], wp[:, :K])
-        return wp
-
-    # ---- channels-last pipeline (bf16, 16x16 patches): activations [N, 256, 64], tap-major column matrices, no layout shuffles
-    # between the convolutions (vision.hip).  The fp32 parity path below keeps the reference's NCHW order end to end.
-    def _conv_operand_cl(self, wname, Cin):
-        """GEMM operand [64, kpad] (tap-major columns, zero padded to a multiple of 8) of a 3x3 conv weight, per weight version"""
-        if self._graph_static:   # captured training step: the permuted copy is rebuilt by every replay, always into the same buffer
-            key = (wname, "static")
-            if key not in self._conv_ops:
-                self._conv_ops[key] = torch.empty(64, _round_up(9 * Cin, 8), device=self.dev, dtype=self.compute_dtype)
-            ops.conv_weight_permute(self.W(wname), self._conv_ops[key], 64, Cin)
-            return self._conv_ops[key]
-        key = (wname, self._wversion)
-        if key not in self._conv_ops:
-            self._conv_ops = {k: v for k, v in self._conv_ops.items() if k[1] in (self._wversion, "static")}
-            wp = torch.empty(64, _round_up(9 * Cin, 8), device=self.dev, dtype=self.compute_dtype)
-            ops.conv_weight_permute(self.W(wname), wp, 64, Cin)
-            self._conv_ops[key] = wp
-        return self._conv_ops[key]
-
-    def _proj_operand_cl(self):
-        """the patch projection weight [d, 64 * hw] with its columns in (pixel, channel) order, per weight version: the channels-last
-        convolution output [N * hw, 64] IS [N, hw * 64], so the projection (and its data gradient) needs no layout shuffle of the
-        activations -- a 67 MB copy of the weight per optimizer step instead of two passes over [N, 16 384] per batch"""
-        wname = "vision_encoder.patch_embeddings.projection.weight"
-        hw, d = self.patch_size * self.patch_size, self.d_model
-        if self._graph_static:
-            key = (wname + "^cl", "static")
-            if key not in self._conv_ops:
-                self._conv_ops[key] = torch.empty(d, hw * 64, device=self.dev, dtype=self.compute_dtype)
-            ops.nchw_to_nhwc(self.W(wname), self._conv_ops[key], d, 64, hw)
-            return self._conv_ops[key]
-        key = (wname + "^cl", self._wversion)
-        if key not in self._conv_ops:
-            self._conv_ops = {k: v for k, v in self._conv_ops.items() if k[1] in (self._wversion, "static")}
-            wp = torch.empty(d, hw * 64, device=self.dev, dtype=self.compute_dtype)
-            ops.nchw_to_nhwc(self.W(wname), wp, d, 64, hw)
-            self._conv_ops[key] = wp
-        return self._conv_ops[key]
-
-    def _conv_operand_t_cl(self, wname):
-        """data-gradient operand [c_in, tap*64 + c_out] of a 64 -> 64 conv weight, per weight version"""
-        if self._graph_static:
-            key = (wname + "^T", "static")
-            if key not in self._conv_ops:
-                self._conv_ops[key] = torch.empty(64, 576, device=self.dev, dtype=self.compute_dtype)
-            ops.conv_weight_permute_t(self.W(wname), self._conv_ops[key], 64, 64)
-            return self._conv_ops[key]
-        key = (wname + "^T", self._wversion)
-        if key not in self._conv_ops:
-            wt = torch.empty(64, 576, device=self.dev, dtype=self.compute_dtype)
-            ops.conv_weight_permute_t(self.W(wname), wt, 64, 64)
-            self._conv_ops[key] = wt
-        return self._conv_ops[key]
-
-    def _conv3x3_fwd_cl(self, x_cl, wname, bname, N, Cin, out=None, res=None):
-        """returns (output [N*256, 64], what the backward needs: the input itself for the implicit 64-channel convs, else the
-        column matrix); ``out`` / ``res``: write into this buffer / add this residual in the epilogue (implicit convolutions only)"""
-        hw = self.patch_size * self.patch_size
-        wp = self._conv_operand_cl(wname, Cin)
-        if Cin == 64 and self.use_implicit_conv:  # implicit GEMM: the shifted pixels are gathered by the LDS-DMA, no column matrix
-            out = self._new(N * hw, 64) if out is None else out
-            ops.conv3x3_implicit_fwd(x_cl, wp, self.W(bname), out, N, sign=1, res=res)
-            return out, x_cl
-        assert out is None and res is None
-        out = self._new(N * hw, 64)
-        if Cin == 3 and wp.shape[1] == 32 and hw == 256 and self.use_conv1_fused:   # one streaming kernel: column matrix + convolution
-            cols = self._new(N * hw, 32)
-            ops.conv1_fused_fwd(x_cl, wp, self.W(bname), cols, out, N)
-            return out, cols
-        cols = self._new(N * hw, wp.shape[1])
-        ops.im2col3x3_nhwc(x_cl, cols, N, Cin, self.patch_size)
-        ops.gemm(cols, wp.t(), out, bias=self.W(bname))
-        return out, cols
-
-    def _conv3x3_bwd_cl(self, dy, cols, wname, bname, N, Cin, need_dx):
-        wp = self._conv_operand_cl(wname, Cin)
-        gp = torch.zeros(64, wp.shape[1], device=self.dev, dtype=torch.float32)
-        implicit = Cin == 64 and cols.shape[1] == 64  # `cols` is the conv input
-        if implicit:   # (the bias gradient -- column sums of dy -- comes out of the same kernel)
-            ops.conv3x3_implicit_wgrad(dy, cols, gp, N, gbias_acc=self.G(bname))
-        else:
-            ops.gemm(dy.t(), cols, gp, beta=1.0)
-            ops.colsum_acc(dy, self.G(bname))
-        ops.conv_wgrad_unpermute(gp, self.G(wname), 64, Cin)
-        if not need_dx:
-            return None
-        if implicit:
-            dx = self._new(N * self.patch_size * self.patch_size, Cin)
-            ops.conv3x3_implicit_fwd(dy, self._conv_operand_t_cl(wname), None, dx, N, sign=-1)
-            return dx
-        dcols = self._new(cols.shape[0], wp.shape[1])
-        ops.gemm(dy, wp, dcols)
-        dx = self._new(N * self.patch_size * self.patch_size, Cin)
-        ops.col2im3x3_nhwc(dcols, dx, N, Cin, self.patch_size)
-        return dx
-
-    def _vision_fwd_cl(self, pixels, c, n_img, C, Hh, Ww):
-        p, d = self.patch_size, self.d_model
-        hw = p * p
-        N = n_img * (Hh // p) * (Ww // p)
-        pe = "vision_encoder.patch_embeddings."
-        patches = self._new(N * hw, C)
-        ops.patch_normalize_nhwc(pixels, patches, p)
-        c.c1, c.cols1 = self._conv3x3_fwd_cl(patches, pe + "conv1.weight", pe + "conv1.bias", N, C)
-        a0 = self._new(N * hw, 64)
-        c.m0, c.r0 = self._new(N * 32, dtype=torch.float32), self._new(N * 32, dtype=torch.float32)
-        ops.groupnorm_gelu_nhwc_fwd(c.c1, self.W(pe + "residual_path.0.weight"), self.W(pe + "residual_path.0.bias"), a0, c.m0, c.r0, N, 64, hw)
-        c.c2, c.cols2 = self._conv3x3_fwd_cl(a0, pe + "residual_path.2.weight", pe + "residual_path.2.bias", N, 64)
-        a1 = self._new(N * hw, 64)
-        c.m1, c.r1 = self._new(N * 32, dtype=torch.float32), self._new(N * 32, dtype=torch.float32)
-        ops.groupnorm_gelu_nhwc_fwd(c.c2, self.W(pe + "residual_path.3.weight"), self.W(pe + "residual_path.3.bias"), a1, c.m1, c.r1, N, 64, hw)
-        if self.use_proj_cl and self.use_implicit_conv and self.use_conv_res_epilogue:
-            # the last convolution adds the residual in its epilogue and writes straight into the projection's (row-padded) operand
-            Np = _round_up(N, 256) if N >= 512 else N
-            ypad = self._new(Np * hw, 64)
-            _, c.cols3 = self._conv3x3_fwd_cl(a1, pe + "residual_path.5.weight", pe + "residual_path.5.bias", N, 64, out=ypad[:N * hw], res=c.c1)
-            if Np > N:
-                ypad[N * hw:].zero_()
-            c.y, c.y_cl, c.Np = ypad.view(Np, hw * 64), True, Np
-            emb_pad = self._new(Np, d)
-            ops.gemm(c.y, self._proj_operand_cl().t(), emb_pad, bias=self.W(pe + "projection.bias"))
-            return emb_pad[:N], N
-        c3, c.cols3 = self._conv3x3_fwd_cl(a1, pe + "residual_path.5.weight", pe + "residual_path.5.bias", N, 64)
-        if self.use_proj_cl:
-            # (y, x, c) flattening against the column-permuted projection weight.  The patch count of a mixed batch is whatever the data gives
-            # (4116, 20 680 ...): rows are padded with zeros to a multiple of 256 so that the K = 16 384 projection and its two gradients take
-            # the 256 x 256 kernels (the 128-tile / generic kernels ran them at 0.24 PFLOP/s) -- the residual add writes into the padded buffer
-            Np = _round_up(N, 256) if N >= 512 else N
-            ypad = self._new(Np * hw, 64)
-            ops.add(c.c1, c3, ypad[:N * hw])                   # residual
-            if Np > N:
-                ypad[N * hw:].zero_()
-            c.y, c.y_cl, c.Np = ypad.view(Np, hw * 64), True, Np
-            emb_pad = self._new(Np, d)
-            ops.gemm(c.y, self._proj_operand_cl().t(), emb_pad, bias=self.W(pe + "projection.bias"))
-            return emb_pad[:N], N
-        ops.add(c.c1, c3, c3)                                  # residual
-        emb = self._new(N, d)
-        c.y, c.y_cl = self._new(N, 64 * hw), False             # (c, y, x) flattening = the projection weight's layout
-        ops.nhwc_to_nchw(c3, c.y, N, 64, hw)
-        ops.gemm(c.y, self.W(pe + "projection.weight").view(d, 64 * hw).t(), emb, bias=self.W(pe + "projection.bias"))
-        return emb, N
-
-    def _vision_bwd_cl(self, dy_cl, c, N):
-        """dy_cl [N*256, 64]: gradient w.r.t. the residual sum, channels-last"""
-        pe = "vision_encoder.patch_embeddings."
-        hw = self.patch_size * self.patch_size
-        da1 = self._conv3x3_bwd_cl(dy_cl, c.cols3, pe + "residual_path.5.weight", pe + "residual_path.5.bias", N, 64, True)
-        dc2 = self._new(N * hw, 64)
-        ops.groupnorm_gelu_nhwc_bwd(da1, c.c2, self.W(pe + "residual_path.3.weight"), self.W(pe + "residual_path.3.bias"), c.m1, c.r1, dc2,
-                                    self.G(pe + "residual_path.3.weight"), self.G(pe + "residual_path.3.bias"), N, 64, hw)
-        da0 = self._conv3x3_bwd_cl(dc2, c.cols2, pe + "residual_path.2.weight", pe + "residual_path.2.bias", N, 64, True)
-        dc1 = self._new(N * hw, 64)
-        ops.groupnorm_gelu_nhwc_bwd(da0, c.c1, self.W(pe + "residual_path.0.weight"), self.W(pe + "residual_path.0.bias"), c.m0, c.r0, dc1,
-                                    self.G(pe + "residual_path.0.weight"), self.G(pe + "residual_path.0.bias"), N, 64, hw,
-                                    res=dy_cl.view(N * hw, 64))    # + the residual branch's gradient, in the same pass
-        self._conv3x3_bwd_cl(dc1, c.cols1, pe + "conv1.weight", pe + "conv1.bias", N, c.C, False)
-
-    def _vision_fwd(self, pixels: torch.Tensor, row_ids=None, col_ids=None):
-        pixels = pixels.to(device=self.dev, dtype=torch.float32).contiguous()
-        n_img, C, Hh, Ww = pixels.shape
-        p, d = self.patch_size, self.d_model
-        hw = p * p
-        h0, w0 = Hh // p, Ww // p
-        N = n_img * h0 * w0
-        pe = "vision_encoder.patch_embeddings."
-        c = _Ctx()
-        c.cl = self.compute_dtype == torch.bfloat16 and hw == 256 and self.use_channels_last
-        if c.cl:
-            emb, N = self._vision_fwd_cl(pixels, c, n_img, C, Hh, Ww)
-            return self._vision_finish(emb, c, N, C, n_img, h0, w0, row_ids, col_ids)
-        patches = self._new(N, C, p, p)
-        ops.patch_normalize(pixels, patches, p)
-        c1, c.cols1 = self._conv3x3_fwd(patches, pe + "conv1.weight", pe + "conv1.bias", N, C)
-        c.c1n = self._new(N, 64, hw)
-        ops.nhwc_to_nchw(c1, c.c1n, N, 64, hw)
-        a0 = self._new(N, 64, hw)
-        c.m0, c.r0 = self._new(N * 32, dtype=torch.float32), self._new(N * 32, dtype=torch.float32)
-        ops.groupnorm_gelu_fwd(c.c1n, self.W(pe + "residual_path.0.weight"), self.W(pe + "residual_path.0.bias"), a0, c.m0, c.r0, N, 64, hw)
-        c2, c.cols2 = self._conv3x3_fwd(a0, pe + "residual_path.2.weight", pe + "residual_path.2.bias", N, 64)
-        c.c2n = self._new(N, 64, hw)
-        ops.nhwc_to_nchw(c2, c.c2n, N, 64, hw)
-        a1 = self._new(N, 64, hw)
-        c.m1, c.r1 = self._new(N * 32, dtype=torch.float32), self._new(N * 32, dtype=torch.float32)
-        ops.groupnorm_gelu_fwd(c.c2n, self.W(pe + "residual_path.3.weight"), self.W(pe + "residual_path.3.bias"), a1, c.m1, c.r1, N, 64, hw)
-        c3, c.cols3 = self._conv3x3_fwd(a1, pe + "residual_path.5.weight", pe + "residual_path.5.bias", N, 64)
-        ops.add(c1, c3, c3)                                   # residual (NHWC)
-        c.y = self._new(N, 64 * hw)                            # NCHW flatten = projection weight layout
-        ops.nhwc_to_nchw(c3, c.y, N, 64, hw)
-        emb = self._new(N, d)
-        ops.gemm(c.y, self.W(pe + "projection.weight").view(d, 64 * hw).t(), emb, bias=self.W(pe + "projection.bias"))
-        return self._vision_finish(emb, c, N, C, n_img, h0, w0, row_ids, col_ids)
-
-    def _vision_finish(self, emb, c, N, C, n_img, h0, w0, row_ids, col_ids):
-        d = self.d_model
-        if row_ids is None:
-            row_ids, col_ids = self._vision_position_ids(h0, w0, n_img)
-        c.row_ids, c.col_ids = self._dev_ids(row_ids).reshape(-1), self._dev_ids(col_ids).reshape(-1)
-        assert c.row_ids.numel() == N
-        # emb += row_position_embeddings[row_ids] + col_position_embeddings[col_ids] (vision_embedding.py:170-178) in one pass over emb
-        ops.vision_pos_add(emb.view(N, d), self.W("vision_encoder.row_position_embeddings.weight"), self.W("vision_encoder.col_position_embeddings.weight"),
-                           c.row_ids, c.col_ids)
-        c.N, c.C, c.n_img = N, C, n_img
-        return emb.view(n_img, h0 * w0, d), c
-
-    def _conv3x3_bwd(self, dy_nhwc, cols, wname, bname, N, Cin, need_dx):
-        K, Kp = Cin * 9, cols.shape[1]
-        if Kp == K:
-            ops.gemm(dy_nhwc.t(), cols, self.G(wname).view(64, K), beta=1.0)
-        else:  # padded columns: reduce into a [64, Kp] float32 scratch, then add its first K columns to the gradient
-            gp = torch.zeros(64, Kp, device=self.dev, dtype=torch.float32)
-            ops.gemm(dy_nhwc.t(), cols, gp, beta=1.0)
-            g = self.G(wname).view(64, K)
-            ops.add2d(gp[:, :K], g, g)
-        ops.colsum_acc(dy_nhwc, self.G(bname))
-        if not need_dx:
-            return None
-        dcols = self._new(cols.shape[0], Kp)
-        ops.gemm(dy_nhwc, self._conv_weight(wname, K, Kp), dcols)
-        dx = self._new(N, Cin, self.patch_size * self.patch_size)
-        ops.col2im3x3(dcols, dx, N, Cin, self.patch_size)
-        return dx
-
-    def _vision_bwd(self, demb: torch.Tensor, c: _Ctx):
-        """demb [N, d] (compute dtype, contiguous)"""
-        p, d = self.patch_size, self.d_model
-        hw, N = p * p, c.N
-        pe = "vision_encoder.patch_embeddings."
-        ops.embed_scatter_add(demb, c.row_ids, self.G("vision_encoder.row_position_embeddings.weight"))
-        ops.embed_scatter_add(demb, c.col_ids, self.G("vision_encoder.col_position_embeddings.weight"))
-        if c.cl and getattr(c, "y_cl", False):
-            # the weight gradient comes out with (pixel, channel) columns: shuffled back per weight row and added (fp32, two passes over 134 MB),
-            # the data gradient [N, hw * 64] is channels-last already
-            Np = c.Np
-            dpad = demb
-            if Np > N:                                             # zero rows for the padded patches
-                dpad = self._new(Np, d)
-                dpad[:N].copy_(demb)
-                dpad[N:].zero_()
-            gp = torch.empty(d, hw * 64, device=self.dev, dtype=torch.float32)
-            ops.gemm(dpad.t(), c.y, gp)
-            gpt = torch.empty(d, 64 * hw, device=self.dev, dtype=torch.float32)
-            ops.nhwc_to_nchw(gp, gpt, d, 64, hw)
-            gw = self.G(pe + "projection.weight").view(d, 64 * hw)
-            ops.add(gpt, gw, gw)
-            ops.colsum_acc(demb, self.G(pe + "projection.bias"))
-            dy_nhwc = self._new(Np * hw, 64)
-            ops.gemm(dpad, self._proj_operand_cl(), dy_nhwc.view(Np, hw * 64))
-            return self._vision_bwd_cl(dy_nhwc[:N * hw], c, N)
-        ops.gemm(demb.t(), c.y, self.G(pe + "projection.weight").view(d, 64 * hw), beta=1.0)
-        ops.colsum_acc(demb, self.G(pe + "projection.bias"))
-        dy = self._new(N, 64 * hw)
-        ops.gemm(demb, self.W(pe + "projection.weight").view(d, 64 * hw), dy)
-        dy_nhwc = self._new(N * hw, 64)
-        ops.nchw_to_nhwc(dy, dy_nhwc, N, 64, hw)
-        if c.cl:
-            return self._vision_bwd_cl(dy_nhwc, c, N)
-        da1 = self._conv3x3_bwd(dy_nhwc, c.cols3, pe + "residual_path.5.weight", pe + "residual_path.5.bias", N, 64, True)
-        dc2n = self._new(N, 64, hw)
-        ops.groupnorm_gelu_bwd(da1, c.c2n, self.W(pe + "residual_path.3.weight"), self.W(pe + "residual_path.3.bias"), c.m1, c.r1, dc2n,
-                               self.G(pe + "residual_path.3.weight"), self.G(pe + "residual_path.3.bias"), N, 64, hw)
-        dc2 = self._new(N * hw, 64)
-        ops.nchw_to_nhwc(dc2n, dc2, N, 64, hw)
-        da0 = self._conv3x3_bwd(dc2, c.cols2, pe + "residual_path.2.weight", pe + "residual_path.2.bias", N, 64, True)
-        dc1n = self._new(N, 64, hw)
-        ops.groupnorm_gelu_bwd(da0, c.c1n, self.W(pe + "residual_path.0.weight"), self.W(pe + "residual_path.0.bias"), c.m0, c.r0, dc1n,
-                               self.G(pe + "residual_path.0.weight"), self.G(pe + "residual_path.0.bias"), N, 64, hw)
-        dc1 = self._new(N * hw, 64)
-        ops.nchw_to_nhwc(dc1n, dc1, N, 64, hw)
-        ops.add(dc1, dy_nhwc, dc1)                             # residual branch
-        self._conv3x3_bwd(dc1, c.cols1, pe + "conv1.weight", pe + "conv1.bias", N, c.C, False)
+        """the name callers outside the package know (PatchEmbedder.position_ids)"""
+        return self.patch_embedder.position_ids(h0, w0, n_img)
 
     # ------------------------------------------------------------------ per-modality embedding (transformer_xl.py:621-748)
     def _embed_task(self, task, compute_loss: bool):
@@ -864,7 +552,7 @@ class TransformerXL(nn.Module):
             if task.vision_seq is not None:
                 img = task.vision_seq
                 img = img.reshape(-1, *img.shape[-3:])
-                v, c.vis = self._vision_fwd(img, getattr(task, "vision_row_ids", None), getattr(task, "vision_col_ids", None))
+                v, c.vis = self.patch_embedder.forward(img, getattr(task, "vision_row_ids", None), getattr(task, "vision_col_ids", None))
                 vis = v.reshape(B, -1, d).contiguous()
                 c.vis_shape = vis.shape
             rl_label = None
@@ -876,7 +564,7 @@ class TransformerXL(nn.Module):
             c.ids, c.pos = ids, pos
         elif kind in ("ICTaskInput", "VQATaskInput"):
             prompt, text = self._dev_ids(task.prompt_seq), self._dev_ids(task.text_seq)
-            v, c.vis = self._vision_fwd(task.img_seq, getattr(task, "vision_row_ids", None), getattr(task, "vision_col_ids", None))
+            v, c.vis = self.patch_embedder.forward(task.img_seq, getattr(task, "vision_row_ids", None), getattr(task, "vision_col_ids", None))
             B, P_, nv, Tt = prompt.shape[0], prompt.shape[1], v.shape[1], text.shape[1]
             L = P_ + nv + Tt
             emb = self._new(B, L, d)
@@ -910,13 +598,13 @@ class TransformerXL(nn.Module):
                 dvis = self._new(*c.vis_shape) if hasattr(c, "vis") else None
                 ops.rl_assemble_bwd(de.contiguous(), c.ids, c.pos, gE, self.G("rl_local_timestep_embedding.weight"), dvis)
                 if dvis is not None:
-                    self._vision_bwd(dvis.view(-1, d), c.vis)
+                    self.patch_embedder.backward(dvis.view(-1, d), c.vis)
             else:
                 P_, nv = c.prompt.shape[1], c.nv
                 for b in range(B):
                     ops.embed_scatter_add(de[b, :P_], c.prompt[b], gE)
                     ops.embed_scatter_add(de[b, P_ + nv:], c.text[b], gE)
-                self._vision_bwd(de[:, P_:P_ + nv].contiguous().view(-1, d), c.vis)
+                self.patch_embedder.backward(de[:, P_:P_ + nv].contiguous().view(-1, d), c.vis)
 
     # ------------------------------------------------------------------ attention
     def _bias(self, name: str, i: int) -> torch.Tensor:
