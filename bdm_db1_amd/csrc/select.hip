@@ -64,6 +64,7 @@ struct SelArgs {
     int top_n;                  // the _top forms (TOP): [rows | n_slots, max_new, top_n] each; 0 and NULL otherwise
     int* top_ids;
     float* top_logprob;
+    const int* params;          // the per-slot form (PER, db1_select_tokens_slots_per): [n_slots, 8], the record of include/db1_hip.h; NULL otherwise
 };
 
 // the unused entries [from, top_n) of one (row, t) of the _top buffers: -1 / -inf
@@ -80,12 +81,20 @@ __device__ __forceinline__ void sel_top_fill(const SelArgs& a, int64_t at, int f
 // row's candidates (the raw logits: no temperature, no top-k / top-p) and the owner of the row writes the token's log-probability next to it.
 // TOP (db1_select_tokens_top, db1_select_tokens_slots_top; LP as well): after that, top_n rounds over the same keys (sel_top_rounds) give the
 // row's best candidates in the arg-max's own order, and the owner of the row writes their columns and (l - max) - lz, the token's expression.
-template <typename T, int NG, bool SLOTS, bool LP, bool TOP>
+// PER (db1_select_tokens_slots_per; SLOTS only, with or without LP / TOP): the window, greedy, top-k, top-p, 1 / temperature and the seed are
+// the slot's own, eight block-uniform words read from params[slot] once the slot is known to be live and its counter in range; a record no
+// launch would have accepted as scalars closes the slot with status bit 2 the way a counter out of range closes it with bit 1.  The other
+// instantiations take the same values from SelArgs and hold no trace of this mode.
+template <typename T, int NG, bool SLOTS, bool LP, bool TOP, bool PER>
 __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
+    static_assert(SLOTS || !PER, "the per-slot parameters belong to the slot form");
     __shared__ SelShared sh;
     const int tid = threadIdx.x;
     int row = blockIdx.x, t;
     bool t_ok;
+    int vlo = a.vlo, vhi = a.vhi, top_k = a.top_k, greedy = a.greedy;
+    float inv_t = a.inv_t, top_p = a.top_p;
+    unsigned k0 = a.k0, k1 = a.k1;
     if constexpr (SLOTS) {
         if (a.row_map) row = a.row_map[blockIdx.x];
         if (row < 0 || row >= a.n_slots) return;     // (a slot that does not exist: nothing to write to)
@@ -104,6 +113,24 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             }
             return;
         }
+        if constexpr (PER) {
+            const int* p = a.params + (int64_t)row * 8;     // (every thread reads the same 32 bytes)
+            greedy = p[0]; top_k = p[1]; vlo = p[2]; vhi = p[3];
+            k0 = (unsigned)p[4]; k1 = (unsigned)p[5];
+            inv_t = __int_as_float(p[6]); top_p = __int_as_float(p[7]);
+            // what sel_launch refuses for the scalar forms (1 / temperature finite and positive <=> temperature is); a greedy slot's
+            // words 1 and 4 .. 7 are never looked at
+            const bool bad = !(vlo >= 0 && vlo < vhi && vhi <= a.V) ||
+                             (!greedy && (!(inv_t > 0.f && inv_t < INFINITY) || top_k < 0 || !(top_p > 0.f && top_p <= 1.f)));
+            if (bad) {     // (block-uniform) out, t, lengths and the log-prob / top-n buffers stay as they are
+                if (tid == 0) {
+                    a.status[row] |= 4;
+                    a.finished[row] = 1;
+                    a.next_ids[(int64_t)row * a.ids_stride] = a.pad;
+                }
+                return;
+            }
+        }
     } else {
         t = *a.t;
         t_ok = t >= 0 && t < a.max_new;
@@ -120,7 +147,7 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
         }
     }
     const T* lg = reinterpret_cast<const T*>(a.logits) + (int64_t)blockIdx.x * a.ld;
-    const int lo = max(a.vlo, 0), hi = min(a.vhi, a.V);
+    const int lo = max(vlo, 0), hi = min(vhi, a.V);
     unsigned key[NG][4];
     unsigned long long best = 0;   // (key << 32) | ~column: max = largest key, lowest column on ties
     unsigned kmin = 0xffffffffu;
@@ -142,23 +169,23 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
     if (kmax == 0) {                                  // nothing finite in the window
         tok = a.pad;
         bits = 1;
-    } else if (a.greedy || a.top_k == 1) {
+    } else if (greedy || top_k == 1) {
         tok = (int)~(unsigned)best;
     } else {
         // top-k: thr_k = the k-th largest key = the largest x with #{key >= x} >= k (bisection over [smallest key, largest key])
         // (bf16 logits: the low 16 bits of every key are 0, the bisection runs over the high 16)
         constexpr int S = sizeof(T) == 2 ? 16 : 0;
         unsigned thr = block_min_u32(kmin, sh, ph);
-        if (a.top_k > 1) {
+        if (top_k > 1) {
             unsigned l = thr >> S, h = kmax >> S;
             while (l < h) {
                 const unsigned mid = l + ((h - l) >> 1) + ((h - l) & 1);
-                if (sel_count_ge<NG>(key, mid << S, sh, ph) >= a.top_k) l = mid; else h = mid - 1;
+                if (sel_count_ge<NG>(key, mid << S, sh, ph) >= top_k) l = mid; else h = mid - 1;
             }
             thr = l << S;
         }
         // top-p: p = softmax(l / T) over {key >= thr_k}; thr_p = the largest key x with mass{key >= x} >= top_p (ties at x kept)
-        if (a.top_p < 1.f) {
+        if (top_p < 1.f) {
             const float m = sel_unkey(kmax);
             float e[NG][4];
             float z = 0.f;
@@ -166,11 +193,11 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             for (int j = 0; j < NG; j++)
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
-                    e[j][q] = key[j][q] >= thr ? expf((sel_unkey(key[j][q]) - m) * a.inv_t) : 0.f;
+                    e[j][q] = key[j][q] >= thr ? expf((sel_unkey(key[j][q]) - m) * inv_t) : 0.f;
                     z += e[j][q];
                 }
             z = block_sum_f(z, sh, ph);
-            const float target = a.top_p * z;
+            const float target = top_p * z;
             unsigned l = thr >> S, h = kmax >> S;
             while (l < h) {
                 const unsigned mid = l + ((h - l) >> 1) + ((h - l) & 1);
@@ -188,12 +215,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             if (any) {
                 const int g = j * SEL_THREADS + tid;
                 unsigned o[4];
-                db1_philox4x32_10((unsigned)g, sid, step, SEL_SITE_SAMPLE, a.k0, a.k1, o);
+                db1_philox4x32_10((unsigned)g, sid, step, SEL_SITE_SAMPLE, k0, k1, o);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     if (key[j][q] < thr) continue;
                     const float u = ((float)(o[q] >> 8) + 0.5f) * 5.9604644775390625e-8f;   // ((x >> 8) + 0.5) * 2^-24: exact in fp32
-                    const float s = sel_unkey(key[j][q]) * a.inv_t - logf(-logf(u));
+                    const float s = sel_unkey(key[j][q]) * inv_t - logf(-logf(u));
                     const unsigned sk = sel_key(s);
                     const unsigned long long p = ((unsigned long long)sk << 32) | (unsigned)~(4 * g + q);
                     sb = p > sb ? p : sb;
@@ -280,18 +307,20 @@ extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
     return 0;
 }
 
-template <typename T, bool SLOTS, bool LP, bool TOP>
+template <typename T, bool SLOTS, bool LP, bool TOP, bool PER = false>
 static void sel_dispatch(int ng, const SelArgs& a, int M, hipStream_t st) {
-    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
-    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
-    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP, TOP><<<M, SEL_THREADS, 0, st>>>(a);
+    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
+    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
+    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
 }
 
 // The host side both entry points share: `a` arrives filled; validation (in one order for both, so an argument list that is wrong in two ways
 // fails with the same code as ever), 1 / temperature, the NG / SLOTS / LP dispatch over M workgroups, the launch check.  `lp`: the _lp
 // forms, which need both log-prob buffers; the others leave them NULL and launch the instantiations without that code.  `top`: the _top
-// forms (lp as well), which need 1 <= top_n <= SEL_MAX_TOP and both of their buffers; a.top_n == 0 otherwise.
-static int sel_launch(const char* who, bool slots, bool lp, bool top, SelArgs& a, int M, int dt, float temperature, void* stream) {
+// forms (lp as well), which need 1 <= top_n <= SEL_MAX_TOP and both of their buffers; a.top_n == 0 otherwise.  `per`: the per-slot form
+// (slots as well): a.params, non-NULL and 32-byte aligned, stands in for the window, the temperature, top-k / top-p and the seed, which the
+// kernel checks slot by slot (device data cannot be checked here).
+static int sel_launch(const char* who, bool slots, bool lp, bool top, bool per, SelArgs& a, int M, int dt, float temperature, void* stream) {
     if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
     if (M <= 0 || M > 65535 || a.V <= 0 || a.ld < a.V || a.max_new <= 0 || a.ids_stride < 0 || a.n_slots <= 0 || (!a.row_map && a.n_slots != M))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d V=%d ld=%lld max_new=%d ids_stride=%lld n_slots=%d%s", who, M, a.V, (long long)a.ld, a.max_new,
@@ -300,17 +329,26 @@ static int sel_launch(const char* who, bool slots, bool lp, bool top, SelArgs& a
     const int ng = sel_ng(a.V);
     if (!ng) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d (at most %d)", who, a.V, SEL_MAX_NG * 4096);
     if (!a.logits || !(slots ? a.t_slot && a.limit : a.t != nullptr) || !a.finished || !a.lengths || !a.out || !a.next_ids || !a.status ||
-        (lp && (!a.logprob || !a.sum_logprob)) || (top && (!a.top_ids || !a.top_logprob)))
+        (lp && (!a.logprob || !a.sum_logprob)) || (top && (!a.top_ids || !a.top_logprob)) || (per && !a.params))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
-    if (a.vlo < 0 || a.vhi > a.V || a.vlo >= a.vhi)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, a.vlo, a.vhi, a.V);
-    if (!a.greedy && !(temperature > 0.f && temperature < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: temperature %g", who, (double)temperature);
-    if (!a.greedy && (a.top_k < 0 || !(a.top_p > 0.f && a.top_p <= 1.f)))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_k %d top_p %g", who, a.top_k, (double)a.top_p);
-    a.inv_t = a.greedy ? 1.f : 1.f / temperature;
+    if (per) {
+        if (reinterpret_cast<uintptr_t>(a.params) % 32) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: params %p is not 32-byte aligned", who, (const void*)a.params);
+    } else {
+        if (a.vlo < 0 || a.vhi > a.V || a.vlo >= a.vhi)
+            DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, a.vlo, a.vhi, a.V);
+        if (!a.greedy && !(temperature > 0.f && temperature < INFINITY))
+            DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: temperature %g", who, (double)temperature);
+        if (!a.greedy && (a.top_k < 0 || !(a.top_p > 0.f && a.top_p <= 1.f)))
+            DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_k %d top_p %g", who, a.top_k, (double)a.top_p);
+        a.inv_t = a.greedy ? 1.f : 1.f / temperature;
+    }
     hipStream_t st = (hipStream_t)stream;
     DB1_DISPATCH_DT(dt, T, {
-        if (slots) {
+        if (per) {
+            if (top) sel_dispatch<T, true, true, true, true>(ng, a, M, st);
+            else if (lp) sel_dispatch<T, true, true, false, true>(ng, a, M, st);
+            else sel_dispatch<T, true, false, false, true>(ng, a, M, st);
+        } else if (slots) {
             if (top) sel_dispatch<T, true, true, true>(ng, a, M, st);
             else if (lp) sel_dispatch<T, true, true, false>(ng, a, M, st);
             else sel_dispatch<T, true, false, false>(ng, a, M, st);
@@ -347,7 +385,7 @@ static int sel_tokens(const char* who, bool lp, bool top, const void* logits, in
                          lengths, out, max_new, next_ids, ids_stride, status);
     a.t = t; a.n_slots = M; a.logprob = logprob; a.sum_logprob = sum_logprob;
     a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob;
-    return sel_launch(who, false, lp, top, a, M, dt, temperature, stream);
+    return sel_launch(who, false, lp, top, false, a, M, dt, temperature, stream);
 }
 
 extern "C" int db1_select_tokens(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
@@ -400,7 +438,7 @@ static int sel_slots(const char* who, bool lp, bool top, const void* logits, int
                          lengths, out, max_new, next_ids, ids_stride, status);
     a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots; a.logprob = logprob; a.sum_logprob = sum_logprob;
     a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob;
-    return sel_launch(who, true, lp, top, a, M, dt, temperature, stream);
+    return sel_launch(who, true, lp, top, false, a, M, dt, temperature, stream);
 }
 
 extern "C" int db1_select_tokens_slots(const void* logits, int M, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
@@ -436,4 +474,21 @@ extern "C" int db1_select_tokens_slots_top(const void* logits, int M, int V, int
     return sel_slots("select_tokens_slots_top", true, true, logits, M, V, ld, dt, vocab_lo, vocab_hi, temperature, top_k, top_p, greedy, seed_lo,
                      seed_hi, eos_id, pad_id, step_base, t, limit, stream_id, finished, lengths, out, max_new, next_ids, ids_stride, status, row_map,
                      n_slots, logprob, sum_logprob, top_n, top_ids, top_logprob, stream);
+}
+
+// The per-slot form: db1_select_tokens_slots[_lp|_top] with the window, greedy, temperature, top-k, top-p and the seed read per slot from
+// params [n_slots, 8] (include/db1_hip.h).  ONE entry point: the log-prob and top-n arguments say which instantiation runs -- none of them
+// (plain), both log-prob buffers (LP), those and top_n with both top-n buffers (TOP); any other combination fails sel_launch's own checks.
+extern "C" int db1_select_tokens_slots_per(const void* logits, int M, int V, int64_t ld, int dt, const int32_t* params, int eos_id, int pad_id,
+                                           int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished,
+                                           int32_t* lengths, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status,
+                                           const int32_t* row_map, int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                                           float* top_logprob, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    const bool top = top_n != 0 || top_ids || top_logprob, lp = top || logprob || sum_logprob;
+    SelArgs a = sel_args(logits, V, ld, 0, V, 0, 1.f, 1, 0, 0, eos_id, pad_id, step_base, stream_id, finished, lengths, out, max_new, next_ids,
+                         ids_stride, status);
+    a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots; a.logprob = logprob; a.sum_logprob = sum_logprob;
+    a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob; a.params = params;
+    return sel_launch("select_tokens_slots_per", true, lp, top, true, a, M, dt, 1.f, stream);
 }

@@ -83,6 +83,33 @@ class GenerationConfig:
 
 
 @dataclass(frozen=True)
+class SamplingParams:
+    """One request's own sampling parameters in a stream run with ``per_request=True`` (serving.py): the fields of ``GenerationConfig`` that
+    ``db1_select_tokens_slots_per`` reads per slot.  ``None`` inherits the stream config's value; for the window that is the RESOLVED one
+    (``vocab_hi``: the text vocabulary under ``caption_stream`` / ``answer_stream``, else the config's, else the model's whole vocabulary).
+    ``eos_id``, ``pad_id``, the constraints and the log-prob switches stay the stream's."""
+    greedy: Optional[bool] = None
+    temperature: Optional[float] = None
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    seed: Optional[int] = None
+    vocab_lo: Optional[int] = None
+    vocab_hi: Optional[int] = None
+
+    def resolve(self, cfg: GenerationConfig, V: int, hi: int) -> dict:
+        """the concrete values under the stream config ``cfg`` of a model with a vocabulary of ``V``, ``hi`` the end of the config's window
+        inside it (``_vocab_window``) -> the keyword arguments of ``ops.pack_slot_params``.  Raises ValueError for what ``GenerationConfig``
+        refuses and for a window that is empty or leaves [0, V)."""
+        mine = {f.name: getattr(self, f.name) for f in dataclasses.fields(self) if getattr(self, f.name) is not None}
+        mine.setdefault("vocab_hi", int(hi))
+        c = dataclasses.replace(cfg, **mine)     # (GenerationConfig's own checks, in its own words)
+        if int(c.vocab_hi) > int(V):
+            raise ValueError(f"vocabulary window [{c.vocab_lo}, {c.vocab_hi}) exceeds the model's vocabulary ({V})")
+        return dict(greedy=bool(c.greedy), temperature=float(c.temperature), top_k=int(c.top_k), top_p=float(c.top_p), seed=int(c.seed),
+                    vocab_lo=int(c.vocab_lo), vocab_hi=int(c.vocab_hi))
+
+
+@dataclass(frozen=True)
 class BeamSearchConfig:
     """Beam search with ``num_beams`` beams per prompt (1 .. 16), ``max_new_tokens`` new tokens (at most the model's ``mem_len``), scores
     normalised by (length)^``length_penalty``; the best ``num_return_sequences`` (<= num_beams) hypotheses of each prompt come back.

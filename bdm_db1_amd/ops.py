@@ -704,6 +704,62 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
              stream())
 
 
+SLOT_PARAM_WORDS = 8
+
+
+def pack_slot_params(greedy, temperature, top_k, top_p, seed, vocab_lo, vocab_hi) -> np.ndarray:
+    """one slot's record of ``select_tokens_slots_per`` (db1_select_tokens_slots_per, include/db1_hip.h) -> int32 [8]; THE place the layout
+    is written down on the host: word 0 ``greedy`` (0 / 1), 1 ``top_k``, 2 ``vocab_lo``, 3 ``vocab_hi``, 4 / 5 the low / high 32 bits of
+    ``seed``, 6 the fp32 bits of ``1 / temperature`` (one fp32 division, the one the scalar forms do at the launch; 1.0 when greedy, as
+    there), 7 the fp32 bits of ``top_p``.  Pure NumPy; nothing is validated here (``SamplingParams.resolve`` does that, and the kernel
+    refuses a bad record slot by slot)."""
+    w = np.zeros(SLOT_PARAM_WORDS, np.uint32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv_t = np.float32(1) if greedy else np.float32(1) / np.float32(temperature)
+    w[0] = 1 if greedy else 0
+    w[1:4] = np.array([top_k, vocab_lo, vocab_hi], np.int64).astype(np.int32).view(np.uint32)
+    w[4], w[5] = seed & 0xFFFFFFFF, seed >> 32
+    w[6:8] = np.array([inv_t, top_p], np.float32).view(np.uint32)
+    return w.view(np.int32)
+
+
+def select_tokens_slots_per(logits2d, params, t, limit, finished, lengths, out, next_ids, status, *, V=None, eos_id=-1, pad_id=0, step_base=0,
+                            stream_id=None, row_map=None, logprob=None, sum_logprob=None, top_n=None, top_ids=None, top_logprob=None):
+    """``select_tokens_slots`` with every slot's OWN sampling parameters (db1_select_tokens_slots_per): ``params`` (int32 [S, 8], contiguous,
+    on the device, 32-byte aligned; one ``pack_slot_params`` record per slot, indexed by the slot like ``t``) takes the place of
+    ``vocab_lo, vocab_hi, greedy, temperature, top_k, top_p, seed``; everything else is as ``select_tokens_slots`` takes it, and a slot comes
+    out exactly as that would leave it under the slot's values.  The records are device data, so the KERNEL checks them: a live slot whose
+    window is not ``0 <= vocab_lo < vocab_hi <= V``, or which samples with ``1 / temperature`` not finite and positive, ``top_k < 0`` or
+    ``top_p`` outside (0, 1], gets status bit 2 (value 4), ``finished`` = 1 and ``pad_id`` in ``next_ids``, nothing else of it touched; a
+    greedy slot ignores words 1 and 4 .. 7.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    who, dev, i32 = "select_tokens_slots_per", logits2d.device, torch.int32
+    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None, lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
+    S = int(t.numel()) if row_map is not None else M
+    if row_map is not None:
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if S < M:
+            raise ValueError(f"{who}: {M} logits rows for {S} slots")
+    for name, x in (("t", t), ("limit", limit), ("finished", finished), ("lengths", lengths), ("status", status)) + \
+            ((("stream_id", stream_id),) if stream_id is not None else ()):
+        _check_tensor(who, name, x, i32, S, dev)
+    if params is None:
+        raise ValueError(f"{who}: params is None")
+    _check_tensor(who, "params", params, i32, (S, SLOT_PARAM_WORDS), dev)
+    if params.data_ptr() % 32:
+        raise ValueError(f"{who}: params must be 32-byte aligned")
+    _check_tensor(who, "out", out, i32, (S, -1), dev)
+    _check_next_ids(who, next_ids, S, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, S, out.shape[1], dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (S, out.shape[1]), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    lib.call("db1_select_tokens_slots_per", P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(params), int(eos_id), int(pad_id),
+             int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0),
+             P(status), P(row_map), S, P(logprob), P(sum_logprob), top, P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0),
+             _vp(0), 0, stream())
+
+
 def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype) -> bool:
     return bool(lib.load().db1_constrain_logits_supported(int(V), int(ld), int(max_new), int(n_bad), dt_code(dtype)))
 

@@ -11,7 +11,10 @@ other rows go on:
     in calls of their own; after a prefill every row holds exactly ``mem_len`` memory entries, whatever its prompt was;
   * the per-token graph (one ``GraphedRingStep`` of ``slots`` rows, kept on the model) ends in db1_select_tokens_slots: every slot has its own
     token counter and limit, advanced by the launch itself, and a vacant slot only feeds ``pad_id`` forward.  The same kernel, given the
-    slots of the newly admitted rows (``row_map``), picks their token 0 from the prefill's last-position logits straight into their slots.
+    slots of the newly admitted rows (``row_map``), picks their token 0 from the prefill's last-position logits straight into their slots;
+  * with ``per_request=True`` the graph ends in db1_select_tokens_slots_per instead, which reads greedy / temperature / top-k / top-p / seed
+    and the vocabulary window of every slot from a device record the admission writes (``SamplingParams``): requests that are decoded
+    differently share one stream, one graph and one batch.
 
 A request's tokens depend on its prompt, its stream id, the seed and its token index: not on the slot it got or on when it was admitted.
 What the host decides -- which slot, which requests share a prefill, the order results come back in -- is ``SlotScheduler``, plain Python.
@@ -26,7 +29,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, GenerationConfig, _batch_size, _constrained, _need_memory,
+from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained, _need_memory,
                          _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _work, caption_prompt,
                          question_prompts)
 
@@ -35,12 +38,14 @@ from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, Ge
 @dataclasses.dataclass
 class Request:
     """one row of a prompt batch: ``index`` (its place in the results, and its default Philox stream), the batch and the row in it, its
-    token limit, and ``key``: requests with equal keys have one prompt shape and can share a prefill"""
+    token limit, and ``key``: requests with equal keys have one prompt shape and can share a prefill; ``params``: its own
+    ``SamplingParams`` in a ``per_request`` stream (None: the stream config's)"""
     index: int
     limit: int
     key: tuple
     prompt: object = None
     row: int = 0
+    params: Optional[SamplingParams] = None
 
 
 @dataclasses.dataclass
@@ -49,6 +54,7 @@ class _Item:
     prompt: object
     indices: object
     limit: Optional[int] = None
+    params: Optional[SamplingParams] = None
 
 
 _SEQ_FIELDS = ("text_seq", "prompt_seq", "img_seq")            # what makes a prompt's shape
@@ -64,21 +70,37 @@ def _shape_key(prompt) -> tuple:
     return tuple(key)
 
 
-def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0) -> Iterator[Request]:
-    """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item) as Requests, numbered in order; raises ValueError for a limit outside
-    [1, cfg.max_new_tokens] or below ``min_new`` (the constraints' minimum length) and what ``generate`` raises for a prompt batch that is
-    not one shape"""
+def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_request: bool = False,
+              window: Optional[Tuple[int, int]] = None) -> Iterator[Request]:
+    """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item; ``per_request``: also (prompt, max_new_tokens or None,
+    SamplingParams or None)) as Requests, numbered in order; raises ValueError for a limit outside [1, cfg.max_new_tokens] or below
+    ``min_new`` (the constraints' minimum length), for params when ``per_request`` is off, for params that do not resolve under ``cfg`` and
+    ``window`` = (V, hi) (``SamplingParams.resolve``; None: not checked here) and what ``generate`` raises for a prompt batch that is not
+    one shape"""
     nxt = 0
     for item in items:
-        indices = None
+        indices = params = None
         if isinstance(item, _Item):
-            prompt, limit, indices = item.prompt, item.limit, item.indices
+            prompt, limit, indices, params = item.prompt, item.limit, item.indices, item.params
         elif isinstance(item, tuple):
-            if len(item) != 2:
-                raise ValueError("generate_stream: a request is a prompt or (prompt, max_new_tokens)")
-            prompt, limit = item
+            if len(item) == 3 and per_request:
+                prompt, limit, params = item
+            elif len(item) == 3 and item[2] is not None:
+                raise ValueError("generate_stream: a request with SamplingParams needs per_request=True")
+            elif len(item) != 2:
+                raise ValueError("generate_stream: a request is a prompt or (prompt, max_new_tokens)" +
+                                 (" or (prompt, max_new_tokens, SamplingParams)" if per_request else ""))
+            else:
+                prompt, limit = item
         else:
             prompt, limit = item, None
+        if params is not None:
+            if not per_request:
+                raise ValueError("generate_stream: a request with SamplingParams needs per_request=True")
+            if not isinstance(params, SamplingParams):
+                raise ValueError(f"generate_stream: SamplingParams expected as a request's third element, got {type(params).__name__}")
+            if window is not None:
+                params.resolve(cfg, *window)
         limit = int(cfg.max_new_tokens if limit is None else limit)
         if not 1 <= limit <= int(cfg.max_new_tokens):
             raise ValueError(f"generate_stream: a request's max_new_tokens {limit} must lie in [1, config.max_new_tokens = {cfg.max_new_tokens}]")
@@ -91,7 +113,7 @@ def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0) -> Itera
         elif len(indices) != G:
             raise ValueError(f"generate_stream: {len(indices)} indices for a prompt batch of {G} rows")
         for r, i in enumerate(indices):
-            yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r)
+            yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r, params=params)
             nxt = max(nxt, int(i) + 1)
 
 
@@ -180,22 +202,31 @@ class SlotScheduler:
 
 # ----------------------------------------------------------------------------------------------------------------------- the device state
 class _SlotState(_SamplingState):
-    """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row"""
+    """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row; ``per``: also every slot's
+    sampling record ``params`` [slots, 8] (``ops.pack_slot_params``), and the selection is db1_select_tokens_slots_per"""
     cache = "_slot_generator"
+    _PER_SLOT = ("vocab_lo", "vocab_hi", "greedy", "temperature", "top_k", "top_p", "seed")     # what the record replaces in ``sel``
 
-    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
+    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None,
+                 per: bool = False):
         super().__init__(model, slots, cfg, V, hi, cons)
         self.t = torch.zeros(slots, **self.i32)
         self.limit = torch.ones(slots, **self.i32)
         self.finished.fill_(1)       # (vacant)
+        self.params = None
+        if per:     # (every slot starts with the config's own record: a vacant slot's is never read, but it is never garbage either)
+            rec = ops.pack_slot_params(**SamplingParams().resolve(cfg, V, hi))
+            self.params = torch.from_numpy(np.tile(rec, (slots, 1))).to(self.dev)
+            self.sel_per = {k: v for k, v in self.sel.items() if k not in self._PER_SLOT}
 
     def start(self):
         self.finished.fill_(1)
         for x in (self.t, self.lengths, self.status):
             x.zero_()
 
-    def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int]) -> torch.Tensor:
-        """fresh state for the requests moving into ``slots`` -> the slots as the int32 device vector ``select`` and ``load_rows`` take"""
+    def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int], records=None) -> torch.Tensor:
+        """fresh state for the requests moving into ``slots`` (``records``: int32 [len(slots), 8], their sampling records, in a per-request
+        stream) -> the slots as the int32 device vector ``select`` and ``load_rows`` take"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
         for x in (self.t, self.lengths, self.status, self.finished):
             x.index_fill_(0, idx, 0)
@@ -206,10 +237,16 @@ class _SlotState(_SamplingState):
         self.clear_top(idx)
         self.limit.index_copy_(0, idx, torch.tensor(limits, dtype=torch.int32).to(self.dev))
         self.stream_id.index_copy_(0, idx, torch.from_numpy(np.asarray(stream_ids, dtype=np.int64).astype(np.int32)).to(self.dev))
+        if self.params is not None:
+            self.params.index_copy_(0, idx, torch.from_numpy(np.ascontiguousarray(records, dtype=np.int32)).to(self.dev))
         return idx.to(torch.int32)
 
     def select(self, logits2d, next_ids, row_map=None):
         self.constrain(logits2d, row_map)
+        if self.params is not None:
+            ops.select_tokens_slots_per(logits2d, self.params, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status,
+                                        row_map=row_map, **self.sel_per)
+            return
         ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map, **self.sel)
 
     def epilogue(self, logits2d, next_ids, ring=None):
@@ -227,7 +264,7 @@ class _SlotState(_SamplingState):
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
 def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig] = None, slots: int = 8, stream_ids=None,
                     stats: Optional[dict] = None, replay: bool = True,
-                    constraints: Optional[DecodingConstraints] = None) -> Iterator[tuple]:
+                    constraints: Optional[DecodingConstraints] = None, per_request: bool = False) -> Iterator[tuple]:
     """Generate for a stream of requests over ``slots`` recycled rows; yields ``(index, ids int32 [limit], length)`` on the host as requests
     finish (requests that are found finished at the same look come in index order).  ``ids[:length]`` are the tokens before EOS, then EOS,
     then ``pad_id``.
@@ -247,7 +284,12 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     below ``min_new_tokens`` raises ValueError.  With ``config.logprobs`` the stream yields ``(index, ids, length, logprobs float32 [limit])``:
     every token's log-probability as ``generate`` returns it (EOS included, 0 after it); with ``config.top_logprobs`` n two more fields,
     ``top_ids int32 [limit, n]`` and ``top_logprobs float32 [limit, n]``, as ``generate`` returns them (-1 / -inf after the request's last
-    token)."""
+    token).  ``per_request`` True: a request may also be ``(prompt, max_new_tokens or None, SamplingParams)`` and is then decoded under its
+    own greedy / temperature / top_k / top_p / seed / vocabulary window (fields left None: the config's); a request without params runs under
+    the config.  The stream's graph then ends in db1_select_tokens_slots_per, which reads every slot's parameters on the device; the flag is
+    needed up front because ``requests`` is consumed lazily and the captured graph holds one kernel or the other, and it joins the
+    generator's cache key.  ``eos_id``, ``pad_id``, the constraints and the log-prob switches stay the stream's.  False: nothing changes, and
+    a request that carries params raises ValueError (a list or tuple of requests: before any launch)."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -260,14 +302,26 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
         raise ValueError(f"db1_select_tokens_slots does not support a vocabulary of {V}")
     key = _constrained("generate_stream", model, (slots, cfg, V, hi), constraints, cfg.max_new_tokens)
     min_new = 0 if constraints is None else constraints.min_new_tokens
+    per_request = bool(per_request)
+    if per_request:     # (with the flag off the key is what it was)
+        key = _per_request_key(key)
     if isinstance(requests, (list, tuple)):
-        for _ in _requests(requests, cfg, min_new):     # (a list can be checked as a whole before the first launch)
+        for _ in _requests(requests, cfg, min_new, per_request, (V, hi)):     # (a list can be checked as a whole before the first launch)
             pass
-    return _stream(model, _requests(requests, cfg, min_new), key, stream_ids, stats, replay)
+    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi)), key, stream_ids, stats, replay, per_request)
 
 
-def _stream(model, reqs, key, stream_ids, stats, replay):
-    slots, cfg = key[0], key[1]
+def _per_request_key(key: tuple) -> tuple:
+    """the state key (slots, cfg, V, hi[, constraints]) of a stream with the per-request flag set: ``_SlotState``'s arguments by name,
+    (slots, cfg, V, hi, cons, per): where the flag sits is decided here and nowhere else (``_stream``, like before, reads only the first
+    four, which every state key starts with)"""
+    slots, cfg, V, hi, *cons = key
+    return (slots, cfg, V, hi, cons[0] if cons else None, True)
+
+
+def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
+    slots, cfg, V, hi = key[:4]
+    inherit = SamplingParams()
     sched = SlotScheduler(slots, reqs)
     counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
     live_steps = 0
@@ -298,7 +352,8 @@ def _stream(model, reqs, key, stream_ids, stats, replay):
                     rs = [r for _, r in members]
                     # one prefill for the group; its last position picks token 0 of every request straight into its slot, its memory moves in
                     logits, mems = _prefill(model, _gather(rs), len(rs))
-                    idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs])
+                    recs = np.stack([ops.pack_slot_params(**(r.params or inherit).resolve(cfg, V, hi)) for r in rs]) if per else None
+                    idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs], recs)
                     st.select(logits[:, -1], step.ids[:, 0], row_map=idx)
                     gen.ring.load_rows(mems, idx)
                     del logits, mems
@@ -316,6 +371,10 @@ def _stream(model, reqs, key, stream_ids, stats, replay):
                             t, length, status = (int(v) for v in meta[j])
                             if status & 2:
                                 raise RuntimeError("db1_select_tokens_slots: a slot's token counter left [0, limit)")
+                            if status & 4:
+                                raise RuntimeError("db1_select_tokens_slots_per: a slot's sampling parameters were refused on the device "
+                                                   "(SamplingParams.resolve validates every record on the host before it is written, so "
+                                                   "this cannot happen unless the slot state was overwritten)")
                             counts["no_candidate"] += status & 1
                             live_steps += t - 1
                             results.append((r.index, out[j, :r.limit].clone(), length) + (() if lp is None else (lp[j, :r.limit].clone(),)) +
@@ -347,34 +406,42 @@ def generate_many(model, requests: Iterable, config: Optional[GenerationConfig] 
 
 
 def _split(item):
-    return item if isinstance(item, tuple) else (item, None)
+    """a stream wrapper's item -> (batch, max_new_tokens or None, what follows: () or (SamplingParams,), passed through as it is)"""
+    if not isinstance(item, tuple):
+        return item, None, ()
+    b, limit, *rest = item
+    return b, limit, tuple(rest)
 
 
 def caption_stream(model, ic_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
-    """``generate_stream`` over ``ICTaskInput`` batches (or ``(batch, max_new_tokens)``): the prompts of ``caption_prompt``, tokens in the text
-    vocabulary unless ``cfg`` says otherwise; every image is one request"""
+    """``generate_stream`` over ``ICTaskInput`` batches (or ``(batch, max_new_tokens)``; ``per_request=True``: or ``(batch, max_new_tokens
+    or None, SamplingParams)``, the params of every image of the batch): the prompts of ``caption_prompt``, tokens in the text vocabulary
+    unless ``cfg`` (or a request's own params) says otherwise; every image is one request"""
     cfg = _text_window(model, cfg or GenerationConfig())
 
     def items():
         for it in ic_batches:
-            b, limit = _split(it)
-            yield caption_prompt(b), limit
+            b, limit, rest = _split(it)
+            yield (caption_prompt(b), limit) + rest
 
     return generate_stream(model, items(), cfg, **kw)
 
 
 def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
-    """``generate_stream`` over ``VQATaskInput`` batches (or ``(batch, max_new_tokens)``) whose questions may differ in length
-    (``question_prompts``), tokens in the text vocabulary unless ``cfg`` says otherwise; every question is one request, and the results'
-    indices number the batches' rows in their original order"""
+    """``generate_stream`` over ``VQATaskInput`` batches (or ``(batch, max_new_tokens)``; ``per_request=True``: or ``(batch, max_new_tokens
+    or None, SamplingParams)``, the params of every question of the batch) whose questions may differ in length (``question_prompts``),
+    tokens in the text vocabulary unless ``cfg`` (or a request's own params) says otherwise; every question is one request, and the
+    results' indices number the batches' rows in their original order"""
     cfg = _text_window(model, cfg or GenerationConfig())
 
     def items():
         base = 0
         for it in vqa_batches:
-            b, limit = _split(it)
+            b, limit, rest = _split(it)
+            if len(rest) > 1:
+                raise ValueError("answer_stream: a request is a batch, (batch, max_new_tokens) or (batch, max_new_tokens, SamplingParams)")
             for prompt, rows in question_prompts(b):
-                yield _Item(prompt, [base + int(r) for r in rows], limit)
+                yield _Item(prompt, [base + int(r) for r in rows], limit, *rest)
             base += _batch_size(b)
 
     return generate_stream(model, items(), cfg, **kw)

@@ -621,6 +621,36 @@ int db1_select_tokens_slots_top(const void* logits, int M, int V, int64_t ld, in
                                 const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths, int32_t* out, int max_new,
                                 int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map, int n_slots, float* logprob,
                                 float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* ws, int64_t ws_bytes, void* stream);
+/* The per-slot form: db1_select_tokens_slots / _lp / _top with the sampling parameters of every SLOT read on the device instead of passed as
+ * launch scalars, so ONE captured launch serves requests that are decoded differently (tests/slot_params_rule.py restates the rule in NumPy).
+ * params is int32 [n_slots, 8], 32 bytes per slot, the base 32-byte aligned, indexed by the SLOT (not by the logits row); floats as their
+ * fp32 bits:
+ *     word 0  greedy (0 / 1)            word 4  seed, low 32 bits
+ *     word 1  top_k                     word 5  seed, high 32 bits
+ *     word 2  vocab_lo                  word 6  inv_temperature = fp32 1 / temperature (ONE fp32 division on the host, the one the scalar
+ *     word 3  vocab_hi                          forms do at the launch; the kernel divides nothing, so no rounding can differ)
+ *                                       word 7  top_p
+ *   - a slot's record is read after the vacant-slot and counter checks of the slot form (a vacant slot's record, and that of a slot whose
+ *     counter is out of range, is never looked at) and before its logits; all eight values are uniform over the slot's workgroup;
+ *   - guard (the launch cannot check device data): a live slot's record is INVALID if not 0 <= vocab_lo < vocab_hi <= V, or if greedy == 0
+ *     and any of: inv_temperature not finite and positive (NaN, 0, negative, inf), top_k < 0, top_p not in (0, 1].  An invalid slot gets
+ *     status bit 2 (status[slot] |= 4), finished[slot] = 1 and pad_id in next_ids[slot * ids_stride]; nothing else of it is touched (out, t,
+ *     lengths, logprob, sum_logprob, top_ids and top_logprob stay): the treatment of a counter out of range.  A greedy slot (word 0 != 0)
+ *     ignores words 1 and 4 .. 7, as the scalar forms ignore those arguments when greedy;
+ *   - otherwise the token, the bookkeeping, the Philox counter (col / 4, stream_id[slot] (NULL: slot), step_base + t[slot], 0xE0000100) under
+ *     the slot's own key (word 4, word 5), the log-prob and the alternatives are exactly those of db1_select_tokens_slots / _lp / _top called
+ *     with the slot's parameters as scalars; the candidates of lse and of the alternatives are the finite logits of the slot's OWN window;
+ *   - eos_id, pad_id, step_base, max_new and the log-prob / top-n switches stay per launch (they fix buffer shapes, and
+ *     db1_constrain_logits reads eos_id as a scalar).
+ * One entry point for the three modes: logprob == sum_logprob == NULL, top_n == 0 and top_ids == top_logprob == NULL is the plain form; both
+ * log-prob buffers (top_n 0, no top buffers) the _lp form; those, 1 <= top_n <= 16 and both top buffers the _top form.  Any other
+ * combination, a NULL params or a params pointer that is not 32-byte aligned is DB1_ERR_BAD_SHAPE before any launch.  The _supported and
+ * _workspace_bytes queries of db1_select_tokens_slots hold for it: no workspace, no atomics, no LDS beyond the selection's. */
+int db1_select_tokens_slots_per(const void* logits, int M, int V, int64_t ld, int dt, const int32_t* params, int eos_id, int pad_id,
+                                int step_base, int32_t* t, const int32_t* limit, const int32_t* stream_id, int32_t* finished, int32_t* lengths,
+                                int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, int32_t* status, const int32_t* row_map,
+                                int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* ws,
+                                int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ beam search (captions / answers / text; tests/beam_rule.py restates
  * the rule in NumPy).  G groups (prompts) of W beams (1 <= W <= 16), M = G * W rows, row b = g * W + j; step t = 0 .. max_new - 1 chooses

@@ -28,6 +28,16 @@ limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS);
 
     python tools/bench_generate.py --stream [requests [slots]]
 
+With --stream --per-request: the stream workload above with every second request greedy and the others at top-p 0.9
+(``caption_stream(..., per_request=True)``, a ``SamplingParams`` on the sampled requests: the graph ends in db1_select_tokens_slots_per)
+next to the shared-config (greedy) stream of the same requests; one JSON line with the totals (``*_total_ms``: the best of 3 timed passes
+after a warm-up pass, as --stream reports it; ``*_runs_ms``: all three, for medians) and replay counts, and
+db1_select_tokens_slots_per against db1_select_tokens_slots alone from the same process and the same events on random bf16 logits
+[slots, 33 025] over the text window: all slots greedy, all at top-p 0.9, and half and half (per-slot form only); the plain
+instantiations only.
+
+    python tools/bench_generate.py --stream --per-request [requests [slots]]
+
 With --constraints: the greedy caption measurement above, unconstrained and with DecodingConstraints(repetition_penalty=1.2,
 no_repeat_ngram_size=3, min_new_tokens=5) -- one db1_constrain_logits launch more in every replay (no EOS, as in every run here, so
 the minimum length bans nothing) --, one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel time of db1_constrain_logits.
@@ -302,6 +312,75 @@ def stream_main(n_req=256, slots=64):
     print(json.dumps(rec), flush=True)
 
 
+def slot_select_kernels_us(M, max_new=4096):
+    """db1_select_tokens_slots and db1_select_tokens_slots_per alone on random bf16 logits [M, V] over the text window, every slot live (the
+    counters are rewound before every measurement: a launch advances them)"""
+    V, hi = int(model.total_vocab_size), int(model.text_vocab_size)
+    logits = (torch.randn(M, V, device=dev) * 3).to(torch.bfloat16)
+    i32 = dict(dtype=torch.int32, device=dev)
+    t, fin, n, status = (torch.zeros(M, **i32) for _ in range(4))
+    limit = torch.full((M,), max_new, **i32)
+    out = torch.zeros(M, max_new, **i32)
+    ids = torch.zeros(M, dtype=torch.long, device=dev)
+    kinds = {"greedy": dict(greedy=True, temperature=1.0, top_k=0, top_p=1.0, seed=1, vocab_lo=0, vocab_hi=hi),
+             "top_p_0.9": dict(greedy=False, temperature=1.0, top_k=0, top_p=0.9, seed=1, vocab_lo=0, vocab_hi=hi)}
+    recs = {k: ops.pack_slot_params(**v) for k, v in kinds.items()}
+    tables = {"greedy": [recs["greedy"]] * M, "top_p_0.9": [recs["top_p_0.9"]] * M,
+              "half_and_half": [recs["greedy" if i % 2 == 0 else "top_p_0.9"] for i in range(M)]}
+    rec = {}
+
+    def measure(fn):
+        for x in (t, fin, n, status):
+            x.zero_()
+        us = device_us(fn)
+        assert int(status.max()) == 0 and int(t.min()) == 53
+        return round(us, 2)
+
+    for name, kw in kinds.items():
+        rec[f"slots_{name}_us"] = measure(lambda: ops.select_tokens_slots(logits, t, limit, fin, n, out, ids, status, V=V, **kw))
+    for name, table in tables.items():
+        params = torch.from_numpy(np.stack(table)).to(dev)
+        rec[f"slots_per_{name}_us"] = measure(lambda: ops.select_tokens_slots_per(logits, params, t, limit, fin, n, out, ids, status, V=V))
+    return rec
+
+
+def stream_per_request_main(n_req=256, slots=64):
+    from bdm_db1_amd import SamplingParams, caption_stream
+    limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
+    cfg = GenerationConfig(max_new_tokens=N_NEW)
+    batches = [batch(slots + k) for k in range((n_req + slots - 1) // slots)]
+    rows = lambda b, r: ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=b.prompt_seq[r:r + 1],
+                                    img_seq=b.img_seq[r:r + 1], text_seq=None)
+    shared = [(rows(batches[i // slots], i % slots), int(limits[i])) for i in range(n_req)]
+    sampled = SamplingParams(greedy=False, top_p=0.9, seed=1)
+    mixed = [r if i % 2 == 0 else r + (sampled,) for i, r in enumerate(shared)]
+    rec = {"requests": n_req, "slots": slots, "limits": "uniform 5..30, seed 2024", "mix": "even requests greedy, odd requests top-p 0.9"}
+
+    def total(reqs, **kw):
+        stats = {}
+
+        def run():
+            for _ in caption_stream(model, reqs, cfg, slots=slots, stats=stats, **kw):
+                pass
+        run()                                  # capture + warm-up
+        ts = []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return round(min(ts), 2), [round(x, 2) for x in ts], stats["replays"]
+
+    rec["shared_total_ms"], rec["shared_runs_ms"], rec["shared_replays"] = total(shared)
+    rec["flag_only_total_ms"], rec["flag_only_runs_ms"], rec["flag_only_replays"] = total(shared, per_request=True)
+    rec["per_request_total_ms"], rec["per_request_runs_ms"], rec["per_request_replays"] = total(mixed, per_request=True)
+    model._slot_generator = None
+    torch.cuda.empty_cache()
+    rec.update(slot_select_kernels_us(slots))
+    print(json.dumps(rec), flush=True)
+
+
 SELECT_MODES = {"greedy": dict(), "top_p_0.9": dict(greedy=False, top_p=0.9, seed=1)}
 
 
@@ -378,8 +457,8 @@ if "--best-of" in args:
     best_of_main(int(args[i + 1]), [int(a) for a in args[:i] + args[i + 2:]] or [16])
     sys.exit(0)
 if "--stream" in args:
-    rest = [int(a) for a in args if a != "--stream"]
-    stream_main(*rest[:2])
+    rest = [int(a) for a in args if a not in ("--stream", "--per-request")]
+    (stream_per_request_main if "--per-request" in args else stream_main)(*rest[:2])
     sys.exit(0)
 if "--num-beams" in args:
     i = args.index("--num-beams")
