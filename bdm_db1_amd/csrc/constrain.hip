@@ -10,11 +10,20 @@
 // No atomics: position i penalises its column only if no earlier position holds the same token (decided from the LDS copy: all lanes read
 // the same word, a broadcast), so every penalised column has exactly one reader and one writer; after a barrier the bans store -inf, and
 // duplicate bans write the same bits.  t, hist, finished and row_map are only read: the launch can be captured and replayed.
+//
+// db1_constrain_logits_pen (tests/penalty_rule.py) is the PEN instantiation of the same kernel: the thread that holds a token's first
+// occurrence also counts its later copies in the staged history (n_c) and takes freq * n_c + pres off the rescaled value before its single
+// store -- three fp32 operations that must each round, hence ``rounded`` below: the build contracts a * b + c into one fma --; then,
+// between two barriers of its own, the bias list adds to the STORED values (one writer per column in each phase, so still no atomics); the
+// bans come last.  The count scan reads the t - i - 1 tokens after position i, 16 bytes at a time: about t^2 / 512 tokens per thread for a
+// history of distinct tokens, as much again as the first-occurrence test.  The plain instantiation holds none of this.
 #include "db1_common.h"
+#include <type_traits>
 
 #define CON_THREADS 256
 #define CON_MAX_NEW 4096                   // the LDS staging: 16 KB of history per workgroup (the models' mem_len is far below)
 #define CON_MAX_BAD 1024
+#define CON_MAX_BIAS 1024
 
 struct ConArgs {
     void* logits;
@@ -30,8 +39,23 @@ struct ConArgs {
     int n_bad, eos, min_new;
 };
 
-template <typename T>
-__global__ __launch_bounds__(CON_THREADS) void constrain_logits_kernel(ConArgs a) {
+struct ConPenArgs : ConArgs {              // what the PEN instantiation reads on top
+    float freq, pres;
+    const int* bias_ids;
+    const float* bias_val;
+    int n_bias;
+};
+
+// The build's -ffp-contract=fast lets the backend fuse a multiplication into the addition that follows whatever the source says (a
+// contract(off) pragma only keeps the front end from doing it).  A value that has passed through an empty asm statement is opaque to that
+// combiner: the product is rounded before it is used.
+__device__ __forceinline__ float rounded(float x) {
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+template <typename T, bool PEN>
+__global__ __launch_bounds__(CON_THREADS) void constrain_logits_kernel(typename std::conditional<PEN, ConPenArgs, ConArgs>::type a) {
     __shared__ __attribute__((aligned(16))) int h[CON_MAX_NEW];
     const int4* h4 = reinterpret_cast<const int4*>(h);
     const int tid = threadIdx.x;
@@ -46,7 +70,9 @@ __global__ __launch_bounds__(CON_THREADS) void constrain_logits_kernel(ConArgs a
     for (int i = tid; i < t; i += CON_THREADS) h[i] = hs[i];
     __syncthreads();
     // repetition penalty: the first occurrence of every distinct token rescales its column (a single fp32 multiplication, rounded to T)
-    if (a.theta != 1.f) {
+    bool edit = a.theta != 1.f;
+    if constexpr (PEN) edit = edit || a.freq != 0.f || a.pres != 0.f;
+    if (edit) {
         for (int i = tid; i < t; i += CON_THREADS) {
             const int c = h[i];
             if (c < 0 || c >= a.V) continue;
@@ -66,10 +92,43 @@ __global__ __launch_bounds__(CON_THREADS) void constrain_logits_kernel(ConArgs a
             if (dup) continue;
             const float l = ldf<T>(lg + c);
             if ((__float_as_uint(l) & 0x7f800000u) == 0x7f800000u) continue;      // NaN, +-inf: left as stored
-            stf<T>(lg + c, l > 0.f ? l * a.inv_theta : l * a.theta);
+            if constexpr (!PEN) {
+                stf<T>(lg + c, l > 0.f ? l * a.inv_theta : l * a.theta);
+            } else {
+                // n_c: this copy and those after it (none before: it is the first).  Single tokens up to the next 16-byte boundary, 16-byte
+                // reads up to the last whole one below t (the words past t in LDS were never written), single tokens again
+                int n = 1, j = i + 1;
+                const int j4 = min((j + 3) & ~3, t), qend = t >> 2;
+                for (; j < j4; j++) n += h[j] == c;
+                for (int q = j >> 2; q < qend; q++) {
+                    const int4 v = h4[q];
+                    n += (v.x == c) + (v.y == c) + (v.z == c) + (v.w == c);
+                }
+                for (j = max(j4, qend << 2); j < t; j++) n += h[j] == c;
+                // three roundings, not two: the products pass through ``rounded`` before anything is added to them
+                float v = l;
+                if (a.theta != 1.f) v = rounded(l > 0.f ? v * a.inv_theta : v * a.theta);
+                if (a.freq != 0.f || a.pres != 0.f) {
+                    float p = rounded((float)n * a.freq);
+                    p = p + a.pres;
+                    v = v - p;
+                }
+                stf<T>(lg + c, v);
+            }
         }
     }
     __syncthreads();      // the penalised values are in memory before a ban of the same column overwrites them
+    if constexpr (PEN) {
+        // the bias: distinct ids, so one reader and one writer per column; it reads what the penalties stored
+        for (int i = tid; i < a.n_bias; i += CON_THREADS) {
+            const int c = a.bias_ids[i];
+            if (c < 0 || c >= a.V) continue;
+            const float l = ldf<T>(lg + c);
+            if ((__float_as_uint(l) & 0x7f800000u) == 0x7f800000u) continue;
+            stf<T>(lg + c, l + a.bias_val[i]);
+        }
+        __syncthreads();  // ... and the biased values before a ban
+    }
     const float ninf = -INFINITY;
     // no-repeat n-gram: position i ends an earlier copy of the last n - 1 tokens -> its token would repeat that n-gram
     if (a.ngram > 0 && a.ngram <= t) {      // (n - 1 tokens before position i >= n - 1, and i < t)
@@ -97,12 +156,44 @@ extern "C" int64_t db1_constrain_logits_workspace_bytes(int M, int V, int max_ne
     return 0;
 }
 
+static int constrain_launch(const char* who, void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist,
+                            int max_new, const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
+                            const int32_t* bad, int n_bad, int eos_id, int min_new, bool pen, float freq, float pres, const int32_t* bias_ids,
+                            const float* bias_val, int n_bias, void* stream);
+
 extern "C" int db1_constrain_logits(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist,
                                     int max_new, const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta,
                                     int ngram, const int32_t* bad, int n_bad, int eos_id, int min_new, void* ws, int64_t ws_bytes,
                                     void* stream) {
     (void)ws; (void)ws_bytes;
-    const char* who = "constrain_logits";
+    return constrain_launch("constrain_logits", logits, M, V, ld, dt, t, t_per_slot, hist, max_new, finished, row_map, n_slots, theta, inv_theta, ngram,
+                            bad, n_bad, eos_id, min_new, false, 0.f, 0.f, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int db1_constrain_logits_pen_supported(int V, int64_t ld, int max_new, int n_bad, int n_bias, int dt) {
+    return db1_constrain_logits_supported(V, ld, max_new, n_bad, dt) && n_bias >= 0 && n_bias <= CON_MAX_BIAS;
+}
+
+extern "C" int64_t db1_constrain_logits_pen_workspace_bytes(int M, int V, int max_new, int n_bad, int n_bias, int dt) {
+    (void)M; (void)V; (void)max_new; (void)n_bad; (void)n_bias; (void)dt;
+    return 0;
+}
+
+extern "C" int db1_constrain_logits_pen(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist,
+                                        int max_new, const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta,
+                                        int ngram, const int32_t* bad, int n_bad, int eos_id, int min_new, float freq, float pres,
+                                        const int32_t* bias_ids, const float* bias_val, int n_bias, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    return constrain_launch("constrain_logits_pen", logits, M, V, ld, dt, t, t_per_slot, hist, max_new, finished, row_map, n_slots, theta, inv_theta,
+                            ngram, bad, n_bad, eos_id, min_new, true, freq, pres, bias_ids, bias_val, n_bias, stream);
+}
+
+// the checks and the launch of both entry points.  ``pen`` with freq == pres == 0 and no bias is the plain rule and launches the plain
+// instantiation: the bits of db1_constrain_logits by construction
+static int constrain_launch(const char* who, void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist,
+                            int max_new, const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
+                            const int32_t* bad, int n_bad, int eos_id, int min_new, bool pen, float freq, float pres, const int32_t* bias_ids,
+                            const float* bias_val, int n_bias, void* stream) {
     if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
     if (M <= 0 || M > 65535 || V <= 0 || ld < V || max_new <= 0 || n_bad < 0 || n_slots <= 0 || (!row_map && n_slots != M))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d V=%d ld=%lld max_new=%d n_bad=%d n_slots=%d%s", who, M, V, (long long)ld, max_new, n_bad, n_slots,
@@ -113,13 +204,23 @@ extern "C" int db1_constrain_logits(void* logits, int M, int V, int64_t ld, int 
     if (!(theta > 0.f && theta < INFINITY) || !(inv_theta > 0.f && inv_theta < INFINITY))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: theta %g (1 / theta %g) must be finite and > 0", who, (double)theta, (double)inv_theta);
     if (ngram < 0 || min_new < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: ngram %d min_new %d must be >= 0", who, ngram, min_new);
-    if (theta == 1.f && ngram == 0 && n_bad == 0 && (eos_id < 0 || min_new == 0)) return DB1_OK;      // no constraint: no launch
-    ConArgs a = {};
+    if (pen) {
+        if (n_bias < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: n_bias=%d", who, n_bias);
+        if (n_bias > CON_MAX_BIAS) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: n_bias=%d (at most %d)", who, n_bias, CON_MAX_BIAS);
+        if (n_bias > 0 && (!bias_ids || !bias_val)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null bias buffer", who);
+        if (!(fabsf(freq) < INFINITY) || !(fabsf(pres) < INFINITY))
+            DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: freq %g pres %g must be finite", who, (double)freq, (double)pres);
+        pen = freq != 0.f || pres != 0.f || n_bias > 0;
+    }
+    if (!pen && theta == 1.f && ngram == 0 && n_bad == 0 && (eos_id < 0 || min_new == 0)) return DB1_OK;      // no constraint: no launch
+    ConPenArgs a = {};
     a.logits = logits; a.ld = ld; a.V = V; a.max_new = max_new; a.n_slots = n_slots; a.t_per_slot = t_per_slot != 0;
     a.t = t; a.hist = hist; a.finished = finished; a.row_map = row_map;
     a.theta = theta; a.inv_theta = inv_theta; a.ngram = ngram; a.bad = bad; a.n_bad = n_bad; a.eos = eos_id; a.min_new = min_new;
+    a.freq = freq; a.pres = pres; a.bias_ids = bias_ids; a.bias_val = bias_val; a.n_bias = n_bias;
     hipStream_t st = (hipStream_t)stream;
-    DB1_DISPATCH_DT(dt, T, { constrain_logits_kernel<T><<<M, CON_THREADS, 0, st>>>(a); });
+    if (pen) DB1_DISPATCH_DT(dt, T, { constrain_logits_kernel<T, true><<<M, CON_THREADS, 0, st>>>(a); });
+    else DB1_DISPATCH_DT(dt, T, { constrain_logits_kernel<T, false><<<M, CON_THREADS, 0, st>>>(static_cast<const ConArgs&>(a)); });
     DB1_CHECK_LAUNCH(who);
     return DB1_OK;
 }

@@ -18,7 +18,9 @@ Sampling's epilogue is ``db1_select_tokens`` (greedy / temperature / top-k / top
 beam whose parent is another row), after a prefill whose memory and last logits are expanded to the W beams of each prompt.  Both rules are
 stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py and tests/beam_rule.py.  With ``constraints=`` (a
 ``DecodingConstraints``) either epilogue is preceded by ``db1_constrain_logits``, which edits the step's logits in place over each row's own
-generated tokens (tests/constraint_rule.py); without, nothing is launched.  scoring.py takes its prefill, its eval-mode switch and its
+generated tokens (tests/constraint_rule.py; with a frequency / presence penalty or a logit bias ``db1_constrain_logits_pen``,
+tests/penalty_rule.py), and with stop sequences the sampling epilogue is followed by ``db1_stop_match`` (tests/stop_rule.py), which ends a row
+whose tokens spell one and removes them; without, nothing is launched.  scoring.py takes its prefill, its eval-mode switch and its
 vocabulary checks from here.
 """
 from __future__ import annotations
@@ -143,6 +145,8 @@ class BeamSearchConfig:
 
 
 MAX_BAD_TOKEN_IDS = 1024
+MAX_LOGIT_BIAS = 1024
+MAX_STOP_SEQUENCES, MAX_STOP_LEN = ops.MAX_STOP_SEQUENCES, ops.MAX_STOP_LEN
 
 
 def _is_count(v) -> bool:
@@ -155,13 +159,70 @@ class DecodingConstraints:
     include/db1_hip.h) over the tokens a row has GENERATED so far (the prompt is not part of the history): ``repetition_penalty`` theta
     (1 = off): the logit of every token already generated is divided by theta if positive, else multiplied; ``no_repeat_ngram_size`` n
     (0 = off): no n-gram occurs twice; ``min_new_tokens``: EOS cannot be chosen before that many tokens (nothing without an ``eos_id``);
-    ``bad_token_ids``: never chosen.  Passed as ``constraints=`` to ``generate``, ``beam_search`` and the streams."""
+    ``bad_token_ids``: never chosen.  ``frequency_penalty`` f / ``presence_penalty`` p (any finite value, 0 = off): f * (the number of times
+    a token has been generated) + p is taken off the logit of every token already generated, after the repetition penalty
+    (``db1_constrain_logits_pen``, tests/penalty_rule.py).  ``logit_bias`` (a mapping, or pairs, token id -> bias; at most 1024): added to
+    those tokens' logits at every step, after the penalties; a ban still overrides it.  ``stop_sequences`` (at most 16 sequences of 1 .. 16
+    token ids): a row whose generated tokens end in one of them ends there, and the matched tokens are removed from what comes back
+    (``db1_stop_match``, tests/stop_rule.py); the longest match wins, then the first listed.  Passed as ``constraints=`` to ``generate``,
+    ``beam_search`` and the streams; ``beam_search`` and ``sample_best_of`` refuse stop sequences."""
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0
     bad_token_ids: Tuple[int, ...] = ()
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    logit_bias: Tuple[Tuple[int, float], ...] = ()
+    stop_sequences: Tuple[Tuple[int, ...], ...] = ()
+
+    def __hash__(self):
+        # (the first four fields alone while the later ones are off: the hash such an object has always had)
+        old = (self.repetition_penalty, self.no_repeat_ngram_size, self.min_new_tokens, self.bad_token_ids)
+        new = (self.frequency_penalty, self.presence_penalty, self.logit_bias, self.stop_sequences)
+        return hash(old if new == (0.0, 0.0, (), ()) else old + new)
+
+    def _check_new_fields(self):
+        for name in ("frequency_penalty", "presence_penalty"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not abs(float(v)) < float("inf"):
+                raise ValueError(f"{name} {v!r} must be a finite number")
+            with np.errstate(over="ignore"):
+                if not abs(float(np.float32(v))) < float("inf"):
+                    raise ValueError(f"{name} {v!r} must be finite in float32")
+            object.__setattr__(self, name, float(v))
+        bias = self.logit_bias
+        try:
+            pairs = [tuple(kv) for kv in (bias.items() if hasattr(bias, "items") else bias)]
+        except TypeError:
+            raise ValueError(f"logit_bias {bias!r} must be a mapping or an iterable of (token id, bias)") from None
+        if len(pairs) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias: {len(pairs)} entries (at most {MAX_LOGIT_BIAS})")
+        for kv in pairs:
+            if len(kv) != 2 or not _is_count(kv[0]):
+                raise ValueError(f"logit_bias: {kv!r} must be (token id, bias) with an integer id >= 0")
+            b = kv[1]
+            if isinstance(b, bool) or not isinstance(b, (int, float, np.integer, np.floating)) or not abs(float(np.float32(b))) < float("inf"):
+                raise ValueError(f"logit_bias: the bias {b!r} of token {kv[0]} must be a finite number")
+        pairs = sorted((int(k), float(b)) for k, b in pairs)
+        if len({k for k, _ in pairs}) != len(pairs):
+            raise ValueError("logit_bias: the token ids must be distinct")
+        object.__setattr__(self, "logit_bias", tuple(pairs))
+        try:
+            seqs = [tuple(q) for q in self.stop_sequences]
+        except TypeError:
+            raise ValueError(f"stop_sequences {self.stop_sequences!r} must be sequences of token ids") from None
+        if len(seqs) > MAX_STOP_SEQUENCES:
+            raise ValueError(f"stop_sequences: {len(seqs)} sequences (at most {MAX_STOP_SEQUENCES})")
+        for q in seqs:
+            if not 1 <= len(q) <= MAX_STOP_LEN:
+                raise ValueError(f"stop_sequences: a sequence of {len(q)} tokens (1 .. {MAX_STOP_LEN})")
+            for v in q:
+                if not _is_count(v):
+                    raise ValueError(f"stop_sequences: {v!r} must be an integer >= 0")
+        object.__setattr__(self, "stop_sequences", tuple(tuple(int(v) for v in q) for q in seqs))
 
     def __post_init__(self):
+        self._check_new_fields()
         theta = float(self.repetition_penalty)
         if not 0.0 < theta < float("inf"):
             raise ValueError(f"repetition_penalty {self.repetition_penalty} must be finite and > 0")
@@ -183,8 +244,17 @@ class DecodingConstraints:
     def applies(self, eos_id: Optional[int] = 0) -> bool:
         """whether anything is edited under a config with this ``eos_id`` (None: no EOS, so the minimum length holds nothing back).  THE
         definition of a no-op: False means no launch, and the generator's cache key stays what it is without constraints"""
+        return self.edits_logits(eos_id) or bool(self.stop_sequences)
+
+    @property
+    def edits_more(self) -> bool:
+        """a frequency or presence penalty or a bias is set: the logits are edited by ``db1_constrain_logits_pen``"""
+        return bool(self.frequency_penalty != 0.0 or self.presence_penalty != 0.0 or self.logit_bias)
+
+    def edits_logits(self, eos_id: Optional[int] = 0) -> bool:
+        """``applies`` without the stop sequences, which edit no logit: whether a constrain launch precedes the selection"""
         return bool(self.repetition_penalty != 1.0 or self.no_repeat_ngram_size or self.bad_token_ids or
-                    (self.min_new_tokens and eos_id is not None))
+                    (self.min_new_tokens and eos_id is not None) or self.edits_more)
 
     @property
     def is_noop(self) -> bool:
@@ -245,24 +315,46 @@ def _constrained(who: str, model, key: tuple, constraints, limit: int) -> tuple:
         raise TypeError(f"{who}: DecodingConstraints expected, got {type(constraints).__name__}")
     if constraints.min_new_tokens > int(limit):
         raise ValueError(f"{who}: min_new_tokens {constraints.min_new_tokens} exceeds max_new_tokens {limit}")
+    if constraints.stop_sequences and who in ("beam_search", "sample_best_of"):
+        raise ValueError(f"{who}: stop_sequences are not supported (beams and best-of-n rank whole hypotheses; use generate or a stream)")
     if not constraints.applies(key[1].eos_id):
         return key
     V = key[2]
     if not ops.constrain_logits_supported(V, V, key[1].max_new_tokens, len(constraints.bad_token_ids), model.compute_dtype):
         raise ValueError(f"{who}: db1_constrain_logits does not support max_new_tokens {key[1].max_new_tokens}")
+    if constraints.edits_more and not ops.constrain_logits_pen_supported(V, V, key[1].max_new_tokens, len(constraints.bad_token_ids),
+                                                                         len(constraints.logit_bias), model.compute_dtype):
+        raise ValueError(f"{who}: db1_constrain_logits_pen does not support {len(constraints.logit_bias)} biases")
+    if constraints.stop_sequences and not ops.stop_match_supported(len(constraints.stop_sequences), key[1].max_new_tokens):
+        raise ValueError(f"{who}: db1_stop_match does not support {len(constraints.stop_sequences)} stop sequences")
     return key + (constraints,)
 
 
 def _constrain_args(cons: Optional[DecodingConstraints], cfg, V: int, dev) -> Optional[dict]:
     """the keyword arguments a state's ``ops.constrain_logits`` call takes from its constraints (the banned ids as a device vector, made
     once); None: no launch"""
-    if cons is None or not cons.applies(cfg.eos_id):
+    if cons is None or not cons.edits_logits(cfg.eos_id):
         return None
     eos = -1 if cfg.eos_id is None else int(cfg.eos_id)
     min_new = cons.min_new_tokens if eos >= 0 else 0
     bad = torch.tensor(cons.bad_token_ids, dtype=torch.int32).to(dev) if cons.bad_token_ids else None
-    return dict(V=V, repetition_penalty=cons.repetition_penalty, no_repeat_ngram_size=cons.no_repeat_ngram_size, bad=bad, eos_id=eos,
+    args = dict(V=V, repetition_penalty=cons.repetition_penalty, no_repeat_ngram_size=cons.no_repeat_ngram_size, bad=bad, eos_id=eos,
                 min_new=min_new)
+    if cons.edits_more:      # (only then does the call go to db1_constrain_logits_pen; the bias list is a device vector made once, as ``bad``)
+        args.update(frequency_penalty=cons.frequency_penalty, presence_penalty=cons.presence_penalty)
+        if cons.logit_bias:
+            args.update(bias_ids=torch.tensor([k for k, _ in cons.logit_bias], dtype=torch.int32).to(dev),
+                        bias_val=torch.tensor([b for _, b in cons.logit_bias], dtype=torch.float32).to(dev))
+    return args
+
+
+def _stop_args(cons: Optional[DecodingConstraints], cfg, dev) -> Optional[dict]:
+    """the arguments a state's ``ops.stop_match`` call takes from its constraints (the packed sequences as device tensors, made once);
+    None: no stop sequences, no launch and no buffers"""
+    if cons is None or not cons.stop_sequences:
+        return None
+    tok, n = ops.pack_stop_sequences(cons.stop_sequences)
+    return dict(stop_tok=torch.from_numpy(tok).to(dev), stop_len=torch.from_numpy(n).to(dev), pad_id=int(cfg.pad_id))
 
 
 def _text_window(model, cfg):
@@ -395,6 +487,18 @@ class _SamplingState:
             self.top_ids = torch.full((M, cfg.max_new_tokens, n), -1, **i32)
             self.top_logprob = torch.full((M, cfg.max_new_tokens, n), float("-inf"), dtype=torch.float32, device=model.dev)
             self.sel.update(top_n=n, top_ids=self.top_ids, top_logprob=self.top_logprob)
+        # stop sequences: the packed lists and two more vectors per row, only when there are any
+        self.stop = _stop_args(cons, cfg, model.dev)
+        self.checked = self.stop_hit = None
+        if self.stop is not None:
+            self.checked, self.stop_hit = torch.zeros(M, **i32), torch.zeros(M, **i32)
+            self.stop.update({k: self.sel[k] for k in ("logprob", "sum_logprob", "top_n", "top_ids", "top_logprob") if k in self.sel})
+
+    def stop_match(self, next_ids, row_map=None):
+        """the stop sequences, after the selection: rows whose output now ends in one lose it and end (none configured: no launch)"""
+        if self.stop is not None:
+            ops.stop_match(lengths=self.lengths, checked=self.checked, finished=self.finished, stop_hit=self.stop_hit, out=self.out,
+                           next_ids=next_ids, row_map=row_map, **self.stop)
 
     def clear_top(self, idx=None):
         """-1 / -inf into the alternatives of every row (``idx``: int64 device vector, of those rows): nothing written yet"""
@@ -422,7 +526,7 @@ class _State(_SamplingState):
         self.stream_id.copy_(torch.arange(M, dtype=torch.int32))
 
     def start(self, stream_ids=None):
-        for x in (self.t, self.finished, self.lengths, self.status):
+        for x in (self.t, self.finished, self.lengths, self.status) + (() if self.stop is None else (self.checked, self.stop_hit)):
             x.zero_()
         self.out.fill_(self.cfg.pad_id)
         if self.logprob is not None:
@@ -444,6 +548,7 @@ class _State(_SamplingState):
     def epilogue(self, logits2d, next_ids, ring=None):
         self.constrain(logits2d)
         self.select(logits2d, next_ids)
+        self.stop_match(next_ids)
         self.t.add_(1)
 
     def reorder_list(self, mems):
@@ -462,7 +567,8 @@ class _State(_SamplingState):
         return out, lengths
 
     def stats(self) -> dict:
-        return {}
+        """``stop_hits`` (with stop sequences only): per row 0, or the index + 1 of the sequence that ended it"""
+        return {} if self.stop is None else dict(stop_hits=[int(v) for v in self.stop_hit.cpu()])
 
 
 class _BestOfState(_State):
@@ -649,7 +755,10 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     model has one (bf16, ``use_decode``, d_head 128), else the eager list-form loop; False forces the eager loop.  ``stats`` (a dict):
     receives the path taken and the number of per-token calls.  ``replay`` False (ring path): the same forward and epilogue run eagerly over
     the same ring instead of as a graph replay.  ``constraints`` (a ``DecodingConstraints``): applied to every step's logits
-    on the device, over the tokens generated so far, before the token is chosen.  With ``config.logprobs``: (ids, lengths, logprobs float32
+    on the device, over the tokens generated so far, before the token is chosen; a row ended by one of its ``stop_sequences`` comes back
+    without the matched tokens (``lengths[r]`` counts those before them, ``pad_id`` after; log-probs 0 and alternatives -1 / -inf there,
+    ``sum_logprob`` the sum of the kept ones) and ``stats`` then also receives ``stop_hits``: per row 0, or the matched sequence's index + 1.
+    With ``config.logprobs``: (ids, lengths, logprobs float32
     [M, max_new_tokens], sum_logprob float32 [M]) -- ``logprobs[r, t]`` is the log-probability of ``ids[r, t]`` under the model's
     distribution over the window (after the constraints, before temperature / top-k / top-p), EOS included, 0 after it; ``sum_logprob[r]``
     their fp32 sum in token order.  With ``config.top_logprobs`` n two more: top_ids int32 and top_logprobs float32, both

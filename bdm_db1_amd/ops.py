@@ -764,14 +764,21 @@ def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype)
     return bool(lib.load().db1_constrain_logits_supported(int(V), int(ld), int(max_new), int(n_bad), dt_code(dtype)))
 
 
+def constrain_logits_pen_supported(V: int, ld: int, max_new: int, n_bad: int, n_bias: int, dtype) -> bool:
+    return bool(lib.load().db1_constrain_logits_pen_supported(int(V), int(ld), int(max_new), int(n_bad), int(n_bias), dt_code(dtype)))
+
+
 def constrain_logits(logits2d, t, hist, *, V=None, finished=None, row_map=None, repetition_penalty=1.0, no_repeat_ngram_size=0, bad=None,
-                     eos_id=-1, min_new=0):
+                     eos_id=-1, min_new=0, frequency_penalty=0.0, presence_penalty=0.0, bias_ids=None, bias_val=None):
     """the decoding constraints of one step, IN PLACE on ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) before a selection
     or beam step reads it (db1_constrain_logits, rule in include/db1_hip.h): the repetition penalty over each row's history, the no-repeat
     n-gram ban, the banned ids ``bad`` (int32, device; None: none) and EOS banned while t < ``min_new``; a ban is a -inf.  ``hist`` (int32
     [S, max_new]): the tokens every slot has generated so far; ``t`` (int32, device, READ only): [1], one counter for all rows, or [S], one
     per slot; ``finished`` (int32 [S] or None): rows left alone; ``row_map`` (int32 [M]) as ``select_tokens_slots`` takes it, None: row i is
-    slot i and S = M.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    slot i and S = M.  ``frequency_penalty`` / ``presence_penalty`` (finite, 0 = off) and the bias list ``bias_ids`` (int32) / ``bias_val``
+    (float32), device vectors of one length <= 1024 with DISTINCT ids, both or neither: with any of them set the call goes to
+    db1_constrain_logits_pen (freq * count + pres off every generated token's logit, the biases added after; the rule is stated with the
+    prototype), else to db1_constrain_logits exactly as before.  Capturable; raises ValueError on bad arguments before anything is launched."""
     who, dev, i32 = "constrain_logits", logits2d.device, torch.int32
     if not torch.is_tensor(hist) or hist.dim() != 2:
         raise ValueError(f"{who}: hist must be a contiguous {i32} tensor of shape (slots, max_new) on {dev}")
@@ -807,9 +814,93 @@ def constrain_logits(logits2d, t, hist, *, V=None, finished=None, row_map=None, 
         raise ValueError(f"{who}: repetition_penalty {repetition_penalty} and its inverse must be finite and > 0 in float32")
     if int(no_repeat_ngram_size) < 0 or int(min_new) < 0:
         raise ValueError(f"{who}: no_repeat_ngram_size {no_repeat_ngram_size} and min_new {min_new} must be >= 0")
-    lib.call("db1_constrain_logits", P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(t), int(t.numel() == S and S > 1), P(hist), mx,
-             P(finished), P(row_map), S, theta32, float(np.float32(1.0 / theta32)), min(int(no_repeat_ngram_size), 2 ** 31 - 1),
-             P(bad if n_bad else None), n_bad, max(int(eos_id), -1), min(int(min_new), 2 ** 31 - 1), _vp(0), 0, stream())
+    with np.errstate(over="ignore"):
+        freq, pres = float(np.float32(frequency_penalty)), float(np.float32(presence_penalty))
+    if not (abs(freq) < float("inf") and abs(pres) < float("inf")):
+        raise ValueError(f"{who}: frequency_penalty {frequency_penalty} and presence_penalty {presence_penalty} must be finite in float32")
+    if (bias_ids is None) != (bias_val is None):
+        raise ValueError(f"{who}: bias_ids and bias_val go together (one of them is None)")
+    n_bias = 0
+    if bias_ids is not None:
+        if not torch.is_tensor(bias_ids) or not torch.is_tensor(bias_val) or bias_ids.numel() != bias_val.numel():
+            raise ValueError(f"{who}: bias_ids ({i32}) and bias_val (float32) must be device vectors of one length")
+        n_bias = int(bias_ids.numel())
+        if n_bias > 1024:
+            raise ValueError(f"{who}: {n_bias} biases (at most 1024)")
+        _check_tensor(who, "bias_ids", bias_ids, i32, n_bias, dev)
+        _check_tensor(who, "bias_val", bias_val, torch.float32, n_bias, dev)
+    head = (P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(t), int(t.numel() == S and S > 1), P(hist), mx, P(finished), P(row_map), S,
+            theta32, float(np.float32(1.0 / theta32)), min(int(no_repeat_ngram_size), 2 ** 31 - 1), P(bad if n_bad else None), n_bad,
+            max(int(eos_id), -1), min(int(min_new), 2 ** 31 - 1))
+    if freq != 0.0 or pres != 0.0 or n_bias:
+        if not constrain_logits_pen_supported(V, max(ld, V), mx, n_bad, n_bias, logits2d.dtype):
+            raise ValueError(f"{who}: db1_constrain_logits_pen does not support these shapes")
+        lib.call("db1_constrain_logits_pen", *head, freq, pres, P(bias_ids if n_bias else None), P(bias_val if n_bias else None), n_bias,
+                 _vp(0), 0, stream())
+        return
+    lib.call("db1_constrain_logits", *head, _vp(0), 0, stream())
+
+
+MAX_STOP_SEQUENCES = 16
+MAX_STOP_LEN = 16
+
+
+def stop_match_supported(n_stop: int, max_new: int) -> bool:
+    return bool(lib.load().db1_stop_match_supported(int(n_stop), int(max_new)))
+
+
+def pack_stop_sequences(seqs):
+    """stop sequences (1 .. 16 of 1 .. 16 token ids >= 0 each) -> (``stop_tok`` int32 [n, 16], sequence k in row k from column 0, the rest
+    -1; ``stop_len`` int32 [n]): THE place the layout db1_stop_match reads is written down on the host.  Pure NumPy; raises ValueError."""
+    seqs = [[int(v) for v in q] for q in seqs]
+    if not 1 <= len(seqs) <= MAX_STOP_SEQUENCES:
+        raise ValueError(f"pack_stop_sequences: {len(seqs)} sequences (1 .. {MAX_STOP_SEQUENCES})")
+    tok = np.full((len(seqs), MAX_STOP_LEN), -1, np.int32)
+    for k, q in enumerate(seqs):
+        if not 1 <= len(q) <= MAX_STOP_LEN or min(q) < 0 or max(q) >= 2 ** 31:
+            raise ValueError(f"pack_stop_sequences: sequence {k} must hold 1 .. {MAX_STOP_LEN} token ids >= 0")
+        tok[k, :len(q)] = q
+    return tok, np.array([len(q) for q in seqs], np.int32)
+
+
+def stop_match(stop_tok, stop_len, lengths, checked, finished, stop_hit, out, next_ids, *, pad_id=0, row_map=None, logprob=None,
+               sum_logprob=None, top_n=None, top_ids=None, top_logprob=None):
+    """the stop sequences of one step, after its selection launch (db1_stop_match, rule in include/db1_hip.h): a slot whose ``lengths`` moved
+    since the last look (``checked``) and whose output now ends in one of the sequences ``stop_tok`` int32 [n, 16] / ``stop_len`` int32 [n]
+    (device, ``pack_stop_sequences``) loses the matched tokens (``pad_id`` in ``out`` [S, max_new] and in ``next_ids``), gets ``finished`` = 1,
+    ``stop_hit`` = the sequence's index + 1 and ``lengths`` = ``checked`` = what is kept.  ``lengths`` / ``checked`` / ``finished`` /
+    ``stop_hit``: int32 [S]; ``row_map`` (int32 [M]) as ``select_tokens_slots`` takes it, None: every slot.  ``logprob`` / ``sum_logprob``
+    and ``top_n`` / ``top_ids`` / ``top_logprob`` as the selection takes them: the removed positions get 0 and -1 / -inf, the sum is rebuilt.
+    Capturable; raises ValueError on bad arguments before anything is launched."""
+    who, i32 = "stop_match", torch.int32
+    if not torch.is_tensor(out) or out.dim() != 2:
+        raise ValueError(f"{who}: out must be a contiguous {i32} tensor of shape (slots, max_new)")
+    dev = out.device
+    S, mx = out.shape
+    if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len) or stop_tok.dim() != 2:
+        raise ValueError(f"{who}: stop_tok [n, {MAX_STOP_LEN}] and stop_len [n] must be {i32} tensors on {dev}")
+    n = int(stop_tok.shape[0])
+    if not 1 <= n <= MAX_STOP_SEQUENCES or not stop_match_supported(n, mx):
+        raise ValueError(f"{who}: {n} stop sequences (1 .. {MAX_STOP_SEQUENCES}), max_new {mx}")
+    _check_tensor(who, "stop_tok", stop_tok, i32, (n, MAX_STOP_LEN), dev)
+    _check_tensor(who, "stop_len", stop_len, i32, (n,), dev)
+    _check_tensor(who, "out", out, i32, (S, mx), dev)
+    for name, x in (("lengths", lengths), ("checked", checked), ("finished", finished), ("stop_hit", stop_hit)):
+        _check_tensor(who, name, x, i32, S, dev)
+    M = S
+    if row_map is not None:
+        M = int(row_map.numel())
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if not 1 <= M <= S:
+            raise ValueError(f"{who}: {M} rows for {S} slots")
+    _check_next_ids(who, next_ids, S, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, S, mx, dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (S, mx), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    lib.call("db1_stop_match", P(stop_tok), P(stop_len), n, int(pad_id), P(lengths), P(checked), P(finished), P(stop_hit), P(out), mx,
+             P(next_ids), next_ids.stride(0), P(row_map), M, S, P(logprob) if lp else _vp(0), P(sum_logprob) if lp else _vp(0), top,
+             P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0), stream())
 
 
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:

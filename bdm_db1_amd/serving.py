@@ -221,14 +221,14 @@ class _SlotState(_SamplingState):
 
     def start(self):
         self.finished.fill_(1)
-        for x in (self.t, self.lengths, self.status):
+        for x in (self.t, self.lengths, self.status) + (() if self.stop is None else (self.checked, self.stop_hit)):
             x.zero_()
 
     def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int], records=None) -> torch.Tensor:
         """fresh state for the requests moving into ``slots`` (``records``: int32 [len(slots), 8], their sampling records, in a per-request
         stream) -> the slots as the int32 device vector ``select`` and ``load_rows`` take"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
-        for x in (self.t, self.lengths, self.status, self.finished):
+        for x in (self.t, self.lengths, self.status, self.finished) + (() if self.stop is None else (self.checked, self.stop_hit)):
             x.index_fill_(0, idx, 0)
         self.out.index_fill_(0, idx, self.cfg.pad_id)
         if self.logprob is not None:         # (a new tenant does not inherit the last one's log-probs or their sum)
@@ -242,20 +242,25 @@ class _SlotState(_SamplingState):
         return idx.to(torch.int32)
 
     def select(self, logits2d, next_ids, row_map=None):
+        """constrain -> select -> stop, all over the same rows: the prefill's token 0 (``row_map``: the new tenants) and every replay"""
         self.constrain(logits2d, row_map)
         if self.params is not None:
             ops.select_tokens_slots_per(logits2d, self.params, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status,
                                         row_map=row_map, **self.sel_per)
-            return
-        ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map, **self.sel)
+        else:
+            ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map,
+                                    **self.sel)
+        self.stop_match(next_ids, row_map)
 
     def epilogue(self, logits2d, next_ids, ring=None):
         self.select(logits2d, next_ids)      # (the launch advances every live slot's t itself)
 
     def read(self, slots: List[int]):
-        """(out rows, [t, length, status] rows, logprob rows or None, (top_ids rows, top_logprob rows) or None) of ``slots`` on the host"""
+        """(out rows, [t, length, status(, stop_hit)] rows, logprob rows or None, (top_ids rows, top_logprob rows) or None) of ``slots`` on the
+        host; the fourth column only with stop sequences"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
-        meta = torch.stack((self.t, self.lengths, self.status), 1).index_select(0, idx).cpu()
+        cols = (self.t, self.lengths, self.status) + (() if self.stop is None else (self.stop_hit,))
+        meta = torch.stack(cols, 1).index_select(0, idx).cpu()
         lp = None if self.logprob is None else self.logprob.index_select(0, idx).cpu()
         top = None if self.top_ids is None else (self.top_ids.index_select(0, idx).cpu(), self.top_logprob.index_select(0, idx).cpu())
         return self.out.index_select(0, idx).cpu(), meta, lp, top
@@ -281,7 +286,8 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     model: the slots, the ring and the graph are kept on the model, so a second ``generate_stream`` whose first result is asked for while
     another is still running raises RuntimeError (run the first to its end or ``close()`` it).  ``constraints`` (a ``DecodingConstraints``):
     applied on the device to every step's logits over each request's own tokens so far, whatever slot it sits in; a request whose limit is
-    below ``min_new_tokens`` raises ValueError.  With ``config.logprobs`` the stream yields ``(index, ids, length, logprobs float32 [limit])``:
+    below ``min_new_tokens`` raises ValueError; a request ended by one of the ``stop_sequences`` comes back without the matched tokens and
+    frees its slot at the host's next look, and ``stats`` then also receives ``stopped``, their count.  With ``config.logprobs`` the stream yields ``(index, ids, length, logprobs float32 [limit])``:
     every token's log-probability as ``generate`` returns it (EOS included, 0 after it); with ``config.top_logprobs`` n two more fields,
     ``top_ids int32 [limit, n]`` and ``top_logprobs float32 [limit, n]``, as ``generate`` returns them (-1 / -inf after the request's last
     token).  ``per_request`` True: a request may also be ``(prompt, max_new_tokens or None, SamplingParams)`` and is then decoded under its
@@ -324,6 +330,8 @@ def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
     inherit = SamplingParams()
     sched = SlotScheduler(slots, reqs)
     counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
+    if len(key) > 4 and key[4] is not None and key[4].stop_sequences:      # (the key set is what it was without stop sequences)
+        counts["stopped"] = 0
     live_steps = 0
 
     def report():
@@ -368,7 +376,9 @@ def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
                     if done:
                         out, meta, lp, top = st.read([s for s, _ in done])
                         for j, (_, r) in enumerate(done):
-                            t, length, status = (int(v) for v in meta[j])
+                            t, length, status, *hit = (int(v) for v in meta[j])
+                            if hit and hit[0]:
+                                counts["stopped"] += 1
                             if status & 2:
                                 raise RuntimeError("db1_select_tokens_slots: a slot's token counter left [0, limit)")
                             if status & 4:

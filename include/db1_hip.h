@@ -732,6 +732,58 @@ int64_t db1_constrain_logits_workspace_bytes(int M, int V, int max_new, int n_ba
 int db1_constrain_logits(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist, int max_new,
                          const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
                          const int32_t* bad, int n_bad, int eos_id, int min_new, void* ws, int64_t ws_bytes, void* stream);
+/* db1_constrain_logits_pen: db1_constrain_logits with a frequency penalty freq, a presence penalty pres (any finite value, negative ones
+ * included; 0 = off) and an additive bias list bias_ids / bias_val [n_bias] (device, n_bias <= 1024; the ids DISTINCT: the caller's to keep,
+ * a device list cannot be checked at the launch) -- tests/penalty_rule.py restates the rule in NumPy.  The guard (1) and the bans (3 .. 7)
+ * are db1_constrain_logits' own and the bans still come last, so a ban overrides everything.  Step 2 becomes, for a row that passed the guard:
+ *   2a. penalties: every DISTINCT token c of H with 0 <= c < V and l[c] finite is edited once; n_c = its number of occurrences in H (entries
+ *       of H outside [0, V) are neither penalised nor counted):
+ *         v = l32, the stored value widened to fp32;
+ *         theta != 1:            v = l32 > 0 ? v * inv_theta : v * theta            (the multiplication of db1_constrain_logits)
+ *         freq != 0 || pres != 0: p = fp32(n_c) * freq;  p = p + pres;  v = v - p    (three fp32 operations, each rounded, NONE fused: not
+ *                                                                                   with each other and not with the multiplication above)
+ *         l[c] <- round(v), ONE store: identity (fp32), round to nearest even (bf16);
+ *   2b. after a workgroup barrier, the bias: for every (id, b) with 0 <= id < V whose STORED logit, as the penalties left it, is finite:
+ *       l[id] <- round(widen(l[id]) + b), one fp32 addition.  A column that is in the history and in the bias list is therefore rounded
+ *       twice in bf16: that is the rule (one writer per column per phase, no atomics).  Non-finite logits are left as stored;
+ *   then a barrier, then the bans.
+ * The thread that holds a token's first occurrence counts its later copies in the staged history: this count scan roughly doubles the
+ * worst-case O(t^2 / 256) term of the first-occurrence test (all tokens distinct); O(t + n_bad + n_bias) columns are touched.  No atomics,
+ * LDS the 16 KB of history; t, hist, finished, row_map and the three lists are only READ: capturable.  The new mode is a compile-time flag
+ * of the kernel: db1_constrain_logits launches the instantiation it always did, and with freq == 0, pres == 0 and n_bias == 0 this entry
+ * point launches that one too (the same bits; no launch when nothing else is set either).  _supported adds n_bias <= 1024; no workspace. */
+int db1_constrain_logits_pen_supported(int V, int64_t ld, int max_new, int n_bad, int n_bias, int dt);
+int64_t db1_constrain_logits_pen_workspace_bytes(int M, int V, int max_new, int n_bad, int n_bias, int dt);
+int db1_constrain_logits_pen(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, int t_per_slot, const int32_t* hist, int max_new,
+                             const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
+                             const int32_t* bad, int n_bad, int eos_id, int min_new, float freq, float pres, const int32_t* bias_ids,
+                             const float* bias_val, int n_bias, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------ stop sequences (tests/stop_rule.py restates the rule in NumPy).
+ * db1_stop_match runs AFTER the selection launch of a step (db1_select_tokens / _slots / _slots_per and their _lp / _top forms) on the state
+ * that launch has just updated, and ends every row whose generated tokens now end in one of n_stop token sequences (1 <= n_stop <= 16):
+ * stop_tok int32 [n_stop, 16] and stop_len int32 [n_stop] (each 1 .. 16; a length outside matches nothing), both on the device.  Two int32
+ * vectors of state per slot next to the selection's: checked (the value of lengths at the last look) and stop_hit; both zero when a
+ * generation starts or a request moves into a slot.  For logits row i with s = row_map[i] (NULL: s = i, and then n_slots == M; an s outside
+ * [0, n_slots) is skipped):
+ *   1. n = lengths[s]; n == checked[s]: nothing of the slot is touched.  The selection grows lengths exactly when it writes a token that is
+ *      not EOS, so this skips vacant slots, rows that finished earlier, rows that just wrote EOS and rows without a candidate, and it does
+ *      examine a slot that reached its limit on this very token; neither t nor the lockstep / slot distinction is needed;
+ *   2. checked[s] = n; n < 1 or n > max_new: nothing else;
+ *   3. sequence k of length L matches if L <= n and out[s, n - L + j] == stop_tok[k, j] for all j < L (nothing before column 0 is read: only
+ *      generated tokens are matched, never the prompt); the longest match wins, the lowest k among equals; no match: done;
+ *   4. on a match, m = n - L: out[s, m .. n) = pad_id, lengths[s] = checked[s] = m, finished[s] = 1, stop_hit[s] = k + 1,
+ *      next_ids[s * ids_stride] = pad_id; with logprob / sum_logprob (both or neither): logprob[s, m .. n) = 0 and sum_logprob[s] = the fp32
+ *      sum of logprob[s, 0 .. m) added one by one from 0.0f -- the bits the selection's running sum had after token m - 1; with top_n /
+ *      top_ids / top_logprob (all or none, only with the log-prob pair; top_n 0 and NULL: none): [s, m .. n, :] = -1 / -inf.
+ * One wave per row: lane k tests sequence k, one fixed-order wave maximum picks the winner, the lanes clear the range, lane 0 re-adds the
+ * sum.  No atomics, no workspace, no LDS; nothing is read back: capturable and replayable.  A bad combination of the optional buffers, a
+ * NULL required one or a shape out of range is DB1_ERR_BAD_SHAPE, n_stop > 16 DB1_ERR_UNSUPPORTED (_supported), before any launch. */
+int db1_stop_match_supported(int n_stop, int max_new);
+int db1_stop_match(const int32_t* stop_tok, const int32_t* stop_len, int n_stop, int pad_id, int32_t* lengths, int32_t* checked,
+                   int32_t* finished, int32_t* stop_hit, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride,
+                   const int32_t* row_map, int M, int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                   float* top_logprob, void* stream);
 
 /* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
  * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window

@@ -44,6 +44,17 @@ the minimum length bans nothing) --, one JSON line per M; under rocprofv3 --kern
 
     python tools/bench_generate.py --constraints [M ...]
 
+--constraints takes the newer fields as flags of their own, added to the constraints above: --penalties (frequency_penalty 0.5,
+presence_penalty 0.5: the launch becomes db1_constrain_logits_pen), --logit-bias N (an N-entry bias, ids spread over the text vocabulary)
+and --stop-sequences (two sequences of ids outside the text window, so they never match: one db1_stop_match launch more in every replay
+and no row ends early).  --constrain-kernels [M]: the kernels alone, device time per call from events in ONE process:
+db1_constrain_logits (theta 1.2) and db1_constrain_logits_pen (theta 1.2, both penalties, a 16-entry bias) on bf16 logits [M, 33 025] over
+histories of t = 255 / 1023 / 4095 DISTINCT tokens (the worst case of the first-occurrence and count scans), and db1_stop_match with 16
+sequences of 16 tokens whose first 15 tokens every row's tail matches (every lane compares to the end, nothing is trimmed).
+
+    python tools/bench_generate.py --constraints --penalties --logit-bias 16 --stop-sequences [M ...]
+    python tools/bench_generate.py --constrain-kernels [M]
+
 With --logprobs: the greedy and top-p 0.9 caption measurements above with ``GenerationConfig(logprobs=False)`` and ``logprobs=True`` (the
 replay ends in db1_select_tokens_lp instead of db1_select_tokens), and the two kernels alone on random bf16 logits [M, 33 025] over the text
 window (device time per call from events over 50 calls), one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel times of
@@ -381,6 +392,41 @@ def stream_per_request_main(n_req=256, slots=64):
     print(json.dumps(rec), flush=True)
 
 
+def constrain_kernels_us(M=64, max_new=4096, ts=(255, 1023, 4095)):
+    """db1_constrain_logits, db1_constrain_logits_pen and db1_stop_match alone (the docstring above says on what)"""
+    V, hi = int(model.total_vocab_size), int(model.text_vocab_size)
+    logits = (torch.randn(M, V, device=dev) * 3).to(torch.bfloat16)
+    i32 = dict(dtype=torch.int32, device=dev)
+    hist = ((torch.arange(max_new, device=dev)[None, :] * 7 + torch.arange(M, device=dev)[:, None] * 13) % hi).to(torch.int32).contiguous()
+    assert all(len(set(r.tolist())) == max_new for r in hist[:2].cpu())
+    bias_ids = (torch.arange(16, device=dev) * 2001).to(torch.int32)
+    bias_val = torch.linspace(-2, 2, 16, device=dev)
+    rec = {"M": M}
+    for t in ts:
+        tt = torch.tensor([t], **i32)
+        rec[f"constrain_t{t}_us"] = round(device_us(lambda: ops.constrain_logits(logits, tt, hist, V=V, repetition_penalty=1.2)), 2)
+        rec[f"constrain_pen_t{t}_us"] = round(device_us(lambda: ops.constrain_logits(
+            logits, tt, hist, V=V, repetition_penalty=1.2, frequency_penalty=0.5, presence_penalty=0.5, bias_ids=bias_ids, bias_val=bias_val)), 2)
+        rec[f"count_scan_t{t}_us"] = round(rec[f"constrain_pen_t{t}_us"] - rec[f"constrain_t{t}_us"], 2)
+    # db1_stop_match: every row holds 20 tokens whose last 15 are the first 15 of every sequence; ``checked`` is rewound before every launch
+    seqs = [list(range(100, 115)) + [200 + k] for k in range(16)]
+    tok, n = ops.pack_stop_sequences(seqs)
+    tok, n = torch.from_numpy(tok).to(dev), torch.from_numpy(n).to(dev)
+    lengths, checked, fin, hit = torch.full((M,), 20, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32)
+    out = torch.zeros(M, N_NEW, **i32)
+    out[:, 4:19] = torch.arange(100, 115, **i32)
+    out[:, 19] = 114
+    ids = torch.zeros(M, dtype=torch.long, device=dev)
+
+    def stop():
+        checked.zero_()
+        ops.stop_match(tok, n, lengths, checked, fin, hit, out, ids)
+    rewind = device_us(lambda: checked.zero_())
+    rec["stop_match_16x16_us"] = round(device_us(stop) - rewind, 2)
+    assert int(hit.max()) == 0 and int(checked.min()) == 20
+    return rec
+
+
 SELECT_MODES = {"greedy": dict(), "top_p_0.9": dict(greedy=False, top_p=0.9, seed=1)}
 
 
@@ -465,13 +511,31 @@ if "--num-beams" in args:
     W = int(args[i + 1])
     beam_main(W, [int(a) for a in args[:i] + args[i + 2:]] or [1, 16])
     sys.exit(0)
+if "--constrain-kernels" in args:
+    print(json.dumps(constrain_kernels_us(*[int(a) for a in args if a != "--constrain-kernels"][:1])), flush=True)
+    sys.exit(0)
 if "--constraints" in args:
     cons = DecodingConstraints(repetition_penalty=1.2, no_repeat_ngram_size=3, min_new_tokens=5)
+    if "--penalties" in args:
+        cons = dataclasses.replace(cons, frequency_penalty=0.5, presence_penalty=0.5)
+    if "--logit-bias" in args:
+        i = args.index("--logit-bias")
+        nb = int(args[i + 1])
+        args = args[:i] + args[i + 2:]
+        cons = dataclasses.replace(cons, logit_bias={(k * int(model.text_vocab_size)) // nb: (k % 5 - 2) * 0.5 for k in range(nb)})
+    if "--stop-sequences" in args:      # (ids past the text window are never generated: the sequences never match)
+        tv = int(model.text_vocab_size)
+        cons = dataclasses.replace(cons, stop_sequences=[(tv, tv + 1), (tv + 2, tv + 3, tv + 4)])
+    args = [a for a in args if a not in ("--penalties", "--stop-sequences")]
     for M in [int(a) for a in args if a != "--constraints"] or [1, 16, 64]:
         rec = {"M": M, "new_tokens": N_NEW, "constraints": dataclasses.asdict(cons)}
         rec["greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW)), 4)
         rec["constrained_greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW), constraints=cons), 4)
         rec["constrained_minus_plain_us"] = round((rec["constrained_greedy_ms_per_token"] - rec["greedy_ms_per_token"]) * 1e3, 2)
+        if cons.edits_more or cons.stop_sequences:      # the kernels' own time at this M, mid-caption (t = 15), from events in this process
+            model._generator = None
+            torch.cuda.empty_cache()
+            rec.update({k: v for k, v in constrain_kernels_us(M, N_NEW, (15,)).items() if k != "M"})
         print(json.dumps(rec), flush=True)
     sys.exit(0)
 Ms = [int(a) for a in args] or [1, 16, 64]
