@@ -9,6 +9,9 @@
 // writes the row's scalars and re-adds the kept log-probs one by one from 0.0f: the order, and so the bits, of the selection's own running
 // sum.  A workgroup owns its slot (row_map entries are distinct): no atomics, no workspace; every argument is a pointer or a launch scalar
 // and nothing is read back: the launch can be captured and replayed.
+//
+// db1_stop_match_per (tests/slot_constraints_rule.py) is the PER instantiation: every slot has its own list, stop_tok [n_slots, 16, 16] and
+// stop_len [n_slots, 16], and all 16 lanes look (an unused entry has length 0, which matches nothing).  Nothing else differs.
 #include "db1_common.h"
 
 #define STOP_THREADS 64
@@ -33,6 +36,7 @@ struct StopArgs {
     float* top_logprob;
 };
 
+template <bool PER>
 __global__ __launch_bounds__(STOP_THREADS) void stop_match_kernel(StopArgs a) {
     const int lane = threadIdx.x;
     const int s = a.row_map ? a.row_map[blockIdx.x] : (int)blockIdx.x;
@@ -44,10 +48,11 @@ __global__ __launch_bounds__(STOP_THREADS) void stop_match_kernel(StopArgs a) {
     int* o = a.out + (int64_t)s * a.max_new;
     // lane k: does sequence k end the row?  (a length outside 1 .. 16 in the device list matches nothing: nothing is read through it)
     int key = 0;
-    if (lane < a.n_stop) {
-        const int len = a.stop_len[lane];
+    if (lane < (PER ? STOP_MAX_SEQ : a.n_stop)) {
+        const int e = PER ? s * STOP_MAX_SEQ + lane : lane;      // (PER: the slot's own list)
+        const int len = a.stop_len[e];
         if (len >= 1 && len <= STOP_MAX_LEN && len <= n) {
-            const int* q = a.stop_tok + lane * STOP_MAX_LEN;
+            const int* q = a.stop_tok + e * STOP_MAX_LEN;
             bool same = true;
             for (int j = 0; j < len; j++) same = same && o[n - len + j] == q[j];
             if (same) key = (len << 6) | (63 - lane);    // longest first, then the lowest k
@@ -107,7 +112,31 @@ extern "C" int db1_stop_match(const int32_t* stop_tok, const int32_t* stop_len, 
     a.lengths = lengths; a.checked = checked; a.finished = finished; a.stop_hit = stop_hit; a.out = out; a.next_ids = next_ids;
     a.ids_stride = ids_stride; a.row_map = row_map; a.logprob = logprob; a.sum_logprob = sum_logprob; a.top_ids = top_ids;
     a.top_logprob = top_logprob;
-    stop_match_kernel<<<M, STOP_THREADS, 0, (hipStream_t)stream>>>(a);
+    stop_match_kernel<false><<<M, STOP_THREADS, 0, (hipStream_t)stream>>>(a);
+    DB1_CHECK_LAUNCH(who);
+    return DB1_OK;
+}
+
+extern "C" int db1_stop_match_per(const int32_t* stop_tok, const int32_t* stop_len, int pad_id, int32_t* lengths, int32_t* checked,
+                                  int32_t* finished, int32_t* stop_hit, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride,
+                                  const int32_t* row_map, int M, int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
+                                  float* top_logprob, void* stream) {
+    const char* who = "stop_match_per";
+    if (M <= 0 || M > 65535 || n_slots <= 0 || max_new <= 0 || (!row_map && n_slots != M))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d n_slots=%d max_new=%d%s", who, M, n_slots, max_new,
+                 !row_map ? " (no row_map: n_slots must equal M)" : "");
+    if (!stop_tok || !stop_len || !lengths || !checked || !finished || !stop_hit || !out || !next_ids)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
+    if ((logprob == nullptr) != (sum_logprob == nullptr)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: logprob and sum_logprob go together", who);
+    const bool top = top_n != 0 || top_ids || top_logprob;
+    if (top && (top_n < 1 || top_n > 16 || !top_ids || !top_logprob || !logprob))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_n=%d needs 1 <= top_n <= 16, top_ids, top_logprob and the log-prob buffers", who, top_n);
+    StopArgs a = {};
+    a.stop_tok = stop_tok; a.stop_len = stop_len; a.n_stop = STOP_MAX_SEQ; a.pad_id = pad_id; a.max_new = max_new; a.n_slots = n_slots;
+    a.top_n = top_n; a.lengths = lengths; a.checked = checked; a.finished = finished; a.stop_hit = stop_hit; a.out = out; a.next_ids = next_ids;
+    a.ids_stride = ids_stride; a.row_map = row_map; a.logprob = logprob; a.sum_logprob = sum_logprob; a.top_ids = top_ids;
+    a.top_logprob = top_logprob;
+    stop_match_kernel<true><<<M, STOP_THREADS, 0, (hipStream_t)stream>>>(a);
     DB1_CHECK_LAUNCH(who);
     return DB1_OK;
 }

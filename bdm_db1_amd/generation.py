@@ -89,7 +89,8 @@ class SamplingParams:
     """One request's own sampling parameters in a stream run with ``per_request=True`` (serving.py): the fields of ``GenerationConfig`` that
     ``db1_select_tokens_slots_per`` reads per slot.  ``None`` inherits the stream config's value; for the window that is the RESOLVED one
     (``vocab_hi``: the text vocabulary under ``caption_stream`` / ``answer_stream``, else the config's, else the model's whole vocabulary).
-    ``eos_id``, ``pad_id``, the constraints and the log-prob switches stay the stream's."""
+    ``eos_id``, ``pad_id`` and the log-prob switches stay the stream's; so do the constraints, unless the stream also sets
+    ``per_request_constraints`` (serving.py): then a request may carry its own ``DecodingConstraints`` as a fourth element."""
     greedy: Optional[bool] = None
     temperature: Optional[float] = None
     top_k: Optional[int] = None
@@ -165,7 +166,9 @@ class DecodingConstraints:
     those tokens' logits at every step, after the penalties; a ban still overrides it.  ``stop_sequences`` (at most 16 sequences of 1 .. 16
     token ids): a row whose generated tokens end in one of them ends there, and the matched tokens are removed from what comes back
     (``db1_stop_match``, tests/stop_rule.py); the longest match wins, then the first listed.  Passed as ``constraints=`` to ``generate``,
-    ``beam_search`` and the streams; ``beam_search`` and ``sample_best_of`` refuse stop sequences."""
+    ``beam_search`` and the streams; ``beam_search`` and ``sample_best_of`` refuse stop sequences.  In a stream with
+    ``per_request_constraints=True`` a request may carry an object of its own, which replaces the stream's as a whole
+    (``db1_constrain_logits_slots_per`` / ``db1_stop_match_per`` read every slot's values from device tables)."""
     repetition_penalty: float = 1.0
     no_repeat_ngram_size: int = 0
     min_new_tokens: int = 0

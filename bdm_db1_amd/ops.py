@@ -903,6 +903,150 @@ def stop_match(stop_tok, stop_len, lengths, checked, finished, stop_hit, out, ne
              P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0), stream())
 
 
+SLOT_CONS_WORDS = 8
+MAX_SLOT_LIST = 1024      # the most a slot's banned-id or bias row can hold (db1_constrain_logits_slots_supported)
+
+
+def pack_slot_constraints(cons, eos_id, bad_cap: int, bias_cap: int):
+    """one slot's constraints as ``constrain_logits_slots_per`` and ``stop_match_per`` read them (include/db1_hip.h) -> (``rec`` int32 [8],
+    ``bad`` int32 [bad_cap], ``bias_ids`` int32 [bias_cap], ``bias_val`` float32 [bias_cap], ``stop_tok`` int32 [16, 16], ``stop_len``
+    int32 [16]); THE place the record's layout is written down on the host: word 0 the fp32 bits of ``theta`` (the repetition penalty), 1
+    those of ``1 / theta`` (one fp32 division, the one the scalar forms do), 2 ``ngram``, 3 ``min_new`` (0 when ``eos_id`` is None or
+    negative), 4 / 5 the fp32 bits of the frequency / presence penalty, 6 ``n_bad``, 7 ``n_bias``.  Unused list entries are -1 (ids) and
+    0.0 (bias values); the stop table is ``pack_stop_sequences``' with length 0 in the unused entries.  ``cons``: a ``DecodingConstraints``
+    or None (the record that edits nothing).  Pure NumPy; raises ValueError for what the kernel's guard would refuse and for lists beyond
+    the capacities."""
+    bad_cap, bias_cap = int(bad_cap), int(bias_cap)
+    if not (0 <= bad_cap <= MAX_SLOT_LIST and 0 <= bias_cap <= MAX_SLOT_LIST):
+        raise ValueError(f"pack_slot_constraints: capacities {bad_cap}, {bias_cap} must lie in [0, {MAX_SLOT_LIST}]")
+    theta, ngram, min_new, freq, pres, ids, bias, stops = 1.0, 0, 0, 0.0, 0.0, (), (), ()
+    if cons is not None:
+        theta, ngram, min_new = cons.repetition_penalty, cons.no_repeat_ngram_size, cons.min_new_tokens
+        freq, pres, ids, bias, stops = cons.frequency_penalty, cons.presence_penalty, cons.bad_token_ids, cons.logit_bias, cons.stop_sequences
+    if len(ids) > bad_cap:
+        raise ValueError(f"pack_slot_constraints: {len(ids)} banned ids for a capacity of {bad_cap}")
+    if len(bias) > bias_cap:
+        raise ValueError(f"pack_slot_constraints: {len(bias)} biases for a capacity of {bias_cap}")
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        f = np.array([theta, 0.0, freq, pres], np.float32)
+        f[1] = np.float32(1) / f[0]
+    if not (np.isfinite(f).all() and f[0] > 0 and f[1] > 0):
+        raise ValueError(f"pack_slot_constraints: repetition_penalty {theta} and its inverse must be finite and > 0, frequency_penalty {freq} "
+                         f"and presence_penalty {pres} finite, all in float32")
+    if int(ngram) < 0 or int(min_new) < 0:
+        raise ValueError(f"pack_slot_constraints: no_repeat_ngram_size {ngram} and min_new_tokens {min_new} must be >= 0")
+    if eos_id is None or int(eos_id) < 0:
+        min_new = 0
+    w = np.zeros(SLOT_CONS_WORDS, np.uint32)
+    w[0:2] = f[0:2].view(np.uint32)
+    w[2:4] = np.minimum(np.array([ngram, min_new], np.int64), 2 ** 31 - 1).astype(np.int32).view(np.uint32)
+    w[4:6] = f[2:4].view(np.uint32)
+    w[6], w[7] = len(ids), len(bias)
+    bad = np.full(bad_cap, -1, np.int32)
+    bad[:len(ids)] = np.asarray(ids, np.int64)
+    bias_ids, bias_val = np.full(bias_cap, -1, np.int32), np.zeros(bias_cap, np.float32)
+    bias_ids[:len(bias)] = [k for k, _ in bias]
+    bias_val[:len(bias)] = [b for _, b in bias]
+    stop_tok, stop_len = np.full((MAX_STOP_SEQUENCES, MAX_STOP_LEN), -1, np.int32), np.zeros(MAX_STOP_SEQUENCES, np.int32)
+    if stops:
+        tok, n = pack_stop_sequences(stops)
+        stop_tok[:len(n)], stop_len[:len(n)] = tok, n
+    return w.view(np.int32), bad, bias_ids, bias_val, stop_tok, stop_len
+
+
+def constrain_logits_slots_supported(V: int, ld: int, max_new: int, bad_cap: int, bias_cap: int, dtype) -> bool:
+    return bool(lib.load().db1_constrain_logits_slots_supported(int(V), int(ld), int(max_new), int(bad_cap), int(bias_cap), dt_code(dtype)))
+
+
+def constrain_logits_slots_per(logits2d, cons, t, hist, finished, status, *, V=None, row_map=None, bad=None, bias_ids=None, bias_val=None,
+                               eos_id=-1):
+    """``constrain_logits`` with every slot's OWN constraints (db1_constrain_logits_slots_per, rule in include/db1_hip.h): ``cons`` (int32
+    [S, 8], contiguous, on the device, 32-byte aligned; one ``pack_slot_constraints`` record per slot, indexed by the slot like ``t``), the
+    banned ids ``bad`` (int32 [S, bad_cap]) and the biases ``bias_ids`` (int32) / ``bias_val`` (float32) [S, bias_cap], row s the lists of
+    slot s (None: a capacity of 0), take the place of the scalars and the shared lists; ``t`` int32 [S], ``hist`` int32 [S, max_new].  A
+    valid slot's row comes out exactly as ``constrain_logits`` would leave it under the slot's values.  The records are device data, so the
+    KERNEL checks them: a live slot whose record it refuses gets status bit 3 (value 8) in ``status`` and ``finished`` = 1 (both int32 [S],
+    written), its logits untouched.  Capturable; raises ValueError on bad arguments before anything is launched."""
+    who, dev, i32 = "constrain_logits_slots_per", logits2d.device, torch.int32
+    if not torch.is_tensor(hist) or hist.dim() != 2:
+        raise ValueError(f"{who}: hist must be a contiguous {i32} tensor of shape (slots, max_new) on {dev}")
+    S, mx = hist.shape
+    if not 1 <= mx <= 4096:
+        raise ValueError(f"{who}: max_new {mx} (the columns of hist) must lie in [1, 4096]")
+    caps = []
+    for name, x in (("bad", bad), ("bias_ids", bias_ids), ("bias_val", bias_val)):
+        if x is not None and (not torch.is_tensor(x) or x.dim() != 2):
+            raise ValueError(f"{who}: {name} must be a tensor of shape (slots, capacity) on {dev}, or None")
+        caps.append(0 if x is None else int(x.shape[1]))
+    bad_cap, bias_cap = caps[0], caps[1]
+    if caps[1] != caps[2]:
+        raise ValueError(f"{who}: bias_ids and bias_val must have one shape (or both be None)")
+    if bad_cap > MAX_SLOT_LIST or bias_cap > MAX_SLOT_LIST:
+        raise ValueError(f"{who}: capacities {bad_cap}, {bias_cap} (at most {MAX_SLOT_LIST})")
+    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None,
+                                   lambda V, ld: constrain_logits_slots_supported(V, max(ld, V), mx, bad_cap, bias_cap, logits2d.dtype))
+    _check_tensor(who, "hist", hist, i32, (S, mx), dev)
+    if row_map is not None:
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if S < M:
+            raise ValueError(f"{who}: {M} logits rows for {S} slots")
+    elif S != M:
+        raise ValueError(f"{who}: hist holds {S} rows for {M} logits rows (no row_map)")
+    for name, x in (("t", t), ("finished", finished), ("status", status), ("cons", cons)):
+        if not torch.is_tensor(x):      # (none of them is optional here: the guard writes finished and status)
+            raise ValueError(f"{who}: {name} must be a {i32} tensor on {dev}, got {type(x).__name__}")
+    for name, x in (("t", t), ("finished", finished), ("status", status)):
+        _check_tensor(who, name, x, i32, S, dev)
+    _check_tensor(who, "cons", cons, i32, (S, SLOT_CONS_WORDS), dev)
+    if cons.data_ptr() % 32:
+        raise ValueError(f"{who}: cons must be 32-byte aligned")
+    if bad_cap:
+        _check_tensor(who, "bad", bad, i32, (S, bad_cap), dev)
+    if bias_cap:
+        _check_tensor(who, "bias_ids", bias_ids, i32, (S, bias_cap), dev)
+        _check_tensor(who, "bias_val", bias_val, torch.float32, (S, bias_cap), dev)
+    lib.call("db1_constrain_logits_slots_per", P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(t), P(hist), mx, P(finished), P(status),
+             P(row_map), S, P(cons), P(bad if bad_cap else None), bad_cap, P(bias_ids if bias_cap else None),
+             P(bias_val if bias_cap else None), bias_cap, max(int(eos_id), -1), _vp(0), 0, stream())
+
+
+def stop_match_per(stop_tok, stop_len, lengths, checked, finished, stop_hit, out, next_ids, *, pad_id=0, row_map=None, logprob=None,
+                   sum_logprob=None, top_n=None, top_ids=None, top_logprob=None):
+    """``stop_match`` with every slot's OWN list (db1_stop_match_per, rule in include/db1_hip.h): ``stop_tok`` int32 [S, 16, 16] and
+    ``stop_len`` int32 [S, 16] (device; slot s's ``pack_slot_constraints`` table at [s]; an unused entry has length 0), everything else as
+    ``stop_match`` takes it, and a slot comes out exactly as that would leave it under the slot's list.  Capturable; raises ValueError on
+    bad arguments before anything is launched."""
+    who, i32 = "stop_match_per", torch.int32
+    if not torch.is_tensor(out) or out.dim() != 2:
+        raise ValueError(f"{who}: out must be a contiguous {i32} tensor of shape (slots, max_new)")
+    dev = out.device
+    S, mx = out.shape
+    if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len):
+        raise ValueError(f"{who}: stop_tok [slots, {MAX_STOP_SEQUENCES}, {MAX_STOP_LEN}] and stop_len [slots, {MAX_STOP_SEQUENCES}] must be "
+                         f"{i32} tensors on {dev}")
+    if mx < 1:
+        raise ValueError(f"{who}: max_new {mx}")
+    _check_tensor(who, "stop_tok", stop_tok, i32, (S, MAX_STOP_SEQUENCES, MAX_STOP_LEN), dev)
+    _check_tensor(who, "stop_len", stop_len, i32, (S, MAX_STOP_SEQUENCES), dev)
+    _check_tensor(who, "out", out, i32, (S, mx), dev)
+    for name, x in (("lengths", lengths), ("checked", checked), ("finished", finished), ("stop_hit", stop_hit)):
+        _check_tensor(who, name, x, i32, S, dev)
+    M = S
+    if row_map is not None:
+        M = int(row_map.numel())
+        _check_tensor(who, "row_map", row_map, i32, M, dev)
+        if not 1 <= M <= S:
+            raise ValueError(f"{who}: {M} rows for {S} slots")
+    _check_next_ids(who, next_ids, S, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, S, mx, dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (S, mx), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    lib.call("db1_stop_match_per", P(stop_tok), P(stop_len), int(pad_id), P(lengths), P(checked), P(finished), P(stop_hit), P(out), mx,
+             P(next_ids), next_ids.stride(0), P(row_map), M, S, P(logprob) if lp else _vp(0), P(sum_logprob) if lp else _vp(0), top,
+             P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0), stream())
+
+
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:
     return bool(lib.load().db1_beam_step_supported(int(V), int(ld), int(W), dt_code(dtype)))
 

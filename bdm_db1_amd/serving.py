@@ -14,7 +14,9 @@ other rows go on:
     slots of the newly admitted rows (``row_map``), picks their token 0 from the prefill's last-position logits straight into their slots;
   * with ``per_request=True`` the graph ends in db1_select_tokens_slots_per instead, which reads greedy / temperature / top-k / top-p / seed
     and the vocabulary window of every slot from a device record the admission writes (``SamplingParams``): requests that are decoded
-    differently share one stream, one graph and one batch.
+    differently share one stream, one graph and one batch;
+  * with ``per_request_constraints=True`` the selection is framed by db1_constrain_logits_slots_per and db1_stop_match_per, which read every
+    slot's penalties, bans, bias and stop sequences from device tables the admission writes (a ``DecodingConstraints`` per request).
 
 A request's tokens depend on its prompt, its stream id, the seed and its token index: not on the slot it got or on when it was admitted.
 What the host decides -- which slot, which requests share a prefill, the order results come back in -- is ``SlotScheduler``, plain Python.
@@ -39,13 +41,15 @@ from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, Ge
 class Request:
     """one row of a prompt batch: ``index`` (its place in the results, and its default Philox stream), the batch and the row in it, its
     token limit, and ``key``: requests with equal keys have one prompt shape and can share a prefill; ``params``: its own
-    ``SamplingParams`` in a ``per_request`` stream (None: the stream config's)"""
+    ``SamplingParams`` in a ``per_request`` stream (None: the stream config's); ``constraints``: its own ``DecodingConstraints`` in a
+    ``per_request_constraints`` stream (None: the stream's)"""
     index: int
     limit: int
     key: tuple
     prompt: object = None
     row: int = 0
     params: Optional[SamplingParams] = None
+    constraints: Optional[DecodingConstraints] = None
 
 
 @dataclasses.dataclass
@@ -55,6 +59,7 @@ class _Item:
     indices: object
     limit: Optional[int] = None
     params: Optional[SamplingParams] = None
+    constraints: Optional[DecodingConstraints] = None
 
 
 _SEQ_FIELDS = ("text_seq", "prompt_seq", "img_seq")            # what makes a prompt's shape
@@ -71,19 +76,25 @@ def _shape_key(prompt) -> tuple:
 
 
 def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_request: bool = False,
-              window: Optional[Tuple[int, int]] = None) -> Iterator[Request]:
+              window: Optional[Tuple[int, int]] = None, caps: Optional[Tuple[int, int]] = None) -> Iterator[Request]:
     """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item; ``per_request``: also (prompt, max_new_tokens or None,
-    SamplingParams or None)) as Requests, numbered in order; raises ValueError for a limit outside [1, cfg.max_new_tokens] or below
-    ``min_new`` (the constraints' minimum length), for params when ``per_request`` is off, for params that do not resolve under ``cfg`` and
-    ``window`` = (V, hi) (``SamplingParams.resolve``; None: not checked here) and what ``generate`` raises for a prompt batch that is not
-    one shape"""
+    SamplingParams or None); ``caps`` = (max_bad_token_ids, max_logit_bias), the per-request-constraints flag: also (prompt,
+    max_new_tokens or None, SamplingParams or None, DecodingConstraints or None)) as Requests, numbered in order; raises ValueError for a
+    limit outside [1, cfg.max_new_tokens] or below ``min_new`` (the minimum length of the constraints the request runs under: its own, else
+    the stream's), for params when ``per_request`` is off, for params that do not resolve under ``cfg`` and ``window`` = (V, hi)
+    (``SamplingParams.resolve``; None: not checked here), for constraints when ``caps`` is None, that are no ``DecodingConstraints`` or
+    that hold more banned ids or biases than ``caps``, and what ``generate`` raises for a prompt batch that is not one shape"""
     nxt = 0
     for item in items:
-        indices = params = None
+        indices = params = cons = None
         if isinstance(item, _Item):
-            prompt, limit, indices, params = item.prompt, item.limit, item.indices, item.params
+            prompt, limit, indices, params, cons = item.prompt, item.limit, item.indices, item.params, item.constraints
         elif isinstance(item, tuple):
-            if len(item) == 3 and per_request:
+            if len(item) == 4 and caps is not None:
+                prompt, limit, params, cons = item
+            elif len(item) == 4 and item[3] is not None:
+                raise ValueError("generate_stream: a request with DecodingConstraints needs per_request_constraints=True")
+            elif len(item) == 3 and per_request:
                 prompt, limit, params = item
             elif len(item) == 3 and item[2] is not None:
                 raise ValueError("generate_stream: a request with SamplingParams needs per_request=True")
@@ -101,11 +112,19 @@ def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_requ
                 raise ValueError(f"generate_stream: SamplingParams expected as a request's third element, got {type(params).__name__}")
             if window is not None:
                 params.resolve(cfg, *window)
+        need = min_new
+        if cons is not None:
+            if caps is None:
+                raise ValueError("generate_stream: a request with DecodingConstraints needs per_request_constraints=True")
+            if not isinstance(cons, DecodingConstraints):
+                raise ValueError(f"generate_stream: DecodingConstraints expected as a request's fourth element, got {type(cons).__name__}")
+            _fits(cons, caps, "a request's")
+            need = cons.min_new_tokens     # (the request's object replaces the stream's as a whole)
         limit = int(cfg.max_new_tokens if limit is None else limit)
         if not 1 <= limit <= int(cfg.max_new_tokens):
             raise ValueError(f"generate_stream: a request's max_new_tokens {limit} must lie in [1, config.max_new_tokens = {cfg.max_new_tokens}]")
-        if limit < min_new:
-            raise ValueError(f"generate_stream: min_new_tokens {min_new} exceeds a request's max_new_tokens {limit}")
+        if limit < need:
+            raise ValueError(f"generate_stream: min_new_tokens {need} exceeds a request's max_new_tokens {limit}")
         G = _batch_size(prompt)
         key = _shape_key(prompt)
         if indices is None:
@@ -113,8 +132,16 @@ def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_requ
         elif len(indices) != G:
             raise ValueError(f"generate_stream: {len(indices)} indices for a prompt batch of {G} rows")
         for r, i in enumerate(indices):
-            yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r, params=params)
+            yield Request(index=int(i), limit=limit, key=key, prompt=prompt, row=r, params=params, constraints=cons)
             nxt = max(nxt, int(i) + 1)
+
+
+def _fits(cons: DecodingConstraints, caps: Tuple[int, int], whose: str):
+    """raise ValueError if ``cons`` holds more banned ids or biases than the stream's capacities ``caps``"""
+    if len(cons.bad_token_ids) > caps[0]:
+        raise ValueError(f"generate_stream: {whose} {len(cons.bad_token_ids)} bad_token_ids exceed max_bad_token_ids = {caps[0]}")
+    if len(cons.logit_bias) > caps[1]:
+        raise ValueError(f"generate_stream: {whose} {len(cons.logit_bias)} logit_bias entries exceed max_logit_bias = {caps[1]}")
 
 
 def _gather(reqs: List[Request]):
@@ -203,13 +230,17 @@ class SlotScheduler:
 # ----------------------------------------------------------------------------------------------------------------------- the device state
 class _SlotState(_SamplingState):
     """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row; ``per``: also every slot's
-    sampling record ``params`` [slots, 8] (``ops.pack_slot_params``), and the selection is db1_select_tokens_slots_per"""
+    sampling record ``params`` [slots, 8] (``ops.pack_slot_params``), and the selection is db1_select_tokens_slots_per; ``caps`` =
+    (max_bad_token_ids, max_logit_bias): every slot's constraints live in device tables (``ops.pack_slot_constraints``: the record
+    ``cons_rec`` [slots, 8], ``bad`` [slots, caps[0]], ``bias_ids`` / ``bias_val`` [slots, caps[1]], ``stop_tok`` [slots, 16, 16] and
+    ``stop_len`` [slots, 16]), ``cons`` is only what a slot starts with and a request without its own runs under, and the selection is
+    framed by db1_constrain_logits_slots_per and db1_stop_match_per, both always launched"""
     cache = "_slot_generator"
     _PER_SLOT = ("vocab_lo", "vocab_hi", "greedy", "temperature", "top_k", "top_p", "seed")     # what the record replaces in ``sel``
 
     def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None,
-                 per: bool = False):
-        super().__init__(model, slots, cfg, V, hi, cons)
+                 per: bool = False, caps: Optional[Tuple[int, int]] = None):
+        super().__init__(model, slots, cfg, V, hi, None if caps is not None else cons)
         self.t = torch.zeros(slots, **self.i32)
         self.limit = torch.ones(slots, **self.i32)
         self.finished.fill_(1)       # (vacant)
@@ -218,17 +249,30 @@ class _SlotState(_SamplingState):
             rec = ops.pack_slot_params(**SamplingParams().resolve(cfg, V, hi))
             self.params = torch.from_numpy(np.tile(rec, (slots, 1))).to(self.dev)
             self.sel_per = {k: v for k, v in self.sel.items() if k not in self._PER_SLOT}
+        self.caps, self.tables = caps, None
+        if caps is not None:     # (every slot starts with the stream's own constraints, as it starts with the config's sampling record)
+            self.eos = -1 if cfg.eos_id is None else int(cfg.eos_id)
+            self.stream_rows = ops.pack_slot_constraints(cons, cfg.eos_id, *caps)
+            self.tables = [torch.from_numpy(np.tile(x, (slots,) + (1,) * x.ndim)).to(self.dev) for x in self.stream_rows]
+            self.cons_rec, self.bad, self.bias_ids, self.bias_val, self.stop_tok, self.stop_len = self.tables
+            self.checked, self.stop_hit = torch.zeros(slots, **self.i32), torch.zeros(slots, **self.i32)
+            self.stop_per = {k: self.sel[k] for k in ("logprob", "sum_logprob", "top_n", "top_ids", "top_logprob") if k in self.sel}
 
     def start(self):
         self.finished.fill_(1)
-        for x in (self.t, self.lengths, self.status) + (() if self.stop is None else (self.checked, self.stop_hit)):
+        for x in (self.t, self.lengths, self.status) + (() if self.checked is None else (self.checked, self.stop_hit)):
             x.zero_()
+        if self.tables is not None:
+            for tab, row in zip(self.tables, self.stream_rows):
+                tab.copy_(torch.from_numpy(row).to(self.dev).expand_as(tab))
 
-    def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int], records=None) -> torch.Tensor:
+    def occupy(self, slots: List[int], limits: List[int], stream_ids: List[int], records=None, constraints=None) -> torch.Tensor:
         """fresh state for the requests moving into ``slots`` (``records``: int32 [len(slots), 8], their sampling records, in a per-request
-        stream) -> the slots as the int32 device vector ``select`` and ``load_rows`` take"""
+        stream; ``constraints``: one ``ops.pack_slot_constraints`` result per request, in a per-request-constraints stream: every table
+        row of the slot is overwritten, so nothing of the last tenant's lists stays) -> the slots as the int32 device vector ``select`` and
+        ``load_rows`` take"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
-        for x in (self.t, self.lengths, self.status, self.finished) + (() if self.stop is None else (self.checked, self.stop_hit)):
+        for x in (self.t, self.lengths, self.status, self.finished) + (() if self.checked is None else (self.checked, self.stop_hit)):
             x.index_fill_(0, idx, 0)
         self.out.index_fill_(0, idx, self.cfg.pad_id)
         if self.logprob is not None:         # (a new tenant does not inherit the last one's log-probs or their sum)
@@ -239,7 +283,29 @@ class _SlotState(_SamplingState):
         self.stream_id.index_copy_(0, idx, torch.from_numpy(np.asarray(stream_ids, dtype=np.int64).astype(np.int32)).to(self.dev))
         if self.params is not None:
             self.params.index_copy_(0, idx, torch.from_numpy(np.ascontiguousarray(records, dtype=np.int32)).to(self.dev))
+        if self.tables is not None:     # (the six rows of every new tenant side by side as 32-bit words: ONE copy to the device)
+            n = len(slots)
+            words = np.concatenate([np.stack([c[k] for c in constraints]).reshape(n, -1).view(np.int32) for k in range(len(self.tables))], 1)
+            words, at = torch.from_numpy(words).to(self.dev), 0
+            for tab in self.tables:
+                w = tab[0].numel()
+                if w:
+                    tab.index_copy_(0, idx, words[:, at:at + w].contiguous().view(tab.dtype).reshape(n, *tab.shape[1:]))
+                at += w
         return idx.to(torch.int32)
+
+    def constrain(self, logits2d, row_map=None):
+        if self.tables is None:
+            return super().constrain(logits2d, row_map)
+        ops.constrain_logits_slots_per(logits2d, self.cons_rec, self.t, self.out, self.finished, self.status, V=self.V, row_map=row_map,
+                                       bad=self.bad if self.caps[0] else None, bias_ids=self.bias_ids if self.caps[1] else None,
+                                       bias_val=self.bias_val if self.caps[1] else None, eos_id=self.eos)
+
+    def stop_match(self, next_ids, row_map=None):
+        if self.tables is None:
+            return super().stop_match(next_ids, row_map)
+        ops.stop_match_per(self.stop_tok, self.stop_len, self.lengths, self.checked, self.finished, self.stop_hit, self.out, next_ids,
+                           pad_id=int(self.cfg.pad_id), row_map=row_map, **self.stop_per)
 
     def select(self, logits2d, next_ids, row_map=None):
         """constrain -> select -> stop, all over the same rows: the prefill's token 0 (``row_map``: the new tenants) and every replay"""
@@ -257,9 +323,9 @@ class _SlotState(_SamplingState):
 
     def read(self, slots: List[int]):
         """(out rows, [t, length, status(, stop_hit)] rows, logprob rows or None, (top_ids rows, top_logprob rows) or None) of ``slots`` on the
-        host; the fourth column only with stop sequences"""
+        host; the fourth column only with stop sequences (per-request constraints: always)"""
         idx = torch.tensor(slots, dtype=torch.int64).to(self.dev)
-        cols = (self.t, self.lengths, self.status) + (() if self.stop is None else (self.stop_hit,))
+        cols = (self.t, self.lengths, self.status) + (() if self.checked is None else (self.stop_hit,))
         meta = torch.stack(cols, 1).index_select(0, idx).cpu()
         lp = None if self.logprob is None else self.logprob.index_select(0, idx).cpu()
         top = None if self.top_ids is None else (self.top_ids.index_select(0, idx).cpu(), self.top_logprob.index_select(0, idx).cpu())
@@ -269,7 +335,8 @@ class _SlotState(_SamplingState):
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
 def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig] = None, slots: int = 8, stream_ids=None,
                     stats: Optional[dict] = None, replay: bool = True,
-                    constraints: Optional[DecodingConstraints] = None, per_request: bool = False) -> Iterator[tuple]:
+                    constraints: Optional[DecodingConstraints] = None, per_request: bool = False, per_request_constraints: bool = False,
+                    max_bad_token_ids: int = 64, max_logit_bias: int = 64) -> Iterator[tuple]:
     """Generate for a stream of requests over ``slots`` recycled rows; yields ``(index, ids int32 [limit], length)`` on the host as requests
     finish (requests that are found finished at the same look come in index order).  ``ids[:length]`` are the tokens before EOS, then EOS,
     then ``pad_id``.
@@ -295,7 +362,15 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     the config.  The stream's graph then ends in db1_select_tokens_slots_per, which reads every slot's parameters on the device; the flag is
     needed up front because ``requests`` is consumed lazily and the captured graph holds one kernel or the other, and it joins the
     generator's cache key.  ``eos_id``, ``pad_id``, the constraints and the log-prob switches stay the stream's.  False: nothing changes, and
-    a request that carries params raises ValueError (a list or tuple of requests: before any launch)."""
+    a request that carries params raises ValueError (a list or tuple of requests: before any launch).  ``per_request_constraints`` True: a
+    request may also be ``(prompt, max_new_tokens or None, SamplingParams or None, DecodingConstraints or None)`` (the third element None
+    unless ``per_request`` is set too: the two flags are independent) and then runs under its OWN constraints, which replace the stream's
+    ``constraints=`` as a whole (there are no "inherit" fields); a request without one runs under the stream's, or under none.  The
+    graph's epilogue is then db1_constrain_logits_slots_per, the selection, db1_stop_match_per, all three always captured, reading every
+    slot's record and lists from device tables the admission writes; ``max_bad_token_ids`` / ``max_logit_bias`` (0 .. 1024 each) are the
+    tables' widths, the most banned ids / biases ANY request (or the stream's object) may hold.  The flag is needed up front for the
+    reason ``per_request`` is and joins the cache key with the two capacities; ``stats["stopped"]`` is then always present.  False: nothing
+    changes, and a request that carries constraints raises ValueError."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -311,10 +386,32 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     per_request = bool(per_request)
     if per_request:     # (with the flag off the key is what it was)
         key = _per_request_key(key)
+    caps = None
+    if per_request_constraints:     # (with the flag off the key is what it was, and neither capacity is looked at)
+        caps = _capacities(max_bad_token_ids, max_logit_bias)
+        if not ops.constrain_logits_slots_supported(V, V, cfg.max_new_tokens, caps[0], caps[1], model.compute_dtype):
+            raise ValueError(f"db1_constrain_logits_slots_per does not support a vocabulary of {V} with max_new_tokens {cfg.max_new_tokens}")
+        if constraints is not None:
+            _fits(constraints, caps, "the stream's")
+        key = _per_request_constraints_key(key, per_request, caps)
     if isinstance(requests, (list, tuple)):
-        for _ in _requests(requests, cfg, min_new, per_request, (V, hi)):     # (a list can be checked as a whole before the first launch)
+        for _ in _requests(requests, cfg, min_new, per_request, (V, hi), caps):     # (a list can be checked as a whole before the first launch)
             pass
-    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi)), key, stream_ids, stats, replay, per_request)
+    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi), caps), key, stream_ids, stats, replay, per_request)
+
+
+def _capacities(max_bad_token_ids, max_logit_bias) -> Tuple[int, int]:
+    for name, v in (("max_bad_token_ids", max_bad_token_ids), ("max_logit_bias", max_logit_bias)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= ops.MAX_SLOT_LIST:
+            raise ValueError(f"generate_stream: {name} {v!r} must be an integer in [0, {ops.MAX_SLOT_LIST}]")
+    return int(max_bad_token_ids), int(max_logit_bias)
+
+
+def _per_request_constraints_key(key: tuple, per: bool, caps: Tuple[int, int]) -> tuple:
+    """the state key of a stream with the per-request-constraints flag set, (slots, cfg, V, hi, cons, per, caps): ``_SlotState``'s
+    arguments by name, as ``_per_request_key`` builds them, with the two capacities last"""
+    slots, cfg, V, hi, cons, _ = _per_request_key(key[:5] if len(key) > 4 else key)
+    return (slots, cfg, V, hi, cons, bool(per), caps)
 
 
 def _per_request_key(key: tuple) -> tuple:
@@ -330,7 +427,9 @@ def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
     inherit = SamplingParams()
     sched = SlotScheduler(slots, reqs)
     counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
-    if len(key) > 4 and key[4] is not None and key[4].stop_sequences:      # (the key set is what it was without stop sequences)
+    caps = key[6] if len(key) > 6 else None
+    stream_cons = key[4] if len(key) > 4 else None
+    if caps is not None or (stream_cons is not None and stream_cons.stop_sequences):      # (the key set is what it was without stop sequences)
         counts["stopped"] = 0
     live_steps = 0
 
@@ -361,7 +460,12 @@ def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
                     # one prefill for the group; its last position picks token 0 of every request straight into its slot, its memory moves in
                     logits, mems = _prefill(model, _gather(rs), len(rs))
                     recs = np.stack([ops.pack_slot_params(**(r.params or inherit).resolve(cfg, V, hi)) for r in rs]) if per else None
-                    idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs], recs)
+                    packed = None
+                    if caps is not None:     # (packing validates every record on the host before it is written)
+                        packed = [st.stream_rows if r.constraints is None else ops.pack_slot_constraints(r.constraints, cfg.eos_id, *caps)
+                                  for r in rs]
+                    idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs], recs,
+                                    packed)
                     st.select(logits[:, -1], step.ids[:, 0], row_map=idx)
                     gen.ring.load_rows(mems, idx)
                     del logits, mems
@@ -385,6 +489,10 @@ def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
                                 raise RuntimeError("db1_select_tokens_slots_per: a slot's sampling parameters were refused on the device "
                                                    "(SamplingParams.resolve validates every record on the host before it is written, so "
                                                    "this cannot happen unless the slot state was overwritten)")
+                            if status & 8:
+                                raise RuntimeError("db1_constrain_logits_slots_per: a slot's constraints were refused on the device "
+                                                   "(ops.pack_slot_constraints validates every record on the host before it is written, "
+                                                   "so this cannot happen unless the slot state was overwritten)")
                             counts["no_candidate"] += status & 1
                             live_steps += t - 1
                             results.append((r.index, out[j, :r.limit].clone(), length) + (() if lp is None else (lp[j, :r.limit].clone(),)) +
@@ -416,7 +524,8 @@ def generate_many(model, requests: Iterable, config: Optional[GenerationConfig] 
 
 
 def _split(item):
-    """a stream wrapper's item -> (batch, max_new_tokens or None, what follows: () or (SamplingParams,), passed through as it is)"""
+    """a stream wrapper's item -> (batch, max_new_tokens or None, what follows: (), (SamplingParams,) or (SamplingParams or None,
+    DecodingConstraints or None), passed through as it is)"""
     if not isinstance(item, tuple):
         return item, None, ()
     b, limit, *rest = item
@@ -425,7 +534,8 @@ def _split(item):
 
 def caption_stream(model, ic_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
     """``generate_stream`` over ``ICTaskInput`` batches (or ``(batch, max_new_tokens)``; ``per_request=True``: or ``(batch, max_new_tokens
-    or None, SamplingParams)``, the params of every image of the batch): the prompts of ``caption_prompt``, tokens in the text vocabulary
+    or None, SamplingParams)``, the params of every image of the batch; ``per_request_constraints=True``: with a fourth element, the
+    ``DecodingConstraints`` of every image of the batch): the prompts of ``caption_prompt``, tokens in the text vocabulary
     unless ``cfg`` (or a request's own params) says otherwise; every image is one request"""
     cfg = _text_window(model, cfg or GenerationConfig())
 
@@ -439,7 +549,8 @@ def caption_stream(model, ic_batches: Iterable, cfg: Optional[GenerationConfig] 
 
 def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] = None, **kw):
     """``generate_stream`` over ``VQATaskInput`` batches (or ``(batch, max_new_tokens)``; ``per_request=True``: or ``(batch, max_new_tokens
-    or None, SamplingParams)``, the params of every question of the batch) whose questions may differ in length (``question_prompts``),
+    or None, SamplingParams)``, the params of every question of the batch; ``per_request_constraints=True``: with a fourth element, the
+    ``DecodingConstraints`` of every question of the batch) whose questions may differ in length (``question_prompts``),
     tokens in the text vocabulary unless ``cfg`` (or a request's own params) says otherwise; every question is one request, and the
     results' indices number the batches' rows in their original order"""
     cfg = _text_window(model, cfg or GenerationConfig())
@@ -448,8 +559,9 @@ def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] 
         base = 0
         for it in vqa_batches:
             b, limit, rest = _split(it)
-            if len(rest) > 1:
-                raise ValueError("answer_stream: a request is a batch, (batch, max_new_tokens) or (batch, max_new_tokens, SamplingParams)")
+            if len(rest) > 2:
+                raise ValueError("answer_stream: a request is a batch, (batch, max_new_tokens), (batch, max_new_tokens, SamplingParams) or "
+                                 "(batch, max_new_tokens, SamplingParams, DecodingConstraints)")
             for prompt, rows in question_prompts(b):
                 yield _Item(prompt, [base + int(r) for r in rows], limit, *rest)
             base += _batch_size(b)

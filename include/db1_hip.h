@@ -758,6 +758,43 @@ int db1_constrain_logits_pen(void* logits, int M, int V, int64_t ld, int dt, con
                              const int32_t* finished, const int32_t* row_map, int n_slots, float theta, float inv_theta, int ngram,
                              const int32_t* bad, int n_bad, int eos_id, int min_new, float freq, float pres, const int32_t* bias_ids,
                              const float* bias_val, int n_bias, void* ws, int64_t ws_bytes, void* stream);
+/* db1_constrain_logits_slots_per: db1_constrain_logits_pen with the constraints of every SLOT read on the device instead of passed as launch
+ * scalars and one shared list each, so ONE captured launch serves requests that are constrained differently (tests/slot_constraints_rule.py
+ * restates the rule in NumPy on top of tests/penalty_rule.py).  t is int32 [n_slots] (always per slot), hist [n_slots, max_new]; cons is
+ * int32 [n_slots, 8], 32 bytes per slot, the base 32-byte aligned, indexed by the SLOT (not by the logits row); floats as their fp32 bits:
+ *     word 0  theta (the repetition penalty)        word 4  freq
+ *     word 1  inv_theta = fp32 1 / theta (ONE fp32  word 5  pres
+ *             division on the host, the one the     word 6  n_bad  (entries used of the slot's row of bad)
+ *             scalar forms do; the kernel divides   word 7  n_bias (entries used of the slot's rows of bias_ids / bias_val)
+ *             nothing)
+ *     word 2  ngram
+ *     word 3  min_new (already 0 when there is no eos_id)
+ * bad is int32 [n_slots, bad_cap], bias_ids int32 and bias_val float [n_slots, bias_cap], row s the lists of slot s (the bias ids of a slot
+ * DISTINCT); 0 <= bad_cap, bias_cap <= 1024, and a capacity of 0 allows NULL for its lists.  eos_id stays per launch.  For logits row i with
+ * slot = row_map[i] (NULL: i, and then n_slots == M):
+ *   1. guard, in this order: a slot outside [0, n_slots); finished[slot] != 0; t[slot] outside [0, max_new): the row is left alone and the
+ *      record is never looked at;
+ *   2. the eight words are read (uniform over the workgroup, before the history is staged).  The launch cannot check device data, so the
+ *      kernel does: a record is INVALID if theta or inv_theta is not finite and positive, ngram < 0, min_new < 0, freq or pres is not finite,
+ *      n_bad is outside [0, bad_cap] or n_bias outside [0, bias_cap].  An invalid slot gets status bit 3 (status[slot] |= 8) and
+ *      finished[slot] = 1, written by one thread; no bit of its logits changes, and the selection that follows treats it as any finished slot
+ *      (pad_id fed forward);
+ *   3. a record that edits nothing (theta == 1, freq == pres == 0, ngram == 0, n_bad == n_bias == 0, and eos_id < 0 or min_new == 0) leaves
+ *      before the history is staged: the row keeps its bits;
+ *   4. otherwise the row's bits are exactly those of db1_constrain_logits_pen called with the slot's values as scalars and the slot's own
+ *      list rows (with freq == pres == 0 and n_bias == 0 those of db1_constrain_logits): the same phases in the same order, the same
+ *      unfused products.
+ * A compile-time mode of the same kernel; the other two entry points launch the instantiations they always did.  Its queries are those of
+ * the slot form, db1_constrain_logits_slots_supported / _workspace_bytes (as db1_select_tokens_slots' hold for its _per form): they take the
+ * two capacities where db1_constrain_logits_pen's take n_bad and n_bias.  No atomics, no workspace (the query returns 0), LDS the 16 KB of history; only finished and status of an invalid slot are written besides the logits: capturable.
+ * A NULL cons, finished or status, a cons that is not 32-byte aligned or a NULL list with a capacity above 0 is DB1_ERR_BAD_SHAPE, a
+ * capacity above 1024 or max_new above 4096 DB1_ERR_UNSUPPORTED (_supported), before any launch. */
+int db1_constrain_logits_slots_supported(int V, int64_t ld, int max_new, int bad_cap, int bias_cap, int dt);
+int64_t db1_constrain_logits_slots_workspace_bytes(int M, int V, int max_new, int bad_cap, int bias_cap, int dt);
+int db1_constrain_logits_slots_per(void* logits, int M, int V, int64_t ld, int dt, const int32_t* t, const int32_t* hist, int max_new,
+                                   int32_t* finished, int32_t* status, const int32_t* row_map, int n_slots, const int32_t* cons,
+                                   const int32_t* bad, int bad_cap, const int32_t* bias_ids, const float* bias_val, int bias_cap, int eos_id,
+                                   void* ws, int64_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ stop sequences (tests/stop_rule.py restates the rule in NumPy).
  * db1_stop_match runs AFTER the selection launch of a step (db1_select_tokens / _slots / _slots_per and their _lp / _top forms) on the state
@@ -784,6 +821,15 @@ int db1_stop_match(const int32_t* stop_tok, const int32_t* stop_len, int n_stop,
                    int32_t* finished, int32_t* stop_hit, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride,
                    const int32_t* row_map, int M, int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids,
                    float* top_logprob, void* stream);
+/* db1_stop_match_per: db1_stop_match with every SLOT's own list (tests/slot_constraints_rule.py): stop_tok is int32 [n_slots, 16, 16] and
+ * stop_len int32 [n_slots, 16], both indexed by the slot s of step 1 above.  There is no n_stop: all 16 entries of the slot's list are
+ * looked at, and an unused entry has length 0 (a length outside 1 .. 16 matches nothing, as above; a slot whose 16 lengths are 0 has no
+ * stop sequence).  Everything else -- steps 1 .. 4, the longest match and then the lowest index, what is cleared, the sum rebuilt in token
+ * order -- is bit for bit db1_stop_match called with the slot's own list.  A compile-time mode of the same kernel: one wave per row, no LDS,
+ * no atomics, no workspace; capturable.  The same refusals before any launch. */
+int db1_stop_match_per(const int32_t* stop_tok, const int32_t* stop_len, int pad_id, int32_t* lengths, int32_t* checked, int32_t* finished,
+                       int32_t* stop_hit, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, const int32_t* row_map, int M,
+                       int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* stream);
 
 /* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
  * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window

@@ -38,6 +38,17 @@ instantiations only.
 
     python tools/bench_generate.py --stream --per-request [requests [slots]]
 
+With --stream --per-request-constraints: the stream workload above (greedy) in three forms: flag off, ``per_request_constraints=True``
+with no request carrying constraints, and the flag with every second request under DecodingConstraints(repetition_penalty=1.2,
+no_repeat_ngram_size=3) -- the graph's epilogue is db1_constrain_logits_slots_per, the selection, db1_stop_match_per --; one JSON line
+with the totals (``*_total_ms`` / ``*_runs_ms`` as --per-request reports them) and replay counts, and the two per-slot kernels alone on
+bf16 logits [slots, 33 025] after t = 29 tokens per slot: all records no-op, all under those constraints, half of each, next to
+db1_constrain_logits with the same scalars; db1_stop_match_per over empty tables and over 16 x 16 tables next to db1_stop_match.
+
+    python tools/bench_generate.py --stream --per-request-constraints [requests [slots]]
+    python tools/bench_generate.py --slot-constrain-kernels noop|constrained|half_and_half [M]   (the two kernels alone over ONE kind of
+                                                                                                  table: the run to trace)
+
 With --constraints: the greedy caption measurement above, unconstrained and with DecodingConstraints(repetition_penalty=1.2,
 no_repeat_ngram_size=3, min_new_tokens=5) -- one db1_constrain_logits launch more in every replay (no EOS, as in every run here, so
 the minimum length bans nothing) --, one JSON line per M; under rocprofv3 --kernel-trace --stats: the kernel time of db1_constrain_logits.
@@ -392,6 +403,92 @@ def stream_per_request_main(n_req=256, slots=64):
     print(json.dumps(rec), flush=True)
 
 
+def slot_constrain_kernels_us(M, t=N_NEW - 1, bad_cap=64, bias_cap=64, only=None):
+    """db1_constrain_logits_slots_per and db1_stop_match_per alone (the docstring above says on what)"""
+    V, hi = int(model.total_vocab_size), int(model.text_vocab_size)
+    logits = (torch.randn(M, V, device=dev) * 3).to(torch.bfloat16)
+    i32 = dict(dtype=torch.int32, device=dev)
+    hist = ((torch.arange(N_NEW, device=dev)[None, :] * 7 + torch.arange(M, device=dev)[:, None] * 13) % hi).to(torch.int32).contiguous()
+    tt, fin, status = torch.full((M,), t, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32)
+    cons = DecodingConstraints(repetition_penalty=1.2, no_repeat_ngram_size=3)
+    rows = {"noop": ops.pack_slot_constraints(None, None, bad_cap, bias_cap), "constrained": ops.pack_slot_constraints(cons, None, bad_cap, bias_cap)}
+    tables = {"noop": [rows["noop"]] * M, "constrained": [rows["constrained"]] * M,
+              "half_and_half": [rows["noop" if i % 2 == 0 else "constrained"] for i in range(M)]}
+    rec = {}
+    for name, table in tables.items():
+        if only not in (None, name):
+            continue
+        c, bad, bi, bv = (torch.from_numpy(np.stack([r[k] for r in table])).to(dev) for k in range(4))
+        rec[f"constrain_slots_per_{name}_us"] = round(device_us(lambda: ops.constrain_logits_slots_per(
+            logits, c, tt, hist, fin, status, V=V, bad=bad, bias_ids=bi, bias_val=bv)), 2)
+    assert int(status.max()) == 0 and int(fin.max()) == 0
+    rec["constrain_scalar_us"] = round(device_us(lambda: ops.constrain_logits(logits, tt, hist, V=V, finished=fin, repetition_penalty=1.2,
+                                                                               no_repeat_ngram_size=3)), 2)
+    # the stop kernels: every row holds 20 tokens whose last 15 are the first 15 of every sequence; ``checked`` is rewound before every launch
+    seqs = [list(range(100, 115)) + [200 + k] for k in range(16)]
+    full = ops.pack_slot_constraints(DecodingConstraints(stop_sequences=seqs), None, 0, 0)
+    lengths, checked, hit = torch.full((M,), 20, **i32), torch.zeros(M, **i32), torch.zeros(M, **i32)
+    out = torch.zeros(M, N_NEW, **i32)
+    out[:, 4:19] = torch.arange(100, 115, **i32)
+    out[:, 19] = 114
+    ids = torch.zeros(M, dtype=torch.long, device=dev)
+    rewind = device_us(lambda: checked.zero_())
+
+    def timed(fn):
+        def go():
+            checked.zero_()
+            fn()
+        return round(device_us(go) - rewind, 2)
+
+    for name, row in (("empty", rows["noop"]), ("16x16", full)):
+        if only not in (None, "noop" if name == "empty" else "constrained"):
+            continue
+        tok, n = (torch.from_numpy(np.tile(row[k], (M,) + (1,) * row[k].ndim)).to(dev) for k in (4, 5))
+        rec[f"stop_match_per_{name}_us"] = timed(lambda: ops.stop_match_per(tok, n, lengths, checked, fin, hit, out, ids))
+    tok, n = torch.from_numpy(full[4]).to(dev), torch.from_numpy(full[5]).to(dev)
+    rec["stop_match_16x16_us"] = timed(lambda: ops.stop_match(tok, n, lengths, checked, fin, hit, out, ids))
+    assert int(hit.max()) == 0 and int(checked.min()) == 20
+    return rec
+
+
+def stream_per_request_constraints_main(n_req=256, slots=64):
+    from bdm_db1_amd import caption_stream
+    limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
+    cfg = GenerationConfig(max_new_tokens=N_NEW)
+    batches = [batch(slots + k) for k in range((n_req + slots - 1) // slots)]
+    rows = lambda b, r: ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=b.prompt_seq[r:r + 1],
+                                    img_seq=b.img_seq[r:r + 1], text_seq=None)
+    shared = [(rows(batches[i // slots], i % slots), int(limits[i])) for i in range(n_req)]
+    cons = DecodingConstraints(repetition_penalty=1.2, no_repeat_ngram_size=3)
+    mixed = [r if i % 2 == 0 else r + (None, cons) for i, r in enumerate(shared)]
+    rec = {"requests": n_req, "slots": slots, "limits": "uniform 5..30, seed 2024",
+           "mix": "even requests unconstrained, odd requests repetition_penalty 1.2 + no_repeat_ngram_size 3"}
+
+    def total(reqs, **kw):
+        stats = {}
+
+        def run():
+            for _ in caption_stream(model, reqs, cfg, slots=slots, stats=stats, **kw):
+                pass
+        run()                                  # capture + warm-up
+        ts = []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return round(min(ts), 2), [round(x, 2) for x in ts], stats["replays"]
+
+    rec["flag_off_total_ms"], rec["flag_off_runs_ms"], rec["flag_off_replays"] = total(shared)
+    rec["flag_only_total_ms"], rec["flag_only_runs_ms"], rec["flag_only_replays"] = total(shared, per_request_constraints=True)
+    rec["mixed_total_ms"], rec["mixed_runs_ms"], rec["mixed_replays"] = total(mixed, per_request_constraints=True)
+    model._slot_generator = None
+    torch.cuda.empty_cache()
+    rec.update(slot_constrain_kernels_us(slots))
+    print(json.dumps(rec), flush=True)
+
+
 def constrain_kernels_us(M=64, max_new=4096, ts=(255, 1023, 4095)):
     """db1_constrain_logits, db1_constrain_logits_pen and db1_stop_match alone (the docstring above says on what)"""
     V, hi = int(model.total_vocab_size), int(model.text_vocab_size)
@@ -503,13 +600,19 @@ if "--best-of" in args:
     best_of_main(int(args[i + 1]), [int(a) for a in args[:i] + args[i + 2:]] or [16])
     sys.exit(0)
 if "--stream" in args:
-    rest = [int(a) for a in args if a not in ("--stream", "--per-request")]
-    (stream_per_request_main if "--per-request" in args else stream_main)(*rest[:2])
+    rest = [int(a) for a in args if a not in ("--stream", "--per-request", "--per-request-constraints")]
+    (stream_per_request_constraints_main if "--per-request-constraints" in args else
+     stream_per_request_main if "--per-request" in args else stream_main)(*rest[:2])
     sys.exit(0)
 if "--num-beams" in args:
     i = args.index("--num-beams")
     W = int(args[i + 1])
     beam_main(W, [int(a) for a in args[:i] + args[i + 2:]] or [1, 16])
+    sys.exit(0)
+if "--slot-constrain-kernels" in args:
+    i = args.index("--slot-constrain-kernels")
+    M = int(args[i + 2]) if len(args) > i + 2 else 64
+    print(json.dumps({"M": M, **slot_constrain_kernels_us(M, only=args[i + 1])}), flush=True)
     sys.exit(0)
 if "--constrain-kernels" in args:
     print(json.dumps(constrain_kernels_us(*[int(a) for a in args if a != "--constrain-kernels"][:1])), flush=True)
