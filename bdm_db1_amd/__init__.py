@@ -5,7 +5,7 @@ if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
 __all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "GraphedTrainStep",
            "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
-           "DecodingConstraints", "SamplingParams", "sample_best_of", "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers",
+           "DecodingConstraints", "SamplingParams", "sample_best_of", "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers", "score_document", "document_segments",
            "generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler"]
 
 
@@ -29,7 +29,7 @@ def __getattr__(name):
                 "DecodingConstraints", "SamplingParams", "sample_best_of"):
         from . import generation
         return getattr(generation, name)
-    if name in ("ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers"):
+    if name in ("ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers", "score_document", "document_segments"):
         from . import scoring
         return getattr(scoring, name)
     if name in ("generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler"):

@@ -1,0 +1,266 @@
+// Relative-position attention over Transformer-XL memory for ANY number of new queries (prompt prefill, long-text scoring): q = 1 .. 8192
+// new queries against klen = mlen + q keys / values (bf16, d_head = 128), operands and rule of relattn_decode.hip:
+//     s[i,j] = ((q_i+u).k_j + (q_i+v).R[clip(mlen+i-j, 0, nd-1)]) * scale,   visible iff  i - shift < j <= i + mlen,   j in [0, klen)
+// One launch, no partials, no merge, no workspace, no atomics: a workgroup of 256 threads owns 64 consecutive queries of one (b, h) and walks
+// every 32-key step that any of its rows can see, in key order -- two launches on the same inputs give the same bits.
+//   grid = (ceil(q / 64), heads, batch); wave w owns queries 16 w .. 16 w + 15 of the block, as in relattn_decode_kernel.
+//   K and V of a step are staged ONCE per workgroup in LDS (the four waves read the same keys), double-buffered: the rows of step s + 1
+//   travel in registers while step s is computed and are written to the other buffer before the step's single barrier.  Because of the
+//   barrier no wave leaves the loop early: a wave without rows, or outside its own window, walks the block's steps and computes nothing.
+//   16-byte slots are XOR-swizzled so that both kinds of read are conflict-free: K (ds_read_b128, row = key) slot ^ (row & 15);
+//   V (ds_read_b64_tr_b16, 8 rows x 32 bytes per 32-lane half) slot ^ 2 (row & 7).
+//   The R rows live in an LDS ring of 128 rows indexed by the (unclamped) distance mod 128: the 64 x 32 block of a step touches the 96
+//   distances mlen + ib0 - j0 - 31 .. + 95, the next step the same window moved down by 32, so a step fetches 32 new rows (holding
+//   R[clip(distance)]) into the quarter of the ring the current window does not use -- 24 KB of loads per step and workgroup instead of the
+//   64 KB that four waves fetching their own 48 rows need (measured: that form ran at the L2's rate, 0.90 ms at the caption prompt's shape).
+//   Per step and wave the arithmetic is the decode kernel's: S^T = K.Qu^T (2 x 4 v_mfma_f32_16x16x32_bf16), the relative term for the 47
+//   distances the 16 x 32 block touches (3 x 4 MFMA against R rows) through the wave's LDS scratch [48 dist][16 q]
+//   and the skewed read-back, online softmax, P rounded to bf16, O^T += V^T.P^T (8 MFMA).  Then ONE normalisation, one bf16 store, and
+//   lse = m + log(l) (the sum over the fp32 probabilities).
+#include "db1_common.h"
+
+typedef __attribute__((ext_vector_type(8))) short mem_bf16x8;
+typedef __attribute__((ext_vector_type(4))) short mem_bf16x4;
+typedef __attribute__((ext_vector_type(4))) float mem_f32x4;
+typedef __attribute__((ext_vector_type(2))) float mem_f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 mem_bf16x2;
+#define MEM_LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
+
+#define MEM_D 128
+#define MEM_QB 64                       // queries per workgroup
+#define MEM_TILE (32 * 256)             // one 32-key tile of K or V: [32][128] bf16
+#define MEM_TW (48 * 16 * 4)            // the wave's distance scratch [48][16] f32
+#define MEM_RING (128 * 256)            // R rows of 128 consecutive distances: [128][128] bf16
+#define MEM_LDS (4 * MEM_TILE + MEM_RING + 4 * MEM_TW)   // K[2], V[2], R ring, T scratch x 4 waves: 76 KB, two workgroups per CU
+#define MEM_MAX_Q 8192
+#define MEM_MAX_KLEN 16384
+
+struct MemArgs {
+    const bf16_t* qu; const bf16_t* qv; const bf16_t* k; const bf16_t* v; const bf16_t* R;
+    bf16_t* out; float* lse;
+    int64_t kv_rs, kv_bs;
+    int B, q, klen, mlen, H, shift, nd;
+    float scale;
+};
+
+__device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
+    mem_f32x2 v = {lo, hi};
+    mem_bf16x2 r = __builtin_convertvector(v, mem_bf16x2);
+    return *reinterpret_cast<unsigned*>(&r);
+}
+
+__global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // MEM_LDS bytes
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ib0 = blockIdx.x * MEM_QB, h = blockIdx.y, b = blockIdx.z;
+    const int i0 = ib0 + wave * 16;
+    const int a = lane & 15, g = lane >> 4;
+    const int HD = p.H * MEM_D;
+    char* Rr = smem + 4 * MEM_TILE;
+    float* Tw = reinterpret_cast<float*>(smem + 4 * MEM_TILE + MEM_RING + wave * MEM_TW);
+    const int i = i0 + a;                                  // this lane's query
+    const int qi = i < p.q ? i : p.q - 1;                  // rows beyond q repeat the last query (never stored)
+    const bf16_t* qu = p.qu + ((int64_t)b * p.q + qi) * HD + h * MEM_D + g * 8;
+    const bf16_t* qv = p.qv + ((int64_t)b * p.q + qi) * HD + h * MEM_D + g * 8;
+    mem_bf16x8 fqu[4], fqv[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++) {
+        fqu[ks] = *reinterpret_cast<const mem_bf16x8*>(qu + ks * 32);
+        fqv[ks] = *reinterpret_cast<const mem_bf16x8*>(qv + ks * 32);
+    }
+    const bf16_t* kg = p.k + (int64_t)b * p.kv_bs + h * MEM_D;
+    const bf16_t* vg = p.v + (int64_t)b * p.kv_bs + h * MEM_D;
+    const bf16_t* Rg = p.R + h * MEM_D;
+    // the block's steps: keys max(0, ib0 - shift + 1) .. ilast + mlen (= the last row's diagonal key < klen), aligned at multiples of 32
+    const int ilast = ib0 + MEM_QB - 1 < p.q ? ib0 + MEM_QB - 1 : p.q - 1;
+    const int jlo = ib0 - p.shift + 1 > 0 ? ib0 - p.shift + 1 : 0;
+    const int st_lo = jlo >> 5, st_hi = (ilast + p.mlen) >> 5;
+    // staging: thread t moves the 16-byte pieces (row = idx >> 4, slot = idx & 15), idx = t and t + 256, of K and of V
+    const int srow = threadIdx.x >> 4, sch = threadIdx.x & 15;               // piece 0; piece 1 is row srow + 16 (same row & 15, row & 7)
+    const int soff_k = srow * 256 + ((sch ^ (srow & 15)) << 4), soff_v = srow * 256 + ((sch ^ ((srow & 7) << 1)) << 4);
+    uint4 kst0, kst1, vst0, vst1;
+    // rows past klen are clamped: their probabilities are exactly zero
+#define MEM_STAGE_LOAD(st_)                                                                                   \
+    {                                                                                                         \
+        const int ja_ = (st_) * 32 + srow < p.klen ? (st_) * 32 + srow : p.klen - 1;                          \
+        const int jb_ = (st_) * 32 + srow + 16 < p.klen ? (st_) * 32 + srow + 16 : p.klen - 1;                \
+        kst0 = *reinterpret_cast<const uint4*>(kg + (int64_t)ja_ * p.kv_rs + sch * 8);                        \
+        vst0 = *reinterpret_cast<const uint4*>(vg + (int64_t)ja_ * p.kv_rs + sch * 8);                        \
+        kst1 = *reinterpret_cast<const uint4*>(kg + (int64_t)jb_ * p.kv_rs + sch * 8);                        \
+        vst1 = *reinterpret_cast<const uint4*>(vg + (int64_t)jb_ * p.kv_rs + sch * 8);                        \
+    }
+#define MEM_STAGE_STORE(buf_)                                                                                 \
+    {                                                                                                         \
+        *reinterpret_cast<uint4*>(smem + (buf_) * MEM_TILE + soff_k) = kst0;                                  \
+        *reinterpret_cast<uint4*>(smem + (buf_) * MEM_TILE + soff_k + 16 * 256) = kst1;                       \
+        *reinterpret_cast<uint4*>(smem + (2 + (buf_)) * MEM_TILE + soff_v) = vst0;                            \
+        *reinterpret_cast<uint4*>(smem + (2 + (buf_)) * MEM_TILE + soff_v + 16 * 256) = vst1;                 \
+    }
+    // R ring: 32 rows of consecutive distances u0 .. u0 + 31 (row srow and srow + 16 per thread); out-of-range distances hold the clamped
+    // row (they belong to masked pairs).  u & 127 and u & 15 are the residues of a negative u too (two's complement).
+    uint4 rst0, rst1;
+#define MEM_R_STAGE_LOAD(u0_)                                                                                 \
+    {                                                                                                         \
+        const int ua_ = (u0_) + srow, ub_ = (u0_) + srow + 16;                                                \
+        const int da_ = ua_ < 0 ? 0 : (ua_ > p.nd - 1 ? p.nd - 1 : ua_);                                      \
+        const int db_ = ub_ < 0 ? 0 : (ub_ > p.nd - 1 ? p.nd - 1 : ub_);                                      \
+        rst0 = *reinterpret_cast<const uint4*>(Rg + (int64_t)da_ * HD + sch * 8);                             \
+        rst1 = *reinterpret_cast<const uint4*>(Rg + (int64_t)db_ * HD + sch * 8);                             \
+    }
+#define MEM_R_STAGE_STORE(u0_)                                                                                \
+    {                                                                                                         \
+        const int ua_ = (u0_) + srow, ub_ = (u0_) + srow + 16;                                                \
+        *reinterpret_cast<uint4*>(Rr + (ua_ & 127) * 256 + ((sch ^ (ua_ & 15)) << 4)) = rst0;                 \
+        *reinterpret_cast<uint4*>(Rr + (ub_ & 127) * 256 + ((sch ^ (ub_ & 15)) << 4)) = rst1;                 \
+    }
+    const int DL0 = p.mlen + ib0 - 31;           // the block's lowest distance at step st is DL0 - 32 st
+    mem_f32x4 acc_o[8];
+#pragma unroll
+    for (int db = 0; db < 8; db++) acc_o[db] = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+    float m_i = -1.0e30f, l_i = 0.f;
+    MEM_STAGE_LOAD(st_lo)
+#pragma unroll
+    for (int t = 0; t < 3; t++) {                // the first step's window: 96 rows
+        MEM_R_STAGE_LOAD(DL0 - 32 * st_lo + 32 * t)
+        MEM_R_STAGE_STORE(DL0 - 32 * st_lo + 32 * t)
+    }
+    MEM_STAGE_STORE(0)
+    __syncthreads();
+    for (int st = st_lo; st <= st_hi; st++) {
+        const int cur = (st - st_lo) & 1;
+        const int j0 = st * 32;
+        // this wave's tile has a row and the step meets the window of one of its rows?  (wave-uniform; the barrier below is reached either way)
+        const bool act = i0 < p.q && !(j0 > i0 + 15 + p.mlen || j0 + 31 <= i0 - p.shift);
+        if (st < st_hi) {   // the next step's rows are requested before this step's arithmetic
+            MEM_STAGE_LOAD(st + 1)
+            MEM_R_STAGE_LOAD(DL0 - 32 * (st + 1))
+        }
+        if (act) {
+            // ---- relative term: distances d_lo .. d_lo + 47 with d_lo = mlen + i0 - j0 - 31, rows of the ring  ->  Tw[dist][query]
+            const int d_lo = p.mlen + i0 - j0 - 31;
+#pragma unroll
+            for (int tb = 0; tb < 3; tb++) {
+                const int u = d_lo + 16 * tb + a;
+                const char* rrow = Rr + (u & 127) * 256;
+                mem_f32x4 acc_t = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < 4; ks++) {
+                    const mem_bf16x8 rf = *reinterpret_cast<const mem_bf16x8*>(rrow + (((ks * 4 + g) ^ (u & 15)) << 4));
+                    acc_t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rf, fqv[ks], acc_t, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 4; r++) Tw[(16 * tb + 4 * g + r) * 16 + a] = acc_t[r];
+            }
+            const char* Ks = smem + cur * MEM_TILE;
+            const char* Vs = smem + (2 + cur) * MEM_TILE;
+            // ---- S^T[key][query] for the two 16-key blocks
+            mem_f32x4 acc_s[2];
+#pragma unroll
+            for (int blk = 0; blk < 2; blk++) {
+                acc_s[blk] = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+                const int row = 16 * blk + a;
+#pragma unroll
+                for (int ks = 0; ks < 4; ks++) {
+                    const mem_bf16x8 kf = *reinterpret_cast<const mem_bf16x8*>(Ks + row * 256 + (((ks * 4 + g) ^ (row & 15)) << 4));
+                    acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, fqu[ks], acc_s[blk], 0, 0, 0);
+                }
+            }
+            // (same wave wrote and reads the scratch; LDS operations of a wave complete in order)
+            float s[8];
+#pragma unroll
+            for (int blk = 0; blk < 2; blk++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int bcol = 16 * blk + 4 * g + r;  // key j0 + bcol
+                    const int j = j0 + bcol;
+                    const float v = (acc_s[blk][r] + Tw[(a - bcol + 31) * 16 + a]) * p.scale;
+                    const bool vis = (j < p.klen) && (j <= i + p.mlen) && (j > i - p.shift) && (i < p.q);
+                    s[blk * 4 + r] = vis ? v : -1.0e30f;
+                }
+            float mb = s[0];
+#pragma unroll
+            for (int t = 1; t < 8; t++) mb = fmaxf(mb, s[t]);
+            mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+            mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+            const float m_new = fmaxf(m_i, mb);
+            const float alpha = __expf(m_i - m_new);
+            float rs = 0.f;
+#pragma unroll
+            for (int t = 0; t < 8; t++) { s[t] = s[t] > -1.0e29f ? __expf(s[t] - m_new) : 0.f; rs += s[t]; }
+            rs += __shfl_xor(rs, 16, 64);
+            rs += __shfl_xor(rs, 32, 64);
+            l_i = l_i * alpha + rs;
+            m_i = m_new;
+            union { unsigned u[4]; mem_bf16x8 v; } pb;
+#pragma unroll
+            for (int t = 0; t < 4; t++) pb.u[t] = mem_pk(s[2 * t], s[2 * t + 1]);
+            // ---- O^T[d][query] += V^T . P^T over the 32 keys (key permutation of relattn_decode_kernel: slots 0-3 = keys 4g..4g+3 of the
+            // first 16-key block, slots 4-7 = the same keys of the second); lane reads 8 bytes of row 4g + (a >> 2) (+ 16), columns db*16 + (a & 3)*4
+            const int vrow = 4 * g + (a >> 2);                       // (vrow & 7) == ((vrow + 16) & 7): one swizzle for both reads
+            const int vsw = (vrow & 7) << 1;
+#pragma unroll
+            for (int db = 0; db < 8; db++) {
+                const int slot = (db * 2 + ((a & 3) >> 1)) ^ vsw;
+                const char* base = Vs + vrow * 256 + (slot << 4) + ((a & 1) << 3);
+                const mem_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(MEM_LDS_PTR(mem_bf16x4, const_cast<char*>(base)));
+                const mem_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(MEM_LDS_PTR(mem_bf16x4, const_cast<char*>(base) + 16 * 256));
+                const mem_bf16x8 vt = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+                for (int r = 0; r < 4; r++) acc_o[db][r] *= alpha;
+                acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
+            }
+        }
+        if (st < st_hi) {   // (every wave finished reading that buffer, and that quarter of the ring, before the previous step's barrier)
+            MEM_STAGE_STORE(cur ^ 1)
+            MEM_R_STAGE_STORE(DL0 - 32 * (st + 1))
+        }
+        __syncthreads();
+    }
+    // ---- one normalisation, one store: lane holds query a, d = db*16 + 4g + r.  Every row i < q saw at least one key (shift + mlen >= 1)
+    if (i < p.q) {
+        const float inv = l_i > 0.f ? 1.0f / l_i : 0.f;
+        bf16_t* dst = p.out + ((int64_t)b * p.q + i) * HD + h * MEM_D + 4 * g;
+#pragma unroll
+        for (int db = 0; db < 8; db++) {
+            uint2 w;
+            w.x = f2bf_pk(acc_o[db][0] * inv, acc_o[db][1] * inv);
+            w.y = f2bf_pk(acc_o[db][2] * inv, acc_o[db][3] * inv);
+            *reinterpret_cast<uint2*>(dst + db * 16) = w;
+        }
+        if (p.lse && g == 0) p.lse[((int64_t)b * p.H + h) * p.q + i] = m_i + __logf(l_i);
+    }
+}
+
+extern "C" int db1_relattn_mem_supported(int B, int q, int klen, int mlen, int H, int D, int shift, int dt) {
+    return (dt == DB1_BF16 && D == MEM_D && B > 0 && H > 0 && B <= 65535 && H <= 65535 && q >= 1 && q <= MEM_MAX_Q && mlen >= 0 &&
+            klen == mlen + q && klen <= MEM_MAX_KLEN && shift >= 0 && (int64_t)shift + mlen >= 1) ? 1 : 0;
+}
+
+extern "C" int64_t db1_relattn_mem_workspace_bytes(int B, int q, int klen, int H) {
+    (void)B; (void)q; (void)klen; (void)H;
+    return 0;
+}
+
+extern "C" int db1_relattn_mem_fwd(const void* qu, const void* qv, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_batch_stride,
+                                   const void* R, int nd, void* out, float* lse, int B, int q, int klen, int mlen, int H, int D, int shift,
+                                   float scale, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (q >= 1 && mlen >= 0 && klen != mlen + q) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: klen (%d) must be mlen (%d) + q (%d)", klen, mlen, q);
+    if (!db1_relattn_mem_supported(B, q, klen, mlen, H, D, shift, DB1_BF16))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_mem: needs bf16, d_head = 128, 1 <= q <= 8192, klen = mlen + q <= 16384, shift >= 0, shift + mlen >= 1 "
+                                      "(got q=%d klen=%d mlen=%d D=%d shift=%d)", q, klen, mlen, D, shift);
+    if (nd < 1 || !R || !qu || !qv || !k || !v || !out) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: R rows (%d) or a null operand", nd);
+    if (kv_row_stride < (int64_t)H * MEM_D || kv_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: key / value row stride below H * D");
+    if ((kv_row_stride % 8) || (kv_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) || !db1_aligned16(k) || !db1_aligned16(v) ||
+        !db1_aligned16(R) || !db1_aligned16(out) || (((uintptr_t)lse) & 3))
+        DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_mem: operands must be 16-byte aligned, strides multiples of 8 elements");
+    MemArgs a;
+    a.qu = (const bf16_t*)qu; a.qv = (const bf16_t*)qv; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.R = (const bf16_t*)R;
+    a.out = (bf16_t*)out; a.lse = lse; a.kv_rs = kv_row_stride; a.kv_bs = kv_batch_stride;
+    a.B = B; a.q = q; a.klen = klen; a.mlen = mlen; a.H = H; a.shift = shift; a.nd = nd; a.scale = scale;
+    static Db1PerDeviceOnce attr_once;
+    attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
+    relattn_mem_kernel<<<dim3((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B), 256, MEM_LDS, (hipStream_t)stream>>>(a);
+    DB1_CHECK_LAUNCH("relattn_mem");
+    return DB1_OK;
+}

@@ -300,6 +300,7 @@ class TransformerXL(nn.Module):
         self.loss_grad_scale = 1.0       # d(loss * this) is what backward() accumulates: 1 / gradient-accumulation steps (set by the engine)
         self.use_flash = True            # fused attention when the shape is supported
         self.use_flash_bwd = True        # fused backward kernels (False: recompute through the materialised path)
+        self.use_mem_attn = False        # inference calls with memory and more than 64 new tokens: one fused launch (db1_relattn_mem_fwd) instead of the materialised path
         # what the flash backward recomputes (include/db1_hip.h, db1_relattn_flash_bwd): "forward" = nothing, the forward keeps its
         # unnormalised probabilities per layer (B*H*L*L bf16 + B*H*L*L/32 floats each: 2.2 GiB per layer at 64 x 1024 tokens);
         # "scratch" = the query side recomputes and leaves P / dS in one scratch buffer for the key side; "recompute" = both sides
@@ -649,6 +650,13 @@ class TransformerXL(nn.Module):
             ops.relattn_flash_fwd(qu, qv, qkv.view(B, Lk, 3, H, D), R, av, lse, B, Lq, H, D, shift, 1.0 / math.sqrt(D), probs=probs, mblk=mblk)
             if c is not None:
                 c.lse, c.qu, c.qv, c.probs, c.mblk = lse, qu, qv, probs, mblk
+        elif (self.use_mem_attn and c is None and pdrop is ops.NO_DROP and qkv.dtype == torch.bfloat16 and
+              ops.relattn_mem_supported(B, Lq, Lk, mlen, H, D, shift, qkv.dtype)):
+            # inference over a memory (prompt prefill, long-text scoring): no [H, B, Lq, Lk] buffer, one launch on the k / v views of qkv
+            qu, qv = self._new(B, Lq, H, D), self._new(B, Lq, H, D)
+            ops.relattn_add_head_bias(qkv, u, vb, qu, qv, B, Lq, Lk, H, D)
+            qkv5 = qkv.view(B, Lk, 3, H, D)
+            ops.relattn_mem_fwd(qu, qv, qkv5[:, :, 1], qkv5[:, :, 2], R, av, None, B, Lq, Lk, mlen, H, D, shift, 1.0 / math.sqrt(D))
         else:
             Pm, _, _, _ = self._attn_probs(qkv, R, u, vb, B, Lq, Lk, mlen, shift)
             if pdrop is not ops.NO_DROP:
@@ -1187,7 +1195,9 @@ class TransformerXL(nn.Module):
             return self._forward(tasks_input, compute_loss, mems)
 
     def _forward(self, tasks_input: Sequence, compute_loss: bool = True, mems=None):
-        assert not (compute_loss and mems is not None), "During training, Gato does not use memory mechanism."
+        # (scoring.score(..., mems=) is the one caller with labels AND memory: an eval-mode forward without gradients that ends in the score sink)
+        scoring = self._score_sink is not None and not self.training and not torch.is_grad_enabled()
+        assert not (compute_loss and mems is not None) or scoring, "During training, Gato does not use memory mechanism."
         keep = compute_loss and torch.is_grad_enabled()
         d = self.d_model
         embs, labels, masks, ecs, shapes = [], [], [], [], []

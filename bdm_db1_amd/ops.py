@@ -1250,6 +1250,23 @@ def relattn_decode_fwd(qu, qv, k, v, R, out, B, q, klen, mlen, H, D, shift, scal
              B, q, klen, mlen, H, D, shift, float(scale), ws, wsn, stream())
 
 
+def relattn_mem_supported(B, q, klen, mlen, H, D, shift, dtype, kv_row_stride=None, kv_batch_stride=None) -> bool:
+    """db1_relattn_mem_supported, and (when given) the key / value strides the entry point accepts: multiples of 8 elements"""
+    if any(s is not None and int(s) % 8 for s in (kv_row_stride, kv_batch_stride)):
+        return False
+    return bool(lib.load().db1_relattn_mem_supported(B, q, klen, mlen, H, D, shift, dt_code(dtype)))
+
+
+def relattn_mem_fwd(qu, qv, k, v, R, out, lse, B, q, klen, mlen, H, D, shift, scale):
+    """attention of q new queries (any number up to 8192) over klen = mlen + q keys in one launch (db1_relattn_mem_fwd).
+    k, v: views [B, klen, H, D] (any row / batch stride, unit stride inside a head row); lse: float32 [B, H, q] or None"""
+    assert k.stride(3) == 1 and k.stride(2) == D and v.stride() == k.stride()
+    if any(t.dtype != torch.bfloat16 for t in (qu, qv, k, v, R, out)) or (lse is not None and lse.dtype != torch.float32):
+        raise lib.Db1Error("relattn_mem_fwd: bf16 operands (float32 lse) only")     # (the entry point takes no dtype: refused here, nothing launched)
+    lib.call("db1_relattn_mem_fwd", P(qu), P(qv), P(k), P(v), k.stride(1), k.stride(0), P(R), R.shape[0], P(out), P(lse),
+             B, q, klen, mlen, H, D, shift, float(scale), _vp(0), 0, stream())
+
+
 _tickets = {}
 
 

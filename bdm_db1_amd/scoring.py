@@ -81,6 +81,7 @@ class ScoreResult:
     top_logprob: Optional[List[np.ndarray]] = None
     status: int = 0        # OR of the status bits of the rows with mask != 0 (1: the label is no candidate, 2: the row has no candidate)
     stats: Dict[str, int] = field(default_factory=dict)
+    mems: Optional[list] = None     # ``score(..., mems=)`` / ``score_document``: the memory the (last) forward returned
 
     @property
     def loss(self) -> float:
@@ -126,10 +127,11 @@ def _check_window(model, cfg: ScoreConfig) -> ScoreConfig:
 
 
 @torch.no_grad()
-def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResult:
+def score(model, tasks_input, config: Optional[ScoreConfig] = None, mems=None) -> ScoreResult:
     """Score the labels of ``tasks_input`` (what ``model.forward`` takes: ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` /
     ``RLTaskInput`` with ``label`` and ``loss_mask``) under the model: ONE eval-mode forward without gradients whose head is the
-    ``db1_lmhead_score`` sweep.  The model's mode is restored; no gradient or optimizer state is touched."""
+    ``db1_lmhead_score`` sweep.  The model's mode is restored; no gradient or optimizer state is touched.  ``mems`` (the list
+    ``model.init_mem`` or an earlier call returned): the forward attends to it, and ``ScoreResult.mems`` is the memory it returns."""
     cfg = _check_window(model, config or ScoreConfig())
     tasks_input = list(tasks_input)
     if not tasks_input:
@@ -143,7 +145,7 @@ def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResu
     with _eval_mode(model):
         model._score_sink = sink
         try:
-            model(tasks_input, compute_loss=True)
+            out = model(tasks_input, compute_loss=True, mems=mems)
         finally:
             model._score_sink = None
     if sink.sweeps != 1:
@@ -153,7 +155,7 @@ def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResu
     kinds = [_KINDS[type(t).__name__] for t in tasks_input]
     res = ScoreResult(sum_logprob=seg[:, 0].copy(), tokens=seg[:, 1].copy(), hits=seg[:, 2].copy(),
                       task=np.repeat(np.arange(len(shapes), dtype=np.int64), [b for b, _ in shapes]), kinds=kinds,
-                      stats=dict(sweeps=sink.sweeps))
+                      stats=dict(sweeps=sink.sweeps), mems=out[2] if mems is not None else None)
     st = status.cpu().numpy()[msk.cpu().numpy() != 0]            # only rows that count: a masked-out label outside the window says nothing
     res.status = int(np.bitwise_or.reduce(st)) if st.size else 0
     if cfg.return_tokens:
@@ -171,6 +173,106 @@ def score(model, tasks_input, config: Optional[ScoreConfig] = None) -> ScoreResu
                 res.top_ids.append(ti[r0:r0 + b * l].reshape(b, l, -1))
                 res.top_logprob.append(tl[r0:r0 + b * l].reshape(b, l, -1))
                 r0 += b * l
+    return res
+
+
+def document_segments(n: int, segment_len: int) -> List[Tuple[int, int]]:
+    """[begin, end) of the consecutive segments ``score_document`` feeds: ``segment_len`` positions each and a remainder.  A remainder of ONE
+    position takes one from the segment before it (a 1-token call raises for models without ``same_length``); where that segment would be
+    left with one position itself (``segment_len`` 2) the two are joined instead.  No segment has length 1."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or isinstance(segment_len, bool) or not isinstance(segment_len, (int, np.integer)):
+        raise ValueError(f"document_segments: integers expected, got {n!r} and {segment_len!r}")
+    n, s = int(n), int(segment_len)
+    if s < 2:
+        raise ValueError(f"segment_len {s} must be at least 2")
+    if n < 2:
+        raise ValueError(f"a document of {n} scored positions is too short (at least 2)")
+    cuts = list(range(0, n, s)) + [n]
+    if len(cuts) > 2 and cuts[-1] - cuts[-2] == 1:
+        if s > 2:
+            cuts[-2] -= 1
+        else:
+            del cuts[-2]
+    return [(cuts[i], cuts[i + 1]) for i in range(len(cuts) - 1)]
+
+
+def _mem_attn_servable(model, B: int, seg_max: int) -> bool:
+    """can db1_relattn_mem_fwd serve this model's calls with memory?  (host arithmetic first: no library call for a plainly unfit model)"""
+    if model.compute_dtype != torch.bfloat16 or int(model.d_head) != 128:
+        return False
+    mlen, L = int(model.mem_len), max(int(seg_max), 65)
+    return ops.relattn_mem_supported(B, L, mlen + L, mlen, int(model.n_head), int(model.d_head), int(model._window(L, mlen)), model.compute_dtype)
+
+
+@torch.no_grad()
+def score_document(model, tokens, config: Optional[ScoreConfig] = None, segment_len: Optional[int] = None, lengths=None, mems=None,
+                   fused: Optional[bool] = None) -> ScoreResult:
+    """Score texts longer than one segment with segment-level recurrence.  ``tokens``: ints ``[B, T]``, T >= 3; position p of n = T - 1 feeds
+    ``tokens[:, p]`` and is labelled ``tokens[:, p + 1]``; ``lengths`` (ints ``[B]`` in ``[2, T]``): row b's positions p >= lengths[b] - 1 do
+    not count.  The positions go through ``score(..., mems=)`` in the segments of ``document_segments(n, segment_len)`` (default
+    ``model.n_position``), the memory starting from ``mems`` or ``model.init_mem(B)`` and handed on from segment to segment.
+
+    One ``"nlp"`` task comes back: with ``return_tokens`` ``logprob`` / ``top1`` / ``rank`` (and the top-n fields) are ``[B, n]``;
+    ``sum_logprob`` / ``tokens`` / ``hits`` per row are the segments' values added in segment order in float64 and stored as float32;
+    ``status`` is the OR over the segments; ``stats = dict(segments=S, sweeps=S)``; ``mems`` is the final memory (pass it back to go on).
+    ``fused``: None leaves ``model.use_mem_attn`` as it is, True / False sets it for this call (True on a model the fused kernel cannot serve
+    raises ValueError before anything is launched)."""
+    tok = np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)
+    if tok.dtype == object or tok.dtype.kind not in "iu" or tok.ndim != 2:
+        raise ValueError("score_document: tokens must be an integer [B, T] array (rows of one length)")
+    B, T = tok.shape
+    if B < 1 or T < 3:
+        raise ValueError(f"score_document: tokens of shape {tok.shape}: at least one row and T >= 3")
+    n = T - 1
+    seg_len = int(model.n_position) if segment_len is None else segment_len
+    segs = document_segments(n, seg_len)
+    if lengths is None:
+        ln = np.full(B, T, np.int64)
+    else:
+        ln = np.asarray(lengths.cpu() if torch.is_tensor(lengths) else lengths)
+        if ln.dtype == object or ln.dtype.kind not in "iu" or ln.shape != (B,) or ln.min() < 2 or ln.max() > T:
+            raise ValueError(f"score_document: lengths must be {B} integers in [2, {T}]")
+    _need_memory(model, "score_document")
+    V = int(model.total_vocab_size)
+    if tok.min() < 0 or tok.max() >= V:
+        raise ValueError(f"score_document: tokens must lie in [0, {V})")
+    if fused is not None and not isinstance(fused, (bool, np.bool_)):
+        raise ValueError(f"score_document: fused must be None, True or False, got {fused!r}")
+    if fused and not _mem_attn_servable(model, B, max(e - b for b, e in segs)):
+        raise ValueError("score_document: fused=True, but db1_relattn_mem_fwd cannot serve this model (bf16, d_head 128, a window of at least one key)")
+    cfg = _check_window(model, config or ScoreConfig())
+    from .data import NLPTaskInput
+    dev = model.dev
+    ids = torch.from_numpy(np.ascontiguousarray(tok[:, :n].astype(np.int64))).to(dev)
+    lab = torch.from_numpy(np.ascontiguousarray(tok[:, 1:].astype(np.int64))).to(dev)
+    msk = torch.from_numpy((np.arange(n)[None, :] < (ln.astype(np.int64)[:, None] - 1)).astype(np.float32)).to(dev)
+    cur = mems if mems is not None else model.init_mem(B)
+    was = model.use_mem_attn
+    parts = []
+    try:
+        if fused is not None:
+            model.use_mem_attn = bool(fused)
+        for b0, e0 in segs:
+            x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=msk[:, b0:e0].contiguous(), label=lab[:, b0:e0].contiguous(),
+                             text_seq=ids[:, b0:e0].contiguous(), text_len=None)
+            r = score(model, [x], cfg, mems=cur)
+            cur = r.mems
+            parts.append(r)
+    finally:
+        model.use_mem_attn = was
+    tot = [np.zeros(B, np.float64) for _ in range(3)]
+    for r in parts:       # (segment order, float64)
+        for acc, x in zip(tot, (r.sum_logprob, r.tokens, r.hits)):
+            acc += x.astype(np.float64)
+    res = ScoreResult(sum_logprob=tot[0].astype(np.float32), tokens=tot[1].astype(np.float32), hits=tot[2].astype(np.float32),
+                      task=np.zeros(B, np.int64), kinds=["nlp"], stats=dict(segments=len(segs), sweeps=sum(r.stats["sweeps"] for r in parts)),
+                      mems=cur)
+    for r in parts:
+        res.status |= int(r.status)
+    if cfg.return_tokens:
+        for name in ("logprob", "top1", "rank", "top_ids", "top_logprob"):
+            if getattr(parts[0], name) is not None:
+                setattr(res, name, [np.concatenate([getattr(r, name)[0] for r in parts], axis=1)])
     return res
 
 

@@ -288,6 +288,17 @@ int db1_relattn_decode_fwd(const void* qu, const void* qv, const void* k, const 
                            int64_t kv_batch_stride, const void* R, int nd, void* out, int B, int q, int klen, int mlen, int H,
                            int D, int shift, float scale, void* ws, int64_t ws_bytes, void* stream);
 
+/* The same attention for ANY number of new queries (prompt prefill over a memory, long-text scoring), in ONE launch without partials, merge,
+ * workspace or atomics (two launches on the same inputs give the same bits): operands, layout and visibility rule of db1_relattn_decode_fwd;
+ * lse [B, H, q] float32 (NULL: not written) = log of the sum of exp(score) over the visible keys.
+ * Supported: bf16, D == 128, 1 <= q <= 8192, mlen >= 0, klen == mlen + q <= 16384, shift >= 0 with shift + mlen >= 1 (every row sees a
+ * key; shift == 0 is same_length over a full memory), nd >= 1, strides multiples of 8 elements, 16-byte aligned operands. */
+int db1_relattn_mem_supported(int B, int q, int klen, int mlen, int H, int D, int shift, int dt);
+int64_t db1_relattn_mem_workspace_bytes(int B, int q, int klen, int H);      /* 0 */
+int db1_relattn_mem_fwd(const void* qu, const void* qv, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_batch_stride,
+                        const void* R, int nd, void* out, float* lse, int B, int q, int klen, int mlen, int H, int D, int shift,
+                        float scale, void* ws, int64_t ws_bytes, void* stream);
+
 /* The same attention over a RING of cached keys / values (hipGraph-friendly inference: nothing is concatenated or copied per call):
  * kv_ring [B, cap, 2, H, D] bf16, cap >= mlen + q; logical key j < mlen is ring row (ring_state[0] + j) % cap; the q new keys / values come
  * from this call's packed projections qkv_new [B, q, 3, H, D] and are appended at rows (ring_state[0] + mlen + i) % cap by the same

@@ -27,6 +27,8 @@ limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS);
   * db1_ring_load_rows alone: 16 rows into a ring of 64, device time from events, bytes read + written.
 
     python tools/bench_generate.py --stream [requests [slots]]
+    python tools/bench_generate.py --stream --mem-attn [requests [slots]]   (model.use_mem_attn = True: the admissions' prefills through
+                                                                            db1_relattn_mem_fwd; the line carries "mem_attn": true)
 
 With --stream --per-request: the stream workload above with every second request greedy and the others at top-p 0.9
 (``caption_stream(..., per_request=True)``, a ``SamplingParams`` on the sampled requests: the graph ends in db1_select_tokens_slots_per)
@@ -232,7 +234,8 @@ def stream_main(n_req=256, slots=64):
     rows = lambda b, r: ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=b.prompt_seq[r:r + 1],
                                     img_seq=b.img_seq[r:r + 1], text_seq=None)
     reqs = [(rows(batches[i // slots], i % slots), int(limits[i])) for i in range(n_req)]
-    rec = {"requests": n_req, "slots": slots, "limits": "uniform 5..30, seed 2024", "mean_limit": round(float(limits.mean()), 2)}
+    rec = {"requests": n_req, "slots": slots, "limits": "uniform 5..30, seed 2024", "mean_limit": round(float(limits.mean()), 2),
+           "mem_attn": bool(model.use_mem_attn)}
 
     def timed(fn):
         fn()                                   # capture + warm-up
@@ -582,6 +585,9 @@ def best_of_main(N, Gs):
 
 
 args = sys.argv[1:]
+if "--mem-attn" in args:       # calls with memory and more than 64 new tokens (the prompt prefills) take the fused attention over memory
+    model.use_mem_attn = True
+    args = [a for a in args if a != "--mem-attn"]
 TOP_N = None
 if "--top-logprobs" in args:
     i = args.index("--top-logprobs")
