@@ -28,6 +28,7 @@ from __future__ import annotations
 import contextlib
 import dataclasses
 from dataclasses import dataclass, field
+from functools import partial
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -265,6 +266,22 @@ class DecodingConstraints:
         return not self.applies()
 
 
+@dataclass(frozen=True)
+class DecodeKey:
+    """What a decoding state is built from and its cached ring generator is kept under: ``rows`` prompts (a stream: slots), the config, the
+    vocabulary ``V`` and the window's end ``hi`` (``_vocab_window``); ``constraints``: those that apply, None when they edit nothing
+    (``_constrained``); ``n``: samples per prompt (best-of-n only); ``per_request``: the slots carry their own ``SamplingParams``; ``caps``:
+    (max_bad_token_ids, max_logit_bias) of a stream whose slots carry their own constraints.  Two calls share a state iff their keys are equal."""
+    rows: int
+    cfg: object
+    V: int
+    hi: int
+    constraints: Optional[DecodingConstraints] = None
+    n: Optional[int] = None
+    per_request: bool = False
+    caps: Optional[Tuple[int, int]] = None
+
+
 def clip_at_eos(ids, lengths) -> List[List[int]]:
     """the tokens ``Decoder.decode(..., clip_at_eos=True)`` keeps (text_decoder.py:53-58), as id lists: row r's first ``lengths[r]`` ids"""
     ids = np.asarray(ids)
@@ -308,10 +325,10 @@ def _vocab_window(model, cfg) -> Tuple[int, int]:
     return V, hi
 
 
-def _constrained(who: str, model, key: tuple, constraints, limit: int) -> tuple:
-    """the state key ``key`` = (rows, cfg, V, hi) with the constraints appended -- unless they are None or edit nothing under this config
-    (``DecodingConstraints.applies``): then the key, and with it the state, the launches and the cached generator, is exactly what it is
-    without them.  Raises before anything is launched."""
+def _constrained(who: str, model, key: DecodeKey, constraints, limit: int) -> DecodeKey:
+    """the state key ``key`` with ``constraints`` set -- unless they are None or edit nothing under this config
+    (``DecodingConstraints.applies``): then the key itself, and with it the state, the launches and the cached generator, is exactly what
+    it is without them.  Raises before anything is launched."""
     if constraints is None:
         return key
     if not isinstance(constraints, DecodingConstraints):
@@ -320,17 +337,17 @@ def _constrained(who: str, model, key: tuple, constraints, limit: int) -> tuple:
         raise ValueError(f"{who}: min_new_tokens {constraints.min_new_tokens} exceeds max_new_tokens {limit}")
     if constraints.stop_sequences and who in ("beam_search", "sample_best_of"):
         raise ValueError(f"{who}: stop_sequences are not supported (beams and best-of-n rank whole hypotheses; use generate or a stream)")
-    if not constraints.applies(key[1].eos_id):
+    if not constraints.applies(key.cfg.eos_id):
         return key
-    V = key[2]
-    if not ops.constrain_logits_supported(V, V, key[1].max_new_tokens, len(constraints.bad_token_ids), model.compute_dtype):
-        raise ValueError(f"{who}: db1_constrain_logits does not support max_new_tokens {key[1].max_new_tokens}")
-    if constraints.edits_more and not ops.constrain_logits_pen_supported(V, V, key[1].max_new_tokens, len(constraints.bad_token_ids),
-                                                                         len(constraints.logit_bias), model.compute_dtype):
+    V, mx = key.V, key.cfg.max_new_tokens
+    if not ops.constrain_logits_supported(V, V, mx, len(constraints.bad_token_ids), model.compute_dtype):
+        raise ValueError(f"{who}: db1_constrain_logits does not support max_new_tokens {mx}")
+    if constraints.edits_more and not ops.constrain_logits_pen_supported(V, V, mx, len(constraints.bad_token_ids), len(constraints.logit_bias),
+                                                                         model.compute_dtype):
         raise ValueError(f"{who}: db1_constrain_logits_pen does not support {len(constraints.logit_bias)} biases")
-    if constraints.stop_sequences and not ops.stop_match_supported(len(constraints.stop_sequences), key[1].max_new_tokens):
+    if constraints.stop_sequences and not ops.stop_match_supported(len(constraints.stop_sequences), mx):
         raise ValueError(f"{who}: db1_stop_match does not support {len(constraints.stop_sequences)} stop sequences")
-    return key + (constraints,)
+    return dataclasses.replace(key, constraints=constraints)
 
 
 def _constrain_args(cons: Optional[DecodingConstraints], cfg, V: int, dev) -> Optional[dict]:
@@ -351,13 +368,13 @@ def _constrain_args(cons: Optional[DecodingConstraints], cfg, V: int, dev) -> Op
     return args
 
 
-def _stop_args(cons: Optional[DecodingConstraints], cfg, dev) -> Optional[dict]:
-    """the arguments a state's ``ops.stop_match`` call takes from its constraints (the packed sequences as device tensors, made once);
-    None: no stop sequences, no launch and no buffers"""
+def _stop_args(cons: Optional[DecodingConstraints], cfg, dev, lp_top: dict) -> Optional[dict]:
+    """the arguments a state's ``ops.stop_match`` call takes from its constraints (the packed sequences as device tensors, made once) and
+    its log-prob / top-n outputs ``lp_top``; None: no stop sequences, no launch and no buffers"""
     if cons is None or not cons.stop_sequences:
         return None
     tok, n = ops.pack_stop_sequences(cons.stop_sequences)
-    return dict(stop_tok=torch.from_numpy(tok).to(dev), stop_len=torch.from_numpy(n).to(dev), pad_id=int(cfg.pad_id))
+    return dict(stop_tok=torch.from_numpy(tok).to(dev), stop_len=torch.from_numpy(n).to(dev), pad_id=int(cfg.pad_id), **lp_top)
 
 
 def _text_window(model, cfg):
@@ -464,44 +481,53 @@ def _ring_ok(model) -> bool:
 # is kept under), ``start(...)``, ``epilogue(logits_last, next_ids, ring=None)`` -- select, reorder ``ring`` if beams, then t += 1 --,
 # ``reorder_list(mems)``, ``all_done()`` (a host read), ``result()`` and ``stats()``.  The stream (serving.py) asks its ``_SlotState`` for
 # ``M``, ``expand``, ``cache``, ``start()`` and ``epilogue``.
+_no_launch = lambda *args, **kw: None      # the step of an epilogue that has nothing to do
+
+
 class _SamplingState:
-    """what the two sampling states (``_State``, serving's ``_SlotState``) share: the per-row flags, stream ids and output, all zero / pad_id,
-    and ``sel``, the keyword arguments their ``ops.select_*`` call takes from ``cfg, V, hi``; with ``cfg.logprobs`` also the tokens'
-    log-probs ``logprob`` [M, max_new_tokens] and their per-row sum ``sum_logprob`` (None otherwise: the plain entry point is called); with
-    ``cfg.top_logprobs`` n also the alternatives ``top_ids`` / ``top_logprob`` [M, max_new_tokens, n], -1 / -inf where nothing was written"""
+    """what the two sampling states (``_State``, serving's ``_SlotState``) share: ``counters`` token counters ``t``, the per-row flags, stream
+    ids and output, all zero / pad_id; with ``cfg.logprobs`` the tokens' log-probs ``logprob`` [M, max_new_tokens] and their per-row sum
+    ``sum_logprob``; with ``cfg.top_logprobs`` n the alternatives ``top_ids`` / ``top_logprob`` [M, max_new_tokens, n], -1 / -inf where
+    nothing was written (each None when off).  ``lp_top``: those outputs as keywords; ``sel``: the keywords of the ``ops.select_*`` call.
+    An epilogue is constrain -> select -> stop.  Each step is bound ONCE, here, to its launch and its buffers (``_constrain`` / ``_stop``
+    from ``cons``, ``_pick`` by the subclass) or to ``_no_launch``; ``con`` / ``stop`` are the launch's keywords, None for no launch."""
     expand = None
 
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
+    def __init__(self, model, key: DecodeKey, M: int, counters: int, cons: Optional[DecodingConstraints]):
+        cfg, V = key.cfg, key.V
         self.i32 = i32 = dict(dtype=torch.int32, device=model.dev)
-        self.M, self.cfg, self.V, self.hi, self.dev = M, cfg, V, hi, model.dev
+        self.M, self.cfg, self.V, self.hi, self.dev = M, cfg, V, key.hi, model.dev
+        self.t = torch.zeros(counters, **i32)
         self.finished, self.lengths, self.status, self.stream_id = (torch.zeros(M, **i32) for _ in range(4))
         self.out = torch.full((M, cfg.max_new_tokens), cfg.pad_id, **i32)
-        self.sel = dict(V=V, vocab_lo=cfg.vocab_lo, vocab_hi=hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k, top_p=cfg.top_p,
-                        seed=cfg.seed, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, stream_id=self.stream_id)
-        self.con = _constrain_args(cons, cfg, V, model.dev)
+        self.lp_top = {}
         self.logprob = self.sum_logprob = None
         if cfg.logprobs:
             self.logprob = torch.zeros(M, cfg.max_new_tokens, dtype=torch.float32, device=model.dev)
             self.sum_logprob = torch.zeros(M, dtype=torch.float32, device=model.dev)
-            self.sel.update(logprob=self.logprob, sum_logprob=self.sum_logprob)
+            self.lp_top.update(logprob=self.logprob, sum_logprob=self.sum_logprob)
         self.top_ids = self.top_logprob = None
         if cfg.top_logprobs:
             n = int(cfg.top_logprobs)
             self.top_ids = torch.full((M, cfg.max_new_tokens, n), -1, **i32)
             self.top_logprob = torch.full((M, cfg.max_new_tokens, n), float("-inf"), dtype=torch.float32, device=model.dev)
-            self.sel.update(top_n=n, top_ids=self.top_ids, top_logprob=self.top_logprob)
+            self.lp_top.update(top_n=n, top_ids=self.top_ids, top_logprob=self.top_logprob)
+        self.sel_shared = dict(V=V, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, stream_id=self.stream_id, **self.lp_top)
+        self.sel = dict(self.sel_shared, vocab_lo=cfg.vocab_lo, vocab_hi=key.hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k,
+                        top_p=cfg.top_p, seed=cfg.seed)
+        self.con = _constrain_args(cons, cfg, V, model.dev)
+        self._constrain = _no_launch if self.con is None else partial(ops.constrain_logits, t=self.t, hist=self.out, finished=self.finished, **self.con)
         # stop sequences: the packed lists and two more vectors per row, only when there are any
-        self.stop = _stop_args(cons, cfg, model.dev)
-        self.checked = self.stop_hit = None
+        self.stop = _stop_args(cons, cfg, model.dev, self.lp_top)
+        self.checked, self.stop_hit, self._stop = None, None, _no_launch
         if self.stop is not None:
             self.checked, self.stop_hit = torch.zeros(M, **i32), torch.zeros(M, **i32)
-            self.stop.update({k: self.sel[k] for k in ("logprob", "sum_logprob", "top_n", "top_ids", "top_logprob") if k in self.sel})
+            self._stop = partial(ops.stop_match, lengths=self.lengths, checked=self.checked, finished=self.finished, stop_hit=self.stop_hit,
+                                 out=self.out, **self.stop)
 
     def stop_match(self, next_ids, row_map=None):
         """the stop sequences, after the selection: rows whose output now ends in one lose it and end (none configured: no launch)"""
-        if self.stop is not None:
-            ops.stop_match(lengths=self.lengths, checked=self.checked, finished=self.finished, stop_hit=self.stop_hit, out=self.out,
-                           next_ids=next_ids, row_map=row_map, **self.stop)
+        self._stop(next_ids=next_ids, row_map=row_map)
 
     def clear_top(self, idx=None):
         """-1 / -inf into the alternatives of every row (``idx``: int64 device vector, of those rows): nothing written yet"""
@@ -515,17 +541,17 @@ class _SamplingState:
 
     def constrain(self, logits2d, row_map=None):
         """the decoding constraints, in place on the step's logits, over every row's own output so far (no constraints: no launch)"""
-        if self.con is not None:
-            ops.constrain_logits(logits2d, self.t, self.out, finished=self.finished, row_map=row_map, **self.con)
+        self._constrain(logits2d, row_map=row_map)
 
 
 class _State(_SamplingState):
     """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
     cache = "_generator"
 
-    def __init__(self, model, M: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
-        super().__init__(model, M, cfg, V, hi, cons)
-        self.t = torch.zeros(1, **self.i32)
+    def __init__(self, model, key: DecodeKey):
+        M = key.rows if key.n is None else key.rows * key.n      # (best-of-n: n rows per prompt)
+        super().__init__(model, key, M, 1, key.constraints)
+        self._pick = partial(ops.select_tokens, t=self.t, finished=self.finished, lengths=self.lengths, out=self.out, status=self.status, **self.sel)
         self.stream_id.copy_(torch.arange(M, dtype=torch.int32))
 
     def start(self, stream_ids=None):
@@ -546,7 +572,7 @@ class _State(_SamplingState):
 
     def select(self, logits2d, next_ids):
         """db1_select_tokens on the last-position logits [M, V] of step t; the tokens go to ``next_ids`` (int64 [M])"""
-        ops.select_tokens(logits2d, self.t, self.finished, self.lengths, self.out, next_ids, self.status, **self.sel)
+        self._pick(logits2d, next_ids=next_ids)
 
     def epilogue(self, logits2d, next_ids, ring=None):
         self.constrain(logits2d)
@@ -579,9 +605,9 @@ class _BestOfState(_State):
     log-probs always on; ``result`` adds the status, which the ranking needs"""
     cache = "_best_of_generator"
 
-    def __init__(self, model, G: int, cfg: GenerationConfig, V: int, hi: int, n: int, cons: Optional[DecodingConstraints] = None):
-        super().__init__(model, G * n, cfg, V, hi, cons)
-        self.G, self.expand = G, n
+    def __init__(self, model, key: DecodeKey):
+        super().__init__(model, key)
+        self.G, self.expand = key.rows, key.n
 
     def result(self):
         return super().result() + (self.status.cpu(),)
@@ -591,8 +617,8 @@ class _BeamState:
     """the device state of one beam search over G groups of W beams (include/db1_hip.h, db1_beam_step)"""
     cache = "_beam_generator"
 
-    def __init__(self, model, G: int, cfg: BeamSearchConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None):
-        dev = model.dev
+    def __init__(self, model, key: DecodeKey):
+        G, cfg, V, hi, dev = key.rows, key.cfg, key.V, key.hi, model.dev
         W, mx = int(cfg.num_beams), int(cfg.max_new_tokens)
         i32 = dict(dtype=torch.int32, device=dev)
         self.G, self.W, self.M, self.cfg, self.V, self.hi = G, W, G * W, cfg, V, hi
@@ -609,7 +635,7 @@ class _BeamState:
         self.done = torch.zeros(G, **i32)
         self.switches = torch.zeros(G, **i32)
         self.status = torch.zeros(G, **i32)
-        self.con = _constrain_args(cons, cfg, V, dev)
+        self.con = _constrain_args(key.constraints, cfg, V, dev)
 
     def start(self):
         pad = self.cfg.pad_id
@@ -698,13 +724,13 @@ def _ring_generator(model, State, key) -> _RingGenerator:
     gen = getattr(model, State.cache, None)
     if gen is None or gen.key != key or gen.step._version != model._wversion:
         setattr(model, State.cache, None)        # (free the old ring before the new one is allocated)
-        gen = _RingGenerator(model, State(model, *key), key)
+        gen = _RingGenerator(model, State(model, key), key)
         setattr(model, State.cache, gen)
     return gen
 
 
 def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, stats: Optional[dict], start=()):
-    """``max_new_tokens`` steps of ``State(model, *key)`` after ``prompt`` (``key[0]`` rows) -> ``state.result()``.  On the ring path
+    """``max_new_tokens`` steps of ``State(model, key)`` after ``prompt`` (``key.rows`` rows) -> ``state.result()``.  On the ring path
     (``graphed``, as ``generate`` documents it): over the cached ring generator, one graph replay per token (``replay`` False: the same forward
     and epilogue launched eagerly over the same ring); else eagerly over the list-form memory.  The callers have validated everything else:
     nothing is launched before that."""
@@ -716,11 +742,11 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             gen = _ring_generator(model, State, key)
             st, ids = gen.state, gen.step.ids
         else:
-            st = State(model, *key)
+            st = State(model, key)
             ids = torch.zeros(st.M, 1, dtype=torch.long, device=model.dev)
         st.start(*start)
         # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
-        logits, mems = _prefill(model, prompt, key[0], st.expand)
+        logits, mems = _prefill(model, prompt, key.rows, st.expand)
         last = logits[:, -1]
         st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids[:, 0])
         del logits, last
@@ -774,7 +800,7 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
-    key = _constrained("generate", model, (M, cfg, V, hi), constraints, cfg.max_new_tokens)
+    key = _constrained("generate", model, DecodeKey(rows=M, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
     return _decode(model, prompt, _State, key, graphed, replay, stats, start=(stream_ids,))
 
 
@@ -864,7 +890,7 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
         raise ValueError(f"eos_id {cfg.eos_id} lies outside the model's vocabulary ({V})")
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
-    key = _constrained("beam_search", model, (G, cfg, V, hi), constraints, cfg.max_new_tokens)
+    key = _constrained("beam_search", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
     return _decode(model, prompt, _BeamState, key, graphed, replay, stats)
 
 
@@ -930,7 +956,7 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
         if stream_ids.shape != (G, n):
             raise ValueError(f"sample_best_of: stream_ids of shape [{G}, {n}] expected, got {tuple(stream_ids.shape)}")
         stream_ids = stream_ids.reshape(-1)
-    key = _constrained("sample_best_of", model, (G, cfg, V, hi, n), constraints, cfg.max_new_tokens)
+    key = _constrained("sample_best_of", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi, n=n), constraints, cfg.max_new_tokens)
     out, lengths, _, sums, status = _decode(model, prompt, _BestOfState, key, graphed, True, stats, start=(stream_ids,))
     out, lengths = out.numpy().reshape(G, n, -1), lengths.numpy().reshape(G, n)
     mx = out.shape[2]

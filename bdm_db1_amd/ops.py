@@ -627,6 +627,66 @@ def _check_top(who, top_n, top_ids, top_logprob, shape, dev) -> int:
     return int(top_n)
 
 
+def _check_slots(who, M, S, row_map, dev) -> int:
+    """``S`` slots behind ``M`` logits rows -> S: with a ``row_map`` (int32 [M]) at least M of them; without one, row i is slot i and S = M"""
+    if row_map is not None:
+        _check_tensor(who, "row_map", row_map, torch.int32, M, dev)
+        if S < M:
+            raise ValueError(f"{who}: {M} logits rows for {S} slots")
+    elif S != M:
+        raise ValueError(f"{who}: hist holds {S} rows for {M} logits rows (no row_map)")
+    return S
+
+
+def _check_vectors(who, dev, n, optional=(), **vectors):
+    """each of ``vectors`` (name=tensor, in the order given) is a contiguous int32 vector of ``n`` elements; one named in ``optional`` may be None"""
+    for name, x in vectors.items():
+        if x is not None or name not in optional:
+            _check_tensor(who, name, x, torch.int32, n, dev)
+
+
+def _check_outputs(who, rows, max_new, dev, next_ids, logprob, sum_logprob, top_n, top_ids, top_logprob):
+    """what a selection or stop launch writes per row next to ``out`` [rows, max_new]: ``next_ids``, the optional log-prob outputs and the
+    optional top-n outputs, which need the log-prob ones -> (lp: whether those are there, top: the top-n count or 0)"""
+    _check_next_ids(who, next_ids, rows, dev)
+    lp = _check_logprobs(who, logprob, sum_logprob, rows, max_new, dev)
+    top = _check_top(who, top_n, top_ids, top_logprob, (rows, max_new), dev)
+    if top and not lp:
+        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    return lp, top
+
+
+def _output_args(lp, top, logprob, sum_logprob, top_ids, top_logprob):
+    """the five log-prob / top-n arguments of an entry point that always takes them (``lp, top`` from ``_check_outputs``): NULL, 0 for what is off"""
+    return (P(logprob) if lp else _vp(0), P(sum_logprob) if lp else _vp(0), top, P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0))
+
+
+def _own_output_args(lp, top, *outputs):
+    """those of the plain / ``_lp`` / ``_top`` entry points, each of which takes only its own: none, the first two, all five"""
+    args = _output_args(lp, top, *outputs)
+    return (args[:2] if lp else ()) + (args[2:] if top else ())
+
+
+def _check_hist(who, hist, dev):
+    """``hist`` is a 2-D tensor -> (S, max_new), its shape; dtype, layout and device are looked at with the rows (``_check_constrain_rows``)"""
+    if not torch.is_tensor(hist) or hist.dim() != 2:
+        raise ValueError(f"{who}: hist must be a contiguous {torch.int32} tensor of shape (slots, max_new) on {dev}")
+    return hist.shape
+
+
+def _check_max_new(who, mx):
+    if not 1 <= mx <= 4096:
+        raise ValueError(f"{who}: max_new {mx} (the columns of hist) must lie in [1, 4096]")
+
+
+def _check_constrain_rows(who, logits2d, V, hist, row_map, supported):
+    """what the two constrain wrappers share once their lists are measured: the logits, the history and the slots behind the rows -> (M, ld, V)"""
+    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None, supported)
+    _check_tensor(who, "hist", hist, torch.int32, tuple(hist.shape), logits2d.device)
+    _check_slots(who, M, hist.shape[0], row_map, logits2d.device)
+    return M, ld, V
+
+
 def select_tokens_supported(V: int, ld: int, dtype) -> bool:
     return bool(lib.load().db1_select_tokens_supported(int(V), int(ld), dt_code(dtype)))
 
@@ -643,24 +703,20 @@ def select_tokens(logits2d, t, finished, lengths, out, next_ids, status, *, V=No
     ``top_logprob`` (float32), both [M, max_new, top_n], all or none and only with the log-prob outputs: the row's ``top_n`` most likely
     tokens and their log-probabilities go to [row, t, :] (db1_select_tokens_top, rule in include/db1_hip.h; everything else is
     bit-identical).  Capturable; raises ValueError on bad arguments before anything is launched."""
-    who, dev, i32 = "select_tokens", logits2d.device, torch.int32
+    who, dev = "select_tokens", logits2d.device
     M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
                                                  lambda V, ld: select_tokens_supported(V, max(ld, V), logits2d.dtype))
     _check_sampling(who, greedy, temperature, top_k, top_p)
-    for name, x, n in (("finished", finished, M), ("lengths", lengths, M), ("status", status, M), ("t", t, 1)) + \
-            ((("stream_id", stream_id, M),) if stream_id is not None else ()):
-        _check_tensor(who, name, x, i32, n, dev)
-    _check_tensor(who, "out", out, i32, (M, -1), dev)
-    _check_next_ids(who, next_ids, M, dev)
-    lp = _check_logprobs(who, logprob, sum_logprob, M, out.shape[1], dev)
-    top = _check_top(who, top_n, top_ids, top_logprob, (M, out.shape[1]), dev)
-    if top and not lp:
-        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    _check_vectors(who, dev, M, finished=finished, lengths=lengths, status=status)
+    _check_vectors(who, dev, 1, t=t)
+    _check_vectors(who, dev, M, optional=("stream_id",), stream_id=stream_id)
+    _check_tensor(who, "out", out, torch.int32, (M, -1), dev)
+    lp, top = _check_outputs(who, M, out.shape[1], dev, next_ids, logprob, sum_logprob, top_n, top_ids, top_logprob)
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     lib.call("db1_select_tokens_top" if top else "db1_select_tokens_lp" if lp else "db1_select_tokens", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi,
              float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
              int(step_base), P(t), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0), P(status),
-             *((P(logprob), P(sum_logprob)) if lp else ()), *((top, P(top_ids), P(top_logprob)) if top else ()), _vp(0), 0, stream())
+             *_own_output_args(lp, top, logprob, sum_logprob, top_ids, top_logprob), _vp(0), 0, stream())
 
 
 def select_tokens_slots_supported(V: int, ld: int, dtype) -> bool:
@@ -678,30 +734,41 @@ def select_tokens_slots(logits2d, t, limit, finished, lengths, out, next_ids, st
     (float32 [S]), both or neither, as ``select_tokens`` takes them, indexed by the slot (db1_select_tokens_slots_lp); ``top_n``, ``top_ids``
     and ``top_logprob`` ([S, max_new, top_n]) likewise (db1_select_tokens_slots_top).  Capturable; raises ValueError on bad arguments
     before anything is launched."""
-    who, dev, i32 = "select_tokens_slots", logits2d.device, torch.int32
-    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
-                                                 lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
-    _check_sampling(who, greedy, temperature, top_k, top_p)
-    S = int(t.numel()) if row_map is not None else M
-    if row_map is not None:
-        _check_tensor(who, "row_map", row_map, i32, M, dev)
-        if S < M:
-            raise ValueError(f"{who}: {M} logits rows for {S} slots")
-    for name, x in (("t", t), ("limit", limit), ("finished", finished), ("lengths", lengths), ("status", status)) + \
-            ((("stream_id", stream_id),) if stream_id is not None else ()):
-        _check_tensor(who, name, x, i32, S, dev)
-    _check_tensor(who, "out", out, i32, (S, -1), dev)
-    _check_next_ids(who, next_ids, S, dev)
-    lp = _check_logprobs(who, logprob, sum_logprob, S, out.shape[1], dev)
-    top = _check_top(who, top_n, top_ids, top_logprob, (S, out.shape[1]), dev)
-    if top and not lp:
-        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
+    _select_slots("select_tokens_slots", logits2d, None, (vocab_lo, vocab_hi, greedy, temperature, top_k, top_p, seed), t, limit, finished, lengths,
+                  out, next_ids, status, V, eos_id, pad_id, step_base, stream_id, row_map, logprob, sum_logprob, top_n, top_ids, top_logprob)
+
+
+def _select_slots(who, logits2d, params, sampling, t, limit, finished, lengths, out, next_ids, status, V, eos_id, pad_id, step_base, stream_id,
+                  row_map, logprob, sum_logprob, top_n, top_ids, top_logprob):
+    """the body of ``select_tokens_slots`` (``sampling``: the seven scalars every slot shares) and ``select_tokens_slots_per`` (None: ``params``)"""
+    dev, per = logits2d.device, sampling is None
+    supported = lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype)
+    if per:
+        M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None, supported)
+    else:
+        vocab_lo, vocab_hi, greedy, temperature, top_k, top_p, seed = sampling
+        M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi, supported)
+        _check_sampling(who, greedy, temperature, top_k, top_p)
+    S = _check_slots(who, M, int(t.numel()) if row_map is not None else M, row_map, dev)
+    _check_vectors(who, dev, S, optional=("stream_id",), t=t, limit=limit, finished=finished, lengths=lengths, status=status, stream_id=stream_id)
+    if per:
+        if params is None:
+            raise ValueError(f"{who}: params is None")
+        _check_tensor(who, "params", params, torch.int32, (S, SLOT_PARAM_WORDS), dev)
+        if params.data_ptr() % 32:
+            raise ValueError(f"{who}: params must be 32-byte aligned")
+    _check_tensor(who, "out", out, torch.int32, (S, -1), dev)
+    lp, top = _check_outputs(who, S, out.shape[1], dev, next_ids, logprob, sum_logprob, top_n, top_ids, top_logprob)
+    head = (P(logits2d), M, V, max(ld, V), dt_code(logits2d))
+    slots = (int(eos_id), int(pad_id), int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids),
+             next_ids.stride(0), P(status), P(row_map), S)
+    outputs = (lp, top, logprob, sum_logprob, top_ids, top_logprob)
+    if per:
+        lib.call("db1_select_tokens_slots_per", *head, P(params), *slots, *_output_args(*outputs), _vp(0), 0, stream())
+        return
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-    lib.call("db1_select_tokens_slots_top" if top else "db1_select_tokens_slots_lp" if lp else "db1_select_tokens_slots", P(logits2d), M, V, max(ld, V), dt_code(logits2d), vocab_lo,
-             vocab_hi, float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(eos_id), int(pad_id),
-             int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0),
-             P(status), P(row_map), S, *((P(logprob), P(sum_logprob)) if lp else ()), *((top, P(top_ids), P(top_logprob)) if top else ()), _vp(0), 0,
-             stream())
+    lib.call("db1_select_tokens_slots_top" if top else "db1_select_tokens_slots_lp" if lp else "db1_select_tokens_slots", *head, vocab_lo, vocab_hi,
+             float(temperature), int(top_k), float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, *slots, *_own_output_args(*outputs), _vp(0), 0, stream())
 
 
 SLOT_PARAM_WORDS = 8
@@ -733,31 +800,8 @@ def select_tokens_slots_per(logits2d, params, t, limit, finished, lengths, out, 
     window is not ``0 <= vocab_lo < vocab_hi <= V``, or which samples with ``1 / temperature`` not finite and positive, ``top_k < 0`` or
     ``top_p`` outside (0, 1], gets status bit 2 (value 4), ``finished`` = 1 and ``pad_id`` in ``next_ids``, nothing else of it touched; a
     greedy slot ignores words 1 and 4 .. 7.  Capturable; raises ValueError on bad arguments before anything is launched."""
-    who, dev, i32 = "select_tokens_slots_per", logits2d.device, torch.int32
-    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None, lambda V, ld: select_tokens_slots_supported(V, max(ld, V), logits2d.dtype))
-    S = int(t.numel()) if row_map is not None else M
-    if row_map is not None:
-        _check_tensor(who, "row_map", row_map, i32, M, dev)
-        if S < M:
-            raise ValueError(f"{who}: {M} logits rows for {S} slots")
-    for name, x in (("t", t), ("limit", limit), ("finished", finished), ("lengths", lengths), ("status", status)) + \
-            ((("stream_id", stream_id),) if stream_id is not None else ()):
-        _check_tensor(who, name, x, i32, S, dev)
-    if params is None:
-        raise ValueError(f"{who}: params is None")
-    _check_tensor(who, "params", params, i32, (S, SLOT_PARAM_WORDS), dev)
-    if params.data_ptr() % 32:
-        raise ValueError(f"{who}: params must be 32-byte aligned")
-    _check_tensor(who, "out", out, i32, (S, -1), dev)
-    _check_next_ids(who, next_ids, S, dev)
-    lp = _check_logprobs(who, logprob, sum_logprob, S, out.shape[1], dev)
-    top = _check_top(who, top_n, top_ids, top_logprob, (S, out.shape[1]), dev)
-    if top and not lp:
-        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
-    lib.call("db1_select_tokens_slots_per", P(logits2d), M, V, max(ld, V), dt_code(logits2d), P(params), int(eos_id), int(pad_id),
-             int(step_base), P(t), P(limit), P(stream_id), P(finished), P(lengths), P(out), out.shape[1], P(next_ids), next_ids.stride(0),
-             P(status), P(row_map), S, P(logprob), P(sum_logprob), top, P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0),
-             _vp(0), 0, stream())
+    _select_slots("select_tokens_slots_per", logits2d, params, None, t, limit, finished, lengths, out, next_ids, status, V, eos_id, pad_id,
+                  step_base, stream_id, row_map, logprob, sum_logprob, top_n, top_ids, top_logprob)
 
 
 def constrain_logits_supported(V: int, ld: int, max_new: int, n_bad: int, dtype) -> bool:
@@ -780,32 +824,20 @@ def constrain_logits(logits2d, t, hist, *, V=None, finished=None, row_map=None, 
     db1_constrain_logits_pen (freq * count + pres off every generated token's logit, the biases added after; the rule is stated with the
     prototype), else to db1_constrain_logits exactly as before.  Capturable; raises ValueError on bad arguments before anything is launched."""
     who, dev, i32 = "constrain_logits", logits2d.device, torch.int32
-    if not torch.is_tensor(hist) or hist.dim() != 2:
-        raise ValueError(f"{who}: hist must be a contiguous {i32} tensor of shape (slots, max_new) on {dev}")
+    S, mx = _check_hist(who, hist, dev)
     if not torch.is_tensor(t) or not (bad is None or torch.is_tensor(bad)):
         raise ValueError(f"{who}: t and bad must be {i32} tensors on {dev} (bad: or None)")
-    S, mx = hist.shape
     n_bad = 0 if bad is None else int(bad.numel())
-    if not 1 <= mx <= 4096:
-        raise ValueError(f"{who}: max_new {mx} (the columns of hist) must lie in [1, 4096]")
+    _check_max_new(who, mx)
     if n_bad > 1024:
         raise ValueError(f"{who}: {n_bad} banned ids (at most 1024)")
-    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None,
-                                   lambda V, ld: constrain_logits_supported(V, max(ld, V), mx, n_bad, logits2d.dtype))
-    _check_tensor(who, "hist", hist, i32, (S, mx), dev)
-    if row_map is not None:
-        _check_tensor(who, "row_map", row_map, i32, M, dev)
-        if S < M:
-            raise ValueError(f"{who}: {M} logits rows for {S} slots")
-    elif S != M:
-        raise ValueError(f"{who}: hist holds {S} rows for {M} logits rows (no row_map)")
+    M, ld, V = _check_constrain_rows(who, logits2d, V, hist, row_map,
+                                     lambda V, ld: constrain_logits_supported(V, max(ld, V), mx, n_bad, logits2d.dtype))
     if t.numel() not in (1, S):
         raise ValueError(f"{who}: t must hold 1 or {S} elements")
-    _check_tensor(who, "t", t, i32, int(t.numel()), dev)
-    if finished is not None:
-        _check_tensor(who, "finished", finished, i32, S, dev)
-    if bad is not None:
-        _check_tensor(who, "bad", bad, i32, n_bad, dev)
+    _check_vectors(who, dev, int(t.numel()), t=t)
+    _check_vectors(who, dev, S, optional=("finished",), finished=finished)
+    _check_vectors(who, dev, n_bad, optional=("bad",), bad=bad)
     theta = float(repetition_penalty)
     if not 0.0 < theta < float("inf"):
         raise ValueError(f"{who}: repetition_penalty {repetition_penalty} must be finite and > 0")
@@ -872,35 +904,45 @@ def stop_match(stop_tok, stop_len, lengths, checked, finished, stop_hit, out, ne
     ``stop_hit``: int32 [S]; ``row_map`` (int32 [M]) as ``select_tokens_slots`` takes it, None: every slot.  ``logprob`` / ``sum_logprob``
     and ``top_n`` / ``top_ids`` / ``top_logprob`` as the selection takes them: the removed positions get 0 and -1 / -inf, the sum is rebuilt.
     Capturable; raises ValueError on bad arguments before anything is launched."""
-    who, i32 = "stop_match", torch.int32
+    _stop_match("stop_match", False, stop_tok, stop_len, lengths, checked, finished, stop_hit, out, next_ids, pad_id, row_map, logprob,
+                sum_logprob, top_n, top_ids, top_logprob)
+
+
+def _stop_match(who, per, stop_tok, stop_len, lengths, checked, finished, stop_hit, out, next_ids, pad_id, row_map, logprob, sum_logprob, top_n,
+                top_ids, top_logprob):
+    """the body of ``stop_match`` (one list [n, 16] / [n]; n goes to the launch) and ``stop_match_per`` (``per``: [S, 16, 16] / [S, 16])"""
+    i32 = torch.int32
     if not torch.is_tensor(out) or out.dim() != 2:
         raise ValueError(f"{who}: out must be a contiguous {i32} tensor of shape (slots, max_new)")
-    dev = out.device
-    S, mx = out.shape
-    if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len) or stop_tok.dim() != 2:
-        raise ValueError(f"{who}: stop_tok [n, {MAX_STOP_LEN}] and stop_len [n] must be {i32} tensors on {dev}")
-    n = int(stop_tok.shape[0])
-    if not 1 <= n <= MAX_STOP_SEQUENCES or not stop_match_supported(n, mx):
-        raise ValueError(f"{who}: {n} stop sequences (1 .. {MAX_STOP_SEQUENCES}), max_new {mx}")
-    _check_tensor(who, "stop_tok", stop_tok, i32, (n, MAX_STOP_LEN), dev)
-    _check_tensor(who, "stop_len", stop_len, i32, (n,), dev)
+    dev, (S, mx) = out.device, out.shape
+    if per:
+        if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len):
+            raise ValueError(f"{who}: stop_tok [slots, {MAX_STOP_SEQUENCES}, {MAX_STOP_LEN}] and stop_len [slots, {MAX_STOP_SEQUENCES}] must be "
+                             f"{i32} tensors on {dev}")
+        if mx < 1:
+            raise ValueError(f"{who}: max_new {mx}")
+        n_arg, tok_shape, len_shape = (), (S, MAX_STOP_SEQUENCES, MAX_STOP_LEN), (S, MAX_STOP_SEQUENCES)
+    else:
+        if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len) or stop_tok.dim() != 2:
+            raise ValueError(f"{who}: stop_tok [n, {MAX_STOP_LEN}] and stop_len [n] must be {i32} tensors on {dev}")
+        n = int(stop_tok.shape[0])
+        if not 1 <= n <= MAX_STOP_SEQUENCES or not stop_match_supported(n, mx):
+            raise ValueError(f"{who}: {n} stop sequences (1 .. {MAX_STOP_SEQUENCES}), max_new {mx}")
+        n_arg, tok_shape, len_shape = (n,), (n, MAX_STOP_LEN), (n,)
+    _check_tensor(who, "stop_tok", stop_tok, i32, tok_shape, dev)
+    _check_tensor(who, "stop_len", stop_len, i32, len_shape, dev)
     _check_tensor(who, "out", out, i32, (S, mx), dev)
-    for name, x in (("lengths", lengths), ("checked", checked), ("finished", finished), ("stop_hit", stop_hit)):
-        _check_tensor(who, name, x, i32, S, dev)
+    _check_vectors(who, dev, S, lengths=lengths, checked=checked, finished=finished, stop_hit=stop_hit)
     M = S
     if row_map is not None:
         M = int(row_map.numel())
         _check_tensor(who, "row_map", row_map, i32, M, dev)
         if not 1 <= M <= S:
             raise ValueError(f"{who}: {M} rows for {S} slots")
-    _check_next_ids(who, next_ids, S, dev)
-    lp = _check_logprobs(who, logprob, sum_logprob, S, mx, dev)
-    top = _check_top(who, top_n, top_ids, top_logprob, (S, mx), dev)
-    if top and not lp:
-        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
-    lib.call("db1_stop_match", P(stop_tok), P(stop_len), n, int(pad_id), P(lengths), P(checked), P(finished), P(stop_hit), P(out), mx,
-             P(next_ids), next_ids.stride(0), P(row_map), M, S, P(logprob) if lp else _vp(0), P(sum_logprob) if lp else _vp(0), top,
-             P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0), stream())
+    lp, top = _check_outputs(who, S, mx, dev, next_ids, logprob, sum_logprob, top_n, top_ids, top_logprob)
+    lib.call("db1_stop_match_per" if per else "db1_stop_match", P(stop_tok), P(stop_len), *n_arg, int(pad_id), P(lengths), P(checked), P(finished),
+             P(stop_hit), P(out), mx, P(next_ids), next_ids.stride(0), P(row_map), M, S,
+             *_output_args(lp, top, logprob, sum_logprob, top_ids, top_logprob), stream())
 
 
 SLOT_CONS_WORDS = 8
@@ -968,11 +1010,8 @@ def constrain_logits_slots_per(logits2d, cons, t, hist, finished, status, *, V=N
     KERNEL checks them: a live slot whose record it refuses gets status bit 3 (value 8) in ``status`` and ``finished`` = 1 (both int32 [S],
     written), its logits untouched.  Capturable; raises ValueError on bad arguments before anything is launched."""
     who, dev, i32 = "constrain_logits_slots_per", logits2d.device, torch.int32
-    if not torch.is_tensor(hist) or hist.dim() != 2:
-        raise ValueError(f"{who}: hist must be a contiguous {i32} tensor of shape (slots, max_new) on {dev}")
-    S, mx = hist.shape
-    if not 1 <= mx <= 4096:
-        raise ValueError(f"{who}: max_new {mx} (the columns of hist) must lie in [1, 4096]")
+    S, mx = _check_hist(who, hist, dev)
+    _check_max_new(who, mx)
     caps = []
     for name, x in (("bad", bad), ("bias_ids", bias_ids), ("bias_val", bias_val)):
         if x is not None and (not torch.is_tensor(x) or x.dim() != 2):
@@ -983,20 +1022,12 @@ def constrain_logits_slots_per(logits2d, cons, t, hist, finished, status, *, V=N
         raise ValueError(f"{who}: bias_ids and bias_val must have one shape (or both be None)")
     if bad_cap > MAX_SLOT_LIST or bias_cap > MAX_SLOT_LIST:
         raise ValueError(f"{who}: capacities {bad_cap}, {bias_cap} (at most {MAX_SLOT_LIST})")
-    M, ld, V, _, _ = _check_logits(who, logits2d, V, 0, None,
-                                   lambda V, ld: constrain_logits_slots_supported(V, max(ld, V), mx, bad_cap, bias_cap, logits2d.dtype))
-    _check_tensor(who, "hist", hist, i32, (S, mx), dev)
-    if row_map is not None:
-        _check_tensor(who, "row_map", row_map, i32, M, dev)
-        if S < M:
-            raise ValueError(f"{who}: {M} logits rows for {S} slots")
-    elif S != M:
-        raise ValueError(f"{who}: hist holds {S} rows for {M} logits rows (no row_map)")
+    M, ld, V = _check_constrain_rows(who, logits2d, V, hist, row_map,
+                                     lambda V, ld: constrain_logits_slots_supported(V, max(ld, V), mx, bad_cap, bias_cap, logits2d.dtype))
     for name, x in (("t", t), ("finished", finished), ("status", status), ("cons", cons)):
         if not torch.is_tensor(x):      # (none of them is optional here: the guard writes finished and status)
             raise ValueError(f"{who}: {name} must be a {i32} tensor on {dev}, got {type(x).__name__}")
-    for name, x in (("t", t), ("finished", finished), ("status", status)):
-        _check_tensor(who, name, x, i32, S, dev)
+    _check_vectors(who, dev, S, t=t, finished=finished, status=status)
     _check_tensor(who, "cons", cons, i32, (S, SLOT_CONS_WORDS), dev)
     if cons.data_ptr() % 32:
         raise ValueError(f"{who}: cons must be 32-byte aligned")
@@ -1016,35 +1047,8 @@ def stop_match_per(stop_tok, stop_len, lengths, checked, finished, stop_hit, out
     ``stop_len`` int32 [S, 16] (device; slot s's ``pack_slot_constraints`` table at [s]; an unused entry has length 0), everything else as
     ``stop_match`` takes it, and a slot comes out exactly as that would leave it under the slot's list.  Capturable; raises ValueError on
     bad arguments before anything is launched."""
-    who, i32 = "stop_match_per", torch.int32
-    if not torch.is_tensor(out) or out.dim() != 2:
-        raise ValueError(f"{who}: out must be a contiguous {i32} tensor of shape (slots, max_new)")
-    dev = out.device
-    S, mx = out.shape
-    if not torch.is_tensor(stop_tok) or not torch.is_tensor(stop_len):
-        raise ValueError(f"{who}: stop_tok [slots, {MAX_STOP_SEQUENCES}, {MAX_STOP_LEN}] and stop_len [slots, {MAX_STOP_SEQUENCES}] must be "
-                         f"{i32} tensors on {dev}")
-    if mx < 1:
-        raise ValueError(f"{who}: max_new {mx}")
-    _check_tensor(who, "stop_tok", stop_tok, i32, (S, MAX_STOP_SEQUENCES, MAX_STOP_LEN), dev)
-    _check_tensor(who, "stop_len", stop_len, i32, (S, MAX_STOP_SEQUENCES), dev)
-    _check_tensor(who, "out", out, i32, (S, mx), dev)
-    for name, x in (("lengths", lengths), ("checked", checked), ("finished", finished), ("stop_hit", stop_hit)):
-        _check_tensor(who, name, x, i32, S, dev)
-    M = S
-    if row_map is not None:
-        M = int(row_map.numel())
-        _check_tensor(who, "row_map", row_map, i32, M, dev)
-        if not 1 <= M <= S:
-            raise ValueError(f"{who}: {M} rows for {S} slots")
-    _check_next_ids(who, next_ids, S, dev)
-    lp = _check_logprobs(who, logprob, sum_logprob, S, mx, dev)
-    top = _check_top(who, top_n, top_ids, top_logprob, (S, mx), dev)
-    if top and not lp:
-        raise ValueError(f"{who}: top_n needs logprob and sum_logprob")
-    lib.call("db1_stop_match_per", P(stop_tok), P(stop_len), int(pad_id), P(lengths), P(checked), P(finished), P(stop_hit), P(out), mx,
-             P(next_ids), next_ids.stride(0), P(row_map), M, S, P(logprob) if lp else _vp(0), P(sum_logprob) if lp else _vp(0), top,
-             P(top_ids) if top else _vp(0), P(top_logprob) if top else _vp(0), stream())
+    _stop_match("stop_match_per", True, stop_tok, stop_len, lengths, checked, finished, stop_hit, out, next_ids, pad_id, row_map, logprob,
+                sum_logprob, top_n, top_ids, top_logprob)
 
 
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:

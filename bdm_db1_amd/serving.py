@@ -25,15 +25,16 @@ from __future__ import annotations
 
 import dataclasses
 from collections import OrderedDict
+from functools import partial
 from typing import Iterable, Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
-from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained, _need_memory,
-                         _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _work, caption_prompt,
-                         question_prompts)
+from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodeKey, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained,
+                         _need_memory, _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _work,
+                         caption_prompt, question_prompts)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- requests
@@ -229,34 +230,39 @@ class SlotScheduler:
 
 # ----------------------------------------------------------------------------------------------------------------------- the device state
 class _SlotState(_SamplingState):
-    """the device state of ``slots`` slots: per-slot token counter, limit, flags, stream id and output row; ``per``: also every slot's
-    sampling record ``params`` [slots, 8] (``ops.pack_slot_params``), and the selection is db1_select_tokens_slots_per; ``caps`` =
-    (max_bad_token_ids, max_logit_bias): every slot's constraints live in device tables (``ops.pack_slot_constraints``: the record
-    ``cons_rec`` [slots, 8], ``bad`` [slots, caps[0]], ``bias_ids`` / ``bias_val`` [slots, caps[1]], ``stop_tok`` [slots, 16, 16] and
-    ``stop_len`` [slots, 16]), ``cons`` is only what a slot starts with and a request without its own runs under, and the selection is
-    framed by db1_constrain_logits_slots_per and db1_stop_match_per, both always launched"""
+    """the device state of ``key.rows`` slots: per-slot token counter, limit, flags, stream id and output row; ``key.per_request``: also
+    every slot's sampling record ``params`` [slots, 8] (``ops.pack_slot_params``), and the selection is db1_select_tokens_slots_per;
+    ``key.caps`` = (max_bad_token_ids, max_logit_bias): every slot's constraints live in device tables (``ops.pack_slot_constraints``:
+    the record ``cons_rec`` [slots, 8], ``bad`` [slots, caps[0]], ``bias_ids`` / ``bias_val`` [slots, caps[1]], ``stop_tok``
+    [slots, 16, 16] and ``stop_len`` [slots, 16]), ``key.constraints`` is only what a slot starts with and a request without its own runs
+    under, and the selection is framed by db1_constrain_logits_slots_per and db1_stop_match_per, both always launched"""
     cache = "_slot_generator"
-    _PER_SLOT = ("vocab_lo", "vocab_hi", "greedy", "temperature", "top_k", "top_p", "seed")     # what the record replaces in ``sel``
 
-    def __init__(self, model, slots: int, cfg: GenerationConfig, V: int, hi: int, cons: Optional[DecodingConstraints] = None,
-                 per: bool = False, caps: Optional[Tuple[int, int]] = None):
-        super().__init__(model, slots, cfg, V, hi, None if caps is not None else cons)
-        self.t = torch.zeros(slots, **self.i32)
+    def __init__(self, model, key: DecodeKey):
+        slots, cfg, caps = key.rows, key.cfg, key.caps
+        super().__init__(model, key, slots, slots, None if caps is not None else key.constraints)
         self.limit = torch.ones(slots, **self.i32)
         self.finished.fill_(1)       # (vacant)
+        state = dict(t=self.t, limit=self.limit, finished=self.finished, lengths=self.lengths, out=self.out, status=self.status)
         self.params = None
-        if per:     # (every slot starts with the config's own record: a vacant slot's is never read, but it is never garbage either)
-            rec = ops.pack_slot_params(**SamplingParams().resolve(cfg, V, hi))
+        if not key.per_request:
+            self._pick = partial(ops.select_tokens_slots, **state, **self.sel)
+        else:     # (every slot starts with the config's own record: a vacant slot's is never read, but it is never garbage either)
+            rec = ops.pack_slot_params(**SamplingParams().resolve(cfg, key.V, key.hi))
             self.params = torch.from_numpy(np.tile(rec, (slots, 1))).to(self.dev)
-            self.sel_per = {k: v for k, v in self.sel.items() if k not in self._PER_SLOT}
+            self._pick = partial(ops.select_tokens_slots_per, params=self.params, **state, **self.sel_shared)
         self.caps, self.tables = caps, None
         if caps is not None:     # (every slot starts with the stream's own constraints, as it starts with the config's sampling record)
             self.eos = -1 if cfg.eos_id is None else int(cfg.eos_id)
-            self.stream_rows = ops.pack_slot_constraints(cons, cfg.eos_id, *caps)
+            self.stream_rows = ops.pack_slot_constraints(key.constraints, cfg.eos_id, *caps)
             self.tables = [torch.from_numpy(np.tile(x, (slots,) + (1,) * x.ndim)).to(self.dev) for x in self.stream_rows]
             self.cons_rec, self.bad, self.bias_ids, self.bias_val, self.stop_tok, self.stop_len = self.tables
             self.checked, self.stop_hit = torch.zeros(slots, **self.i32), torch.zeros(slots, **self.i32)
-            self.stop_per = {k: self.sel[k] for k in ("logprob", "sum_logprob", "top_n", "top_ids", "top_logprob") if k in self.sel}
+            self._constrain = partial(ops.constrain_logits_slots_per, cons=self.cons_rec, t=self.t, hist=self.out, finished=self.finished,
+                                      status=self.status, V=self.V, bad=self.bad if caps[0] else None, bias_ids=self.bias_ids if caps[1] else None,
+                                      bias_val=self.bias_val if caps[1] else None, eos_id=self.eos)
+            self._stop = partial(ops.stop_match_per, stop_tok=self.stop_tok, stop_len=self.stop_len, lengths=self.lengths, checked=self.checked,
+                                 finished=self.finished, stop_hit=self.stop_hit, out=self.out, pad_id=int(cfg.pad_id), **self.lp_top)
 
     def start(self):
         self.finished.fill_(1)
@@ -294,28 +300,10 @@ class _SlotState(_SamplingState):
                 at += w
         return idx.to(torch.int32)
 
-    def constrain(self, logits2d, row_map=None):
-        if self.tables is None:
-            return super().constrain(logits2d, row_map)
-        ops.constrain_logits_slots_per(logits2d, self.cons_rec, self.t, self.out, self.finished, self.status, V=self.V, row_map=row_map,
-                                       bad=self.bad if self.caps[0] else None, bias_ids=self.bias_ids if self.caps[1] else None,
-                                       bias_val=self.bias_val if self.caps[1] else None, eos_id=self.eos)
-
-    def stop_match(self, next_ids, row_map=None):
-        if self.tables is None:
-            return super().stop_match(next_ids, row_map)
-        ops.stop_match_per(self.stop_tok, self.stop_len, self.lengths, self.checked, self.finished, self.stop_hit, self.out, next_ids,
-                           pad_id=int(self.cfg.pad_id), row_map=row_map, **self.stop_per)
-
     def select(self, logits2d, next_ids, row_map=None):
         """constrain -> select -> stop, all over the same rows: the prefill's token 0 (``row_map``: the new tenants) and every replay"""
         self.constrain(logits2d, row_map)
-        if self.params is not None:
-            ops.select_tokens_slots_per(logits2d, self.params, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status,
-                                        row_map=row_map, **self.sel_per)
-        else:
-            ops.select_tokens_slots(logits2d, self.t, self.limit, self.finished, self.lengths, self.out, next_ids, self.status, row_map=row_map,
-                                    **self.sel)
+        self._pick(logits2d, next_ids=next_ids, row_map=row_map)
         self.stop_match(next_ids, row_map)
 
     def epilogue(self, logits2d, next_ids, ring=None):
@@ -381,11 +369,9 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_slots_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens_slots does not support a vocabulary of {V}")
-    key = _constrained("generate_stream", model, (slots, cfg, V, hi), constraints, cfg.max_new_tokens)
-    min_new = 0 if constraints is None else constraints.min_new_tokens
     per_request = bool(per_request)
-    if per_request:     # (with the flag off the key is what it was)
-        key = _per_request_key(key)
+    key = _constrained("generate_stream", model, DecodeKey(rows=slots, cfg=cfg, V=V, hi=hi, per_request=per_request), constraints, cfg.max_new_tokens)
+    min_new = 0 if constraints is None else constraints.min_new_tokens
     caps = None
     if per_request_constraints:     # (with the flag off the key is what it was, and neither capacity is looked at)
         caps = _capacities(max_bad_token_ids, max_logit_bias)
@@ -393,11 +379,11 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
             raise ValueError(f"db1_constrain_logits_slots_per does not support a vocabulary of {V} with max_new_tokens {cfg.max_new_tokens}")
         if constraints is not None:
             _fits(constraints, caps, "the stream's")
-        key = _per_request_constraints_key(key, per_request, caps)
+        key = dataclasses.replace(key, caps=caps)
     if isinstance(requests, (list, tuple)):
         for _ in _requests(requests, cfg, min_new, per_request, (V, hi), caps):     # (a list can be checked as a whole before the first launch)
             pass
-    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi), caps), key, stream_ids, stats, replay, per_request)
+    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi), caps), key, stream_ids, stats, replay)
 
 
 def _capacities(max_bad_token_ids, max_logit_bias) -> Tuple[int, int]:
@@ -407,29 +393,12 @@ def _capacities(max_bad_token_ids, max_logit_bias) -> Tuple[int, int]:
     return int(max_bad_token_ids), int(max_logit_bias)
 
 
-def _per_request_constraints_key(key: tuple, per: bool, caps: Tuple[int, int]) -> tuple:
-    """the state key of a stream with the per-request-constraints flag set, (slots, cfg, V, hi, cons, per, caps): ``_SlotState``'s
-    arguments by name, as ``_per_request_key`` builds them, with the two capacities last"""
-    slots, cfg, V, hi, cons, _ = _per_request_key(key[:5] if len(key) > 4 else key)
-    return (slots, cfg, V, hi, cons, bool(per), caps)
-
-
-def _per_request_key(key: tuple) -> tuple:
-    """the state key (slots, cfg, V, hi[, constraints]) of a stream with the per-request flag set: ``_SlotState``'s arguments by name,
-    (slots, cfg, V, hi, cons, per): where the flag sits is decided here and nowhere else (``_stream``, like before, reads only the first
-    four, which every state key starts with)"""
-    slots, cfg, V, hi, *cons = key
-    return (slots, cfg, V, hi, cons[0] if cons else None, True)
-
-
-def _stream(model, reqs, key, stream_ids, stats, replay, per=False):
-    slots, cfg, V, hi = key[:4]
+def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
+    slots, cfg, V, hi, per, caps = key.rows, key.cfg, key.V, key.hi, key.per_request, key.caps
     inherit = SamplingParams()
     sched = SlotScheduler(slots, reqs)
     counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
-    caps = key[6] if len(key) > 6 else None
-    stream_cons = key[4] if len(key) > 4 else None
-    if caps is not None or (stream_cons is not None and stream_cons.stop_sequences):      # (the key set is what it was without stop sequences)
+    if caps is not None or (key.constraints is not None and key.constraints.stop_sequences):      # (the key set is what it was without stop sequences)
         counts["stopped"] = 0
     live_steps = 0
 

@@ -315,7 +315,8 @@ def test_cache_key_and_the_unconstrained_path():
     b_before = beam_search(model, x, bc)
     s_before = generate_many(model, [x], gc, slots=2)
     gen, bgen, sgen = model._generator, model._beam_generator, model._slot_generator
-    assert len(gen.key) == 4 and gen.state.con is None
+    k = gen.key
+    assert k.constraints is None and not k.per_request and k.caps is None and k.n is None and gen.state.con is None
     same = generate(model, x, gc, constraints=None)
     noop = generate(model, x, gc, constraints=DecodingConstraints())
     assert model._generator is gen                               # None, then a no-op object: the cached generator is reused
@@ -327,7 +328,8 @@ def test_cache_key_and_the_unconstrained_path():
     cons = DecodingConstraints(repetition_penalty=1.2)
     generate(model, x, gc, constraints=cons)
     real = model._generator
-    assert real is not gen and real.key[-1] == cons and real.state.con is not None
+    k = real.key
+    assert real is not gen and k.constraints == cons and not k.per_request and k.caps is None and k.n is None and real.state.con is not None
     generate(model, x, gc, constraints=DecodingConstraints(repetition_penalty=1.2))
     assert model._generator is real                              # an equal constraint: the same graph
     generate(model, x, gc, constraints=DecodingConstraints(repetition_penalty=1.2, bad_token_ids=(5,)))
@@ -342,7 +344,8 @@ def test_cache_key_and_the_unconstrained_path():
     assert all(torch.equal(p, q) for p, q in zip(s_after[0], s_before[0])) and s_after[1] == s_before[1]
     # min_new_tokens without an EOS edits nothing: the unconstrained generator is reused, no graph is captured for it
     plain_gen = model._generator
-    assert len(plain_gen.key) == 4
+    k = plain_gen.key
+    assert k.constraints is None and not k.per_request and k.caps is None and k.n is None
     generate(model, x, gc, constraints=DecodingConstraints(min_new_tokens=3))
     assert model._generator is plain_gen and plain_gen.state.con is None
     assert not DecodingConstraints(min_new_tokens=3).applies(None) and DecodingConstraints(min_new_tokens=3).applies(5)

@@ -245,7 +245,7 @@ def test_no_op_objects_keep_the_cache_key_and_beams_refuse_stop_sequences():
     from bdm_db1_amd import DecodingConstraints as D, GenerationConfig
     from bdm_db1_amd import generation as G
     gc = GenerationConfig(max_new_tokens=8)
-    key = (2, gc, 100, 90)
+    key = G.DecodeKey(rows=2, cfg=gc, V=100, hi=90, constraints=None, n=None, per_request=False, caps=None)
     model = SimpleNamespace(compute_dtype=None)                   # (never looked at: a no-op returns before any query)
     for c in (None, D(), D(frequency_penalty=0.0, presence_penalty=0.0, logit_bias=(), stop_sequences=()), D(min_new_tokens=3)):
         assert G._constrained("generate", model, key, c, 8) is key

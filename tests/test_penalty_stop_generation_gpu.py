@@ -227,7 +227,8 @@ def test_generate_equals_a_host_driven_loop_under_the_rule(model):
     e_ids, _ = generate(model, x, gc, replay=False, constraints=cons)
     HostState = _host_states(_rule_kw(cons))[0]
     with torch.no_grad():
-        h_ids, h_len = G._decode(model, x, HostState, (3, gc, int(model.total_vocab_size), 540), True, False, None, start=(None,))
+        h_ids, h_len = G._decode(model, x, HostState, G.DecodeKey(rows=3, cfg=gc, V=int(model.total_vocab_size), hi=540, constraints=None, n=None,
+                                                                   per_request=False, caps=None), True, False, None, start=(None,))
     assert torch.equal(ids, h_ids) and torch.equal(lengths, h_len) and torch.equal(ids, e_ids)
     assert (ids.numpy() != base).any() and not np.isin(ids.numpy(), cons.bad_token_ids).any()
     model._host_generator = None
@@ -261,7 +262,8 @@ def test_beam_search_equals_a_host_driven_search_under_the_rule(model):
     assert stats["path"] == "ring"
     HostBeam = _host_states(_rule_kw(cons))[1]
     with torch.no_grad():
-        h_ids, h_len, h_sc = G._decode(model, x, HostBeam, (2, bc, int(model.total_vocab_size), 540), True, False, None)
+        h_ids, h_len, h_sc = G._decode(model, x, HostBeam, G.DecodeKey(rows=2, cfg=bc, V=int(model.total_vocab_size), hi=540, constraints=None, n=None,
+                                                                        per_request=False, caps=None), True, False, None)
     assert torch.equal(ids, h_ids) and torch.equal(lengths, h_len) and (_bits(scores) == _bits(h_sc)).all()
     assert (ids.numpy() != base).any()
     model._host_beam_generator = None
@@ -282,7 +284,9 @@ def test_defaults_change_nothing():
     same = generate(model, x, gc, stats=s1, constraints=off)
     s_same = generate_many(model, [x], gc, slots=2, stats=t1, constraints=off)
     assert model._generator is gen and model._slot_generator is sgen          # the cached generators are reused: the key is what it was
-    assert len(gen.key) == 4 and gen.state.con is None and gen.state.stop is None and gen.state.checked is None and gen.state.stop_hit is None
+    k = gen.key
+    assert k.constraints is None and not k.per_request and k.caps is None and k.n is None
+    assert gen.state.con is None and gen.state.stop is None and gen.state.checked is None and gen.state.stop_hit is None
     assert torch.equal(same[0], before[0]) and torch.equal(same[1], before[1])
     assert all(torch.equal(p, q) for p, q in zip(s_same[0], s_before[0])) and s_same[1] == s_before[1]
     assert set(s1) == set(s0) == {"path", "token_calls"} and set(t1) == set(t0) and "stopped" not in t0
@@ -293,6 +297,8 @@ def test_defaults_change_nothing():
     # stop sequences alone: a new key, no constrain launch, the stop state exists
     generate(model, x, gc, constraints=DecodingConstraints(stop_sequences=[(5,)]))
     st = model._generator.state
-    assert len(model._generator.key) == 5 and st.con is None and st.stop is not None and st.checked.shape == (3,)
+    k = model._generator.key
+    assert k.constraints == DecodingConstraints(stop_sequences=[(5,)]) and not k.per_request and k.caps is None and k.n is None
+    assert st.con is None and st.stop is not None and st.checked.shape == (3,)
     after = generate(model, x, gc)
     assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[1])

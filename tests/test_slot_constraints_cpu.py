@@ -198,32 +198,38 @@ def test_every_refusal_comes_before_a_launch(no_launch):
 def test_the_cache_key_changes_only_with_the_flag(no_launch):
     from bdm_db1_amd import DecodingConstraints as D
     from bdm_db1_amd import GenerationConfig, generate_stream
+    import dataclasses
     import inspect
     from bdm_db1_amd import answer_stream, caption_stream, generate_many, serving
+    from bdm_db1_amd.generation import DecodeKey
     model, seen = no_launch
     cfg = GenerationConfig(max_new_tokens=8)
     c = D(repetition_penalty=1.2)
+    key = lambda constraints, per_request, caps: DecodeKey(rows=3, cfg=cfg, V=V, hi=V, constraints=constraints, n=None, per_request=per_request,
+                                                           caps=caps)
     keys = {}
     for name, kw in (("plain", {}), ("cons", dict(constraints=c)), ("per", dict(per_request=True)), ("noop", dict(constraints=D())),
                      ("caps_ignored", dict(max_bad_token_ids=7, max_logit_bias=9)), ("bad_caps_ignored", dict(max_bad_token_ids=5000))):
         generate_stream(model, [_text(4)], cfg, slots=3, **kw)
         keys[name] = seen["key"]
-    assert keys["plain"] == (3, cfg, V, V) == keys["noop"] == keys["caps_ignored"] == keys["bad_caps_ignored"]
-    assert keys["cons"] == (3, cfg, V, V, c) and keys["per"] == (3, cfg, V, V, None, True)
+    assert keys["plain"] == key(None, False, None) == keys["noop"] == keys["caps_ignored"] == keys["bad_caps_ignored"]
+    assert keys["cons"] == key(c, False, None) and keys["per"] == key(None, True, None)
     on = dict(per_request_constraints=True)
     for name, kw in (("on", on), ("on_cons", dict(on, constraints=c)), ("on_per", dict(on, per_request=True)),
                      ("on_caps", dict(on, max_bad_token_ids=7, max_logit_bias=0)), ("on_noop", dict(on, constraints=D()))):
         generate_stream(model, [_text(4)], cfg, slots=3, **kw)
         keys[name] = seen["key"]
-    assert keys["on"] == (3, cfg, V, V, None, False, (64, 64)) == keys["on_noop"] and keys["on_cons"] == (3, cfg, V, V, c, False, (64, 64))
-    assert keys["on_per"] == (3, cfg, V, V, None, True, (64, 64)) and keys["on_caps"] == (3, cfg, V, V, None, False, (7, 0))
+    assert keys["on"] == key(None, False, (64, 64)) == keys["on_noop"] and keys["on_cons"] == key(c, False, (64, 64))
+    assert keys["on_per"] == key(None, True, (64, 64)) and keys["on_caps"] == key(None, False, (7, 0))
     distinct = []
     for k in keys.values():
         if k not in distinct:
             distinct.append(k)
     assert len(distinct) == 7
-    # the key is _SlotState's arguments by name, and the public entry points take the keywords
-    assert list(inspect.signature(serving._SlotState.__init__).parameters)[1:] == ["model", "slots", "cfg", "V", "hi", "cons", "per", "caps"]
+    # the key's fields are exactly these, every state is built from (model, key), and the public entry points take the keywords
+    assert [f.name for f in dataclasses.fields(DecodeKey)] == ["rows", "cfg", "V", "hi", "constraints", "n", "per_request", "caps"]
+    assert all(type(k) is DecodeKey for k in keys.values()) and len(set(keys.values())) == 7           # (hashable, compared by value)
+    assert list(inspect.signature(serving._SlotState.__init__).parameters) == ["self", "model", "key"]
     sig = inspect.signature(generate_stream).parameters
     assert (sig["per_request_constraints"].default, sig["max_bad_token_ids"].default, sig["max_logit_bias"].default) == (False, 64, 64)
     for fn in (generate_many, caption_stream, answer_stream):

@@ -80,11 +80,13 @@ def base(model, prompts):
 
 def test_the_flag_alone_changes_nothing(model, prompts, base):
     from bdm_db1_amd import DecodingConstraints as D
+    from bdm_db1_amd.generation import DecodeKey
     reqs = list(zip(prompts, LIMITS))
     on, s_on = _run(model, reqs, _cfg(), **ON)
     _equal(on, base[0])
     assert "stopped" not in base[1] and s_on["stopped"] == 0 and set(s_on) == set(base[1]) | {"stopped"}
-    assert len(model._slot_generator.key) == 7 and model._slot_generator.key[5:] == (False, (32, 4))
+    assert model._slot_generator.key == DecodeKey(rows=SLOTS, cfg=_cfg(), V=model.total_vocab_size, hi=WIN, constraints=None, n=None,
+                                                  per_request=False, caps=(32, 4))
     # ... and with a stream-level object every request runs under
     C = D(repetition_penalty=1.2, no_repeat_ngram_size=2, frequency_penalty=0.3, logit_bias={int(base[0][0][1][0]): -3.0})
     off_c, _ = _run(model, reqs, _cfg(), constraints=C)
@@ -205,6 +207,7 @@ def test_a_neighbours_constraints_touch_nobody_else_and_a_slot_keeps_nothing_of_
 
 def test_the_flag_works_together_with_per_request_sampling(model, prompts):
     from bdm_db1_amd import DecodingConstraints as D
+    from bdm_db1_amd.generation import DecodeKey
     from bdm_db1_amd import SamplingParams as SP
     reqs = list(zip(prompts, LIMITS))
     cfg = _cfg()
@@ -212,7 +215,8 @@ def test_the_flag_works_together_with_per_request_sampling(model, prompts):
     sps = [None, SP(greedy=True), SP(temperature=0.7, top_k=5), None, SP(seed=99, top_p=0.5), SP(greedy=True, vocab_lo=LO + 10, vocab_hi=WIN - 5), None,
            SP(temperature=1.5)]
     both, _ = _run(model, [(p, lim, sp, C) for (p, lim), sp in zip(reqs, sps)], cfg, per_request=True, **ON)
-    assert model._slot_generator.key[5:] == (True, (32, 4))
+    assert model._slot_generator.key == DecodeKey(rows=SLOTS, cfg=cfg, V=model.total_vocab_size, hi=WIN, constraints=None, n=None,
+                                                  per_request=True, caps=(32, 4))
     want, _ = _run(model, [(p, lim, sp) for (p, lim), sp in zip(reqs, sps)], cfg, per_request=True, constraints=C)
     _equal(both, want)
     # constraints per request and params per request, both differing from request to request

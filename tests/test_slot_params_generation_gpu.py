@@ -72,6 +72,7 @@ def _check_request(model, x, ids, length, limit, v, who=None):
 @pytest.mark.parametrize("kind", ["greedy", "sampled", "logprobs"])
 def test_the_flag_alone_changes_nothing(model, prompts, kind):
     from bdm_db1_amd import generate_many
+    from bdm_db1_amd.generation import DecodeKey
     cfg = _cfg(kind != "sampled", **(dict(logprobs=True, top_logprobs=3) if kind == "logprobs" else {}))
     reqs = [(_text(p), lim) for p, lim in zip(prompts, LIMITS)]
     s0, s1 = {}, {}
@@ -85,7 +86,9 @@ def test_the_flag_alone_changes_nothing(model, prompts, kind):
             assert (x == y) if isinstance(x, int) else (x.dtype == y.dtype and x.numpy().tobytes() == y.numpy().tobytes())
     assert s0 == s1
     # the flag is part of the generator's key, and only when it is set
-    assert key0 == (SLOTS, cfg, model.total_vocab_size, HI) and model._slot_generator.key == key0 + (None, True)
+    plain = DecodeKey(rows=SLOTS, cfg=cfg, V=model.total_vocab_size, hi=HI, constraints=None, n=None, per_request=False, caps=None)
+    assert key0 == plain and model._slot_generator.key == DecodeKey(rows=SLOTS, cfg=cfg, V=model.total_vocab_size, hi=HI, constraints=None,
+                                                                    n=None, per_request=True, caps=None)
     assert model._slot_generator.state.params.shape == (SLOTS, 8)
 
 

@@ -176,9 +176,9 @@ def device_us(fn, calls=50):
 def beam_kernels_us(G, W, t_reorder=N_NEW - 1):
     """db1_beam_step on random bf16 logits at step 1 (every beam live) and db1_ring_reorder at t = t_reorder over a ring of M rows"""
     from bdm_db1_amd.decode import RingMemory
-    from bdm_db1_amd.generation import _BeamState
+    from bdm_db1_amd.generation import DecodeKey, _BeamState
     M, V, hi = G * W, int(model.total_vocab_size), int(model.text_vocab_size)
-    st = _BeamState(model, G, BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, vocab_hi=hi), V, hi)
+    st = _BeamState(model, DecodeKey(rows=G, cfg=BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, vocab_hi=hi), V=V, hi=hi))
     logits = torch.randn(M, V, device=dev).to(torch.bfloat16)
     ids = torch.zeros(M, 1, dtype=torch.long, device=dev)
     st.start()
@@ -227,7 +227,7 @@ def stream_main(n_req=256, slots=64):
     from bdm_db1_amd import caption_stream
     from bdm_db1_amd.decode import RingMemory
     from bdm_db1_amd.serving import _SlotState
-    from bdm_db1_amd.generation import _ring_generator, _text_window, _vocab_window
+    from bdm_db1_amd.generation import DecodeKey, _ring_generator, _text_window, _vocab_window
     limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
     cfg = GenerationConfig(max_new_tokens=N_NEW)
     batches = [batch(slots + k) for k in range((n_req + slots - 1) // slots)]       # (another seed per batch)
@@ -303,7 +303,7 @@ def stream_main(n_req=256, slots=64):
     rec.update(stream_replays=stats["replays"], prefill_calls=stats["prefill_calls"], occupancy=round(stats["occupancy"], 4))
     tcfg = _text_window(model, cfg)
     V, hi = _vocab_window(model, tcfg)
-    sg = _ring_generator(model, _SlotState, (slots, tcfg, V, hi))
+    sg = _ring_generator(model, _SlotState, DecodeKey(rows=slots, cfg=tcfg, V=V, hi=hi))
     st = sg.state
 
     def live():
