@@ -83,21 +83,31 @@ class GraphedMemoryStep:
 
 class RingMemory:
     """Transformer-XL memory for hipGraph-replayed inference: per layer the projected keys / values of the last ``mem_len`` tokens in a
-    ring [B, mem_len + 64, 2, H, D], appended IN PLACE by the attention launch of each call (db1_relattn_decode_ring_fwd), and a device
-    scalar with the ring's origin.  Pass it as ``mems`` (``model(x, compute_loss=False, mems=ring)`` returns it back as the new memory).
+    ring [B, mem_len + 64, 2, H, D] (``kv_dtype`` "fp8": [B, mem_len + 64, 264 H] bytes), appended IN PLACE by the attention launch of
+    each call (db1_relattn_decode_ring_fwd / db1_relattn_decode_ring_kv8_fwd), and a device scalar with the ring's origin.  Pass it as ``mems`` (``model(x, compute_loss=False, mems=ring)`` returns it back as the new memory).
     What it does not keep is the reference's memory CONTENT -- the hidden states (transformer_xl.py:470-504): a caller that reads or edits
     ``mems[i]`` needs the list form (``model.init_mem``); evaluate_rl's loop only hands the memory back to the model."""
 
-    def __init__(self, model, batch_size: int):
+    def __init__(self, model, batch_size: int, kv_dtype: str = "bf16"):
+        """``kv_dtype`` "fp8": the keys / values as e4m3 payload with one power-of-two scale per (row, position, K or V, head) -- rings of
+        uint8 [B, cap, 264 H], about half the bytes to stream per token and to hold (the format: include/db1_hip.h, "fp8 K/V ring")."""
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"RingMemory: kv_dtype must be 'bf16' or 'fp8' (got {kv_dtype!r})")
         if model.compute_dtype != torch.bfloat16 or not model.use_decode or model.d_head != 128 or not model.mem_len:
             raise ValueError("RingMemory needs the bf16 K/V-cached decode path (d_head 128, mem_len > 0)")
-        self.model, self.B = model, batch_size
+        from . import ops
+        if kv_dtype == "fp8" and not ops.relattn_decode_ring_kv8_supported(batch_size, 1, int(model.mem_len) + 1, model.n_head, model.d_head):
+            raise ValueError(f"RingMemory: no fp8 K/V ring for this model (d_head 128, an even number of heads and mem_len <= 2047 expected; "
+                             f"got n_head {model.n_head}, d_head {model.d_head}, mem_len {model.mem_len})")
+        self.model, self.B, self.kv_dtype = model, batch_size, kv_dtype
         self.cap = int(model.mem_len) + 64
         dev = model.dev
-        self.kv = [torch.zeros(batch_size, self.cap, 2, model.n_head, model.d_head, device=dev, dtype=torch.bfloat16) for _ in range(model.n_layer)]
+        if kv_dtype == "fp8":
+            self.kv = [torch.zeros(batch_size, self.cap, ops.kv8_slot_bytes(model.n_head, model.d_head), device=dev, dtype=torch.uint8) for _ in range(model.n_layer)]
+        else:
+            self.kv = [torch.zeros(batch_size, self.cap, 2, model.n_head, model.d_head, device=dev, dtype=torch.bfloat16) for _ in range(model.n_layer)]
         self.state = torch.zeros(1, dtype=torch.int32, device=dev)
         self.load_status = torch.zeros(1, dtype=torch.int32, device=dev)   # (what load_rows skipped: db1_ring_load_rows' status word)
-        from . import ops
         self._ptrs = ops.ring_pointers(self.kv)   # (the layers' base pointers for reorder: made here, never under a capture)
         self.reset()
 
@@ -109,12 +119,16 @@ class RingMemory:
         """fill the ring from a list-form memory (``model.init_mem`` layout: per layer the hidden states [B, mem_len, d] a call with
         ``mems=`` returned, e.g. after a prompt longer than 64 tokens ran through the list-form path): the projection ``reset`` does for the
         zero memory, applied to the given states; origin 0"""
+        from . import ops
         model, mlen = self.model, int(self.model.mem_len)
         if len(mems) != model.n_layer or any(tuple(m.shape) != (self.B, mlen, model.n_embed) for m in mems):
             raise ValueError(f"RingMemory.load: expected {model.n_layer} tensors of shape ({self.B}, {mlen}, {model.n_embed})")
         with torch.no_grad():
             for ring, kv in zip(self.kv, self._project(mems, self.B)):
-                ring[:, :mlen].copy_(kv)
+                if self.kv_dtype == "fp8":
+                    ops.kv8_quantize(kv.contiguous(), ring[:, :mlen])
+                else:
+                    ring[:, :mlen].copy_(kv)
             self.state.zero_()
 
     def _project(self, mems, n: int):
@@ -143,7 +157,13 @@ class RingMemory:
         if n == 0:
             return
         with torch.no_grad():
-            ops.ring_load_rows(self.kv, self._ptrs, self._project(mems, n), self.state, mlen, rows, self.load_status)
+            src = self._project(mems, n)
+            if self.kv_dtype == "fp8":   # quantised into a temporary; the slots then travel as bytes like the bf16 ones
+                slots = [torch.empty(n, mlen, self.kv[0].shape[2], device=model.dev, dtype=torch.uint8) for _ in src]
+                for kv, sl in zip(src, slots):
+                    ops.kv8_quantize(kv.contiguous(), sl)
+                src = slots
+            ops.ring_load_rows(self.kv, self._ptrs, src, self.state, mlen, rows, self.load_status)
 
     def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
         """beam search: after the call that appended token t - 1, give row b the keys / values of the last ``t`` tokens of row

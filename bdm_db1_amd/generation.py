@@ -280,6 +280,16 @@ class DecodeKey:
     n: Optional[int] = None
     per_request: bool = False
     caps: Optional[Tuple[int, int]] = None
+    kv_cache = "bf16"        # (no field: the key of the default ring is what it was; ``DecodeKeyFp8`` carries the other value)
+
+
+@dataclass(frozen=True)
+class DecodeKeyFp8(DecodeKey):
+    """the key of a decoding state over an fp8 K/V ring (``kv_cache="fp8"``): ``kv_cache`` as the last field.  Keys of different classes
+    never compare equal, so an fp8 generator and a bf16 one are never taken for each other.  Created by ``_with_kv_cache`` ONLY, which
+    validates the model and the path first: a ``DecodeKeyFp8(kv_cache="bf16")`` built by hand would name the default ring and still never
+    equal the plain key."""
+    kv_cache: str = "fp8"
 
 
 def clip_at_eos(ids, lengths) -> List[List[int]]:
@@ -474,6 +484,20 @@ def _check_chain(model):
 
 def _ring_ok(model) -> bool:
     return (model.compute_dtype == torch.bfloat16 and bool(model.use_decode) and int(model.mem_len or 0) > 0 and model.d_head == 128)
+
+
+def _with_kv_cache(who: str, model, key: DecodeKey, kv_cache: str, graphed: Optional[bool] = None) -> DecodeKey:
+    """``key`` for the K/V ring format ``kv_cache``: "bf16" -- the key itself; "fp8" -- a ``DecodeKeyFp8`` of the same fields, for a call that
+    takes the ring path on a model the fp8 attention supports.  Raises ValueError before anything is launched."""
+    if kv_cache == "bf16":
+        return key
+    if kv_cache != "fp8":
+        raise ValueError(f"{who}: kv_cache must be 'bf16' or 'fp8' (got {kv_cache!r})")
+    if graphed is False or not _ring_ok(model):
+        raise ValueError(f"{who}: kv_cache='fp8' needs the ring path (a bf16 model with use_decode, d_head 128 and mem_len > 0; not graphed=False)")
+    if not ops.relattn_decode_ring_kv8_supported(1, 1, int(model.mem_len) + 1, model.n_head, model.d_head):
+        raise ValueError(f"{who}: kv_cache='fp8' needs an even number of heads and mem_len <= 2047 (n_head {model.n_head}, mem_len {model.mem_len})")
+    return DecodeKeyFp8(**{f.name: getattr(key, f.name) for f in dataclasses.fields(key)})
 
 
 # ----------------------------------------------------------------------------------------------------------------------- the device states
@@ -697,7 +721,7 @@ class _RingGenerator:
 
     def __init__(self, model, state, key):
         self.model, self.key, self.state = model, key, state
-        self.ring = RingMemory(model, state.M)
+        self.ring = RingMemory(model, state.M, kv_dtype=key.kv_cache)
         self.step = GraphedRingStep(model, state.M, 1, memory=self.ring, epilogue=self.epilogue)
 
     def epilogue(self, step, logits):
@@ -776,7 +800,7 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
 @torch.no_grad()
 def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
              stats: Optional[dict] = None, replay: bool = True,
-             constraints: Optional[DecodingConstraints] = None):
+             constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16"):
     """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
     of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
     after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
@@ -793,7 +817,9 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     their fp32 sum in token order.  With ``config.top_logprobs`` n two more: top_ids int32 and top_logprobs float32, both
     [M, max_new_tokens, n] -- the n most likely tokens of step t under that same distribution, the most likely first (ties: the lower id),
     and their log-probabilities; -1 / -inf where the step had fewer candidates and at every position after a row's last written token
-    (where ``logprobs`` holds 0).  Greedy: ``top_ids[r, t, 0] == ids[r, t]``."""
+    (where ``logprobs`` holds 0).  Greedy: ``top_ids[r, t, 0] == ids[r, t]``.  ``kv_cache`` "fp8" (ring path only; ValueError otherwise):
+    the memory's keys / values are held as e4m3 with a power-of-two scale per (row, position, K or V, head) -- half the bytes per token
+    step and per slot, results within the e4m3 rounding of the keys / values; "bf16" (default): everything is what it is without it."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate")
     M = _batch_size(prompt)
@@ -801,6 +827,7 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     if not ops.select_tokens_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
     key = _constrained("generate", model, DecodeKey(rows=M, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
+    key = _with_kv_cache("generate", model, key, kv_cache, graphed)
     return _decode(model, prompt, _State, key, graphed, replay, stats, start=(stream_ids,))
 
 
@@ -866,7 +893,8 @@ def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
 
 @torch.no_grad()
 def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
-                replay: bool = True, constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                replay: bool = True, constraints: Optional[DecodingConstraints] = None,
+                kv_cache: str = "bf16") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Beam search after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of G prompts of one shape ->
     (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R = ``num_return_sequences``: each prompt's
     best hypotheses, best first.  ``ids[g, r, :lengths[g, r]]`` are the tokens before EOS (then EOS, then ``pad_id``); the score is the sum of
@@ -876,7 +904,8 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     forces the eager loop (the list-form memory is reordered with index_select).  ``replay`` False (ring path): the same forward and epilogue
     run eagerly over the same ring instead of as a graph replay.  ``stats`` (a dict): receives the path taken, the number of per-token calls
     and ``parent_switches``, the number of (step, row) pairs (step > 0) whose parent was another row.  ``constraints`` (a
-    ``DecodingConstraints``): applied to every step's logits on the device, over each beam's own tokens so far, before the beam step."""
+    ``DecodingConstraints``): applied to every step's logits on the device, over each beam's own tokens so far, before the beam step.
+    ``kv_cache``: as ``generate`` takes it (db1_ring_reorder copies fp8 slots as the bytes they are)."""
     cfg = config or BeamSearchConfig()
     if not isinstance(cfg, BeamSearchConfig):
         raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
@@ -891,6 +920,7 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
     key = _constrained("beam_search", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
+    key = _with_kv_cache("beam_search", model, key, kv_cache, graphed)
     return _decode(model, prompt, _BeamState, key, graphed, replay, stats)
 
 
@@ -934,7 +964,7 @@ def _check_best_of(cfg, n, num_return_sequences, length_penalty):
 @torch.no_grad()
 def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, length_penalty: float = 1.0, num_return_sequences: int = 1,
                    stream_ids=None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
-                   constraints: Optional[DecodingConstraints] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                   constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Best-of-n sampling after ``prompt`` (G prompts of one shape): n sampled continuations of every prompt, ranked by their normalised
     log-probability -> (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R =
     ``num_return_sequences``, best first: the triple ``beam_search`` returns.  ``config``: a sampling ``GenerationConfig`` (``greedy`` raises);
@@ -942,7 +972,7 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
     logits are expanded n-fold, as ``beam_search`` expands them to its beams, and row g * n + j samples from Philox stream g * n + j
     (``stream_ids`` of shape [G, n]: the streams to use instead).  score = sum_logprob / L^``length_penalty``, L = the tokens before EOS + 1
     for a row that ended with EOS, else its length; a row that met a step without a candidate scores -inf; ties go to the lower j.  The
-    ranking is NumPy on the host over [G, n].  ``graphed``, ``stats`` and ``constraints`` as ``generate`` takes them."""
+    ranking is NumPy on the host over [G, n].  ``graphed``, ``stats``, ``constraints`` and ``kv_cache`` as ``generate`` takes them."""
     cfg = config or GenerationConfig(greedy=False)
     n, R = _check_best_of(cfg, n, num_return_sequences, length_penalty)
     cfg = dataclasses.replace(cfg, logprobs=True)
@@ -957,6 +987,7 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
             raise ValueError(f"sample_best_of: stream_ids of shape [{G}, {n}] expected, got {tuple(stream_ids.shape)}")
         stream_ids = stream_ids.reshape(-1)
     key = _constrained("sample_best_of", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi, n=n), constraints, cfg.max_new_tokens)
+    key = _with_kv_cache("sample_best_of", model, key, kv_cache, graphed)
     out, lengths, _, sums, status = _decode(model, prompt, _BestOfState, key, graphed, True, stats, start=(stream_ids,))
     out, lengths = out.numpy().reshape(G, n, -1), lengths.numpy().reshape(G, n)
     mx = out.shape[2]

@@ -736,12 +736,13 @@ class TransformerXL(nn.Module):
         H, D = self.n_head, self.d_head
         u, vb = self._bias("r_w_bias", i), self._bias("r_r_bias", i)
         if getattr(dec, "ring", None) is not None:   # K / V of the memory in a ring, appended in place by the attention launch (decode.RingMemory)
+            ring_fwd = ops.relattn_decode_ring_kv8_fwd if getattr(dec.ring, "kv_dtype", "bf16") == "fp8" else ops.relattn_decode_ring_fwd
             if getattr(dec, "partials", False):       # one or two new tokens: the output projection merges the chunk partials itself
                 part = self._new(ops.relattn_decode_ring_part_numel(B, L, mlen + L, H), dtype=torch.float32)
-                ops.relattn_decode_ring_fwd(qkv, u, vb, dec.ring.kv[i], dec.ring.state, dec.R[i], None, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D), part=part)
+                ring_fwd(qkv, u, vb, dec.ring.kv[i], dec.ring.state, dec.R[i], None, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D), part=part)
                 return part
             av = self._new(B, L, H, D)
-            ops.relattn_decode_ring_fwd(qkv, u, vb, dec.ring.kv[i], dec.ring.state, dec.R[i], av, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D))
+            ring_fwd(qkv, u, vb, dec.ring.kv[i], dec.ring.state, dec.R[i], av, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D))
             return av
         qu, qv = self._new(B, L, H, D), self._new(B, L, H, D)
         ops.relattn_add_head_bias(qkv, u, vb, qu, qv, B, L, L, H, D)

@@ -1302,6 +1302,90 @@ def relattn_decode_ring_part_numel(B, q, klen, H) -> int:
     return int(lib.load().db1_relattn_decode_ring_workspace_bytes(int(B), int(q), int(klen), int(H))) // 4
 
 
+# ---- the fp8 K/V ring (include/db1_hip.h, "fp8 K/V ring"): rings are uint8 [B, cap, kv8_slot_bytes(H, D)]
+def kv8_slot_bytes(H, D) -> int:
+    """bytes of one fp8 slot (db1_kv8_slot_bytes: 264 H), 0 where the format is not defined (d_head != 128, an odd number of heads)"""
+    return int(lib.load().db1_kv8_slot_bytes(int(H), int(D)))
+
+
+def relattn_decode_ring_kv8_supported(B, q, klen, H, D) -> bool:
+    return bool(lib.load().db1_relattn_decode_ring_kv8_supported(int(B), int(q), int(klen), int(H), int(D)))
+
+
+def relattn_decode_ring_kv8_fwd(qkv_new, u, vb, kv_ring, state, R, out, B, q, mlen, H, D, shift, scale, fused_merge=False, part=None):
+    """relattn_decode_ring_fwd over an fp8 ring (db1_relattn_decode_ring_kv8_fwd): kv_ring uint8 [B, cap, kv8_slot_bytes(H, D)]; every other
+    operand, ``part`` and ``fused_merge`` as there.  The call's own keys / values are appended quantised."""
+    if kv_ring.dtype != torch.uint8 or kv_ring.dim() != 3 or not kv_ring.is_contiguous() or kv_ring.shape[0] != B or \
+            kv_ring.shape[2] != kv8_slot_bytes(H, D):
+        raise ValueError(f"relattn_decode_ring_kv8_fwd: the ring must be a contiguous uint8 [{B}, cap, {kv8_slot_bytes(H, D)}] tensor")
+    cap = kv_ring.shape[1]
+    if part is not None:
+        ws, wsn = P(part), part.numel() * 4
+    else:
+        ws, wsn = _ws("db1_relattn_decode_ring_kv8_workspace_bytes", (B, q, mlen + q, H), qkv_new.device)
+    lib.call("db1_relattn_decode_ring_kv8_fwd", P(qkv_new), P(u), P(vb), P(kv_ring), P(state), cap, P(R), R.shape[0], P(out), B, q, mlen, H, D, shift,
+             float(scale), ws, wsn, P(decode_tickets(qkv_new.device)) if (fused_merge and out is not None) else _vp(0), stream())
+
+
+def kv8_quantize(src, dst):
+    """projected keys / values ``src`` (bf16 [n, mlen, 2, H, D], contiguous) -> fp8 slots ``dst`` (uint8 [n, mlen, slot]; the row stride is
+    free, e.g. ``ring[:, :mlen]``) -- db1_kv8_quantize, one launch"""
+    if src.dim() != 5 or src.shape[2] != 2 or src.dtype != torch.bfloat16 or not src.is_contiguous():
+        raise ValueError("kv8_quantize: src must be a contiguous bf16 [n, mlen, 2, H, D] tensor")
+    n, mlen, _, H, D = src.shape
+    slot = kv8_slot_bytes(H, D)
+    if not slot:
+        raise ValueError(f"kv8_quantize: no fp8 slot for H={H}, D={D} (d_head 128 and an even number of heads expected)")
+    if dst.dtype != torch.uint8 or tuple(dst.shape) != (n, mlen, slot) or dst.device != src.device or dst.stride(2) != 1 or dst.stride(1) != slot:
+        raise ValueError(f"kv8_quantize: dst must be a uint8 [{n}, {mlen}, {slot}] tensor (or such a view of a ring) on {src.device}")
+    if n == 0:
+        return
+    lib.call("db1_kv8_quantize", P(src), P(dst), n, mlen, H, D, dst.stride(0) if n > 1 else max(dst.stride(0), mlen * slot), stream())
+
+
+def _kv8_scale_exp(amax):
+    """the exponent of the canonical scale: the smallest power of two s with amax <= 448 s; 0 for amax == 0; at least -126"""
+    m, e = torch.frexp(amax)                         # amax = m 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    se = torch.where(m > 0.875, e - 8, e - 9).clamp(min=-126)
+    return torch.where(amax == 0, torch.zeros_like(se), se)
+
+
+def kv8_pack(kv, scales=None):
+    """host side (tests, debugging): keys / values ``kv`` [..., 2, H, 128] (CPU, any float dtype holding bf16 values) -> slots uint8
+    [..., 264 H] by the rule of include/db1_hip.h.  ``scales`` [..., 2, H] (powers of two with |x| <= 448 s): use these instead of the
+    canonical ones."""
+    x = kv.detach().to("cpu", torch.float64)
+    if x.dim() < 3 or x.shape[-3] != 2 or x.shape[-1] != 128 or x.shape[-2] % 2:
+        raise ValueError("kv8_pack: kv must be [..., 2, H, 128] with an even H")
+    H, lead = x.shape[-2], tuple(x.shape[:-3])
+    fin = torch.isfinite(x)
+    if scales is None:
+        s = torch.ldexp(torch.ones(lead + (2, H), dtype=torch.float64), _kv8_scale_exp(torch.where(fin, x.abs(), torch.zeros_like(x)).amax(-1)))
+    else:
+        s = scales.detach().to("cpu", torch.float64).expand(lead + (2, H))
+        m, e = torch.frexp(s)
+        if not bool(((m == 0.5) & (e >= -125) & (e <= 128)).all()):
+            raise ValueError("kv8_pack: every scale must be a power of two that is a normal fp32 (2^-126 .. 2^127)")
+    y = torch.where(fin, x / s[..., None], torch.zeros_like(x))
+    if float(y.abs().max()) > 448.0:
+        raise ValueError("kv8_pack: a scale is too small for its block (|x / s| > 448)")
+    pay = y.to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
+    pay = torch.where(fin, pay, torch.full_like(pay, 0x7F))
+    return torch.cat([pay.reshape(lead + (2 * H * 128,)), s.to(torch.float32).reshape(lead + (2 * H,)).contiguous().view(torch.uint8).reshape(lead + (8 * H,))], -1)
+
+
+def kv8_unpack(slots, H):
+    """host side: slots uint8 [..., 264 H] -> (the dequantised keys / values, bf16 [..., 2, H, 128]; the scales, float32 [..., 2, H])"""
+    sl = slots.detach().to("cpu").contiguous()
+    H = int(H)
+    if sl.dtype != torch.uint8 or sl.shape[-1] != 264 * H:
+        raise ValueError(f"kv8_unpack: slots must be uint8 [..., {264 * H}]")
+    lead = tuple(sl.shape[:-1])
+    pay = sl[..., :256 * H].contiguous().view(torch.float8_e4m3fn).to(torch.float32).reshape(lead + (2, H, 128))
+    s = sl[..., 256 * H:].contiguous().view(torch.float32).reshape(lead + (2, H))
+    return (pay * s[..., None]).to(torch.bfloat16), s
+
+
 def linear_decode_attn_supported(B, q, H, D, klen, N) -> bool:
     return bool(lib.load().db1_linear_decode_attn_supported(int(B), int(q), int(H), int(D), (int(klen) + 127) // 128, int(N)))
 

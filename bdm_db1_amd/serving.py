@@ -33,7 +33,7 @@ import torch
 
 from . import ops
 from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodeKey, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained,
-                         _need_memory, _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _work,
+                         _need_memory, _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _with_kv_cache, _work,
                          caption_prompt, question_prompts)
 
 
@@ -324,7 +324,7 @@ class _SlotState(_SamplingState):
 def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig] = None, slots: int = 8, stream_ids=None,
                     stats: Optional[dict] = None, replay: bool = True,
                     constraints: Optional[DecodingConstraints] = None, per_request: bool = False, per_request_constraints: bool = False,
-                    max_bad_token_ids: int = 64, max_logit_bias: int = 64) -> Iterator[tuple]:
+                    max_bad_token_ids: int = 64, max_logit_bias: int = 64, kv_cache: str = "bf16") -> Iterator[tuple]:
     """Generate for a stream of requests over ``slots`` recycled rows; yields ``(index, ids int32 [limit], length)`` on the host as requests
     finish (requests that are found finished at the same look come in index order).  ``ids[:length]`` are the tokens before EOS, then EOS,
     then ``pad_id``.
@@ -358,7 +358,8 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     slot's record and lists from device tables the admission writes; ``max_bad_token_ids`` / ``max_logit_bias`` (0 .. 1024 each) are the
     tables' widths, the most banned ids / biases ANY request (or the stream's object) may hold.  The flag is needed up front for the
     reason ``per_request`` is and joins the cache key with the two capacities; ``stats["stopped"]`` is then always present.  False: nothing
-    changes, and a request that carries constraints raises ValueError."""
+    changes, and a request that carries constraints raises ValueError.  ``kv_cache`` "fp8": the slots' ring holds e4m3 keys / values, as
+    ``generate`` describes it (admissions quantise the prefill's keys / values on their way in); it joins the cache key."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -371,6 +372,7 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
         raise ValueError(f"db1_select_tokens_slots does not support a vocabulary of {V}")
     per_request = bool(per_request)
     key = _constrained("generate_stream", model, DecodeKey(rows=slots, cfg=cfg, V=V, hi=hi, per_request=per_request), constraints, cfg.max_new_tokens)
+    key = _with_kv_cache("generate_stream", model, key, kv_cache)
     min_new = 0 if constraints is None else constraints.min_new_tokens
     caps = None
     if per_request_constraints:     # (with the flag off the key is what it was, and neither capacity is looked at)

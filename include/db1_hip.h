@@ -313,6 +313,33 @@ int db1_ring_advance(int* state, int q, int cap, void* stream);
  * With it (and q <= 16) the key chunk that finishes last for a (batch, head) merges the partial results inside the attention launch.
  * out == NULL (q <= 16): no merge at all, the per-chunk partial results stay in ws for db1_linear_decode_attn. */
 
+/* ------------------------------------------------------------------ fp8 K/V ring (tests/kv8_rule.py restates the format in NumPy).
+ * The same ring with half the bytes per key: kv_ring is [B, cap, slot] BYTES, one slot = one key position of one batch row:
+ *     H * 128 bytes of K payload, H * 128 bytes of V payload, H fp32 K scales, H fp32 V scales     (264 H bytes; D == 128, H even)
+ * Payload: OCP e4m3fn (1-4-3, bias 7, largest finite 448, no infinity, NaN = 0x7f / 0xff) -- the gfx950 conversion format.
+ * Scale, per (row, position, K or V, head) over its 128 bf16 elements: amax = the largest magnitude among the FINITE elements; s = the
+ *     smallest power of two with amax <= 448 s; amax == 0 gives s = 1; the exponent of s is at least -126 (s stays a normal fp32).
+ * Payload = rne_e4m3(x / s): the division is exact and |x / s| <= 448, so the e4m3 rounding is the only rounding and nothing saturates.
+ * Dequantised value = payload * s, exact in bf16 (where it is not subnormal).
+ * Non-finite elements: an infinity or NaN takes no part in amax and is stored as the byte 0x7f (NaN, dequantised NaN) whatever its sign; the
+ *     scale and every other byte of its block are what they would be without it, so it reaches only its own (row, position, K or V, head).
+ * db1_relattn_decode_ring_kv8_fwd: operands and the three forms (out; out == NULL with the partials in ws; tickets) of
+ * db1_relattn_decode_ring_fwd.  Memory keys come from the ring; the call's own keys are read from qkv_new (bf16) and appended to the ring
+ * quantised by the rule above; every other byte of the ring stays.  The result is bit for bit that of db1_relattn_decode_ring_fwd over the
+ * dequantised ring (same chunks, steps, merge order and rounding points; the scales are applied where a power of two is exact: K's to the
+ * fp32 score before the relative term, V's to the probability before its bf16 rounding) as long as no dequantised value is subnormal.
+ * DB1_ERR_UNSUPPORTED: D != 128, odd H, q outside 1 .. 64, klen > 2048; DB1_ERR_BAD_SHAPE: cap < klen or a NULL operand; DB1_ERR_BAD_ALIGN. */
+int64_t db1_kv8_slot_bytes(int H, int D);                                   /* 264 H, or 0 where the format is not defined */
+int db1_relattn_decode_ring_kv8_supported(int B, int q, int klen, int H, int D);
+int64_t db1_relattn_decode_ring_kv8_workspace_bytes(int B, int q, int klen, int H);
+int db1_relattn_decode_ring_kv8_fwd(const void* qkv_new, const void* u, const void* vb, void* kv_ring, const int* ring_state, int cap, const void* R,
+                                    int nd, void* out, int B, int q, int mlen, int H, int D, int shift, float scale, void* ws, int64_t ws_bytes,
+                                    void* tickets, void* stream);
+/* src bf16 [n, mlen, 2, H, D] (projected keys / values) -> slots: position j of row i at dst + i * dst_row_stride + j * slot (bytes; the
+ * stride a multiple of 16 and at least mlen slots, e.g. cap * slot to write into ring[:, :mlen]).  One pass, no workspace. */
+int db1_kv8_quantize_supported(int H, int D);
+int db1_kv8_quantize(const void* src, void* dst, int n, int mlen, int H, int D, int64_t dst_row_stride, void* stream);
+
 /* ------------------------------------------------------------------ the inference layer's linear maps (M <= 64 new tokens), fused
  * y[M, N] = x[M, K] . W^T + bias (bf16, W K-major like nn.Linear.weight, leading dimension K) as a stream over W, finishing the layer's
  * small follow-up work inside the same launch:

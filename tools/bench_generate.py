@@ -81,7 +81,19 @@ the LP and the plain instantiation of select_tokens_kernel.
 With --best-of N the arguments are group counts G (default 16): sample_best_of (N samples per image, top-p 0.9, M = G * N rows) next to
 beam search with N beams over the same images, ms per token as above.
 
-    python tools/bench_generate.py --best-of 4 [G ...]"""
+    python tools/bench_generate.py --best-of 4 [G ...]
+
+--kv-cache fp8 (with the default mode): the same measurements over an fp8 K/V ring (``kv_cache="fp8"``, ``RingMemory(kv_dtype="fp8")``);
+every line carries "kv_cache" and the ring's bytes at that M.
+
+    python tools/bench_generate.py --kv-cache fp8 [M ...]
+
+--kv8-kernels [B ...] (default 1 16 64): the two attention entry points alone, db1_relattn_decode_ring_fwd and
+db1_relattn_decode_ring_kv8_fwd, in alternation in ONE process: q = 1, mlen = 1024, 16 heads, the merge as a second launch (what the
+model's plain path launches) and, for B <= 2, the partials form; device time per call from events over 20 calls, the median of 7 rounds
+each, with the ring bytes a call reads and the rate they amount to.
+
+    python tools/bench_generate.py --kv8-kernels [B ...]"""
 import dataclasses
 import json
 import os
@@ -131,8 +143,45 @@ def gen_ms_per_token(M, cfg, short=10, **kw):
     return (full - part) / (N_NEW - short) * 1e3
 
 
+KV_CACHE = "bf16"      # --kv-cache
+
+
+def kv8_kernels_us(B, mlen=1024, rounds=7, calls=20):
+    """the bf16 and the fp8 ring attention alone at q = 1 (the docstring above says how)"""
+    H, D, cap = model.n_head, model.d_head, mlen + 64
+    g = torch.Generator(device=dev).manual_seed(B)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g).to(torch.bfloat16)
+    qkv, u, vb, R = rnd(B, 1, 3, H, D), rnd(H, D), rnd(H, D), rnd(cap, H * D)
+    ring16 = rnd(B, cap, 2, H, D)
+    ring8 = torch.empty(B, cap, ops.kv8_slot_bytes(H, D), dtype=torch.uint8, device=dev)
+    ops.kv8_quantize(ring16, ring8)
+    state = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(B, 1, H, D, device=dev, dtype=torch.bfloat16)
+    part = torch.empty(ops.relattn_decode_ring_part_numel(B, 1, mlen + 1, H), device=dev, dtype=torch.float32)
+    scale = 1.0 / D ** 0.5
+    fns = {"bf16": lambda o, **kw: ops.relattn_decode_ring_fwd(qkv, u, vb, ring16, state, R, o, B, 1, mlen, H, D, mlen + 1, scale, **kw),
+           "fp8": lambda o, **kw: ops.relattn_decode_ring_kv8_fwd(qkv, u, vb, ring8, state, R, o, B, 1, mlen, H, D, mlen + 1, scale, **kw)}
+    rec = {"B": B, "q": 1, "mlen": mlen, "H": H}
+    forms = [("out", lambda f: f(out))] + ([("partials", lambda f: f(None, part=part))] if B <= 2 else [])
+    for form, call in forms:
+        times = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, f in fns.items():
+                times[k].append(device_us(lambda: call(f), calls))
+        for k, ring in (("bf16", ring16), ("fp8", ring8)):
+            us = float(np.median(times[k]))
+            nbytes = B * mlen * ring[0, 0].numel() * ring.element_size()
+            rec[f"{k}_{form}_us"] = round(us, 2)
+            rec[f"{k}_{form}_min_max_us"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+            rec[f"{k}_ring_MB"] = round(nbytes / 1e6, 2)
+            rec[f"{k}_{form}_TBps"] = round(nbytes / (us * 1e-6) / 1e12, 3)
+        rec[f"fp8_over_bf16_{form}"] = round(rec[f"fp8_{form}_us"] / rec[f"bf16_{form}_us"], 4)
+    return rec
+
+
 def bare_replay_ms(M, calls=N_NEW):
-    step = GraphedRingStep(model, batch_size=M, n_new=1)
+    from bdm_db1_amd.decode import RingMemory
+    step = GraphedRingStep(model, batch_size=M, n_new=1, memory=None if KV_CACHE == "bf16" else RingMemory(model, M, kv_dtype=KV_CACHE))
     for _ in range(5):
         step(step.ids)
     torch.cuda.synchronize()
@@ -647,11 +696,21 @@ if "--constraints" in args:
             rec.update({k: v for k, v in constrain_kernels_us(M, N_NEW, (15,)).items() if k != "M"})
         print(json.dumps(rec), flush=True)
     sys.exit(0)
+if "--kv8-kernels" in args:
+    for B in [int(a) for a in args if a != "--kv8-kernels"] or [1, 16, 64]:
+        print(json.dumps(kv8_kernels_us(B)), flush=True)
+    sys.exit(0)
+if "--kv-cache" in args:
+    i = args.index("--kv-cache")
+    KV_CACHE = args[i + 1]
+    args = args[:i] + args[i + 2:]
+kv_kw = {} if KV_CACHE == "bf16" else dict(kv_cache=KV_CACHE)      # (the default run makes the call it always made)
 Ms = [int(a) for a in args] or [1, 16, 64]
 for M in Ms:
-    rec = {"M": M, "new_tokens": N_NEW}
-    rec["greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW)), 4)
-    rec["top_p_0.9_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW, greedy=False, top_p=0.9, seed=1)), 4)
+    rec = {"M": M, "new_tokens": N_NEW, "kv_cache": KV_CACHE}
+    rec["greedy_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW), **kv_kw), 4)
+    rec["top_p_0.9_ms_per_token"] = round(gen_ms_per_token(M, GenerationConfig(max_new_tokens=N_NEW, greedy=False, top_p=0.9, seed=1), **kv_kw), 4)
+    rec["ring_bytes"] = sum(k.numel() * k.element_size() for k in model._generator.ring.kv)
     model._generator = None
     torch.cuda.empty_cache()
     bare, ring = bare_replay_ms(M)
