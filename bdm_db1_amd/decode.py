@@ -9,10 +9,30 @@ memory back in -- like evaluate_rl's loop -- see no difference.
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 from types import SimpleNamespace
 from typing import List
 
 import torch
+
+
+@contextlib.contextmanager
+def graph_capture(g, **kw):
+    """``torch.cuda.graph(g, **kw)`` with Python's cyclic garbage collector held off until the capture has ended.  A collection that fires
+    inside a capture destroys whatever dead cycles it finds -- a dropped GraphedRingStep with its CUDAGraph and private pool among them --
+    and the HIP calls of those destructors (graph destruction, hipFree of the pool) are illegal while a stream captures: the error is
+    raised inside a destructor and the process aborts.  torch collected before every capture once; since that became an option
+    (``torch.compiler.config.force_cudagraph_gc``, off by default) nothing keeps a collection out of a capture as long as a model forward.
+    The garbage is collected as usual after the capture."""
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, **kw):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def _token_input(ids):
@@ -50,7 +70,7 @@ class GraphedMemoryStep:
     def _capture(self):
         model = self.model
         g = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(g):
+        with torch.no_grad(), graph_capture(g):
             logits, _, m = model([self.x], compute_loss=False, mems=self.mems)
             new_kv = model._dec_state.kv
             for dst, src in zip(self.mems, m):
@@ -204,7 +224,7 @@ class GraphedRingStep:
                 torch.cuda.synchronize()
                 model._chain_watch = None
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with graph_capture(g):
                     logits, _, _ = model([self.x], compute_loss=False, mems=self.memory)
                     if epilogue is not None:
                         epilogue(self, logits)

@@ -25,6 +25,8 @@ from typing import List, Sequence
 
 import torch
 
+from .decode import graph_capture
+
 
 def _tensor_fields(task):
     if dataclasses.is_dataclass(task):
@@ -108,7 +110,7 @@ class GraphedTrainStep:
                 model._wg_slot = slot
                 model._win.n = slot
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
+                with graph_capture(g):
                     self.step_dev.add_(1)
                     _, loss = model(self.static)
                 self.graphs[(slot == 0, slot)], self.loss[(slot == 0, slot)] = g, loss
@@ -121,7 +123,7 @@ class GraphedTrainStep:
                 model._grad_fresh = fresh
                 model._wg_slot = slot
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.pool):
+                with graph_capture(g, pool=self.pool):
                     self.step_dev.add_(1)
                     _, loss = model(self.static)
                     model.backward(grad_scale=model.loss_grad_scale, layer_done_hook=None, flush_wgrads=False)

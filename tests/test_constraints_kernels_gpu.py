@@ -145,6 +145,7 @@ def test_slot_form_row_map_per_slot_counters_and_vacant_slots(dtype):
 
 
 def test_graph_captured_launch_replays_over_changing_t_and_history():
+    from bdm_db1_amd.decode import graph_capture
     from bdm_db1_amd import ops
     dtype, M, V, ld, mx = C.BF16, 64, 33025, 33280, 30
     rng = np.random.default_rng(5)
@@ -167,7 +168,7 @@ def test_graph_captured_launch_replays_over_changing_t_and_history():
         ops.constrain_logits(lg, t_dev, h_dev, **kw)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):      # (the cyclic collector held off: bdm_db1_amd.decode.graph_capture)
         ops.constrain_logits(lg, t_dev, h_dev, **kw)
     for i in range(3):
         lg.copy_(src)

@@ -508,3 +508,30 @@ def test_batched_ring_decode_equals_independent_environments(M):
             lg_g, _ = g(ids)
             lg_e, _, mem_e = model([mk(calls[1])], compute_loss=False, mems=mem_e)
             assert torch.equal(lg_g, lg_e)
+
+
+def test_graph_capture_keeps_the_garbage_collector_out_of_the_capture():
+    """bdm_db1_amd.decode.graph_capture (what every capture of the library goes through): the cyclic collector is off between the begin and
+    the end of the capture -- a collection there would run the destructors of dropped graphs, whose HIP calls a capturing stream forbids --
+    and is what it was afterwards; a collector the caller had switched off stays off"""
+    import gc
+    from bdm_db1_amd.decode import graph_capture
+    a, b = torch.ones(8, device=DEV), torch.zeros(8, device=DEV)
+    torch.cuda.synchronize()
+    assert gc.isenabled()
+    g = torch.cuda.CUDAGraph()
+    with graph_capture(g):
+        assert not gc.isenabled()
+        b.add_(a)
+    assert gc.isenabled()
+    g.replay()
+    g.replay()
+    assert torch.equal(b, torch.full((8,), 2.0, device=DEV))
+    gc.disable()
+    try:
+        with graph_capture(torch.cuda.CUDAGraph()):
+            b.add_(a)
+        assert not gc.isenabled()
+    finally:
+        gc.enable()
+    assert gc.isenabled()

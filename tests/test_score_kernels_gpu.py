@@ -197,6 +197,7 @@ def test_score_segments_against_float64_sums():
 
 
 def test_score_rows_and_sweep_replay_from_a_graph():
+    from bdm_db1_amd.decode import graph_capture
     from bdm_db1_amd import ops
     V, rows, d, T = 1000, 1024, 256, 160
     rng = np.random.default_rng(13)
@@ -215,7 +216,7 @@ def test_score_rows_and_sweep_replay_from_a_graph():
         ops.lmhead_score(h, W, labels, *g_sweep, V=V, vocab_hi=900, chunk_rows=64)      # (warm-up on the side stream: its workspace)
     torch.cuda.current_stream().wait_stream(s)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):      # (the cyclic collector held off: bdm_db1_amd.decode.graph_capture)
         ops.score_rows(logits, labels, *g_rows, V=V, vocab_hi=900)
         ops.lmhead_score(h, W, labels, *g_sweep, V=V, vocab_hi=900, chunk_rows=64)
     for o in g_rows + g_sweep:

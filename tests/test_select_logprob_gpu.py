@@ -215,6 +215,7 @@ def test_slot_form_scores_every_live_slot_at_its_own_counter(dtype, mode):
 
 
 def test_graph_captured_lp_call_equals_the_eager_calls():
+    from bdm_db1_amd.decode import graph_capture
     M, V = 5, 33025
     lg, _, lo, hi, eos = _case(M, V, torch.bfloat16)
     kw = dict(V=V, vocab_lo=lo, vocab_hi=hi, eos_id=eos, greedy=False, top_p=0.9, top_k=200, seed=8)
@@ -234,7 +235,7 @@ def test_graph_captured_lp_call_equals_the_eager_calls():
     gs.logprob.fill_(float("nan"))
     gs.sum_logprob.fill_(SUM0)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):      # (the cyclic collector held off: bdm_db1_amd.decode.graph_capture)
         gs.call(lg, **kw)
         gs.t.add_(1)
     for x in (gs.lengths, gs.finished, gs.status, gs.t):      # (whatever the capture itself may have run)

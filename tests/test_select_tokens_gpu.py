@@ -177,6 +177,7 @@ def test_eos_finished_pad_lengths_and_next_ids():
 
 
 def test_graph_captured_call_equals_the_eager_call():
+    from bdm_db1_amd.decode import graph_capture
     rng = np.random.default_rng(5)
     lg, _ = _logits(rng, 64, 33025, 33088, torch.bfloat16)
     eager = State(64, max_new=4)
@@ -193,7 +194,7 @@ def test_graph_captured_call_equals_the_eager_call():
     torch.cuda.current_stream().wait_stream(side)
     gs.lengths.zero_()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):      # (the cyclic collector held off: bdm_db1_amd.decode.graph_capture)
         ops.select_tokens(lg, gs.t, gs.finished, gs.lengths, gs.out, gs.ids[:, 0], gs.status, V=33025, greedy=False, top_p=0.9, top_k=200, seed=8)
         gs.t.add_(1)
     for i in range(4):

@@ -135,6 +135,7 @@ def test_row_map_with_entries_out_of_range(bufs):
 
 
 def test_graph_captured_launch_replays_over_state_the_host_changes():
+    from bdm_db1_amd.decode import graph_capture
     from bdm_db1_amd import ops
     rng = np.random.default_rng(4)
     n_slots, mx = 16, 24
@@ -151,7 +152,7 @@ def test_graph_captured_launch_replays_over_state_the_host_changes():
         ops.stop_match(*args, **kw)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
+    with graph_capture(graph):      # (the cyclic collector held off: bdm_db1_amd.decode.graph_capture)
         ops.stop_match(*args, **kw)
     host = {k: v.copy() for k, v in base.items()}
     hits = 0
