@@ -41,6 +41,8 @@ struct MemArgs {
     int64_t kv_rs, kv_bs;
     int B, q, klen, mlen, H, shift, nd;
     float scale;
+    const bf16_t* km; const bf16_t* vm;     // KV mode: the memory's keys / values (rows j < mlen); k, v then hold the call's own q rows
+    int64_t m_rs, m_bs;                     // ... their row / batch strides (0: one row / one memory for all)
 };
 
 __device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
@@ -49,6 +51,9 @@ __device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
     return *reinterpret_cast<unsigned*>(&r);
 }
 
+// KV = false: k, v hold all klen rows.  KV = true (db1_relattn_mem_kv_fwd): logical key j < mlen is row j of km / vm, key j >= mlen row
+// j - mlen of k / v -- only the staged rows' addresses differ, so the result is bit for bit that of KV = false over the concatenation.
+template <bool KV>
 __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // MEM_LDS bytes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -71,6 +76,8 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     const bf16_t* kg = p.k + (int64_t)b * p.kv_bs + h * MEM_D;
     const bf16_t* vg = p.v + (int64_t)b * p.kv_bs + h * MEM_D;
     const bf16_t* Rg = p.R + h * MEM_D;
+    const bf16_t* kmg = KV ? p.km + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
+    const bf16_t* vmg = KV ? p.vm + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
     // the block's steps: keys max(0, ib0 - shift + 1) .. ilast + mlen (= the last row's diagonal key < klen), aligned at multiples of 32
     const int ilast = ib0 + MEM_QB - 1 < p.q ? ib0 + MEM_QB - 1 : p.q - 1;
     const int jlo = ib0 - p.shift + 1 > 0 ? ib0 - p.shift + 1 : 0;
@@ -84,10 +91,30 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     {                                                                                                         \
         const int ja_ = (st_) * 32 + srow < p.klen ? (st_) * 32 + srow : p.klen - 1;                          \
         const int jb_ = (st_) * 32 + srow + 16 < p.klen ? (st_) * 32 + srow + 16 : p.klen - 1;                \
-        kst0 = *reinterpret_cast<const uint4*>(kg + (int64_t)ja_ * p.kv_rs + sch * 8);                        \
-        vst0 = *reinterpret_cast<const uint4*>(vg + (int64_t)ja_ * p.kv_rs + sch * 8);                        \
-        kst1 = *reinterpret_cast<const uint4*>(kg + (int64_t)jb_ * p.kv_rs + sch * 8);                        \
-        vst1 = *reinterpret_cast<const uint4*>(vg + (int64_t)jb_ * p.kv_rs + sch * 8);                        \
+        if (KV && !((st_) * 32 < p.mlen && (st_) * 32 + 32 > p.mlen)) {   /* a whole step of one source (workgroup-uniform) */ \
+            const bool mm_ = (st_) * 32 < p.mlen;                                                             \
+            const bf16_t* kb_ = mm_ ? kmg : kg;                                                               \
+            const bf16_t* vb_ = mm_ ? vmg : vg;                                                               \
+            const int64_t rs_ = mm_ ? p.m_rs : p.kv_rs;                                                       \
+            const int sub_ = mm_ ? 0 : p.mlen;                                                                \
+            kst0 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);              \
+            vst0 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);              \
+            kst1 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);              \
+            vst1 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);              \
+        } else if (KV) {   /* the step that straddles the seam: the source is picked per staged row */         \
+            const bool ma_ = ja_ < p.mlen, mb_ = jb_ < p.mlen;                                                \
+            const int64_t oa_ = ma_ ? (int64_t)ja_ * p.m_rs : (int64_t)(ja_ - p.mlen) * p.kv_rs;              \
+            const int64_t ob_ = mb_ ? (int64_t)jb_ * p.m_rs : (int64_t)(jb_ - p.mlen) * p.kv_rs;              \
+            kst0 = *reinterpret_cast<const uint4*>((ma_ ? kmg : kg) + oa_ + sch * 8);                         \
+            vst0 = *reinterpret_cast<const uint4*>((ma_ ? vmg : vg) + oa_ + sch * 8);                         \
+            kst1 = *reinterpret_cast<const uint4*>((mb_ ? kmg : kg) + ob_ + sch * 8);                         \
+            vst1 = *reinterpret_cast<const uint4*>((mb_ ? vmg : vg) + ob_ + sch * 8);                         \
+        } else {                                                                                              \
+            kst0 = *reinterpret_cast<const uint4*>(kg + (int64_t)ja_ * p.kv_rs + sch * 8);                    \
+            vst0 = *reinterpret_cast<const uint4*>(vg + (int64_t)ja_ * p.kv_rs + sch * 8);                    \
+            kst1 = *reinterpret_cast<const uint4*>(kg + (int64_t)jb_ * p.kv_rs + sch * 8);                    \
+            vst1 = *reinterpret_cast<const uint4*>(vg + (int64_t)jb_ * p.kv_rs + sch * 8);                    \
+        }                                                                                                     \
     }
 #define MEM_STAGE_STORE(buf_)                                                                                 \
     {                                                                                                         \
@@ -258,9 +285,47 @@ extern "C" int db1_relattn_mem_fwd(const void* qu, const void* qv, const void* k
     a.qu = (const bf16_t*)qu; a.qv = (const bf16_t*)qv; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.R = (const bf16_t*)R;
     a.out = (bf16_t*)out; a.lse = lse; a.kv_rs = kv_row_stride; a.kv_bs = kv_batch_stride;
     a.B = B; a.q = q; a.klen = klen; a.mlen = mlen; a.H = H; a.shift = shift; a.nd = nd; a.scale = scale;
+    a.km = a.vm = nullptr; a.m_rs = a.m_bs = 0;
     static Db1PerDeviceOnce attr_once;
-    attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
-    relattn_mem_kernel<<<dim3((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B), 256, MEM_LDS, (hipStream_t)stream>>>(a);
+    attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
+    relattn_mem_kernel<false><<<dim3((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B), 256, MEM_LDS, (hipStream_t)stream>>>(a);
     DB1_CHECK_LAUNCH("relattn_mem");
+    return DB1_OK;
+}
+
+// ---- the same attention with the keys / values in two places (include/db1_hip.h): a memory of mlen rows and the call's own q rows
+extern "C" int db1_relattn_mem_kv_supported(int B, int q, int mlen, int H, int D, int shift, int dt) {
+    return (mlen >= 1 && mlen <= MEM_MAX_KLEN && q <= MEM_MAX_KLEN && db1_relattn_mem_supported(B, q, mlen + q, mlen, H, D, shift, dt)) ? 1 : 0;
+}
+
+extern "C" int64_t db1_relattn_mem_kv_workspace_bytes(int B, int q, int mlen, int H) {
+    (void)B; (void)q; (void)mlen; (void)H;
+    return 0;
+}
+
+extern "C" int db1_relattn_mem_kv_fwd(const void* qu, const void* qv, const void* k_new, const void* v_new, int64_t new_row_stride,
+                                      int64_t new_batch_stride, const void* k_mem, const void* v_mem, int64_t mem_row_stride,
+                                      int64_t mem_batch_stride, const void* R, int nd, void* out, float* lse, int B, int q, int mlen, int H, int D,
+                                      int shift, float scale, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (!db1_relattn_mem_kv_supported(B, q, mlen, H, D, shift, DB1_BF16))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_mem_kv: needs bf16, d_head = 128, 1 <= q <= 8192, mlen >= 1, mlen + q <= 16384, shift >= 0 "
+                                      "(got q=%d mlen=%d D=%d shift=%d)", q, mlen, D, shift);
+    if (nd < 1 || !R || !qu || !qv || !k_new || !v_new || !k_mem || !v_mem || !out) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_kv: R rows (%d) or a null operand", nd);
+    if (new_row_stride < (int64_t)H * MEM_D || new_batch_stride < 0 || mem_batch_stride < 0 || (mem_row_stride != 0 && mem_row_stride < (int64_t)H * MEM_D))
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_kv: a key / value row stride below H * D (the memory's may be 0)");
+    if ((new_row_stride % 8) || (new_batch_stride % 8) || (mem_row_stride % 8) || (mem_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) ||
+        !db1_aligned16(k_new) || !db1_aligned16(v_new) || !db1_aligned16(k_mem) || !db1_aligned16(v_mem) || !db1_aligned16(R) || !db1_aligned16(out) ||
+        (((uintptr_t)lse) & 3))
+        DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_mem_kv: operands must be 16-byte aligned, strides multiples of 8 elements");
+    MemArgs a;
+    a.qu = (const bf16_t*)qu; a.qv = (const bf16_t*)qv; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.R = (const bf16_t*)R;
+    a.out = (bf16_t*)out; a.lse = lse; a.kv_rs = new_row_stride; a.kv_bs = new_batch_stride;
+    a.km = (const bf16_t*)k_mem; a.vm = (const bf16_t*)v_mem; a.m_rs = mem_row_stride; a.m_bs = mem_batch_stride;
+    a.B = B; a.q = q; a.klen = mlen + q; a.mlen = mlen; a.H = H; a.shift = shift; a.nd = nd; a.scale = scale;
+    static Db1PerDeviceOnce attr_once;
+    attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
+    relattn_mem_kernel<true><<<dim3((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B), 256, MEM_LDS, (hipStream_t)stream>>>(a);
+    DB1_CHECK_LAUNCH("relattn_mem_kv");
     return DB1_OK;
 }

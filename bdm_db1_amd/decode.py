@@ -151,10 +151,11 @@ class RingMemory:
                     ring[:, :mlen].copy_(kv)
             self.state.zero_()
 
-    def _project(self, mems, n: int):
-        """the projected keys / values of a list-form memory of n rows: per layer a [n, mem_len, 2, H, D] view.  The model keeps the decode
-        state it had, whatever the projection does (``load_rows`` runs in the middle of a stream)."""
-        model, mlen = self.model, int(self.model.mem_len)
+    def _project(self, mems, n: int, mlen: int = None):
+        """the projected keys / values of a list-form memory of n rows: per layer a [n, mem_len, 2, H, D] view (``mlen``: of that many
+        positions instead of mem_len).  The model keeps the decode state it had, whatever the projection does (``load_rows`` runs in the
+        middle of a stream)."""
+        model, mlen = self.model, int(self.model.mem_len if mlen is None else mlen)
         saved, model._dec_state = model._dec_state, None
         try:
             dec = model._decode_begin(list(mems), n, 1, mlen)
@@ -194,6 +195,54 @@ class RingMemory:
         from . import ops
         mlen = int(self.model.mem_len)
         ops.ring_reorder(self.kv, self._ptrs, self.state, mlen, t, mlen if max_t is None else int(max_t), parent, W=group, done=done)
+
+
+class RingPrefill:
+    """A prompt prefill straight into a RingMemory: pass it as ``mems`` and the call's rows start from the zero memory (``model.init_mem``),
+    project only their own tokens, attend over (the zero memory's keys / values, their own) with db1_relattn_mem_kv_fwd, and every layer's
+    last ``mem_len`` keys / values are written into ring rows ``rows`` by db1_ring_prefill_rows, relative to the ring's CURRENT origin (read
+    on the device, not advanced).  The call returns ``(logits, None, this object)``.
+    ``rows``: int32 [n_dst] on the device, distinct rows of the ring (None: all ``ring.B`` rows, in order); ``src``: int32 [n_dst], the call
+    row every destination descends from (None: destination i from call row i) -- ``arange(n_dst) // W`` expands every prompt to W rows
+    without repeating or re-projecting anything.  Shapes and dtypes are checked here, on the host (ValueError before any launch); what the
+    kernel skipped on the device (a row or a source out of range) is reported through ``ring.load_status`` (bits 0 / 2)."""
+    is_ring_prefill = True
+
+    def __init__(self, ring: RingMemory, rows: torch.Tensor = None, src: torch.Tensor = None):
+        if not isinstance(ring, RingMemory):
+            raise ValueError(f"RingPrefill: a RingMemory expected, got {type(ring).__name__}")
+        dev = ring.state.device
+        for name, x in (("rows", rows), ("src", src)):
+            if x is None:
+                continue
+            if not torch.is_tensor(x) or x.dtype != torch.int32 or x.dim() != 1 or x.device != dev or not x.is_contiguous():
+                raise ValueError(f"RingPrefill: {name} must be a contiguous int32 vector on {dev}")
+        n_dst = ring.B if rows is None else int(rows.numel())
+        if n_dst > ring.B:
+            raise ValueError(f"RingPrefill: {n_dst} destinations for a ring of {ring.B} rows")
+        if src is not None and int(src.numel()) != n_dst:
+            raise ValueError(f"RingPrefill: src holds {int(src.numel())} entries for {n_dst} destinations")
+        self.ring, self.src, self.n_dst = ring, src, n_dst
+        self.rows = rows if rows is not None else torch.arange(ring.B, dtype=torch.int32, device=dev)
+
+    def check_batch(self, B: int):
+        """the call's batch size against the destinations: without ``src`` destination i reads call row i"""
+        if self.src is None and self.n_dst > int(B):
+            raise ValueError(f"RingPrefill: {self.n_dst} destinations cannot be indexed by a call of {B} rows without a src map")
+        if self.src is not None and int(B) < 1:
+            raise ValueError("RingPrefill: an empty call")
+
+    def zero_kv(self):
+        """per layer the keys / values of one position of the zero memory, [1, 1, 2, H, D]: what ``RingMemory.reset`` projects
+        (``_project``, on one position of ``init_mem(1)``), once per weight version.  Passed to the kernels with strides 0; not assumed
+        to be zero."""
+        ring, model = self.ring, self.ring.model
+        z = getattr(ring, "_zero_kv", None)
+        if z is None or z[0] != model._wversion:
+            with torch.no_grad():
+                kv = [k.contiguous() for k in ring._project([m[:, :1] for m in model.init_mem(1)], 1, mlen=1)]
+            z = ring._zero_kv = (model._wversion, kv)
+        return z[1]
 
 
 class GraphedRingStep:

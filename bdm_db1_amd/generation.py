@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode import GraphedRingStep, RingMemory, _token_input  # noqa: F401  (scoring.py takes _token_input from here)
+from .decode import GraphedRingStep, RingMemory, RingPrefill, _token_input  # noqa: F401  (scoring.py takes _token_input from here)
 
 
 @dataclass(frozen=True)
@@ -475,6 +475,20 @@ def _prefill(model, prompt, G: int, expand: Optional[int] = None):
     return logits, mems
 
 
+def _use_ring_prefill(model) -> bool:
+    """``model.use_ring_prefill`` on a model that supports it (an unsupported model with the flag set keeps the list-form prefill)"""
+    return bool(getattr(model, "use_ring_prefill", False)) and bool(getattr(model, "ring_prefill_supported", False))
+
+
+def _prefill_ring(model, prompt, ring, rows=None, expand: Optional[int] = None):
+    """the prompt once, straight into ``ring`` (``decode.RingPrefill``): only its own tokens are projected and every layer's last mem_len keys /
+    values go to ring rows ``rows`` (int32 device vector; None: all rows) relative to the ring's current origin -> logits [G, L, V].
+    ``expand`` given: ring row r descends from prompt r // expand -- nothing is repeated or projected twice."""
+    src = None if expand is None else torch.arange(ring.B if rows is None else int(rows.numel()), dtype=torch.int32, device=model.dev) // int(expand)
+    logits, _, _ = model([prompt], compute_loss=False, mems=RingPrefill(ring, rows, src))
+    return logits
+
+
 def _check_chain(model):
     """raise what the hand-off chain of the eager decode launches recorded, if anything"""
     chk = getattr(model, "check_decode_chain", None)
@@ -770,12 +784,18 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             ids = torch.zeros(st.M, 1, dtype=torch.long, device=model.dev)
         st.start(*start)
         # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
-        logits, mems = _prefill(model, prompt, key.rows, st.expand)
+        direct = ring and _use_ring_prefill(model)
+        if direct:      # (model.use_ring_prefill) the prompt's keys / values go straight into every ring row, origin 0
+            gen.ring.state.zero_()
+            gen.ring.load_status.zero_()
+            logits, mems = _prefill_ring(model, prompt, gen.ring, None, st.expand), None
+        else:
+            logits, mems = _prefill(model, prompt, key.rows, st.expand)
         last = logits[:, -1]
         st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids[:, 0])
         del logits, last
         calls = 0
-        if ring:
+        if ring and not direct:
             gen.ring.load(mems)
             del mems
         for i in range(1, st.cfg.max_new_tokens):
@@ -790,6 +810,8 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             calls += 1
         if ring:
             gen.check(replay)
+            if direct and int(gen.ring.load_status.cpu()) != 0:
+                raise RuntimeError("db1_ring_prefill_rows: the prefill skipped a ring row")
         else:
             _check_chain(model)
         if stats is not None:

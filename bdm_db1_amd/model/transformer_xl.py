@@ -301,6 +301,9 @@ class TransformerXL(nn.Module):
         self.use_flash = True            # fused attention when the shape is supported
         self.use_flash_bwd = True        # fused backward kernels (False: recompute through the materialised path)
         self.use_mem_attn = False        # inference calls with memory and more than 64 new tokens: one fused launch (db1_relattn_mem_fwd) instead of the materialised path
+        # generation's prompt prefill (generate, beam_search, sample_best_of, the streams' admissions) projects only the prompt's own tokens and
+        # writes their keys / values straight into the K/V ring (decode.RingPrefill) instead of the list-form path + RingMemory.load / load_rows
+        self.use_ring_prefill = False
         # what the flash backward recomputes (include/db1_hip.h, db1_relattn_flash_bwd): "forward" = nothing, the forward keeps its
         # unnormalised probabilities per layer (B*H*L*L bf16 + B*H*L*L/32 floats each: 2.2 GiB per layer at 64 x 1024 tokens);
         # "scratch" = the query side recomputes and leaves P / dS in one scratch buffer for the key side; "recompute" = both sides
@@ -835,7 +838,7 @@ class TransformerXL(nn.Module):
         return dqkv, dR
 
     # ------------------------------------------------------------------ one decoder layer (post-LN; transformer_xl.py:112-353)
-    def _layer_fwd(self, i, x, R_in, B, L, mlen, shift, mem, keep: bool, dec=None, dstep=None, pend=None):
+    def _layer_fwd(self, i, x, R_in, B, L, mlen, shift, mem, keep: bool, dec=None, dstep=None, pend=None, rp=None):
         d, di, dff = self.d_model, self.d_inner, self.d_ff
         a = 1.0 if self.deepnorm_alpha is None else self.deepnorm_alpha
         p = f"h.{i}."
@@ -861,6 +864,12 @@ class TransformerXL(nn.Module):
             else:
                 ops.gemm(x, self.W(p + "dec_attn.qkv_net.weight").t(), qkv)
             av = self._attention_decode(qkv, i, B, L, mlen, shift, dec)
+        elif rp is not None:  # prefill straight into the K/V ring (decode.RingPrefill, its zero-memory K/V row): only the new tokens are projected
+            qkv = self._new(T, 3 * d)
+            ops.gemm(x, self.W(p + "dec_attn.qkv_net.weight").t(), qkv)
+            R = self._new(R_in.shape[0], d)
+            ops.gemm(R_in, self.W(p + "dec_attn.r_net.weight").t(), R)
+            av = self._attention_ring_prefill(qkv, R, i, B, L, mlen, shift, *rp)
         else:
             if mem is not None:
                 cat = torch.cat([mem.to(self.compute_dtype), x.view(B, L, d)], dim=1).contiguous()  # data movement only (:125)
@@ -1201,6 +1210,10 @@ class TransformerXL(nn.Module):
         assert not (compute_loss and mems is not None) or scoring, "During training, Gato does not use memory mechanism."
         keep = compute_loss and torch.is_grad_enabled()
         d = self.d_model
+        if getattr(mems, "is_ring_prefill", False) and not (self.ring_prefill_supported and mems.ring.model is self and not self.training and
+                                                            not torch.is_grad_enabled() and not compute_loss):
+            raise ValueError("RingPrefill needs an eval-mode call without gradients or loss on the ring's own model: bf16, use_decode, d_head 128, "
+                             "post-LN layers (model.ring_prefill_supported)")
         embs, labels, masks, ecs, shapes = [], [], [], [], []
         for t in tasks_input:
             e, lab, msk, c = self._embed_task(t, compute_loss)
@@ -1218,6 +1231,8 @@ class TransformerXL(nn.Module):
                 dstep = self._drop_step
             if self.embd_pdrop > 0:
                 ops.dropout(h, h, self._drop_args(self.embd_pdrop, self.SITE_EMBED, dstep))                     # :545
+        if getattr(mems, "is_ring_prefill", False):     # decode.RingPrefill: the call starts from the zero memory and fills ring rows
+            return self._forward_ring_prefill(h, mems, ecs, shapes, compute_loss, keep)
         ring = mems if (mems is not None and not isinstance(mems, (list, tuple))) else None   # decode.RingMemory: K / V ring instead of hidden states
         if ring is not None:
             mems = None
@@ -1301,6 +1316,61 @@ class TransformerXL(nn.Module):
             return self._finish_forward(x, hids, lcs, ecs, shapes, labels, masks, R_in, B, L, shift, dstep, keep, compute_loss, mems, ring, dec, mlen)
         finally:
             self._win_on = False
+
+    # ---- prefill straight into the K/V ring (decode.RingPrefill): only the call's own tokens are projected
+    RING_PREFILL_MAX_Q, RING_PREFILL_MAX_KLEN = 8192, 16384
+
+    @property
+    def ring_prefill_supported(self) -> bool:
+        """can a call with ``mems=RingPrefill`` run on this model?  (bf16, the K/V-cached decode path, d_head 128, post-LN layers, a memory.)
+        ``ring_prefill_ok(L)`` adds the call's own length."""
+        return bool(self.compute_dtype == torch.bfloat16 and self.use_decode and self.d_head == 128 and not self.pre_lnorm and int(self.mem_len or 0) > 0)
+
+    def ring_prefill_ok(self, L: int) -> bool:
+        """``ring_prefill_supported`` for a call of ``L`` new tokens per row: 1 <= L <= 8192, mem_len + L <= 16384, and a visibility window
+        db1_relattn_mem_kv_fwd supports"""
+        mlen = int(self.mem_len or 0)
+        return bool(self.ring_prefill_supported and 1 <= int(L) <= self.RING_PREFILL_MAX_Q and mlen + int(L) <= self.RING_PREFILL_MAX_KLEN and
+                    ops.relattn_mem_kv_supported(1, int(L), mlen, self.n_head, self.d_head, self._window(int(L), mlen), self.compute_dtype))
+
+    def _forward_ring_prefill(self, h, rp, ecs, shapes, compute_loss, keep):
+        """the call's B rows start from the zero memory (mlen = mem_len): per layer the qkv projection of the B * L new rows only, attention
+        over (the layer's zero-memory K/V row, strides 0; the call's own K/V) and the last mem_len keys / values into ring rows ``rp.rows``.
+        The ring's origin is not advanced.  -> (logits, None, rp)"""
+        B, L, d = h.shape
+        mlen = int(self.mem_len)
+        ring = rp.ring
+        if not self.ring_prefill_ok(L):
+            raise ValueError(f"RingPrefill: a call of {L} tokens over mem_len {mlen} is not supported (1 <= L <= {self.RING_PREFILL_MAX_Q}, "
+                             f"mem_len + L <= {self.RING_PREFILL_MAX_KLEN})")
+        rp.check_batch(B)
+        if mlen >= ring.cap or len(ring.kv) != self.n_layer:
+            raise ValueError("RingPrefill: the ring does not belong to this model")
+        shift = self._window(L, mlen)
+        if not (L > 1 or (self.same_length and shift <= L - 1)):
+            raise ValueError("attention mask hides nothing (transformer_xl.py:177,205-206)")
+        self.check_decode_chain()
+        zkv = rp.zero_kv()
+        R_in = self._sinusoid(L + mlen)
+        x = h.view(B * L, d)
+        self._win_on, self._R_all = False, None
+        hids = []
+        for i in range(self.n_layer):
+            hids.append(x)
+            x, _ = self._layer_fwd(i, x, R_in, B, L, mlen, shift, None, False, rp=(rp, zkv[i]))
+        res = self._finish_forward(x, hids, [None] * self.n_layer, ecs, shapes, [], [], R_in, B, L, shift, None, keep, compute_loss, None, None, None, mlen)
+        return res + (rp,)
+
+    def _attention_ring_prefill(self, qkv, R, i, B, L, mlen, shift, rp, zkv):
+        H, D = self.n_head, self.d_head
+        qu, qv, av = self._new(B, L, H, D), self._new(B, L, H, D), self._new(B, L, H, D)
+        ops.relattn_add_head_bias(qkv, self._bias("r_w_bias", i), self._bias("r_r_bias", i), qu, qv, B, L, L, H, D)
+        qkv5 = qkv.view(B, L, 3, H, D)
+        k_new, v_new, k_mem, v_mem = qkv5[:, :, 1], qkv5[:, :, 2], zkv[:, :, 0], zkv[:, :, 1]
+        ops.relattn_mem_kv_fwd(qu, qv, k_new, v_new, k_mem, v_mem, R, av, None, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D))
+        # right after the attention, while qkv is alive: the layer's last mem_len keys / values go to the new tenants' ring rows
+        ops.ring_prefill_rows(rp.ring.kv[i], k_new, v_new, k_mem, v_mem, rp.ring.state, mlen, rp.rows, rp.src, rp.ring.load_status)
+        return av
 
     # ---- deferred backward (BackwardWindow): the forwards of an accumulation window write into window-sized buffers, ONE backward at its boundary
     def _window_ok(self, B: int, L: int, shift: int, nd: int) -> bool:

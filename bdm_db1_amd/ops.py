@@ -1271,6 +1271,85 @@ def relattn_mem_fwd(qu, qv, k, v, R, out, lse, B, q, klen, mlen, H, D, shift, sc
              B, q, klen, mlen, H, D, shift, float(scale), _vp(0), 0, stream())
 
 
+def _kv_strides(who, name, x, B, rows, H, D, may_broadcast):
+    """(row stride, batch stride) in elements of a key / value view ``x`` [B, rows, H, D] (unit stride inside a head row); with
+    ``may_broadcast`` a dimension of size 1 (or an expanded one) stands for every index: stride 0"""
+    if x.dim() != 4 or x.shape[2] != H or x.shape[3] != D or x.stride(3) != 1 or x.stride(2) != D:
+        raise ValueError(f"{who}: {name} must be a [batch, rows, {H}, {D}] view with unit stride inside a head row")
+    nb, nr = x.shape[0], x.shape[1]
+    if not (nb == B or (may_broadcast and nb == 1)) or not (nr == rows or (may_broadcast and nr == 1)):
+        raise ValueError(f"{who}: {name} of shape {tuple(x.shape)} for {B} sequences of {rows} rows")
+    return (x.stride(1) if nr > 1 else 0) if may_broadcast else x.stride(1), (x.stride(0) if nb > 1 else 0) if may_broadcast else x.stride(0)
+
+
+def relattn_mem_kv_supported(B, q, mlen, H, D, shift, dtype) -> bool:
+    """db1_relattn_mem_kv_supported: what relattn_mem_supported supports at klen = mlen + q, with mlen >= 1"""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(lib.load().db1_relattn_mem_kv_supported(int(B), int(q), int(mlen), int(H), int(D), int(shift), dt_code(dtype)))
+
+
+def relattn_mem_kv_fwd(qu, qv, k_new, v_new, k_mem, v_mem, R, out, lse, B, q, mlen, H, D, shift, scale):
+    """relattn_mem_fwd with the keys / values in two places (db1_relattn_mem_kv_fwd): key j < mlen is row j of the memory ``k_mem`` /
+    ``v_mem``, key j >= mlen row j - mlen of the call's own ``k_new`` / ``v_new`` -- bit for bit relattn_mem_fwd over the concatenation.
+    k_new, v_new: views [B, q, H, D] (e.g. of qkv_new [B, q, 3, H, D]); k_mem, v_mem: views [B or 1, mlen or 1, H, D] -- a dimension of
+    size 1 (or an expanded one) is passed with stride 0: one row for every position, one memory for every sequence.
+    lse: float32 [B, H, q] or None."""
+    who = "relattn_mem_kv_fwd"
+    if any(t.dtype != torch.bfloat16 for t in (qu, qv, k_new, v_new, k_mem, v_mem, R, out)) or (lse is not None and lse.dtype != torch.float32):
+        raise lib.Db1Error(f"{who}: bf16 operands (float32 lse) only")     # (the entry point takes no dtype: refused here, nothing launched)
+    n_rs, n_bs = _kv_strides(who, "k_new", k_new, B, q, H, D, False)
+    m_rs, m_bs = _kv_strides(who, "k_mem", k_mem, B, mlen, H, D, True)
+    if v_new.shape != k_new.shape or v_new.stride() != k_new.stride() or v_mem.shape != k_mem.shape or v_mem.stride() != k_mem.stride():
+        raise ValueError(f"{who}: the values must have the keys' shape and strides")
+    lib.call("db1_relattn_mem_kv_fwd", P(qu), P(qv), P(k_new), P(v_new), n_rs, n_bs, P(k_mem), P(v_mem), m_rs, m_bs, P(R), R.shape[0], P(out), P(lse),
+             B, q, mlen, H, D, shift, float(scale), _vp(0), 0, stream())
+
+
+def ring_prefill_rows(ring, k_new, v_new, k_mem, v_mem, state, mlen, rows, src, status):
+    """the ring slots of new tenants of ONE layer from (a K/V memory, a call's own K/V) -- db1_ring_prefill_rows, one launch.  ``ring``:
+    [M, cap, 2, H, D] bf16 or an fp8 ring [M, cap, 264 H] uint8, contiguous; k_new, v_new: views [n_src, q, H, D]; k_mem, v_mem: views
+    [n_src or 1, mlen or 1, H, D] (size 1 = stride 0, as relattn_mem_kv_fwd takes them).  Destination i takes ring row ``rows[i]`` (int32
+    [n_dst], distinct, on the device) from source ``src[i]`` (int32 [n_dst]; None: i): position j of the last mlen rows of cat(memory,
+    new) goes to slot (state + j) % cap.  ``state`` (int32 [1]) READ only; ``status`` (int32 [1]) |= 1 for a row outside [0, M), |= 2 for
+    an origin outside [0, cap), |= 4 for a source outside [0, n_src) (each skipped).  Raises ValueError on bad arguments before anything
+    is launched."""
+    who = "ring_prefill_rows"
+    if k_new.dim() != 4:
+        raise ValueError(f"{who}: k_new must be a [n_src, q, H, D] view")
+    n_src, q, H, D = (int(v) for v in k_new.shape)
+    dev, mlen = ring.device, int(mlen)
+    fp8 = ring.dtype == torch.uint8
+    slot = (264 * H,) if fp8 else (2, H, D)
+    if ring.dtype not in (torch.uint8, torch.bfloat16) or ring.dim() != 2 + len(slot) or tuple(ring.shape[2:]) != slot or not ring.is_contiguous() or \
+            ring.data_ptr() % 16:
+        raise ValueError(f"{who}: the ring must be a contiguous 16-byte aligned bf16 [M, cap, 2, {H}, {D}] or uint8 [M, cap, {264 * H}] tensor")
+    M, cap = int(ring.shape[0]), int(ring.shape[1])
+    if any(t.dtype != torch.bfloat16 or t.device != dev for t in (k_new, v_new, k_mem, v_mem)):
+        raise ValueError(f"{who}: the keys / values must be bf16 tensors on {dev}")
+    if not lib.load().db1_ring_prefill_rows_supported(int(fp8), q, mlen, cap, H, D):
+        raise ValueError(f"{who}: needs d_head 128, an even number of heads on an fp8 ring and 1 <= mlen ({mlen}) < cap ({cap}) (H={H}, D={D}, q={q})")
+    n_rs, n_bs = _kv_strides(who, "k_new", k_new, n_src, q, H, D, False)
+    m_rs, m_bs = _kv_strides(who, "k_mem", k_mem, n_src, mlen, H, D, True)
+    if v_new.shape != k_new.shape or v_new.stride() != k_new.stride() or v_mem.shape != k_mem.shape or v_mem.stride() != k_mem.stride():
+        raise ValueError(f"{who}: the values must have the keys' shape and strides")
+    if any(s % 8 for s in (n_rs, n_bs, m_rs, m_bs)) or any(t.data_ptr() % 16 for t in (k_new, v_new, k_mem, v_mem)):
+        raise ValueError(f"{who}: the keys / values must be 16-byte aligned with strides that are multiples of 8 elements")
+    if rows.dim() != 1:
+        raise ValueError(f"{who}: rows must be an int32 vector")
+    n_dst = int(rows.numel())
+    if n_dst > M:
+        raise ValueError(f"{who}: {n_dst} destinations for a ring of {M} rows")
+    for name, x, k in (("state", state, 1), ("rows", rows, n_dst), ("status", status, 1)) + ((("src", src, n_dst),) if src is not None else ()):
+        _check_tensor(who, name, x, torch.int32, k, dev)
+    if src is None and n_dst > n_src:
+        raise ValueError(f"{who}: {n_dst} destinations from {n_src} sources need a src map")
+    if n_dst == 0:
+        return
+    lib.call("db1_ring_prefill_rows", P(ring), int(fp8), M, cap, P(k_new), P(v_new), n_rs, n_bs, P(k_mem), P(v_mem), m_rs, m_bs, P(state), P(rows),
+             P(src), n_dst, n_src, q, mlen, H, D, P(status), stream())
+
+
 _tickets = {}
 
 

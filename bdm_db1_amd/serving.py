@@ -8,7 +8,9 @@ other rows go on:
   * the K/V ring advances all rows together from one device-side origin, so a new request moves in by writing its ``mem_len`` projected keys
     and values relative to the current origin (``RingMemory.load_rows``, db1_ring_load_rows): nothing else in the ring moves;
   * waiting requests of one prompt shape are prefilled together through the list-form path (``generation._prefill``), requests of other shapes
-    in calls of their own; after a prefill every row holds exactly ``mem_len`` memory entries, whatever its prompt was;
+    in calls of their own; after a prefill every row holds exactly ``mem_len`` memory entries, whatever its prompt was.  With
+    ``model.use_ring_prefill`` the group's prefill writes its keys and values straight into the slots' ring rows instead
+    (``generation._prefill_ring``, db1_ring_prefill_rows) and nothing is projected a second time;
   * the per-token graph (one ``GraphedRingStep`` of ``slots`` rows, kept on the model) ends in db1_select_tokens_slots: every slot has its own
     token counter and limit, advanced by the launch itself, and a vacant slot only feeds ``pad_id`` forward.  The same kernel, given the
     slots of the newly admitted rows (``row_map``), picks their token 0 from the prefill's last-position logits straight into their slots;
@@ -33,8 +35,8 @@ import torch
 
 from . import ops
 from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodeKey, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained,
-                         _need_memory, _prefill, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _vocab_window, _with_kv_cache, _work,
-                         caption_prompt, question_prompts)
+                         _need_memory, _prefill, _prefill_ring, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _use_ring_prefill,
+                         _vocab_window, _with_kv_cache, _work, caption_prompt, question_prompts)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- requests
@@ -429,7 +431,9 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
                     rows = [s for s, _ in members]
                     rs = [r for _, r in members]
                     # one prefill for the group; its last position picks token 0 of every request straight into its slot, its memory moves in
-                    logits, mems = _prefill(model, _gather(rs), len(rs))
+                    direct = _use_ring_prefill(model)
+                    if not direct:
+                        logits, mems = _prefill(model, _gather(rs), len(rs))
                     recs = np.stack([ops.pack_slot_params(**(r.params or inherit).resolve(cfg, V, hi)) for r in rs]) if per else None
                     packed = None
                     if caps is not None:     # (packing validates every record on the host before it is written)
@@ -437,8 +441,11 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
                                   for r in rs]
                     idx = st.occupy(rows, [r.limit for r in rs], [r.index if stream_ids is None else int(stream_ids[r.index]) for r in rs], recs,
                                     packed)
+                    if direct:   # (model.use_ring_prefill) the group's keys / values go straight into its slots' ring rows, nothing moves in afterwards
+                        logits, mems = _prefill_ring(model, _gather(rs), gen.ring, idx), None
                     st.select(logits[:, -1], step.ids[:, 0], row_map=idx)
-                    gen.ring.load_rows(mems, idx)
+                    if not direct:
+                        gen.ring.load_rows(mems, idx)
                     del logits, mems
                     counts["prefill_calls"] += 1
                 k = sched.replays_due(cfg.sync_every)
@@ -472,7 +479,7 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
                 if finish:     # nothing waits (admit found no request for the free slots) and every slot is vacant
                     gen.check(replay)
                     if int(gen.ring.load_status.cpu()) != 0:
-                        raise RuntimeError("db1_ring_load_rows: a request was given a row outside the ring")
+                        raise RuntimeError("db1_ring_load_rows / db1_ring_prefill_rows: a request was given a row outside the ring")
             report()
             for r in results:
                 yield r

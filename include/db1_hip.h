@@ -298,6 +298,21 @@ int64_t db1_relattn_mem_workspace_bytes(int B, int q, int klen, int H);      /* 
 int db1_relattn_mem_fwd(const void* qu, const void* qv, const void* k, const void* v, int64_t kv_row_stride, int64_t kv_batch_stride,
                         const void* R, int nd, void* out, float* lse, int B, int q, int klen, int mlen, int H, int D, int shift,
                         float scale, void* ws, int64_t ws_bytes, void* stream);
+/* db1_relattn_mem_fwd with the keys / values in TWO places (a prefill that projects only its own tokens): logical key j < mlen is row j of the
+ * memory, k_mem / v_mem + b*mem_batch_stride + j*mem_row_stride (+ h*D); key j >= mlen is row j - mlen of the call's own q rows, k_new /
+ * v_new + b*new_batch_stride + (j - mlen)*new_row_stride (e.g. views of qkv_new [B, q, 3, H, D]).  EITHER memory stride may be 0: one row
+ * for every position, one memory for every sequence.  Everything else is db1_relattn_mem_fwd's rule with klen = mlen + q, and the result is
+ * bit for bit that of db1_relattn_mem_fwd over the concatenation: the same kernel, steps, order and rounding points -- only the addresses of
+ * the staged rows differ; no atomics, no workspace (_workspace_bytes is 0).
+ * Supported: what db1_relattn_mem_supported supports at klen = mlen + q, with mlen >= 1 (DB1_ERR_UNSUPPORTED otherwise); the new rows'
+ * stride >= H*D, the memory's 0 or >= H*D, nd >= 1, no NULL operand but lse (DB1_ERR_BAD_SHAPE); strides multiples of 8 elements, operands
+ * 16-byte aligned (DB1_ERR_BAD_ALIGN).  Refused before anything is launched. */
+int db1_relattn_mem_kv_supported(int B, int q, int mlen, int H, int D, int shift, int dt);
+int64_t db1_relattn_mem_kv_workspace_bytes(int B, int q, int mlen, int H);     /* 0 */
+int db1_relattn_mem_kv_fwd(const void* qu, const void* qv, const void* k_new, const void* v_new, int64_t new_row_stride,
+                           int64_t new_batch_stride, const void* k_mem, const void* v_mem, int64_t mem_row_stride, int64_t mem_batch_stride,
+                           const void* R, int nd, void* out, float* lse, int B, int q, int mlen, int H, int D, int shift, float scale,
+                           void* ws, int64_t ws_bytes, void* stream);
 
 /* The same attention over a RING of cached keys / values (hipGraph-friendly inference: nothing is concatenated or copied per call):
  * kv_ring [B, cap, 2, H, D] bf16, cap >= mlen + q; logical key j < mlen is ring row (ring_state[0] + j) % cap; the q new keys / values come
@@ -739,6 +754,22 @@ int db1_ring_reorder(const void* const* rings, int n_layers, int M, int W, int c
 int db1_ring_load_rows_supported(int64_t slot_bytes, int mlen, int cap);
 int db1_ring_load_rows(const void* const* rings, const void* const* src, int n_layers, int M, int n, int cap, int64_t slot_bytes,
                        const int32_t* state, int mlen, const int32_t* rows, int32_t* status, void* stream);
+/* Prefill straight into the ring (tests/ring_prefill_rule.py restates the rule in NumPy): the slots of new tenants written from (a K/V memory
+ * of mlen rows, a call's own q rows of K/V) of ONE layer -- operands and strides of db1_relattn_mem_kv_fwd, n_src sequences; `ring` is that
+ * layer's ring, [M, cap, 2, H, D] bf16 (fp8 == 0) or [M, cap, 264 H] bytes (fp8 != 0, the fp8 K/V ring's slot).  For destination i in
+ * [0, n_dst): row = rows[i], s = src[i] (src NULL: s = i); for logical position j in [0, mlen): position j of the LAST mlen rows of
+ * cat(memory of s (mlen rows), new rows of s (q rows)) -- memory row j + q while j + q < mlen, else new row j + q - mlen; q >= mlen takes
+ * everything from the call -- goes to slot (state[0] + j) % cap of ring row `row`.  state[0] is read on the device and not changed.  bf16
+ * ring: the K row and the V row are copied as they are; fp8 ring: quantised by the fp8 K/V ring's rule, bit for bit what db1_kv8_quantize
+ * writes.  No other byte of the ring changes.  *status (int32 [1], |=; the launch's only atomic): bit 0 for a row outside [0, M) (skipped),
+ * bit 1 for an origin outside [0, cap) (nothing written), bit 2 for an s outside [0, n_src) (skipped).  rows must be distinct.  ONE launch.
+ * DB1_ERR_UNSUPPORTED: D != 128, an odd H on an fp8 ring, q < 1, mlen outside [1, cap); DB1_ERR_BAD_SHAPE: a NULL buffer (src may be
+ * NULL), n_dst > M, a row stride below H*D (the memory's may be 0); DB1_ERR_BAD_ALIGN: as db1_relattn_mem_kv_fwd.  n_dst == 0 is a no-op. */
+int db1_ring_prefill_rows_supported(int fp8, int q, int mlen, int cap, int H, int D);
+int db1_ring_prefill_rows(void* ring, int fp8, int M, int cap, const void* k_new, const void* v_new, int64_t new_row_stride,
+                          int64_t new_batch_stride, const void* k_mem, const void* v_mem, int64_t mem_row_stride, int64_t mem_batch_stride,
+                          const int32_t* state, const int32_t* rows, const int32_t* src, int n_dst, int n_src, int q, int mlen, int H, int D,
+                          int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ decoding constraints (tests/constraint_rule.py restates the rule in
  * NumPy).  db1_constrain_logits edits the step's logits [M, ld] (fp32 / bf16; columns >= V are padding) IN PLACE, before

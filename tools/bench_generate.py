@@ -29,6 +29,8 @@ limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS);
     python tools/bench_generate.py --stream [requests [slots]]
     python tools/bench_generate.py --stream --mem-attn [requests [slots]]   (model.use_mem_attn = True: the admissions' prefills through
                                                                             db1_relattn_mem_fwd; the line carries "mem_attn": true)
+    python tools/bench_generate.py --ring-prefill [any of the forms above]   (model.use_ring_prefill = True: the prompt prefills go straight
+                                                                            into the K/V ring; every line carries "ring_prefill": true)
 
 With --stream --per-request: the stream workload above with every second request greedy and the others at top-p 0.9
 (``caption_stream(..., per_request=True)``, a ``SamplingParams`` on the sampled requests: the graph ends in db1_select_tokens_slots_per)
@@ -637,6 +639,11 @@ args = sys.argv[1:]
 if "--mem-attn" in args:       # calls with memory and more than 64 new tokens (the prompt prefills) take the fused attention over memory
     model.use_mem_attn = True
     args = [a for a in args if a != "--mem-attn"]
+if "--ring-prefill" in args:   # the prompt prefills project only their own tokens and write their keys / values straight into the K/V ring
+    model.use_ring_prefill = True
+    args = [a for a in args if a != "--ring-prefill"]
+    _dumps = json.dumps
+    json.dumps = lambda rec, **kw: _dumps(dict(rec, ring_prefill=True) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
 TOP_N = None
 if "--top-logprobs" in args:
     i = args.index("--top-logprobs")
