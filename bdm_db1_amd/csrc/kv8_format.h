@@ -1,5 +1,6 @@
 // The quantising half of the fp8 K/V slot format (include/db1_hip.h, "fp8 K/V ring"; tests/kv8_rule.py): one definition for every kernel
-// that writes slots -- the ring attention's append and db1_kv8_quantize (relattn_decode_kv8.hip), the prefill's slot writer (ring_prefill.hip).
+// that writes slots -- the ring attention's append and db1_kv8_quantize (relattn_decode_kv8.hip), the prefill's slot writers (ring_prefill.hip)
+// -- and, at the end, the widening of a slot's payload to VALUES for the attention over a ring-resident memory (relattn_mem.hip).
 #pragma once
 #include "db1_common.h"
 
@@ -54,4 +55,16 @@ __device__ __forceinline__ void kv8_quant_block(const bf16_t* src, unsigned char
         *reinterpret_cast<uint4*>(pay + c * 16) = make_uint4(a.x, a.y, b.x, b.y);
         if (c == 0) *sc = __uint_as_float((unsigned)(e + 127) << 23);
     }
+}
+
+// The widening half, for a kernel that wants VALUES: 8 payload bytes times the block's scale -> 8 bf16 (v_cvt_pk_f32_fp8, the product in fp32,
+// then the upper halves: a power of two times a 4-bit significand is exact in bf16 unless it is subnormal there; a NaN byte stays NaN)
+typedef __attribute__((ext_vector_type(2))) float kv8fmt_f32x2;
+__device__ __forceinline__ uint4 kv8_widen8_scaled(uint2 w, float sc) {
+    const kv8fmt_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
+    const kv8fmt_f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);
+    return make_uint4(__builtin_amdgcn_perm(__float_as_uint(a[1] * sc), __float_as_uint(a[0] * sc), 0x07060302u),
+                      __builtin_amdgcn_perm(__float_as_uint(b[1] * sc), __float_as_uint(b[0] * sc), 0x07060302u),
+                      __builtin_amdgcn_perm(__float_as_uint(c[1] * sc), __float_as_uint(c[0] * sc), 0x07060302u),
+                      __builtin_amdgcn_perm(__float_as_uint(d[1] * sc), __float_as_uint(d[0] * sc), 0x07060302u));
 }

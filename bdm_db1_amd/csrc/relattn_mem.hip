@@ -18,6 +18,7 @@
 //   and the skewed read-back, online softmax, P rounded to bf16, O^T += V^T.P^T (8 MFMA).  Then ONE normalisation, one bf16 store, and
 //   lse = m + log(l) (the sum over the fp32 probabilities).
 #include "db1_common.h"
+#include "kv8_format.h"
 
 typedef __attribute__((ext_vector_type(8))) short mem_bf16x8;
 typedef __attribute__((ext_vector_type(4))) short mem_bf16x4;
@@ -43,6 +44,9 @@ struct MemArgs {
     float scale;
     const bf16_t* km; const bf16_t* vm;     // KV mode: the memory's keys / values (rows j < mlen); k, v then hold the call's own q rows
     int64_t m_rs, m_bs;                     // ... their row / batch strides (0: one row / one memory for all)
+    const unsigned char* base;              // RING mode: the memory lives in the slots of a K/V ring's layer buffer [M_base, cap_base, slot] ...
+    const int* state_base; const int* base_rows; int* status;   // ... its origin, the ring row of every call row (NULL: b), the guard's status word
+    int M_base, cap_base;
 };
 
 __device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
@@ -53,7 +57,11 @@ __device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
 
 // KV = false: k, v hold all klen rows.  KV = true (db1_relattn_mem_kv_fwd): logical key j < mlen is row j of km / vm, key j >= mlen row
 // j - mlen of k / v -- only the staged rows' addresses differ, so the result is bit for bit that of KV = false over the concatenation.
-template <bool KV>
+// RING (with KV; db1_relattn_mem_ring_fwd): logical key j < mlen is slot (origin + j) % cap_base of ring row base_rows[b] of a K/V ring --
+// RING = 1 a bf16 ring, the slot's [2, H, D] pair as it is; RING = 2 an fp8 ring (kv8_format.h), a thread's 16-byte piece widened from 8
+// payload bytes and multiplied by its block's scale on the way into LDS (exact: a power of two) -- so the LDS tiles, and with them every
+// bit of the result, are those of KV = true over the unpacked, linearised memory.
+template <bool KV, int RING = 0>
 __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // MEM_LDS bytes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -78,6 +86,19 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     const bf16_t* Rg = p.R + h * MEM_D;
     const bf16_t* kmg = KV ? p.km + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
     const bf16_t* vmg = KV ? p.vm + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
+    // RING: the call row's ring row and the origin, clamped into range -- every read stays in bounds, one thread per call row reports it
+    const unsigned char* ringb = nullptr;
+    int rs0 = 0;
+    const int64_t rslot = RING == 2 ? (int64_t)264 * p.H : (int64_t)4 * HD;      // bytes
+    if (RING) {
+        int rrow = p.base_rows ? p.base_rows[b] : b;
+        rs0 = p.state_base[0];
+        const bool bad_row = rrow < 0 || rrow >= p.M_base, bad_origin = rs0 < 0 || rs0 >= p.cap_base;
+        if ((bad_row || bad_origin) && blockIdx.x == 0 && h == 0 && threadIdx.x == 0) atomicOr(p.status, 8);
+        rrow = bad_row ? 0 : rrow;
+        rs0 = bad_origin ? 0 : rs0;
+        ringb = p.base + (int64_t)rrow * p.cap_base * rslot;
+    }
     // the block's steps: keys max(0, ib0 - shift + 1) .. ilast + mlen (= the last row's diagonal key < klen), aligned at multiples of 32
     const int ilast = ib0 + MEM_QB - 1 < p.q ? ib0 + MEM_QB - 1 : p.q - 1;
     const int jlo = ib0 - p.shift + 1 > 0 ? ib0 - p.shift + 1 : 0;
@@ -86,6 +107,23 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     const int srow = threadIdx.x >> 4, sch = threadIdx.x & 15;               // piece 0; piece 1 is row srow + 16 (same row & 15, row & 7)
     const int soff_k = srow * 256 + ((sch ^ (srow & 15)) << 4), soff_v = srow * 256 + ((sch ^ ((srow & 7) << 1)) << 4);
     uint4 kst0, kst1, vst0, vst1;
+    float ksc0 = 1.f, ksc1 = 1.f, vsc0 = 1.f, vsc1 = 1.f;   // RING = 2: the scales of the staged pieces that hold payload (fpay bit 0: piece 0, bit 1: piece 1)
+    unsigned fpay = 0u;
+    // the thread's K and V piece of memory key j_ (< mlen) from its ring slot; on an fp8 ring 8 payload bytes (.x, .y) and the block's scale
+    auto ring_load = [&](int j_, uint4& kx_, uint4& vx_, float& ks_, float& vs_) {
+        const int r_ = rs0 + j_ >= p.cap_base ? rs0 + j_ - p.cap_base : rs0 + j_;
+        const unsigned char* sl_ = ringb + (int64_t)r_ * rslot;
+        if (RING == 2) {
+            const uint2 kp_ = *reinterpret_cast<const uint2*>(sl_ + h * MEM_D + sch * 8), vp_ = *reinterpret_cast<const uint2*>(sl_ + HD + h * MEM_D + sch * 8);
+            kx_ = make_uint4(kp_.x, kp_.y, 0u, 0u);
+            vx_ = make_uint4(vp_.x, vp_.y, 0u, 0u);
+            ks_ = reinterpret_cast<const float*>(sl_ + 2 * HD)[h];
+            vs_ = reinterpret_cast<const float*>(sl_ + 2 * HD)[p.H + h];
+        } else {
+            kx_ = *reinterpret_cast<const uint4*>(sl_ + (h * MEM_D + sch * 8) * 2);
+            vx_ = *reinterpret_cast<const uint4*>(sl_ + (HD + h * MEM_D + sch * 8) * 2);
+        }
+    };
     // rows past klen are clamped: their probabilities are exactly zero
 #define MEM_STAGE_LOAD(st_)                                                                                   \
     {                                                                                                         \
@@ -93,14 +131,34 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
         const int jb_ = (st_) * 32 + srow + 16 < p.klen ? (st_) * 32 + srow + 16 : p.klen - 1;                \
         if (KV && !((st_) * 32 < p.mlen && (st_) * 32 + 32 > p.mlen)) {   /* a whole step of one source (workgroup-uniform) */ \
             const bool mm_ = (st_) * 32 < p.mlen;                                                             \
-            const bf16_t* kb_ = mm_ ? kmg : kg;                                                               \
-            const bf16_t* vb_ = mm_ ? vmg : vg;                                                               \
-            const int64_t rs_ = mm_ ? p.m_rs : p.kv_rs;                                                       \
-            const int sub_ = mm_ ? 0 : p.mlen;                                                                \
-            kst0 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);              \
-            vst0 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);              \
-            kst1 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);              \
-            vst1 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);              \
+            if (RING && mm_) {   /* every staged row is a ring slot; the slot index wraps per row */          \
+                ring_load(ja_, kst0, vst0, ksc0, vsc0);                                                       \
+                ring_load(jb_, kst1, vst1, ksc1, vsc1);                                                       \
+                fpay = 3u;                                                                                    \
+            } else {                                                                                          \
+                const bf16_t* kb_ = mm_ ? kmg : kg;                                                           \
+                const bf16_t* vb_ = mm_ ? vmg : vg;                                                           \
+                const int64_t rs_ = mm_ ? p.m_rs : p.kv_rs;                                                   \
+                const int sub_ = mm_ ? 0 : p.mlen;                                                            \
+                kst0 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);          \
+                vst0 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(ja_ - sub_) * rs_ + sch * 8);          \
+                kst1 = *reinterpret_cast<const uint4*>(kb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);          \
+                vst1 = *reinterpret_cast<const uint4*>(vb_ + (int64_t)(jb_ - sub_) * rs_ + sch * 8);          \
+                fpay = 0u;                                                                                    \
+            }                                                                                                 \
+        } else if (KV && RING) {   /* the seam step over a ring: the source is picked per staged row */       \
+            const bool ma_ = ja_ < p.mlen, mb_ = jb_ < p.mlen;                                                \
+            fpay = (ma_ ? 1u : 0u) | (mb_ ? 2u : 0u);                                                         \
+            if (ma_) ring_load(ja_, kst0, vst0, ksc0, vsc0);                                                  \
+            else {                                                                                            \
+                kst0 = *reinterpret_cast<const uint4*>(kg + (int64_t)(ja_ - p.mlen) * p.kv_rs + sch * 8);     \
+                vst0 = *reinterpret_cast<const uint4*>(vg + (int64_t)(ja_ - p.mlen) * p.kv_rs + sch * 8);     \
+            }                                                                                                 \
+            if (mb_) ring_load(jb_, kst1, vst1, ksc1, vsc1);                                                  \
+            else {                                                                                            \
+                kst1 = *reinterpret_cast<const uint4*>(kg + (int64_t)(jb_ - p.mlen) * p.kv_rs + sch * 8);     \
+                vst1 = *reinterpret_cast<const uint4*>(vg + (int64_t)(jb_ - p.mlen) * p.kv_rs + sch * 8);     \
+            }                                                                                                 \
         } else if (KV) {   /* the step that straddles the seam: the source is picked per staged row */         \
             const bool ma_ = ja_ < p.mlen, mb_ = jb_ < p.mlen;                                                \
             const int64_t oa_ = ma_ ? (int64_t)ja_ * p.m_rs : (int64_t)(ja_ - p.mlen) * p.kv_rs;              \
@@ -118,6 +176,14 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     }
 #define MEM_STAGE_STORE(buf_)                                                                                 \
     {                                                                                                         \
+        if (RING == 2 && (fpay & 1u)) {   /* payload -> bf16 values, only now: the loads travelled during the step's arithmetic */ \
+            kst0 = kv8_widen8_scaled(make_uint2(kst0.x, kst0.y), ksc0);                                       \
+            vst0 = kv8_widen8_scaled(make_uint2(vst0.x, vst0.y), vsc0);                                       \
+        }                                                                                                     \
+        if (RING == 2 && (fpay & 2u)) {                                                                       \
+            kst1 = kv8_widen8_scaled(make_uint2(kst1.x, kst1.y), ksc1);                                       \
+            vst1 = kv8_widen8_scaled(make_uint2(vst1.x, vst1.y), vsc1);                                       \
+        }                                                                                                     \
         *reinterpret_cast<uint4*>(smem + (buf_) * MEM_TILE + soff_k) = kst0;                                  \
         *reinterpret_cast<uint4*>(smem + (buf_) * MEM_TILE + soff_k + 16 * 256) = kst1;                       \
         *reinterpret_cast<uint4*>(smem + (2 + (buf_)) * MEM_TILE + soff_v) = vst0;                            \
@@ -327,5 +393,50 @@ extern "C" int db1_relattn_mem_kv_fwd(const void* qu, const void* qv, const void
     attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
     relattn_mem_kernel<true><<<dim3((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B), 256, MEM_LDS, (hipStream_t)stream>>>(a);
     DB1_CHECK_LAUNCH("relattn_mem_kv");
+    return DB1_OK;
+}
+
+// ---- the same attention with the memory in the slots of a K/V ring, bf16 or fp8 (include/db1_hip.h): a prefix cache's row continued by a call
+extern "C" int db1_relattn_mem_ring_supported(int B, int q, int mlen, int cap_base, int fp8, int H, int D, int shift, int dt) {
+    return (mlen >= 1 && mlen < cap_base && (!fp8 || H % 2 == 0) && db1_relattn_mem_kv_supported(B, q, mlen, H, D, shift, dt)) ? 1 : 0;
+}
+
+extern "C" int64_t db1_relattn_mem_ring_workspace_bytes(int B, int q, int mlen, int H) {
+    (void)B; (void)q; (void)mlen; (void)H;
+    return 0;
+}
+
+extern "C" int db1_relattn_mem_ring_fwd(const void* qu, const void* qv, const void* k_new, const void* v_new, int64_t new_row_stride,
+                                        int64_t new_batch_stride, const void* base, int fp8, int M_base, int cap_base, const int32_t* state_base,
+                                        const int32_t* base_rows, int32_t* status, const void* R, int nd, void* out, float* lse, int B, int q, int mlen,
+                                        int H, int D, int shift, float scale, void* ws, int64_t ws_bytes, void* stream) {
+    (void)ws; (void)ws_bytes;
+    if (!db1_relattn_mem_ring_supported(B, q, mlen, cap_base, fp8, H, D, shift, DB1_BF16))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_mem_ring: needs bf16, d_head = 128, 1 <= q <= 8192, 1 <= mlen < cap_base, mlen + q <= 16384, shift >= 0, an even "
+                                      "number of heads on an fp8 ring (got q=%d mlen=%d cap_base=%d fp8=%d H=%d D=%d shift=%d)", q, mlen, cap_base, fp8, H, D, shift);
+    if (nd < 1 || !R || !qu || !qv || !k_new || !v_new || !base || !state_base || !status || !out)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: R rows (%d) or a null operand", nd);
+    if (M_base < 1 || (!base_rows && B > M_base)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: %d call rows over a base ring of %d rows need base_rows", B, M_base);
+    if (new_row_stride < (int64_t)H * MEM_D || new_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: key / value row stride below H * D");
+    if ((new_row_stride % 8) || (new_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) || !db1_aligned16(k_new) || !db1_aligned16(v_new) ||
+        !db1_aligned16(base) || !db1_aligned16(R) || !db1_aligned16(out) || (((uintptr_t)lse | (uintptr_t)state_base | (uintptr_t)base_rows | (uintptr_t)status) & 3))
+        DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_mem_ring: operands must be 16-byte aligned, strides multiples of 8 elements");
+    MemArgs a;
+    a.qu = (const bf16_t*)qu; a.qv = (const bf16_t*)qv; a.k = (const bf16_t*)k_new; a.v = (const bf16_t*)v_new; a.R = (const bf16_t*)R;
+    a.out = (bf16_t*)out; a.lse = lse; a.kv_rs = new_row_stride; a.kv_bs = new_batch_stride;
+    a.km = a.vm = nullptr; a.m_rs = a.m_bs = 0;
+    a.base = (const unsigned char*)base; a.state_base = state_base; a.base_rows = base_rows; a.status = status; a.M_base = M_base; a.cap_base = cap_base;
+    a.B = B; a.q = q; a.klen = mlen + q; a.mlen = mlen; a.H = H; a.shift = shift; a.nd = nd; a.scale = scale;
+    const dim3 grid((unsigned)((q + MEM_QB - 1) / MEM_QB), (unsigned)H, (unsigned)B);
+    if (fp8) {
+        static Db1PerDeviceOnce attr_once;
+        attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
+        relattn_mem_kernel<true, 2><<<grid, 256, MEM_LDS, (hipStream_t)stream>>>(a);
+    } else {
+        static Db1PerDeviceOnce attr_once;
+        attr_once.run([] { hipFuncSetAttribute((const void*)relattn_mem_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, MEM_LDS); });
+        relattn_mem_kernel<true, 1><<<grid, 256, MEM_LDS, (hipStream_t)stream>>>(a);
+    }
+    DB1_CHECK_LAUNCH("relattn_mem_ring");
     return DB1_OK;
 }

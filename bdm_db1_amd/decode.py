@@ -205,14 +205,26 @@ class RingPrefill:
     ``rows``: int32 [n_dst] on the device, distinct rows of the ring (None: all ``ring.B`` rows, in order); ``src``: int32 [n_dst], the call
     row every destination descends from (None: destination i from call row i) -- ``arange(n_dst) // W`` expands every prompt to W rows
     without repeating or re-projecting anything.  Shapes and dtypes are checked here, on the host (ValueError before any launch); what the
-    kernel skipped on the device (a row or a source out of range) is reported through ``ring.load_status`` (bits 0 / 2)."""
+    kernel skipped on the device (a row or a source out of range) is reported through ``ring.load_status`` (bits 0 / 2).
+    ``base`` (a RingMemory of the same model and kv_dtype, not ``ring`` itself; generation.PrefixCache owns one): the call's rows CONTINUE
+    rows of that ring instead of the zero memory -- call row b starts from the mem_len keys / values of ring row ``base_rows[b]`` (int32
+    [B_call] on the device, repeats allowed; None: the identity, which needs ``base.B`` >= the call's rows) at ``base``'s origin: the
+    attention is db1_relattn_mem_ring_fwd, the slot writer db1_ring_fork_rows, ``base`` is only read, and a base row or origin out of
+    range sets bit 3 of ``ring.load_status``."""
     is_ring_prefill = True
 
-    def __init__(self, ring: RingMemory, rows: torch.Tensor = None, src: torch.Tensor = None):
+    def __init__(self, ring: RingMemory, rows: torch.Tensor = None, src: torch.Tensor = None, base: RingMemory = None, base_rows: torch.Tensor = None):
         if not isinstance(ring, RingMemory):
             raise ValueError(f"RingPrefill: a RingMemory expected, got {type(ring).__name__}")
         dev = ring.state.device
-        for name, x in (("rows", rows), ("src", src)):
+        if base is None and base_rows is not None:
+            raise ValueError("RingPrefill: base_rows without a base ring")
+        if base is not None:
+            if not isinstance(base, RingMemory) or base is ring:
+                raise ValueError("RingPrefill: base must be a RingMemory other than the destination ring")
+            if base.model is not ring.model or base.kv_dtype != ring.kv_dtype or base.state.device != dev:
+                raise ValueError(f"RingPrefill: base must be a ring of the same model, device and kv_dtype ({ring.kv_dtype!r}; got {base.kv_dtype!r})")
+        for name, x in (("rows", rows), ("src", src), ("base_rows", base_rows)):
             if x is None:
                 continue
             if not torch.is_tensor(x) or x.dtype != torch.int32 or x.dim() != 1 or x.device != dev or not x.is_contiguous():
@@ -223,6 +235,7 @@ class RingPrefill:
         if src is not None and int(src.numel()) != n_dst:
             raise ValueError(f"RingPrefill: src holds {int(src.numel())} entries for {n_dst} destinations")
         self.ring, self.src, self.n_dst = ring, src, n_dst
+        self.base, self.base_rows = base, base_rows
         self.rows = rows if rows is not None else torch.arange(ring.B, dtype=torch.int32, device=dev)
 
     def check_batch(self, B: int):
@@ -231,6 +244,10 @@ class RingPrefill:
             raise ValueError(f"RingPrefill: {self.n_dst} destinations cannot be indexed by a call of {B} rows without a src map")
         if self.src is not None and int(B) < 1:
             raise ValueError("RingPrefill: an empty call")
+        if self.base_rows is not None and int(self.base_rows.numel()) != int(B):
+            raise ValueError(f"RingPrefill: base_rows holds {int(self.base_rows.numel())} entries for a call of {B} rows")
+        if self.base is not None and self.base_rows is None and int(B) > self.base.B:
+            raise ValueError(f"RingPrefill: a call of {B} rows over a base ring of {self.base.B} rows needs base_rows")
 
     def zero_kv(self):
         """per layer the keys / values of one position of the zero memory, [1, 1, 2, H, D]: what ``RingMemory.reset`` projects

@@ -392,8 +392,13 @@ def _text_window(model, cfg):
     return cfg if cfg.vocab_hi is not None else dataclasses.replace(cfg, vocab_hi=int(model.text_vocab_size))
 
 
-def _batch_size(prompt) -> int:
+def _batch_size(prompt, prefixed_ok: bool = False) -> int:
     kind = type(prompt).__name__
+    if isinstance(prompt, Prefixed):
+        if not prefixed_ok:
+            raise ValueError("a Prefixed prompt continues a PrefixCache row on the K/V ring: generate, beam_search, sample_best_of and the streams "
+                             "take it; rank_candidates and score_document do not")
+        return len(prompt.handles)
     if kind == "NLPTaskInput":
         seq = prompt.text_seq
         lens = getattr(prompt, "text_len", None)
@@ -485,8 +490,156 @@ def _prefill_ring(model, prompt, ring, rows=None, expand: Optional[int] = None):
     values go to ring rows ``rows`` (int32 device vector; None: all rows) relative to the ring's current origin -> logits [G, L, V].
     ``expand`` given: ring row r descends from prompt r // expand -- nothing is repeated or projected twice."""
     src = None if expand is None else torch.arange(ring.B if rows is None else int(rows.numel()), dtype=torch.int32, device=model.dev) // int(expand)
+    if isinstance(prompt, Prefixed):     # the suffix continues cache rows: ``src`` maps destinations to call rows, ``base_rows`` call rows to cache rows
+        base_rows = torch.tensor(prompt.cache.rows_of(prompt.handles), dtype=torch.int32).to(model.dev)
+        logits, _, _ = model([prompt.suffix], compute_loss=False, mems=RingPrefill(ring, rows, src, prompt.cache.ring, base_rows))
+        return logits
     logits, _, _ = model([prompt], compute_loss=False, mems=RingPrefill(ring, rows, src))
     return logits
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ prefix cache
+@dataclass(frozen=True)
+class PrefixHandle:
+    """one cached prefix: row ``row`` of its cache's ring, as ``put`` number ``serial`` wrote it under weight version ``version``"""
+    row: int
+    serial: int
+    version: int
+
+
+class PrefixCache:
+    """Prefill a shared prompt ONCE and continue it per request: a ``RingMemory`` of ``rows`` rows (``kv_cache`` "bf16" or "fp8") whose
+    origin stays 0, and a free list of its rows (plain Python).  ``put(prompt)`` prefills a batch of G prompts from the zero memory into G
+    free rows (the ring prefill, db1_ring_prefill_rows) and returns their handles; ``Prefixed(cache, handles, suffix)`` is then a prompt
+    for ``generate``, ``beam_search``, ``sample_best_of`` and the streams: only the suffix is embedded and projected, its attention reads
+    the prefix in the cache's slots (db1_relattn_mem_ring_fwd) and db1_ring_fork_rows forks (the cache row, the suffix) into the request's
+    own ring row -- the cache is only read, so any number of requests, at once or one after another, may share one handle.  Segment-level
+    recurrence makes this exact for the model: a position's keys and values depend on earlier positions only, so a cache row holds what a
+    list-form call with ``mems=`` would re-project.  ``release(handles)`` returns rows to the free list; a handle from before a weight
+    change (``model._wversion``), or a released one, raises RuntimeError when used."""
+
+    def __init__(self, model, rows: int, kv_cache: str = "bf16"):
+        if kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"PrefixCache: kv_cache must be 'bf16' or 'fp8' (got {kv_cache!r})")
+        if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or int(rows) < 1:
+            raise ValueError(f"PrefixCache: rows {rows!r} must be a positive integer")
+        if not getattr(model, "ring_prefill_supported", False):
+            raise ValueError("PrefixCache needs the ring prefill (model.ring_prefill_supported: bf16, use_decode, d_head 128, post-LN layers, mem_len > 0)")
+        self.model, self.rows, self.kv_cache = model, int(rows), kv_cache
+        self._free = list(range(self.rows))
+        self._live = {}                 # row -> the handle that holds it
+        self._serial = 0
+        self._ring = None               # (allocated by the first ``put``)
+
+    @property
+    def ring(self) -> RingMemory:
+        if self._ring is None:
+            self._ring = RingMemory(self.model, self.rows, kv_dtype=self.kv_cache)
+        return self._ring
+
+    @property
+    def free(self) -> int:
+        """the number of free rows"""
+        return len(self._free)
+
+    def _take(self, G: int) -> List[PrefixHandle]:
+        """G free rows (the lowest first) as new handles; RuntimeError when fewer are free (nothing is taken then)"""
+        if G > len(self._free):
+            raise RuntimeError(f"PrefixCache: {G} prompts for {len(self._free)} free rows (of {self.rows}): release some handles")
+        rows, self._free = self._free[:G], self._free[G:]
+        out = []
+        for r in rows:
+            self._serial += 1
+            out.append(PrefixHandle(row=r, serial=self._serial, version=int(self.model._wversion)))
+            self._live[r] = out[-1]
+        return out
+
+    def rows_of(self, handles) -> List[int]:
+        """the cache rows of ``handles`` (repeats allowed); RuntimeError for a released handle or one from before a weight change"""
+        out = []
+        for h in handles:
+            if not isinstance(h, PrefixHandle):
+                raise ValueError(f"PrefixCache: a handle returned by put() expected, got {type(h).__name__}")
+            if self._live.get(h.row) != h:
+                raise RuntimeError(f"PrefixCache: the handle of row {h.row} was released (or belongs to another cache)")
+            if h.version != int(self.model._wversion):
+                raise RuntimeError("PrefixCache: the weights changed after the prefix was cached: release the handle and put the prompt again")
+            out.append(h.row)
+        return out
+
+    def release(self, handles):
+        """the rows of ``handles`` become free again (each handle once); their contents stay until a later ``put`` overwrites them"""
+        handles = list(handles)
+        for h in handles:
+            if not isinstance(h, PrefixHandle) or self._live.get(h.row) != h:
+                raise RuntimeError("PrefixCache.release: a handle that is not live in this cache")
+        if len({h.row for h in handles}) != len(handles):
+            raise RuntimeError("PrefixCache.release: a handle given twice")
+        for h in handles:
+            del self._live[h.row]
+            self._free.append(h.row)
+        self._free.sort()
+
+    @torch.no_grad()
+    def put(self, prompt) -> List[PrefixHandle]:
+        """prefill ``prompt`` (ONE batch of G rows of one shape, as ``generate`` takes it) from the zero memory into G free rows -> their
+        handles, in row order of the batch.  The existing ring prefill, whatever ``model.use_ring_prefill`` says."""
+        G = _batch_size(prompt)
+        if not self.model.ring_prefill_supported:
+            raise ValueError("PrefixCache.put: the model no longer supports the ring prefill")
+        handles = self._take(G)
+        try:
+            ring = self.ring
+            with _eval_mode(self.model):
+                ring.load_status.zero_()
+                _prefill_ring(self.model, prompt, ring, torch.tensor([h.row for h in handles], dtype=torch.int32).to(self.model.dev))
+                if int(ring.load_status.cpu()) != 0:
+                    raise RuntimeError("db1_ring_prefill_rows: the prefill skipped a cache row")
+        except BaseException:
+            self.release(handles)
+            raise
+        return handles
+
+
+class Prefixed:
+    """A prompt that continues cached prefixes: row g is (the prefix behind ``handles[g]``, row g of ``suffix``).  ``suffix``: an
+    ``NLPTaskInput`` batch [G, Ls], Ls >= 1, embedded exactly as NLP text; ``handles``: G handles of ``cache`` -- repeats are the point."""
+
+    def __init__(self, cache: PrefixCache, handles, suffix):
+        if not isinstance(cache, PrefixCache):
+            raise ValueError(f"Prefixed: a PrefixCache expected, got {type(cache).__name__}")
+        if type(suffix).__name__ != "NLPTaskInput":
+            raise ValueError(f"Prefixed: the suffix must be an NLPTaskInput batch, got {type(suffix).__name__}")
+        G = _batch_size(suffix)
+        seq = suffix.text_seq
+        if int((seq if torch.is_tensor(seq) else np.asarray(seq)).shape[1]) < 1:
+            raise ValueError("Prefixed: the suffix must hold at least one token per row (Ls >= 1)")
+        handles = list(handles)
+        if len(handles) != G:
+            raise ValueError(f"Prefixed: {len(handles)} handles for a suffix batch of {G} rows")
+        cache.rows_of(handles)
+        self.cache, self.handles, self.suffix = cache, handles, suffix
+
+    @property
+    def suffix_len(self) -> int:
+        seq = self.suffix.text_seq
+        return int((seq if torch.is_tensor(seq) else np.asarray(seq)).shape[1])
+
+
+def _check_prompt(who: str, model, prompt, kv_cache: str, graphed: Optional[bool]):
+    """a ``Prefixed`` prompt needs the ring path of the cache's own model and K/V format: ValueError before anything is launched"""
+    if not isinstance(prompt, Prefixed):
+        return
+    if prompt.cache.model is not model:
+        raise ValueError(f"{who}: the Prefixed prompt's cache belongs to another model")
+    if graphed is False or not _ring_ok(model) or not getattr(model, "ring_prefill_supported", False):
+        raise ValueError(f"{who}: a Prefixed prompt needs the ring path (a bf16 model with use_decode, d_head 128, post-LN layers and mem_len > 0; "
+                         f"not graphed=False)")
+    if prompt.cache.kv_cache != kv_cache:
+        raise ValueError(f"{who}: kv_cache={kv_cache!r} over a PrefixCache of kv_cache={prompt.cache.kv_cache!r}")
+    if not model.ring_prefill_ok(prompt.suffix_len):
+        raise ValueError(f"{who}: a suffix of {prompt.suffix_len} tokens is not supported by the ring prefill")
+    prompt.cache.rows_of(prompt.handles)
 
 
 def _check_chain(model):
@@ -784,8 +937,8 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             ids = torch.zeros(st.M, 1, dtype=torch.long, device=model.dev)
         st.start(*start)
         # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
-        direct = ring and _use_ring_prefill(model)
-        if direct:      # (model.use_ring_prefill) the prompt's keys / values go straight into every ring row, origin 0
+        direct = ring and (_use_ring_prefill(model) or isinstance(prompt, Prefixed))
+        if direct:      # (model.use_ring_prefill, or a Prefixed prompt) the prompt's keys / values go straight into every ring row, origin 0
             gen.ring.state.zero_()
             gen.ring.load_status.zero_()
             logits, mems = _prefill_ring(model, prompt, gen.ring, None, st.expand), None
@@ -811,7 +964,7 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
         if ring:
             gen.check(replay)
             if direct and int(gen.ring.load_status.cpu()) != 0:
-                raise RuntimeError("db1_ring_prefill_rows: the prefill skipped a ring row")
+                raise RuntimeError("db1_ring_prefill_rows / db1_ring_fork_rows: the prefill skipped a ring row or read a cache row out of range")
         else:
             _check_chain(model)
         if stats is not None:
@@ -841,10 +994,13 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     and their log-probabilities; -1 / -inf where the step had fewer candidates and at every position after a row's last written token
     (where ``logprobs`` holds 0).  Greedy: ``top_ids[r, t, 0] == ids[r, t]``.  ``kv_cache`` "fp8" (ring path only; ValueError otherwise):
     the memory's keys / values are held as e4m3 with a power-of-two scale per (row, position, K or V, head) -- half the bytes per token
-    step and per slot, results within the e4m3 rounding of the keys / values; "bf16" (default): everything is what it is without it."""
+    step and per slot, results within the e4m3 rounding of the keys / values; "bf16" (default): everything is what it is without it.
+    ``prompt`` may also be a ``Prefixed`` (``PrefixCache``): its rows continue cached prefixes, only the suffix is projected; ring path
+    only, with the cache's own ``kv_cache`` (ValueError otherwise, before anything is launched)."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate")
-    M = _batch_size(prompt)
+    M = _batch_size(prompt, prefixed_ok=True)
+    _check_prompt("generate", model, prompt, kv_cache, graphed)
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")
@@ -913,6 +1069,35 @@ def question_prompts(vqa_batch) -> List[Tuple[object, np.ndarray]]:
     return [(_question_rows(vqa_batch, q, n, rows), rows) for n, rows in groups]
 
 
+def image_prefix(batch):
+    """the shared part of a ``VQATaskInput`` (or ``ICTaskInput``) batch's prompts, ``[prompt, image patches]`` with no text: what
+    ``PrefixCache.put`` caches once per image.  Text after an image is embedded exactly as NLP text, so this prefix continued by
+    ``question_suffixes``' rows (``Prefixed``) is the prompt ``question_prompts`` builds."""
+    if type(batch).__name__ not in ("ICTaskInput", "VQATaskInput"):
+        raise TypeError(f"image_prefix: ICTaskInput or VQATaskInput expected, got {type(batch).__name__}")
+    return caption_prompt(batch)
+
+
+def question_suffixes(vqa_batch) -> List[Tuple[object, np.ndarray]]:
+    """the questions of a ``VQATaskInput`` batch as ``NLPTaskInput`` suffix batches, one per distinct ``ques_len`` (ascending) ->
+    [(suffix, rows)], the grouping of ``question_prompts``; a question without tokens has no suffix and raises ValueError"""
+    from .data import NLPTaskInput
+    G = _batch_size(vqa_batch)
+    q, ql = _questions(vqa_batch)
+    if ql is None:
+        groups = [(int(q.shape[1]), np.arange(G, dtype=np.int64))]
+    else:
+        if ql.size != G:
+            raise ValueError(f"question_suffixes: {ql.size} question lengths for a batch of {G} rows")
+        if ql.min() < 0 or ql.max() > q.shape[1]:
+            raise ValueError(f"question_suffixes: question lengths must lie in [0, {q.shape[1]}]")
+        groups = [(int(n), np.nonzero(ql == n)[0].astype(np.int64)) for n in np.unique(ql)]
+    if groups[0][0] < 1:
+        raise ValueError("question_suffixes: a question without tokens cannot continue a prefix (Prefixed needs Ls >= 1)")
+    mk = lambda ids: NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids)
+    return [(mk(q.index_select(0, torch.as_tensor(rows, device=q.device))[:, :n].contiguous()), rows) for n, rows in groups]
+
+
 @torch.no_grad()
 def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
                 replay: bool = True, constraints: Optional[DecodingConstraints] = None,
@@ -934,7 +1119,8 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     mlen = _need_memory(model, "beam_search")
     if int(cfg.max_new_tokens) > mlen:
         raise ValueError(f"beam_search: max_new_tokens {cfg.max_new_tokens} exceeds the model's mem_len {mlen}")
-    G = _batch_size(prompt)
+    G = _batch_size(prompt, prefixed_ok=True)
+    _check_prompt("beam_search", model, prompt, kv_cache, graphed)
     W = int(cfg.num_beams)
     V, hi = _vocab_window(model, cfg)
     if cfg.eos_id is not None and int(cfg.eos_id) >= V:
@@ -999,7 +1185,8 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
     n, R = _check_best_of(cfg, n, num_return_sequences, length_penalty)
     cfg = dataclasses.replace(cfg, logprobs=True)
     _need_memory(model, "sample_best_of")
-    G = _batch_size(prompt)
+    G = _batch_size(prompt, prefixed_ok=True)
+    _check_prompt("sample_best_of", model, prompt, kv_cache, graphed)
     V, hi = _vocab_window(model, cfg)
     if not ops.select_tokens_supported(V, V, model.compute_dtype):
         raise ValueError(f"db1_select_tokens does not support a vocabulary of {V}")

@@ -1349,8 +1349,12 @@ class TransformerXL(nn.Module):
         shift = self._window(L, mlen)
         if not (L > 1 or (self.same_length and shift <= L - 1)):
             raise ValueError("attention mask hides nothing (transformer_xl.py:177,205-206)")
+        base = getattr(rp, "base", None)
+        if base is not None and (mlen >= base.cap or len(base.kv) != self.n_layer or base.model is not self or not
+                                 ops.relattn_mem_ring_supported(B, L, mlen, base.cap, base.kv_dtype == "fp8", self.n_head, self.d_head, shift, self.compute_dtype)):
+            raise ValueError("RingPrefill: the base ring does not belong to this model")
         self.check_decode_chain()
-        zkv = rp.zero_kv()
+        zkv = rp.zero_kv() if base is None else [None] * self.n_layer   # (with a base the rows continue ring rows of it, not the zero memory)
         R_in = self._sinusoid(L + mlen)
         x = h.view(B * L, d)
         self._win_on, self._R_all = False, None
@@ -1366,6 +1370,13 @@ class TransformerXL(nn.Module):
         qu, qv, av = self._new(B, L, H, D), self._new(B, L, H, D), self._new(B, L, H, D)
         ops.relattn_add_head_bias(qkv, self._bias("r_w_bias", i), self._bias("r_r_bias", i), qu, qv, B, L, L, H, D)
         qkv5 = qkv.view(B, L, 3, H, D)
+        if rp.base is not None:     # the memory is ring row base_rows[b] of the base ring's layer: read in its slots, forked with the new rows
+            base, ring = rp.base, rp.ring
+            k_new, v_new = qkv5[:, :, 1], qkv5[:, :, 2]
+            ops.relattn_mem_ring_fwd(qu, qv, k_new, v_new, base.kv[i], base.state, rp.base_rows, ring.load_status, R, av, None, B, L, mlen, H, D, shift,
+                                     1.0 / math.sqrt(D))
+            ops.ring_fork_rows(ring.kv[i], base.kv[i], base.state, rp.base_rows, k_new, v_new, ring.state, mlen, rp.rows, rp.src, ring.load_status)
+            return av
         k_new, v_new, k_mem, v_mem = qkv5[:, :, 1], qkv5[:, :, 2], zkv[:, :, 0], zkv[:, :, 1]
         ops.relattn_mem_kv_fwd(qu, qv, k_new, v_new, k_mem, v_mem, R, av, None, B, L, mlen, H, D, shift, 1.0 / math.sqrt(D))
         # right after the attention, while qkv is alive: the layer's last mem_len keys / values go to the new tenants' ring rows

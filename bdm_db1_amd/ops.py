@@ -1350,6 +1350,98 @@ def ring_prefill_rows(ring, k_new, v_new, k_mem, v_mem, state, mlen, rows, src, 
              P(src), n_dst, n_src, q, mlen, H, D, P(status), stream())
 
 
+def _ring_layer(who, name, ring, H, D):
+    """(fp8, M, cap) of a K/V ring's layer buffer: contiguous, 16-byte aligned, bf16 [M, cap, 2, H, D] or uint8 [M, cap, 264 H]"""
+    fp8 = ring.dtype == torch.uint8
+    slot = (264 * H,) if fp8 else (2, H, D)
+    if ring.dtype not in (torch.uint8, torch.bfloat16) or ring.dim() != 2 + len(slot) or tuple(ring.shape[2:]) != slot or not ring.is_contiguous() or \
+            ring.data_ptr() % 16:
+        raise ValueError(f"{who}: {name} must be a contiguous 16-byte aligned bf16 [M, cap, 2, {H}, {D}] or uint8 [M, cap, {264 * H}] tensor")
+    return fp8, int(ring.shape[0]), int(ring.shape[1])
+
+
+def relattn_mem_ring_supported(B, q, mlen, cap_base, fp8, H, D, shift, dtype) -> bool:
+    """db1_relattn_mem_ring_supported: what relattn_mem_kv_supported supports, with 1 <= mlen < cap_base and an even H on an fp8 ring"""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(lib.load().db1_relattn_mem_ring_supported(int(B), int(q), int(mlen), int(cap_base), int(bool(fp8)), int(H), int(D), int(shift), dt_code(dtype)))
+
+
+def relattn_mem_ring_fwd(qu, qv, k_new, v_new, base, state_base, base_rows, status, R, out, lse, B, q, mlen, H, D, shift, scale):
+    """relattn_mem_kv_fwd with the memory in the slots of a K/V ring (db1_relattn_mem_ring_fwd): key j < mlen of call row b is slot
+    (state_base + j) % cap of row ``base_rows[b]`` of ``base`` -- one layer of a ring, bf16 [M, cap, 2, H, D] or fp8 uint8 [M, cap, 264 H],
+    dequantised on the way -- bit for bit relattn_mem_kv_fwd over the unpacked, linearised memory.  ``state_base`` int32 [1] (read on the
+    device); ``base_rows`` int32 [B] or None (the identity; repeats are allowed); ``status`` int32 [1], |= 8 when a base row or the origin
+    was out of range (read as 0: do not trust the output then).  k_new, v_new, lse as relattn_mem_kv_fwd takes them."""
+    who = "relattn_mem_ring_fwd"
+    if any(t.dtype != torch.bfloat16 for t in (qu, qv, k_new, v_new, R, out)) or (lse is not None and lse.dtype != torch.float32):
+        raise lib.Db1Error(f"{who}: bf16 operands (float32 lse) only")     # (the entry point takes no dtype: refused here, nothing launched)
+    fp8, M_base, cap_base = _ring_layer(who, "base", base, H, D)
+    n_rs, n_bs = _kv_strides(who, "k_new", k_new, B, q, H, D, False)
+    if v_new.shape != k_new.shape or v_new.stride() != k_new.stride():
+        raise ValueError(f"{who}: the values must have the keys' shape and strides")
+    dev = base.device
+    for name, x, k in (("state_base", state_base, 1), ("status", status, 1)) + ((("base_rows", base_rows, B),) if base_rows is not None else ()):
+        _check_tensor(who, name, x, torch.int32, k, dev)
+    if base_rows is None and B > M_base:
+        raise ValueError(f"{who}: {B} call rows over a base ring of {M_base} rows need base_rows")
+    lib.call("db1_relattn_mem_ring_fwd", P(qu), P(qv), P(k_new), P(v_new), n_rs, n_bs, P(base), int(fp8), M_base, cap_base, P(state_base), P(base_rows),
+             P(status), P(R), R.shape[0], P(out), P(lse), B, q, mlen, H, D, shift, float(scale), _vp(0), 0, stream())
+
+
+def ring_fork_rows_supported(fp8, q, mlen, cap_base, cap, H, D) -> bool:
+    """db1_ring_fork_rows_supported: what db1_ring_prefill_rows supports at the destination's cap, with mlen < cap_base"""
+    return bool(lib.load().db1_ring_fork_rows_supported(int(bool(fp8)), int(q), int(mlen), int(cap_base), int(cap), int(H), int(D)))
+
+
+def ring_fork_rows(ring, base, state_base, base_rows, k_new, v_new, state, mlen, rows, src, status):
+    """ring_prefill_rows with a ring as the memory (db1_ring_fork_rows, one launch per layer): destination i takes row ``rows[i]`` of
+    ``ring`` from call row s = ``src[i]`` (None: i) over row ``base_rows[s]`` (None: s) of ``base``: position j of the last mlen rows of
+    cat(the base row's mlen slots from ``state_base``, the call's q new rows) goes to slot (state + j) % cap.  Base slots are copied byte
+    for byte (an fp8 slot is never requantised), new rows are copied (bf16) or quantised (fp8).  ``ring`` and ``base``: layer buffers of
+    one format and H (cap may differ) that do not overlap; the int32 vectors on the device; ``status`` |= 1 / 2 / 4 as ring_prefill_rows,
+    |= 8 for a base row or base origin out of range (skipped).  Raises ValueError on bad arguments before anything is launched."""
+    who = "ring_fork_rows"
+    if k_new.dim() != 4:
+        raise ValueError(f"{who}: k_new must be a [n_src, q, H, D] view")
+    n_src, q, H, D = (int(v) for v in k_new.shape)
+    dev, mlen = ring.device, int(mlen)
+    fp8, M, cap = _ring_layer(who, "the ring", ring, H, D)
+    fp8b, M_base, cap_base = _ring_layer(who, "base", base, H, D)
+    if fp8 != fp8b or base.device != dev:
+        raise ValueError(f"{who}: the base ring and the destination ring must have one format and one device")
+    lo, hi = ring.data_ptr(), ring.data_ptr() + ring.numel() * ring.element_size()
+    blo, bhi = base.data_ptr(), base.data_ptr() + base.numel() * base.element_size()
+    if lo < bhi and blo < hi:
+        raise ValueError(f"{who}: the base ring and the destination ring overlap")
+    if any(t.dtype != torch.bfloat16 or t.device != dev for t in (k_new, v_new)):
+        raise ValueError(f"{who}: the keys / values must be bf16 tensors on {dev}")
+    if not ring_fork_rows_supported(fp8, q, mlen, cap_base, cap, H, D):
+        raise ValueError(f"{who}: needs d_head 128, an even number of heads on fp8 rings and 1 <= mlen ({mlen}) < cap ({cap}) and cap_base ({cap_base}) "
+                         f"(H={H}, D={D}, q={q})")
+    n_rs, n_bs = _kv_strides(who, "k_new", k_new, n_src, q, H, D, False)
+    if v_new.shape != k_new.shape or v_new.stride() != k_new.stride():
+        raise ValueError(f"{who}: the values must have the keys' shape and strides")
+    if n_rs % 8 or n_bs % 8 or k_new.data_ptr() % 16 or v_new.data_ptr() % 16:
+        raise ValueError(f"{who}: the keys / values must be 16-byte aligned with strides that are multiples of 8 elements")
+    if rows.dim() != 1:
+        raise ValueError(f"{who}: rows must be an int32 vector")
+    n_dst = int(rows.numel())
+    if n_dst > M:
+        raise ValueError(f"{who}: {n_dst} destinations for a ring of {M} rows")
+    for name, x, k in (("state", state, 1), ("state_base", state_base, 1), ("rows", rows, n_dst), ("status", status, 1)) + \
+            ((("src", src, n_dst),) if src is not None else ()) + ((("base_rows", base_rows, n_src),) if base_rows is not None else ()):
+        _check_tensor(who, name, x, torch.int32, k, dev)
+    if src is None and n_dst > n_src:
+        raise ValueError(f"{who}: {n_dst} destinations from {n_src} sources need a src map")
+    if base_rows is None and n_src > M_base:
+        raise ValueError(f"{who}: {n_src} call rows over a base ring of {M_base} rows need base_rows")
+    if n_dst == 0:
+        return
+    lib.call("db1_ring_fork_rows", P(ring), int(fp8), M, cap, P(base), M_base, cap_base, P(state_base), P(base_rows), P(k_new), P(v_new), n_rs, n_bs,
+             P(state), P(rows), P(src), n_dst, n_src, q, mlen, H, D, P(status), stream())
+
+
 _tickets = {}
 
 

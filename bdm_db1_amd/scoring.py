@@ -217,6 +217,8 @@ def score_document(model, tokens, config: Optional[ScoreConfig] = None, segment_
     ``status`` is the OR over the segments; ``stats = dict(segments=S, sweeps=S)``; ``mems`` is the final memory (pass it back to go on).
     ``fused``: None leaves ``model.use_mem_attn`` as it is, True / False sets it for this call (True on a model the fused kernel cannot serve
     raises ValueError before anything is launched)."""
+    if type(tokens).__name__ == "Prefixed":
+        raise ValueError("score_document: a Prefixed prompt is not supported (scoring runs through the list-form memory; pass ``mems=``)")
     tok = np.asarray(tokens.cpu() if torch.is_tensor(tokens) else tokens)
     if tok.dtype == object or tok.dtype.kind not in "iu" or tok.ndim != 2:
         raise ValueError("score_document: tokens must be an integer [B, T] array (rows of one length)")
@@ -321,6 +323,8 @@ def rank_candidates(model, prompt, candidates, cand_len=None, config: Optional[S
     ones: the attention is causal); ``scores[g, k] = sum_{i < len} logprob[g, k, i] / len^length_penalty``; ``order[g]`` sorts ``scores[g]``
     descending, the lower k first on ties.  Tokens older than ``mem_len`` fall out of the memory, as in generation.  ``stats`` (a dict) receives
     ``model_calls`` (1 when Lc == 1, else 2)."""
+    if type(prompt).__name__ == "Prefixed":
+        _batch_size(prompt)     # (raises: a Prefixed prompt lives on the K/V ring, the candidates run through the list-form memory)
     cfg = _check_window(model, config or ScoreConfig())
     _need_memory(model, "rank_candidates")
     G = _batch_size(prompt)

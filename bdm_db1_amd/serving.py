@@ -35,7 +35,7 @@ import torch
 
 from . import ops
 from .generation import (_PATCH_FIELDS, _PER_ROW_FIELDS, DecodeKey, DecodingConstraints, GenerationConfig, SamplingParams, _batch_size, _constrained,
-                         _need_memory, _prefill, _prefill_ring, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _use_ring_prefill,
+                         _check_prompt, _need_memory, _prefill, _prefill_ring, Prefixed, _ring_generator, _ring_ok, _SamplingState, _take, _text_window, _use_ring_prefill,
                          _vocab_window, _with_kv_cache, _work, caption_prompt, question_prompts)
 
 
@@ -69,6 +69,8 @@ _SEQ_FIELDS = ("text_seq", "prompt_seq", "img_seq")            # what makes a pr
 
 
 def _shape_key(prompt) -> tuple:
+    if isinstance(prompt, Prefixed):     # requests over one cache with one suffix length share one continuation call
+        return ("Prefixed", id(prompt.cache), prompt.suffix_len)
     key = [type(prompt).__name__]
     for f in _SEQ_FIELDS:
         v = getattr(prompt, f, None)
@@ -79,7 +81,7 @@ def _shape_key(prompt) -> tuple:
 
 
 def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_request: bool = False,
-              window: Optional[Tuple[int, int]] = None, caps: Optional[Tuple[int, int]] = None) -> Iterator[Request]:
+              window: Optional[Tuple[int, int]] = None, caps: Optional[Tuple[int, int]] = None, check_prefixed=None) -> Iterator[Request]:
     """the rows of ``items`` (prompt | (prompt, max_new_tokens) | _Item; ``per_request``: also (prompt, max_new_tokens or None,
     SamplingParams or None); ``caps`` = (max_bad_token_ids, max_logit_bias), the per-request-constraints flag: also (prompt,
     max_new_tokens or None, SamplingParams or None, DecodingConstraints or None)) as Requests, numbered in order; raises ValueError for a
@@ -128,7 +130,9 @@ def _requests(items: Iterable, cfg: GenerationConfig, min_new: int = 0, per_requ
             raise ValueError(f"generate_stream: a request's max_new_tokens {limit} must lie in [1, config.max_new_tokens = {cfg.max_new_tokens}]")
         if limit < need:
             raise ValueError(f"generate_stream: min_new_tokens {need} exceeds a request's max_new_tokens {limit}")
-        G = _batch_size(prompt)
+        G = _batch_size(prompt, prefixed_ok=True)
+        if isinstance(prompt, Prefixed) and check_prefixed is not None:     # (``generation._check_prompt`` for the stream's model and kv_cache)
+            check_prefixed(prompt)
         key = _shape_key(prompt)
         if indices is None:
             indices = range(nxt, nxt + G)
@@ -150,6 +154,8 @@ def _fits(cons: DecodingConstraints, caps: Tuple[int, int], whose: str):
 def _gather(reqs: List[Request]):
     """ONE prompt batch holding the rows of ``reqs`` (one shape key), in order"""
     first = reqs[0].prompt
+    if isinstance(first, Prefixed):      # the suffix rows gathered like any prompt's, every row with its own handle
+        return Prefixed(first.cache, [r.prompt.handles[r.row] for r in reqs], _gather([dataclasses.replace(r, prompt=r.prompt.suffix) for r in reqs]))
     if all(r.prompt is first for r in reqs) and [r.row for r in reqs] == list(range(_batch_size(first))):
         return first
     runs = []    # (consecutive requests of one batch are taken together)
@@ -361,7 +367,10 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
     tables' widths, the most banned ids / biases ANY request (or the stream's object) may hold.  The flag is needed up front for the
     reason ``per_request`` is and joins the cache key with the two capacities; ``stats["stopped"]`` is then always present.  False: nothing
     changes, and a request that carries constraints raises ValueError.  ``kv_cache`` "fp8": the slots' ring holds e4m3 keys / values, as
-    ``generate`` describes it (admissions quantise the prefill's keys / values on their way in); it joins the cache key."""
+    ``generate`` describes it (admissions quantise the prefill's keys / values on their way in); it joins the cache key.  A request's prompt
+    may be a ``generation.Prefixed`` (rows that continue prefixes held in a ``PrefixCache`` of this model and ``kv_cache``; ValueError
+    otherwise): waiting requests over one cache with one suffix length share one continuation call into their slots
+    (db1_relattn_mem_ring_fwd, db1_ring_fork_rows), mix with plain requests, and ``stats["prefixed"]`` counts them."""
     cfg = config or GenerationConfig()
     _need_memory(model, "generate_stream")
     if not _ring_ok(model):
@@ -384,10 +393,11 @@ def generate_stream(model, requests: Iterable, config: Optional[GenerationConfig
         if constraints is not None:
             _fits(constraints, caps, "the stream's")
         key = dataclasses.replace(key, caps=caps)
+    chk = lambda p: _check_prompt("generate_stream", model, p, kv_cache, None)      # (a Prefixed request: its cache's model and K/V format)
     if isinstance(requests, (list, tuple)):
-        for _ in _requests(requests, cfg, min_new, per_request, (V, hi), caps):     # (a list can be checked as a whole before the first launch)
+        for _ in _requests(requests, cfg, min_new, per_request, (V, hi), caps, chk):     # (a list can be checked as a whole before the first launch)
             pass
-    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi), caps), key, stream_ids, stats, replay)
+    return _stream(model, _requests(requests, cfg, min_new, per_request, (V, hi), caps, chk), key, stream_ids, stats, replay)
 
 
 def _capacities(max_bad_token_ids, max_logit_bias) -> Tuple[int, int]:
@@ -401,7 +411,7 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
     slots, cfg, V, hi, per, caps = key.rows, key.cfg, key.V, key.hi, key.per_request, key.caps
     inherit = SamplingParams()
     sched = SlotScheduler(slots, reqs)
-    counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0)
+    counts = dict(replays=0, prefill_calls=0, admitted=0, occupancy=0.0, no_candidate=0, prefixed=0)
     if caps is not None or (key.constraints is not None and key.constraints.stop_sequences):      # (the key set is what it was without stop sequences)
         counts["stopped"] = 0
     live_steps = 0
@@ -431,7 +441,9 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
                     rows = [s for s, _ in members]
                     rs = [r for _, r in members]
                     # one prefill for the group; its last position picks token 0 of every request straight into its slot, its memory moves in
-                    direct = _use_ring_prefill(model)
+                    prefixed = isinstance(rs[0].prompt, Prefixed)     # (the group continues rows of a PrefixCache: one call over its suffixes)
+                    direct = prefixed or _use_ring_prefill(model)
+                    counts["prefixed"] += len(rs) if prefixed else 0
                     if not direct:
                         logits, mems = _prefill(model, _gather(rs), len(rs))
                     recs = np.stack([ops.pack_slot_params(**(r.params or inherit).resolve(cfg, V, hi)) for r in rs]) if per else None
@@ -479,7 +491,8 @@ def _stream(model, reqs, key: DecodeKey, stream_ids, stats, replay):
                 if finish:     # nothing waits (admit found no request for the free slots) and every slot is vacant
                     gen.check(replay)
                     if int(gen.ring.load_status.cpu()) != 0:
-                        raise RuntimeError("db1_ring_load_rows / db1_ring_prefill_rows: a request was given a row outside the ring")
+                        raise RuntimeError("db1_ring_load_rows / db1_ring_prefill_rows / db1_ring_fork_rows: a request was given a row outside the "
+                                           "ring, or a cache row out of range")
             report()
             for r in results:
                 yield r
@@ -530,7 +543,8 @@ def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] 
     or None, SamplingParams)``, the params of every question of the batch; ``per_request_constraints=True``: with a fourth element, the
     ``DecodingConstraints`` of every question of the batch) whose questions may differ in length (``question_prompts``),
     tokens in the text vocabulary unless ``cfg`` (or a request's own params) says otherwise; every question is one request, and the
-    results' indices number the batches' rows in their original order"""
+    results' indices number the batches' rows in their original order.  An item's batch may also be a ``Prefixed`` prompt (the questions of
+    ``question_suffixes`` over handles of ``PrefixCache.put(image_prefix(batch))``): its rows are requests like any other"""
     cfg = _text_window(model, cfg or GenerationConfig())
 
     def items():
@@ -540,6 +554,10 @@ def answer_stream(model, vqa_batches: Iterable, cfg: Optional[GenerationConfig] 
             if len(rest) > 2:
                 raise ValueError("answer_stream: a request is a batch, (batch, max_new_tokens), (batch, max_new_tokens, SamplingParams) or "
                                  "(batch, max_new_tokens, SamplingParams, DecodingConstraints)")
+            if isinstance(b, Prefixed):      # questions that continue cached image prefixes (image_prefix / question_suffixes): as they are
+                yield _Item(b, [base + r for r in range(len(b.handles))], limit, *rest)
+                base += len(b.handles)
+                continue
             for prompt, rows in question_prompts(b):
                 yield _Item(prompt, [base + int(r) for r in rows], limit, *rest)
             base += _batch_size(b)

@@ -313,6 +313,27 @@ int db1_relattn_mem_kv_fwd(const void* qu, const void* qv, const void* k_new, co
                            int64_t new_batch_stride, const void* k_mem, const void* v_mem, int64_t mem_row_stride, int64_t mem_batch_stride,
                            const void* R, int nd, void* out, float* lse, int B, int q, int mlen, int H, int D, int shift, float scale,
                            void* ws, int64_t ws_bytes, void* stream);
+/* db1_relattn_mem_kv_fwd with the memory in the SLOTS OF A K/V RING (a prefix cache's row continued by a call; tests/ring_fork_rule.py restates
+ * the rule in NumPy).  `base` is the base ring's layer buffer, [M_base, cap_base, 2, H, D] bf16 (fp8 == 0) or [M_base, cap_base, 264 H] bytes
+ * (fp8 != 0, the fp8 K/V ring's slot); state_base[0], its origin, is read on the device; base_rows (int32 [B]; NULL: the identity, B <=
+ * M_base) names the ring row call row b continues -- repeats are allowed, call rows may share one memory row.
+ * Logical key j < mlen of call row b is slot (state_base[0] + j) % cap_base of ring row base_rows[b]: on a bf16 ring the slot's [2, H, D] pair
+ * as it is, on an fp8 ring payload * scale per (K | V, head) block (ops.kv8_unpack's value, exact in bf16).  Key j >= mlen is row j - mlen of
+ * the call's own k_new / v_new.  Everything else is db1_relattn_mem_fwd's rule at klen = mlen + q, and the result is bit for bit that of
+ * db1_relattn_mem_kv_fwd over the unpacked, linearised memory (the fp8 kernel's caveat: dequantised values that are subnormal in bf16 are not
+ * covered; a NaN byte yields NaN, not particular NaN bits).  No workspace (_workspace_bytes is 0).
+ * Guard (a launch cannot validate device data): a base_rows[b] outside [0, M_base) is read as row 0, an origin outside [0, cap_base) as 0 --
+ * every read stays in bounds --, one thread ORs bit 3 (value 8) into *status (int32 [1]), and the output of those call rows is what the rule
+ * gives for the clamped values: the bit says not to trust it.
+ * Supported: what db1_relattn_mem_kv_supported supports, with 1 <= mlen < cap_base and an even H on an fp8 ring (DB1_ERR_UNSUPPORTED
+ * otherwise); no NULL operand but lse and base_rows, the new rows' stride >= H*D, nd >= 1, M_base >= 1 (DB1_ERR_BAD_SHAPE); alignment as
+ * db1_relattn_mem_kv_fwd, the int32 vectors 4-byte aligned (DB1_ERR_BAD_ALIGN).  Refused before anything is launched. */
+int db1_relattn_mem_ring_supported(int B, int q, int mlen, int cap_base, int fp8, int H, int D, int shift, int dt);
+int64_t db1_relattn_mem_ring_workspace_bytes(int B, int q, int mlen, int H);   /* 0 */
+int db1_relattn_mem_ring_fwd(const void* qu, const void* qv, const void* k_new, const void* v_new, int64_t new_row_stride,
+                             int64_t new_batch_stride, const void* base, int fp8, int M_base, int cap_base, const int32_t* state_base,
+                             const int32_t* base_rows, int32_t* status, const void* R, int nd, void* out, float* lse, int B, int q, int mlen,
+                             int H, int D, int shift, float scale, void* ws, int64_t ws_bytes, void* stream);
 
 /* The same attention over a RING of cached keys / values (hipGraph-friendly inference: nothing is concatenated or copied per call):
  * kv_ring [B, cap, 2, H, D] bf16, cap >= mlen + q; logical key j < mlen is ring row (ring_state[0] + j) % cap; the q new keys / values come
@@ -770,6 +791,23 @@ int db1_ring_prefill_rows(void* ring, int fp8, int M, int cap, const void* k_new
                           int64_t new_batch_stride, const void* k_mem, const void* v_mem, int64_t mem_row_stride, int64_t mem_batch_stride,
                           const int32_t* state, const int32_t* rows, const int32_t* src, int n_dst, int n_src, int q, int mlen, int H, int D,
                           int32_t* status, void* stream);
+/* Fork ring rows (tests/ring_fork_rule.py): db1_ring_prefill_rows with a RING as the memory.  `base` [M_base, cap_base, slot], state_base and
+ * base_rows (int32 [n_src]; NULL: the identity, n_src <= M_base) are db1_relattn_mem_ring_fwd's; both rings have the same format (fp8) and
+ * H, cap may differ.  Destination i takes ring row rows[i] of `ring` from call row s = src[i] (src NULL: i) over base row r = base_rows[s]:
+ * logical position j in [0, mlen) is row c = j + q of cat(memory of r (mlen rows), new rows of s (q rows)).  For c < mlen the SLOT BYTES of
+ * base slot (state_base[0] + c) % cap_base are copied as they are -- an fp8 slot keeps its payload and scales, a fork never requantises --,
+ * otherwise it is new row c - mlen, copied (bf16) or quantised by the fp8 K/V ring's rule (fp8).  The position goes to slot
+ * (state[0] + j) % cap of ring row rows[i].  *status |=: bits 0 / 1 / 2 as db1_ring_prefill_rows, bit 3 (value 8) for a base row outside
+ * [0, M_base) or a base origin outside [0, cap_base) (that destination is skipped).  No other byte of either ring changes; the base ring is
+ * never written.  ONE launch.
+ * DB1_ERR_UNSUPPORTED: what db1_ring_prefill_rows refuses, or mlen >= cap_base; DB1_ERR_BAD_SHAPE: overlapping base and destination
+ * buffers, a NULL buffer (src and base_rows may be NULL), n_dst > M, a row stride below H*D; DB1_ERR_BAD_ALIGN: as db1_ring_prefill_rows.
+ * n_dst == 0 is a no-op. */
+int db1_ring_fork_rows_supported(int fp8, int q, int mlen, int cap_base, int cap, int H, int D);
+int db1_ring_fork_rows(void* ring, int fp8, int M, int cap, const void* base, int M_base, int cap_base, const int32_t* state_base,
+                       const int32_t* base_rows, const void* k_new, const void* v_new, int64_t new_row_stride, int64_t new_batch_stride,
+                       const int32_t* state, const int32_t* rows, const int32_t* src, int n_dst, int n_src, int q, int mlen, int H, int D,
+                       int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ decoding constraints (tests/constraint_rule.py restates the rule in
  * NumPy).  db1_constrain_logits edits the step's logits [M, ld] (fp32 / bf16; columns >= V are padding) IN PLACE, before

@@ -32,6 +32,13 @@ limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS);
     python tools/bench_generate.py --ring-prefill [any of the forms above]   (model.use_ring_prefill = True: the prompt prefills go straight
                                                                             into the K/V ring; every line carries "ring_prefill": true)
 
+With --stream --shared-prefix K: 64 images x K questions of 10 tokens as 64 K requests over 64 slots, the whole VQA prompt per request
+against one ``PrefixCache.put`` per image and a ``Prefixed`` question per request (generation.PrefixCache); totals, admission times, the
+puts' time and the slot graph's replay time, one JSON line.
+
+    python tools/bench_generate.py --stream --shared-prefix 4 [images [slots]]
+    python tools/bench_generate.py --ring-prefill --stream --shared-prefix 4 [images [slots]]   (the unshared form through the ring prefill)
+
 With --stream --per-request: the stream workload above with every second request greedy and the others at top-p 0.9
 (``caption_stream(..., per_request=True)``, a ``SamplingParams`` on the sampled requests: the graph ends in db1_select_tokens_slots_per)
 next to the shared-config (greedy) stream of the same requests; one JSON line with the totals (``*_total_ms``: the best of 3 timed passes
@@ -388,6 +395,87 @@ def stream_main(n_req=256, slots=64):
     print(json.dumps(rec), flush=True)
 
 
+def stream_shared_prefix_main(K, n_img=64, slots=64, q_len=10):
+    """n_img images x K questions of q_len tokens as n_img * K stream requests over ``slots`` slots (per-request limits as --stream draws
+    them), in two forms in ONE process: every request the whole VQA prompt [prompt, patches, question] (``unshared``; with --ring-prefill
+    through the ring prefill), and every image put into a PrefixCache once, every request a ``Prefixed`` question (``shared``; the time of
+    the puts is reported and counted).  Admission time = total - replays * the slot graph's replay time, as --stream reports it."""
+    from bdm_db1_amd import PrefixCache, Prefixed, generate_stream
+    from bdm_db1_amd.data import VQATaskInput
+    from bdm_db1_amd.serving import _SlotState
+    from bdm_db1_amd.generation import DecodeKey, _ring_generator, _text_window, _vocab_window
+    n_req = n_img * K
+    limits = np.random.default_rng(2024).integers(5, N_NEW + 1, n_req)
+    cfg = _text_window(model, GenerationConfig(max_new_tokens=N_NEW))
+    imgs = batch(n_img)
+    ques = torch.from_numpy(np.random.default_rng(7).integers(1, 32000, (n_img, K, q_len))).to(dev)
+    text = lambda ids: NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=ids, text_len=None)
+    prefixes = ICTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=imgs.prompt_seq, img_seq=imgs.img_seq,
+                           text_seq=torch.zeros(n_img, 0, dtype=torch.long))
+    # request r = question r % K of image r // K: the K questions of an image arrive together
+    unshared = [(VQATaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, prompt_seq=imgs.prompt_seq[r // K:r // K + 1],
+                              img_seq=imgs.img_seq[r // K:r // K + 1], text_seq=ques[r // K, r % K][None]), int(limits[r])) for r in range(n_req)]
+    rec = {"images": n_img, "questions_per_image": K, "question_tokens": q_len, "requests": n_req, "slots": slots,
+           "ring_prefill": bool(model.use_ring_prefill), "mem_attn": bool(model.use_mem_attn)}
+
+    def timed(fn):
+        fn()                                   # capture + warm-up
+        ts = []
+        for _ in range(REPS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return min(ts)
+
+    stats = {}
+
+    def run(reqs):
+        for _ in generate_stream(model, reqs, cfg, slots=slots, stats=stats):
+            pass
+    rec["unshared_total_ms"] = round(timed(lambda: run(unshared)), 2)
+    rec.update(unshared_replays=stats["replays"], unshared_prefill_calls=stats["prefill_calls"])
+    cache = PrefixCache(model, n_img)
+    put_ms = []
+
+    def shared():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        handles = cache.put(prefixes)                                 # (all images in one batch, as the unshared admissions batch theirs)
+        torch.cuda.synchronize()
+        put_ms.append((time.perf_counter() - t0) * 1e3)
+        run([(Prefixed(cache, [handles[r // K]], text(ques[r // K, r % K][None])), int(limits[r])) for r in range(n_req)])
+        cache.release(handles)
+    rec["shared_total_ms"] = round(timed(shared), 2)
+    rec.update(shared_put_ms=round(min(put_ms[1:]), 2), shared_replays=stats["replays"], shared_prefill_calls=stats["prefill_calls"],
+               shared_prefixed=stats["prefixed"])
+    V, hi = _vocab_window(model, cfg)
+    sg = _ring_generator(model, _SlotState, DecodeKey(rows=slots, cfg=cfg, V=V, hi=hi))
+    st = sg.state
+
+    def live():
+        st.finished.zero_()
+        st.t.zero_()
+        st.limit.fill_(N_NEW)
+    live()
+    for _ in range(3):
+        sg.step(sg.step.ids)
+    live()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(20):
+        sg.step(sg.step.ids)
+    torch.cuda.synchronize()
+    rec["slot_graph_replay_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 4)
+    sg.step.check(synchronize=True)
+    st.start()
+    rec["unshared_admission_ms"] = round(rec["unshared_total_ms"] - rec["unshared_replays"] * rec["slot_graph_replay_ms"], 2)
+    rec["shared_admission_ms"] = round(rec["shared_total_ms"] - rec["shared_replays"] * rec["slot_graph_replay_ms"], 2)
+    rec["admission_ratio_shared_over_unshared"] = round(rec["shared_admission_ms"] / rec["unshared_admission_ms"], 4)
+    print(json.dumps(rec), flush=True)
+
+
 def slot_select_kernels_us(M, max_new=4096):
     """db1_select_tokens_slots and db1_select_tokens_slots_per alone on random bf16 logits [M, V] over the text window, every slot live (the
     counters are rewound before every measurement: a launch advances them)"""
@@ -660,6 +748,10 @@ if "--logprobs" in args:
 if "--best-of" in args:
     i = args.index("--best-of")
     best_of_main(int(args[i + 1]), [int(a) for a in args[:i] + args[i + 2:]] or [16])
+    sys.exit(0)
+if "--stream" in args and "--shared-prefix" in args:
+    i = args.index("--shared-prefix")
+    stream_shared_prefix_main(int(args[i + 1]), *[int(a) for a in args[:i] + args[i + 2:] if a != "--stream"][:2])
     sys.exit(0)
 if "--stream" in args:
     rest = [int(a) for a in args if a not in ("--stream", "--per-request", "--per-request-constraints")]
