@@ -9,6 +9,7 @@
 // the MFMA like in the tile kernels, so a lane ends with 4 consecutive n of row m = lane & 15 and reuses store_frag.
 #include "gemm_tile.h"
 #include "ln_row.h"
+#include "kv8_format.h"
 
 struct GemmSkinnyArgs {
     const bf16_t* x; const bf16_t* w; void* y; const void* bias;
@@ -200,7 +201,37 @@ __device__ __forceinline__ void skinny_ln_rows(const SkinnyFusedArgs& p, int wav
     }
 }
 
-template <typename TBIAS, typename TP, int MT, bool GEGLU, int PRO>
+// The W piece of one 64-wide k-step as a lane holds it between its request and its MFMAs.  bf16 weights: the two bf16x8 operands themselves.
+// fp8 decode weights (W8; include/db1_hip.h, "fp8 decode weights"): the 16 payload bytes of the same 16 elements -- ONE non-temporal 16-byte
+// load at row * K + ks * 64 + g * 16 -- and the fp32 scale of block ks >> 1 of the row; kv8_widen8_scaled turns the two halves into the same two
+// operands when they are used (payload * scale is exact in bf16), so everything after the load is the bf16 kernel's.
+template <bool W8> struct SkinnyWPiece;
+template <> struct SkinnyWPiece<false> {
+    bf16x8_t b0, b1;
+    __device__ __forceinline__ void load(const void* wrow, const float*, int ks) {
+        b0 = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const bf16_t*>(wrow) + ks * 64));
+        b1 = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(reinterpret_cast<const bf16_t*>(wrow) + ks * 64 + 8));
+    }
+    __device__ __forceinline__ void get(bool ok, bf16x8_t& w0, bf16x8_t& w1) const {
+        const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        w0 = ok ? b0 : zero; w1 = ok ? b1 : zero;
+    }
+};
+template <> struct SkinnyWPiece<true> {
+    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+    u32x4 q; float s;
+    __device__ __forceinline__ void load(const void* wrow, const float* srow, int ks) {
+        q = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(wrow) + ks * 64));
+        s = srow[ks >> 1];
+    }
+    __device__ __forceinline__ void get(bool ok, bf16x8_t& w0, bf16x8_t& w1) const {
+        const uint4 lo = kv8_widen8_scaled(make_uint2(q[0], q[1]), s), hi = kv8_widen8_scaled(make_uint2(q[2], q[3]), s);
+        const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
+        w0 = ok ? __builtin_bit_cast(bf16x8_t, lo) : zero; w1 = ok ? __builtin_bit_cast(bf16x8_t, hi) : zero;
+    }
+};
+
+template <typename TBIAS, typename TP, int MT, bool GEGLU, int PRO, bool W8 = false>
 __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs p) {
     __shared__ f32x4 red[3][MT][64];
     __shared__ unsigned ticket_s;
@@ -210,7 +241,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
     const int wr = GEGLU ? (r < 8 ? nb * 8 + r : p.N + nb * 8 + r - 8) : nb * 16 + r;       // this lane's row of W
     const int kps = p.K / 64 / p.S, per = (kps + 3) / 4;
     const int ks0 = sp * kps + wave * per, ks1 = ks0 + per < (sp + 1) * kps ? ks0 + per : (sp + 1) * kps;
-    const bf16_t* wrow = p.w + (int64_t)wr * p.ldw + g * 16;
+    // (W8: p.w is the packed buffer -- rows of K payload bytes, then the [rows][K / 128] fp32 scales; ldw == K)
+    const void* wrow = W8 ? (const void*)(reinterpret_cast<const unsigned char*>(p.w) + (int64_t)wr * p.ldw + g * 16) : (const void*)(p.w + (int64_t)wr * p.ldw + g * 16);
+    const float* srow = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(p.w) + (int64_t)(GEGLU ? 2 * p.N : p.N) * p.K) + (int64_t)wr * (p.K / 128);
     const bf16_t* xrow[MT];
 #pragma unroll
     for (int t = 0; t < MT; t++) xrow[t] = p.x + (int64_t)(t * 16 + r < p.M ? t * 16 + r : 0) * p.ldx + g * 16;
@@ -226,7 +259,6 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
     f32x4 acc[MT];
 #pragma unroll
     for (int t = 0; t < MT; t++) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
     constexpr int KB = MT == 1 ? 8 : (MT == 2 ? 4 : 2);
     if constexpr (PRO < 0) {
         // The input rows (M <= 2) are the merge of the decode attention's chunk partials
@@ -255,13 +287,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        bf16x8_t b0[KB], b1[KB];
+        SkinnyWPiece<W8> b[KB];
 #pragma unroll
-        for (int u = 0; u < KB; u++) {
-            const int ks = ks0 + u < ks1 ? ks0 + u : ks1 - 1;
-            b0[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64));
-            b1[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64 + 8));
-        }
+        for (int u = 0; u < KB; u++) b[u].load(wrow, srow, ks0 + u < ks1 ? ks0 + u : ks1 - 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int m = 0; m < MR; m++) {
@@ -289,7 +317,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
             const bool ok = ks0 + u < ks1;
             const int ks = ok ? ks0 + u : ks1 - 1;
             const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(xl + ks * 64), a1 = *reinterpret_cast<const bf16x8_t*>(xl + ks * 64 + 8);
-            const bf16x8_t w0 = ok ? b0[u] : zero, w1 = ok ? b1[u] : zero;
+            bf16x8_t w0, w1;
+            b[u].get(ok, w0, w1);
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, a0, acc[0], 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, a1, acc[0], 0, 0, 0);
         }
@@ -324,13 +353,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
                 for (int j = 0; j < 8; j++) { gv.v[j] = ldf((const TP*)p.pre_gamma + col + j); bvv.v[j] = ldf((const TP*)p.pre_beta + col + j); }
             }
             __builtin_amdgcn_sched_barrier(0);
-            bf16x8_t b0[KB], b1[KB];
+            SkinnyWPiece<W8> b[KB];
 #pragma unroll
-            for (int u = 0; u < KB; u++) {
-                const int ks = ks0 + u < ks1 ? ks0 + u : ks1 - 1;
-                b0[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64));
-                b1[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64 + 8));
-            }
+            for (int u = 0; u < KB; u++) b[u].load(wrow, srow, ks0 + u < ks1 ? ks0 + u : ks1 - 1);
             __builtin_amdgcn_sched_barrier(0);
             float part[MR];
 #pragma unroll
@@ -380,20 +405,18 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
                 const bool ok = ks0 + u < ks1;
                 const int ks = ok ? ks0 + u : ks1 - 1;
                 const bf16x8_t a0 = *reinterpret_cast<const bf16x8_t*>(xl + ks * 64), a1 = *reinterpret_cast<const bf16x8_t*>(xl + ks * 64 + 8);
-                const bf16x8_t w0 = ok ? b0[u] : zero, w1 = ok ? b1[u] : zero;
+                bf16x8_t w0, w1;
+                b[u].get(ok, w0, w1);
                 acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, a0, acc[0], 0, 0, 0);
                 acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, a1, acc[0], 0, 0, 0);
             }
         }
     } else
     for (int kb = ks0; kb < ks1; kb += KB) {
-        bf16x8_t b0[KB], b1[KB], a0[MT][KB], a1[MT][KB];
+        SkinnyWPiece<W8> b[KB];
+        bf16x8_t a0[MT][KB], a1[MT][KB];
 #pragma unroll
-        for (int u = 0; u < KB; u++) {
-            const int ks = kb + u < ks1 ? kb + u : ks1 - 1;
-            b0[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64));
-            b1[u] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(wrow + ks * 64 + 8));
-        }
+        for (int u = 0; u < KB; u++) b[u].load(wrow, srow, kb + u < ks1 ? kb + u : ks1 - 1);
 #pragma unroll
         for (int u = 0; u < KB; u++) {
             const int ks = kb + u < ks1 ? kb + u : ks1 - 1;
@@ -407,7 +430,8 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
 #pragma unroll
         for (int u = 0; u < KB; u++) {
             const bool ok = kb + u < ks1;
-            const bf16x8_t w0 = ok ? b0[u] : zero, w1 = ok ? b1[u] : zero;
+            bf16x8_t w0, w1;
+            b[u].get(ok, w0, w1);
 #pragma unroll
             for (int t = 0; t < MT; t++) {
                 acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, a0[t][u], acc[t], 0, 0, 0);
@@ -508,27 +532,37 @@ extern "C" int db1_linear_decode_supported(int M, int N, int K, int geglu, int l
     if ((ln & 2) && (M > 16 || K % 256 || K > 2048)) return 0;
     return 1;
 }
-extern "C" int db1_linear_decode(const void* x, int64_t ldx, const void* w, const void* bias, int dtBias, void* y, int64_t ldy, int M, int N, int K,
-                                 int geglu, const void* pre_res, int64_t ld_pre_res, float pre_alpha, const void* pre_gamma, const void* pre_beta,
-                                 float pre_eps, void* pre_out, int64_t ld_pre_out, const void* res, int64_t ld_res, float alpha, const void* gamma,
-                                 const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
-                                 void* stream) {
+extern "C" int db1_linear_decode_w8_supported(int M, int N, int K, int geglu, int ln) {
+    return (db1_linear_decode_supported(M, N, K, geglu, ln) && K % 128 == 0) ? 1 : 0;
+}
+// db1_linear_decode (w8 == false: w is W [N, K] bf16) and db1_linear_decode_w8 (w is the packed buffer of db1_w8_quantize): one set of checks,
+// one argument block, one dispatch -- the fp8 form differs in the kernel's W load sites only
+static int linear_decode_launch(const bool w8, const void* x, int64_t ldx, const void* w, const void* bias, int dtBias, void* y, int64_t ldy, int M, int N,
+                                int K, int geglu, const void* pre_res, int64_t ld_pre_res, float pre_alpha, const void* pre_gamma, const void* pre_beta,
+                                float pre_eps, void* pre_out, int64_t ld_pre_out, const void* res, int64_t ld_res, float alpha, const void* gamma,
+                                const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
+                                void* stream) {
+    const char* who = w8 ? "linear_decode_w8" : "linear_decode";
     const bool pro = pre_out != nullptr, tail = ln_out != nullptr;
     if (!db1_linear_decode_supported(M, N, K, geglu, (tail ? 1 : 0) | (pro ? 2 : 0)))
-        DB1_FAIL(DB1_ERR_UNSUPPORTED, "linear_decode: M=%d N=%d K=%d geglu=%d ln_out=%d ln_in=%d (needs M <= 64, K %% 64 == 0, N %% 16 == 0; output LayerNorm: rows of 512/1024/2048; input LayerNorm: M <= 16, K %% 256 == 0, K <= 2048)", M, N, K, geglu, tail, pro);
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: M=%d N=%d K=%d geglu=%d ln_out=%d ln_in=%d (needs M <= 64, K %% 64 == 0, N %% 16 == 0; output LayerNorm: rows of 512/1024/2048; input LayerNorm: M <= 16, K %% 256 == 0, K <= 2048)", who, M, N, K, geglu, tail, pro);
+    if (w8 && K % 128) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: K=%d (a scale block is 128 consecutive k of a row: K %% 128 == 0)", who, K);
     if (!x || !w || !y || !tickets || (tail && (!res || !gamma || !beta)) || (pro && (!pre_res || !pre_gamma || !pre_beta)))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "linear_decode: null operand");
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null operand", who);
     if (!db1_aligned16(x) || !db1_aligned16(w) || !db1_aligned16(y) || (ldx % 8) || (ldy % 8) ||
         (tail && (!db1_aligned16(res) || !db1_aligned16(ln_out) || (ld_res % 8) || (ld_out % 8))) ||
         (pro && (!db1_aligned16(pre_res) || !db1_aligned16(pre_out) || (ld_pre_res % 8) || (ld_pre_out % 8))))
-        DB1_FAIL(DB1_ERR_BAD_ALIGN, "linear_decode: operands must be 16-byte aligned with leading dimensions in multiples of 8");
-    if ((bias && !db1_dt_ok(dtBias)) || ((tail || pro) && !db1_dt_ok(dtParam))) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "linear_decode: dtype");
+        DB1_FAIL(DB1_ERR_BAD_ALIGN, "%s: operands must be 16-byte aligned with leading dimensions in multiples of 8", who);
+    if ((bias && !db1_dt_ok(dtBias)) || ((tail || pro) && !db1_dt_ok(dtParam))) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype", who);
+    // (the fp8 form is instantiated for what a bf16 model produces: a bf16 bias or none, bf16 LayerNorm parameters or none)
+    if (w8 && ((bias && dtBias != DB1_BF16) || ((tail || pro) && dtParam != DB1_BF16)))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: the bias and the LayerNorm parameters must be bf16", who);
     SkinnyFusedArgs a;
     a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.bias = bias; a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = K; a.ldy = ldy;
     a.S = pro ? 1 : skinny_fused_split(M, N, K, geglu);
     a.part = nullptr; a.tickets = (unsigned*)tickets;
     if (a.S > 1) {
-        DB1_NEED_WS(ws, ws_bytes, db1_linear_decode_workspace_bytes(M, N, K, geglu), "linear_decode");
+        DB1_NEED_WS(ws, ws_bytes, db1_linear_decode_workspace_bytes(M, N, K, geglu), who);
         a.part = (float*)ws;
     }
     a.res = (const bf16_t*)res; a.gamma = gamma; a.beta = beta; a.ln_out = (bf16_t*)ln_out; a.ld_res = ld_res; a.ld_out = ld_out; a.alpha = alpha; a.eps = eps;
@@ -538,20 +572,37 @@ extern "C" int db1_linear_decode(const void* x, int64_t ldx, const void* w, cons
     hipStream_t st = (hipStream_t)stream;
     const int mt = (M + 15) / 16;
     const bool bb = bias && dtBias == DB1_BF16, pb = (tail || pro) && dtParam == DB1_BF16;
-#define SKF(TB, TPp, MTv, G, PR) gemm_skinny_fused_kernel<TB, TPp, MTv, G, PR><<<grid, 256, 0, st>>>(a)
-#define SKF_MT(TB, TPp, G) do { if (pro && M == 1) SKF(TB, TPp, 1, G, 1); else if (pro && M <= 4) SKF(TB, TPp, 1, G, 4); else if (pro) SKF(TB, TPp, 1, G, 16); \
-                                else if (mt == 1) SKF(TB, TPp, 1, G, 0); else if (mt == 2) SKF(TB, TPp, 2, G, 0); \
-                                else if (mt == 3) SKF(TB, TPp, 3, G, 0); else SKF(TB, TPp, 4, G, 0); } while (0)
-#define SKF_G(TB, TPp) do { if (geglu) SKF_MT(TB, TPp, true); else SKF_MT(TB, TPp, false); } while (0)
-    if (bb && pb) SKF_G(bf16_t, bf16_t);
-    else if (bb) SKF_G(bf16_t, float);
-    else if (pb) SKF_G(float, bf16_t);
-    else SKF_G(float, float);
+#define SKF(TB, TPp, MTv, G, PR, W8v) gemm_skinny_fused_kernel<TB, TPp, MTv, G, PR, W8v><<<grid, 256, 0, st>>>(a)
+#define SKF_MT(TB, TPp, G, W8v) do { if (pro && M == 1) SKF(TB, TPp, 1, G, 1, W8v); else if (pro && M <= 4) SKF(TB, TPp, 1, G, 4, W8v); else if (pro) SKF(TB, TPp, 1, G, 16, W8v); \
+                                     else if (mt == 1) SKF(TB, TPp, 1, G, 0, W8v); else if (mt == 2) SKF(TB, TPp, 2, G, 0, W8v); \
+                                     else if (mt == 3) SKF(TB, TPp, 3, G, 0, W8v); else SKF(TB, TPp, 4, G, 0, W8v); } while (0)
+#define SKF_G(TB, TPp, W8v) do { if (geglu) SKF_MT(TB, TPp, true, W8v); else SKF_MT(TB, TPp, false, W8v); } while (0)
+    if (w8) SKF_G(bf16_t, bf16_t, true);   // (an absent bias / parameter pair is never read: one dtype pair serves)
+    else if (bb && pb) SKF_G(bf16_t, bf16_t, false);
+    else if (bb) SKF_G(bf16_t, float, false);
+    else if (pb) SKF_G(float, bf16_t, false);
+    else SKF_G(float, float, false);
 #undef SKF_G
 #undef SKF_MT
 #undef SKF
-    DB1_CHECK_LAUNCH("linear_decode");
+    DB1_CHECK_LAUNCH(who);
     return DB1_OK;
+}
+extern "C" int db1_linear_decode(const void* x, int64_t ldx, const void* w, const void* bias, int dtBias, void* y, int64_t ldy, int M, int N, int K,
+                                 int geglu, const void* pre_res, int64_t ld_pre_res, float pre_alpha, const void* pre_gamma, const void* pre_beta,
+                                 float pre_eps, void* pre_out, int64_t ld_pre_out, const void* res, int64_t ld_res, float alpha, const void* gamma,
+                                 const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
+                                 void* stream) {
+    return linear_decode_launch(false, x, ldx, w, bias, dtBias, y, ldy, M, N, K, geglu, pre_res, ld_pre_res, pre_alpha, pre_gamma, pre_beta, pre_eps, pre_out,
+                                ld_pre_out, res, ld_res, alpha, gamma, beta, eps, ln_out, ld_out, dtParam, tickets, ws, ws_bytes, stream);
+}
+extern "C" int db1_linear_decode_w8(const void* x, int64_t ldx, const void* w8, const void* bias, int dtBias, void* y, int64_t ldy, int M, int N, int K,
+                                    int geglu, const void* pre_res, int64_t ld_pre_res, float pre_alpha, const void* pre_gamma, const void* pre_beta,
+                                    float pre_eps, void* pre_out, int64_t ld_pre_out, const void* res, int64_t ld_res, float alpha, const void* gamma,
+                                    const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
+                                    void* stream) {
+    return linear_decode_launch(true, x, ldx, w8, bias, dtBias, y, ldy, M, N, K, geglu, pre_res, ld_pre_res, pre_alpha, pre_gamma, pre_beta, pre_eps, pre_out,
+                                ld_pre_out, res, ld_res, alpha, gamma, beta, eps, ln_out, ld_out, dtParam, tickets, ws, ws_bytes, stream);
 }
 
 
@@ -562,19 +613,59 @@ extern "C" int db1_linear_decode_attn_supported(int B, int q, int H, int D, int 
     return (B >= 1 && q >= 1 && B * q <= 2 && D == 128 && H * D <= 2048 && (H * D) % 256 == 0 && nunit >= 1 && nunit <= 12 && N % 16 == 0 && N >= 16 &&
             N / 16 + 1 <= DB1_SKINNY_TICKETS) ? 1 : 0;
 }
-extern "C" int db1_linear_decode_attn(const float* attn_part, int nunit, int B, int q, int H, int D, const void* w, void* y, int64_t ldy, int N, void* stream) {
+extern "C" int db1_linear_decode_attn_w8_supported(int B, int q, int H, int D, int nunit, int N) {   // (H D % 256 == 0 already: whole scale blocks)
+    return db1_linear_decode_attn_supported(B, q, H, D, nunit, N);
+}
+static int linear_decode_attn_launch(const bool w8, const float* attn_part, int nunit, int B, int q, int H, int D, const void* w, void* y, int64_t ldy, int N,
+                                     void* stream) {
+    const char* who = w8 ? "linear_decode_attn_w8" : "linear_decode_attn";
     if (!db1_linear_decode_attn_supported(B, q, H, D, nunit, N))
-        DB1_FAIL(DB1_ERR_UNSUPPORTED, "linear_decode_attn: B=%d q=%d H=%d D=%d chunks=%d N=%d (needs B q <= 2, d_head = 128, H D <= 2048, <= 12 chunks)", B, q, H, D, nunit, N);
-    if (!attn_part || !w || !y) DB1_FAIL(DB1_ERR_BAD_SHAPE, "linear_decode_attn: null operand");
-    if (!db1_aligned16(attn_part) || !db1_aligned16(w) || !db1_aligned16(y) || (ldy % 8)) DB1_FAIL(DB1_ERR_BAD_ALIGN, "linear_decode_attn: alignment");
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: B=%d q=%d H=%d D=%d chunks=%d N=%d (needs B q <= 2, d_head = 128, H D <= 2048, <= 12 chunks)", who, B, q, H, D, nunit, N);
+    if (!attn_part || !w || !y) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null operand", who);
+    if (!db1_aligned16(attn_part) || !db1_aligned16(w) || !db1_aligned16(y) || (ldy % 8)) DB1_FAIL(DB1_ERR_BAD_ALIGN, "%s: alignment", who);
     SkinnyFusedArgs a = {};
     a.x = (const bf16_t*)w;   // (never read: the rows come from attn_part)
     a.w = (const bf16_t*)w; a.y = (bf16_t*)y; a.bias = nullptr; a.M = B * q; a.N = N; a.K = H * D; a.ldx = 0; a.ldw = a.K; a.ldy = ldy; a.S = 1;
     a.att_part = attn_part; a.att_nunit = nunit; a.att_q = q; a.att_H = H;
     const dim3 grid((unsigned)(N / 16), 1u);
     hipStream_t st = (hipStream_t)stream;
-    if (a.M == 1) gemm_skinny_fused_kernel<float, float, 1, false, -1><<<grid, 256, 0, st>>>(a);
+    if (w8) {
+        if (a.M == 1) gemm_skinny_fused_kernel<float, float, 1, false, -1, true><<<grid, 256, 0, st>>>(a);
+        else gemm_skinny_fused_kernel<float, float, 1, false, -2, true><<<grid, 256, 0, st>>>(a);
+    } else if (a.M == 1) gemm_skinny_fused_kernel<float, float, 1, false, -1><<<grid, 256, 0, st>>>(a);
     else gemm_skinny_fused_kernel<float, float, 1, false, -2><<<grid, 256, 0, st>>>(a);
-    DB1_CHECK_LAUNCH("linear_decode_attn");
+    DB1_CHECK_LAUNCH(who);
+    return DB1_OK;
+}
+extern "C" int db1_linear_decode_attn(const float* attn_part, int nunit, int B, int q, int H, int D, const void* w, void* y, int64_t ldy, int N, void* stream) {
+    return linear_decode_attn_launch(false, attn_part, nunit, B, q, H, D, w, y, ldy, N, stream);
+}
+extern "C" int db1_linear_decode_attn_w8(const float* attn_part, int nunit, int B, int q, int H, int D, const void* w8, void* y, int64_t ldy, int N, void* stream) {
+    return linear_decode_attn_launch(true, attn_part, nunit, B, q, H, D, w8, y, ldy, N, stream);
+}
+
+
+// ======================================================================================= fp8 decode weights: the quantiser
+// W [N, K] bf16 (leading dimension ldw) -> the packed buffer (include/db1_hip.h, "fp8 decode weights"): one pass, eight lanes per block of 128 k
+// through kv8_quant_block -- the fp8 K/V ring's rule, bit for bit.  Whole waves enter (shuffles); `active` switches the memory accesses.
+__global__ __launch_bounds__(256) void w8_quantize_kernel(const bf16_t* w, int64_t ldw, int N, int K, unsigned char* out) {
+    const int bpr = K / 128;
+    const int64_t nblk = (int64_t)N * bpr, blk = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 3;
+    const bool active = blk < nblk;
+    const int64_t bl = active ? blk : 0, row = bl / bpr;
+    const int b = (int)(bl - row * bpr);
+    kv8_quant_block(w + row * ldw + b * 128, out + row * K + b * 128, reinterpret_cast<float*>(out + (int64_t)N * K) + bl, (int)(threadIdx.x & 7), active);
+}
+extern "C" int64_t db1_w8_bytes(int N, int K) {
+    if (N < 1 || K < 128 || K % 128) return 0;
+    return (int64_t)N * K + (int64_t)N * (K / 128) * 4;
+}
+extern "C" int db1_w8_quantize(const void* w, int64_t ldw, int N, int K, void* out, void* stream) {
+    if (!db1_w8_bytes(N, K)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "w8_quantize: N=%d K=%d (needs N >= 1, K %% 128 == 0)", N, K);
+    if (!w || !out || ldw < K) DB1_FAIL(DB1_ERR_BAD_SHAPE, "w8_quantize: null operand or ldw < K");
+    if (!db1_aligned16(w) || !db1_aligned16(out) || (ldw % 8)) DB1_FAIL(DB1_ERR_BAD_ALIGN, "w8_quantize: operands must be 16-byte aligned, ldw a multiple of 8");
+    const int64_t nblk = (int64_t)N * (K / 128);
+    w8_quantize_kernel<<<dim3((unsigned)((nblk + 31) / 32)), 256, 0, (hipStream_t)stream>>>((const bf16_t*)w, ldw, N, K, (unsigned char*)out);
+    DB1_CHECK_LAUNCH("w8_quantize");
     return DB1_OK;
 }

@@ -335,6 +335,8 @@ class TransformerXL(nn.Module):
         self.use_decode_attn_partials = True   # ... <= 2 tokens (ring memory): the output projection merges the attention's chunk partials
         self.use_decode_chain = os.environ.get("DB1_DECODE_CHAIN", "1") != "0"   # ... ONE token (ring memory): the linear maps between two attention launches as one persistent launch (db1_decode_chain)
         self._chain_watch = None         # (pinned copy of the chain's error flag, its scratch) of the last chain call: check_decode_chain()
+        self.decode_weights = "bf16"     # "fp8": the fused decode branch streams e4m3 copies of the layers' four linear maps (set_decode_weights)
+        self._w8 = None                  # (version, {parameter name: packed buffer}) -- packed on the first fp8 decode call of a weight version
         self._wversion = 0               # bumped whenever the weights change (invalidates the inference caches)
         self._dec_state = None           # K/V cache of the memory returned by the last forward (see _decode_begin)
         self._dec_R = None               # (version, [R_i = r_net_i(sinusoid(dist)) for dist < mem_len + 64])
@@ -443,7 +445,7 @@ class TransformerXL(nn.Module):
     def mark_weights_changed(self):
         """called after every parameter update (load_state_dict, optimizer step): drops the inference caches"""
         self._wversion += 1
-        self._dec_state, self._dec_R = None, None
+        self._dec_state, self._dec_R, self._w8 = None, None, None
 
     def sync_work_params(self):
         """Refresh the bf16 working copy after the float32 master parameters were edited by hand."""
@@ -456,6 +458,55 @@ class TransformerXL(nn.Module):
 
     def G(self, name: str) -> torch.Tensor:
         return self.arena.view(self.arena.grad, name)
+
+    # ---- fp8 decode weights (include/db1_hip.h, "fp8 decode weights")
+    W8_MAPS = ("dec_attn.qkv_net.weight", "dec_attn.o_net.weight", "pos_ff.CoreNet.0.weight", "pos_ff.CoreNet.2.weight")
+
+    def set_decode_weights(self, fmt: str):
+        """``"bf16"`` (the default) or ``"fp8"``: what the decode calls stream as the layers' linear maps.
+
+        Under ``"fp8"`` every decode call -- at most 64 new tokens over a memory: generate, beam_search, sample_best_of, the streams, the
+        prefix cache's continuations, GraphedRingStep / get_action -- whose layer tail takes the fused branch (``_decode_fused_ok``) runs
+        qkv_net, o_net, CoreNet.0 and CoreNet.2 of every layer on e4m3 copies with one power-of-two scale per 128 k of a row
+        (db1_linear_decode_w8 / db1_linear_decode_attn_w8): 0.516 of the bf16 bytes per token, and bit for bit the bf16 launches over the
+        dequantised copies.  The copies are packed on the first such call of a weight version (``mark_weights_changed`` drops them); that
+        call must run eagerly -- GraphedRingStep's warm-up does -- and raises RuntimeError under a graph capture.  The one-token
+        persistent chain (``use_decode_chain``) is not taken under ``"fp8"``: the per-layer launches with the attention-merge prologue are.
+        On bf16 stay: the head, the embedders, r_net, every call of more than 64 tokens (prefills, the ring prefill, PrefixCache.put) and
+        any decode call that falls off the fused branch (``keep``, dropout, ``use_decode_fused = False``).
+
+        Needs a bf16 model with ``use_decode``, d_model % 128 == 0, d_ff % 128 == 0 and the GEGLU post-LN layer (ValueError otherwise, also
+        for another value).  A change of the value calls ``mark_weights_changed()``: captured steps and cached generators are rebuilt,
+        PrefixCache handles become invalid."""
+        if fmt not in ("bf16", "fp8"):
+            raise ValueError(f"set_decode_weights: {fmt!r} (expected 'bf16' or 'fp8')")
+        if fmt == "fp8":
+            why = None
+            if self.compute_dtype != torch.bfloat16:
+                why = "a bf16 model"
+            elif not self.use_decode:
+                why = "the K/V-cached decode path (use_decode)"
+            elif self.d_model % 128 or self.d_ff % 128:
+                why = f"d_model % 128 == 0 and d_ff % 128 == 0 (got {self.d_model}, {self.d_ff}: a scale block is 128 consecutive k of a row)"
+            elif self.pre_lnorm or self.activation_fn != "geglu":
+                why = "the GEGLU post-LN layer (the fused decode branch)"
+            elif self.W("h.0.pos_ff.layer_norm.weight").dtype != self.W("h.0.pos_ff.layer_norm.bias").dtype:
+                why = "LayerNorm weights and biases of one dtype (the fused decode branch)"
+            if why is not None:
+                raise ValueError(f"set_decode_weights('fp8') needs {why}")
+        if fmt != self.decode_weights:
+            self.decode_weights = fmt
+            self.mark_weights_changed()
+
+    def W8(self, name: str) -> torch.Tensor:
+        """the packed fp8 copy (ops.w8_quantize) of one of the layers' four linear maps, of the current weight version"""
+        if self._w8 is None or self._w8[0] != self._wversion:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("decode_weights='fp8': the first decode call of a weight version packs the fp8 copies and must run eagerly "
+                                   "(GraphedRingStep warms up before it captures)")
+            self._w8 = None      # (free the old copies first)
+            self._w8 = (self._wversion, {f"h.{i}.{m}": ops.w8_quantize(self.W(f"h.{i}.{m}")) for i in range(self.n_layer) for m in self.W8_MAPS})
+        return self._w8[1][name]
 
     @property
     def device(self):
@@ -855,12 +906,16 @@ class TransformerXL(nn.Module):
             if x.data_ptr() != wx.data_ptr():                    # (layer 0: the embedding output; later layers were written there directly)
                 wx.copy_(x)
                 x = wx
+        # the fused decode branch's four linear maps: W streams over the bf16 weights, or (decode_weights == "fp8") over their packed e4m3 copies
+        lin, lin_attn, Wd = ops.linear_decode, ops.linear_decode_attn, self.W
+        if dec is not None and self.decode_weights == "fp8" and self._decode_fused_ok(T, keep, dstep):
+            lin, lin_attn, Wd = ops.linear_decode_w8, ops.linear_decode_attn_w8, self.W8
         if dec is not None:  # K/V-cached inference: only the new tokens are projected (identical maths: qkv_net has no bias)
             qkv = self._new(T, 3 * d)
             if pend is not None:   # the previous layer left its closing LayerNorm to this projection, which also stores the rows to x
-                ops.linear_decode(pend.y, self.W(p + "dec_attn.qkv_net.weight"), None, qkv, pre=(pend.res, pend.alpha, pend.gamma, pend.beta, pend.eps, x))
+                lin(pend.y, Wd(p + "dec_attn.qkv_net.weight"), None, qkv, pre=(pend.res, pend.alpha, pend.gamma, pend.beta, pend.eps, x))
             elif self._decode_fused_ok(T, keep, dstep) and ops.linear_decode_supported(T, 3 * d, d, False, False, False):
-                ops.linear_decode(x, self.W(p + "dec_attn.qkv_net.weight"), None, qkv)    # (<= 64 rows: a stream over W, not a 256-row tile GEMM)
+                lin(x, Wd(p + "dec_attn.qkv_net.weight"), None, qkv)    # (<= 64 rows: a stream over W, not a 256-row tile GEMM)
             else:
                 ops.gemm(x, self.W(p + "dec_attn.qkv_net.weight").t(), qkv)
             av = self._attention_decode(qkv, i, B, L, mlen, shift, dec)
@@ -908,21 +963,20 @@ class TransformerXL(nn.Module):
             o, h1, act, f = self._new(T, d), self._new(T, d), self._new(T, dff), self._new(T, d)
             if self._decode_ln_prologue_ok(T):
                 if getattr(dec, "partials", False):
-                    ops.linear_decode_attn(av, mlen + L, B, L, self.n_head, self.d_head, self.W(p + "dec_attn.o_net.weight"), o)
+                    lin_attn(av, mlen + L, B, L, self.n_head, self.d_head, Wd(p + "dec_attn.o_net.weight"), o)
                 else:
-                    ops.linear_decode(av.view(T, d), self.W(p + "dec_attn.o_net.weight"), None, o)
-                ops.linear_decode(o, self.W(p + "pos_ff.CoreNet.0.weight"), self.W(p + "pos_ff.CoreNet.0.bias"), act, geglu=True,
-                                  pre=(x, a, g1, b1, eps, h1))
-                ops.linear_decode(act, self.W(p + "pos_ff.CoreNet.2.weight"), self.W(p + "pos_ff.CoreNet.2.bias"), f)
+                    lin(av.view(T, d), Wd(p + "dec_attn.o_net.weight"), None, o)
+                lin(o, Wd(p + "pos_ff.CoreNet.0.weight"), self.W(p + "pos_ff.CoreNet.0.bias"), act, geglu=True, pre=(x, a, g1, b1, eps, h1))
+                lin(act, Wd(p + "pos_ff.CoreNet.2.weight"), self.W(p + "pos_ff.CoreNet.2.bias"), f)
                 return _PendingLN(res=h1, y=f, alpha=a, gamma=g2, beta=b2, eps=eps), None
             # (17 .. 64 tokens: the LayerNorms as their own launches -- finishing them inside the linear map by the last workgroup to arrive,
             #  ln= of ops.linear_decode, measured slower inside a graph than the launch boundary it saves)
             stat = lambda: self._new(T, dtype=torch.float32)
-            ops.linear_decode(av.view(T, d), self.W(p + "dec_attn.o_net.weight"), None, o)
+            lin(av.view(T, d), Wd(p + "dec_attn.o_net.weight"), None, o)
             ops.layernorm_residual_fwd(x, o, a, g1, b1, h1, None, stat(), stat(), eps)
-            ops.linear_decode(h1, self.W(p + "pos_ff.CoreNet.0.weight"), self.W(p + "pos_ff.CoreNet.0.bias"), act, geglu=True)
+            lin(h1, Wd(p + "pos_ff.CoreNet.0.weight"), self.W(p + "pos_ff.CoreNet.0.bias"), act, geglu=True)
             out = self._new(T, d)
-            ops.linear_decode(act, self.W(p + "pos_ff.CoreNet.2.weight"), self.W(p + "pos_ff.CoreNet.2.bias"), f)
+            lin(act, Wd(p + "pos_ff.CoreNet.2.weight"), self.W(p + "pos_ff.CoreNet.2.bias"), f)
             ops.layernorm_residual_fwd(h1, f, a, g2, b2, out, None, stat(), stat(), eps)
             return out, None
         o = self._keep(("s1", i), T, d)
@@ -1265,7 +1319,8 @@ class TransformerXL(nn.Module):
         self._win_on = False
         if self.bwd_window_ga > 1 and keep and self.training and mems is None and ring is None:
             R_in = self._window_begin(B, L, shift, R_in, dstep)      # (deferred backward: this micro-step's position table joins the window's)
-        if (ring is not None and B * L == 1 and self.use_decode_chain and getattr(dec, "partials", False) and self.activation_fn == "geglu" and self.n_layer >= 2 and
+        # (the persistent chain streams the bf16 weights: under decode_weights == "fp8" the per-layer launches below run instead)
+        if (ring is not None and B * L == 1 and self.use_decode_chain and self.decode_weights != "fp8" and getattr(dec, "partials", False) and self.activation_fn == "geglu" and self.n_layer >= 2 and
                 ops.decode_chain_supported(d, self.d_ff, self.n_head, self.d_head, mlen + L)):
             x = self._decode_chain_layers(x, mlen, shift, dec)
             hids, lcs = [], []

@@ -1703,9 +1703,18 @@ def linear_decode(x, W, bias, y, geglu=False, ln=None, pre=None):
     """y = x W^T + bias for M <= 64 rows (bf16), optionally through GEGLU (W [2N, K]); inside the same launch (db1_linear_decode)
     pre = (res, alpha, gamma, beta, eps, out): the input rows are x_eff = LayerNorm(alpha * res + x) * gamma + beta, also stored to out;
     ln  = (res, alpha, gamma, beta, eps, out): out = LayerNorm(alpha * res + y) * gamma + beta"""
+    _linear_decode(x, W, bias, y, geglu, ln, pre, False)
+
+
+def _linear_decode(x, W, bias, y, geglu, ln, pre, w8):
+    """linear_decode (W: the bf16 weight) and linear_decode_w8 (W: its packed fp8 buffer): one argument block"""
     M, K = x.shape
     N = y.shape[1]
-    assert x.dtype == torch.bfloat16 and W.dtype == torch.bfloat16 and y.dtype == torch.bfloat16 and W.is_contiguous() and W.shape == ((2 * N if geglu else N), K)
+    assert x.dtype == torch.bfloat16 and y.dtype == torch.bfloat16
+    if w8:
+        _w8_check(W, 2 * N if geglu else N, K, y.device, "linear_decode_w8")
+    else:
+        assert W.dtype == torch.bfloat16 and W.is_contiguous() and W.shape == ((2 * N if geglu else N), K)
     assert x.stride(1) == 1 and y.stride(1) == 1
     ws, wsn = _ws("db1_linear_decode_workspace_bytes", (M, N, K, int(geglu)), y.device)
     dtp = 0
@@ -1720,8 +1729,84 @@ def linear_decode(x, W, bias, y, geglu=False, ln=None, pre=None):
         dtp = dt_code(gamma.dtype) + 100
         return (P(res), res.stride(0), float(alpha), P(gamma), P(beta), float(eps), P(out), out.stride(0))
     a_pre, a_ln = pack(pre), pack(ln)
-    lib.call("db1_linear_decode", P(x), x.stride(0), P(W), P(bias), dt_code(bias.dtype) if bias is not None else 0, P(y), y.stride(0), M, N, K, int(geglu),
-             *a_pre, *a_ln, max(dtp - 100, 0), P(decode_tickets(y.device)), ws, wsn, stream())
+    lib.call("db1_linear_decode_w8" if w8 else "db1_linear_decode", P(x), x.stride(0), P(W), P(bias), dt_code(bias.dtype) if bias is not None else 0, P(y),
+             y.stride(0), M, N, K, int(geglu), *a_pre, *a_ln, max(dtp - 100, 0), P(decode_tickets(y.device)), ws, wsn, stream())
+
+
+# ---- fp8 decode weights (include/db1_hip.h, "fp8 decode weights"): a weight [N, K] is ONE uint8 buffer of w8_bytes(N, K) bytes
+def w8_bytes(N, K) -> int:
+    """bytes of the packed form of a [N, K] weight (db1_w8_bytes: N K payload bytes + N K / 128 fp32 scales), 0 where K % 128 != 0"""
+    return int(lib.load().db1_w8_bytes(int(N), int(K)))
+
+
+def w8_quantize(W, out=None):
+    """a bf16 weight ``W`` [N, K] on the device (rows may be strided: ``W.stride(0) >= K``) -> its packed buffer (uint8 [w8_bytes(N, K)],
+    ``out`` or a new tensor) -- db1_w8_quantize, one launch"""
+    if W.dim() != 2 or W.dtype != torch.bfloat16 or W.stride(1) != 1 or not W.is_cuda:
+        raise ValueError("w8_quantize: W must be a bf16 [N, K] device tensor with contiguous rows")
+    N, K = W.shape
+    nb = w8_bytes(N, K)
+    if not nb:
+        raise ValueError(f"w8_quantize: no fp8 form for N={N}, K={K} (K % 128 == 0 expected)")
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=W.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != nb or out.device != W.device or not out.is_contiguous():
+        raise ValueError(f"w8_quantize: out must be a contiguous uint8 [{nb}] tensor on {W.device}")
+    lib.call("db1_w8_quantize", P(W), W.stride(0), N, K, P(out), stream())
+    return out
+
+
+def w8_pack(W):
+    """host side (tests, debugging): a weight ``W`` [N, K] (CPU, any float dtype holding bf16 values, K % 128 == 0) -> the packed buffer uint8
+    [N K + 4 N K / 128] by the rule of include/db1_hip.h: every block of 128 k of a row is a block of kv8_pack"""
+    x = W.detach().to("cpu", torch.float64)
+    if x.dim() != 2 or x.shape[1] == 0 or x.shape[1] % 128 or x.shape[0] == 0:
+        raise ValueError("w8_pack: W must be [N, K] with K % 128 == 0")
+    N, K = x.shape
+    xb = x.reshape(N, K // 128, 128)
+    fin = torch.isfinite(xb)
+    s = torch.ldexp(torch.ones(N, K // 128, dtype=torch.float64), _kv8_scale_exp(torch.where(fin, xb.abs(), torch.zeros_like(xb)).amax(-1)))
+    y = torch.where(fin, xb / s[..., None], torch.zeros_like(xb))
+    pay = y.to(torch.float32).to(torch.float8_e4m3fn).view(torch.uint8)
+    pay = torch.where(fin, pay, torch.full_like(pay, 0x7F))
+    return torch.cat([pay.reshape(-1), s.to(torch.float32).reshape(-1).contiguous().view(torch.uint8)])
+
+
+def w8_unpack(buf, N, K):
+    """host side: a packed buffer -> (the dequantised weight, bf16 [N, K]; the scales, float32 [N, K / 128])"""
+    b = buf.detach().to("cpu").contiguous()
+    N, K = int(N), int(K)
+    if K <= 0 or K % 128 or N <= 0 or b.dtype != torch.uint8 or b.dim() != 1 or b.numel() != N * K + 4 * N * (K // 128):
+        raise ValueError(f"w8_unpack: buf must be uint8 [{N * K + 4 * N * (K // 128) if K % 128 == 0 else '?'}] (N K payload bytes, then N K / 128 fp32 scales; K % 128 == 0)")
+    pay = b[:N * K].view(torch.float8_e4m3fn).to(torch.float32).reshape(N, K // 128, 128)
+    s = b[N * K:].clone().view(torch.float32).reshape(N, K // 128)
+    return (pay * s[..., None]).reshape(N, K).to(torch.bfloat16), s
+
+
+def linear_decode_w8_supported(M, N, K, geglu=False, ln=False, pre=False) -> bool:
+    return bool(lib.load().db1_linear_decode_w8_supported(int(M), int(N), int(K), int(geglu), int(bool(ln)) | (2 if pre else 0)))
+
+
+def linear_decode_w8(x, W8, bias, y, geglu=False, ln=None, pre=None):
+    """linear_decode with the weight in its fp8 form (db1_linear_decode_w8): ``W8`` is the packed buffer of the [N, K] (geglu: [2 N, K]) weight
+    from w8_quantize.  Bit for bit linear_decode over w8_unpack(W8)."""
+    _linear_decode(x, W8, bias, y, geglu, ln, pre, True)
+
+
+def linear_decode_attn_w8_supported(B, q, H, D, klen, N) -> bool:
+    return bool(lib.load().db1_linear_decode_attn_w8_supported(int(B), int(q), int(H), int(D), (int(klen) + 127) // 128, int(N)))
+
+
+def linear_decode_attn_w8(part, klen, B, q, H, D, W8, y):
+    """linear_decode_attn with the [N, H D] weight in its fp8 form (db1_linear_decode_attn_w8)"""
+    assert y.dtype == torch.bfloat16 and y.stride(1) == 1
+    _w8_check(W8, y.shape[1], H * D, y.device, "linear_decode_attn_w8")
+    lib.call("db1_linear_decode_attn_w8", P(part), (int(klen) + 127) // 128, B, q, H, D, P(W8), P(y), y.stride(0), y.shape[1], stream())
+
+
+def _w8_check(W8, N, K, device, who):
+    if W8.dtype != torch.uint8 or W8.dim() != 1 or not W8.is_contiguous() or W8.device != device or K % 128 or W8.numel() != w8_bytes(N, K):
+        raise ValueError(f"{who}: the weight must be the packed uint8 buffer of a [{N}, {K}] matrix on {device} (w8_quantize; K % 128 == 0)")
 
 
 def ring_advance(state, q, cap):

@@ -404,6 +404,34 @@ int db1_linear_decode(const void* x, int64_t ldx, const void* w, const void* bia
                       const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
                       void* stream);
 
+/* ------------------------------------------------------------------ fp8 decode weights (tests/w8_rule.py restates the format in NumPy).
+ * The same linear maps with about half the bytes of W to stream.  A weight W [N, K] (bf16, K-major, K % 128 == 0) becomes ONE buffer of
+ * db1_w8_bytes(N, K) = N K + 4 N (K / 128) bytes:
+ *     N * K bytes of e4m3 payload, row-major; then N * (K / 128) fp32 scales, row-major      (0.516 of the bf16 bytes)
+ * A block is the 128 consecutive k of one row.  Scale, payload, NaN byte and exponent floor of a block are exactly the fp8 K/V ring's rule
+ * above (tests/kv8_rule.py: quantize): the scale is the smallest power of two s with amax <= 448 s over the block's FINITE elements (1 for a
+ * block of zeros, at least 2^-126), x / s is exact, the e4m3 rounding is the only rounding, payload * s is exact in bf16 (where it is not
+ * subnormal there), a non-finite element is stored as the byte 0x7f and takes no part in amax.
+ * db1_w8_quantize: w [N, K] with leading dimension ldw >= K (elements, a multiple of 8) -> out; one pass, no workspace.
+ * db1_linear_decode_w8 / db1_linear_decode_attn_w8: the operands of db1_linear_decode / db1_linear_decode_attn with the packed buffer in place
+ * of w (geglu: the buffer of the whole [2 N, K] weight); workspace and tickets are db1_linear_decode's.  Only the kernel's W load sites differ
+ * (16 payload bytes + one scale per lane and 64-wide k-step, widened to the bf16 operands in registers): the k partition, MFMA order, LDS
+ * reduction, split-K, epilogues, LayerNorm prologue and tail are the bf16 kernel's, so the result is BIT FOR BIT that of db1_linear_decode /
+ * db1_linear_decode_attn over the dequantised weight (ops.w8_unpack), as long as no dequantised value is subnormal in bf16.
+ * _supported: the bf16 entry point's, and K % 128 == 0.  Refused before anything is launched, with the bf16 entry points' codes: NULL operands
+ * (DB1_ERR_BAD_SHAPE), a buffer that is not 16-byte aligned (DB1_ERR_BAD_ALIGN), K % 128 != 0 (DB1_ERR_UNSUPPORTED), and -- the fp8 form is
+ * instantiated for what a bf16 model produces -- an fp32 bias or fp32 LayerNorm parameters (DB1_ERR_UNSUPPORTED). */
+int64_t db1_w8_bytes(int N, int K);                                         /* 0 where the format is not defined */
+int db1_w8_quantize(const void* w, int64_t ldw, int N, int K, void* out, void* stream);
+int db1_linear_decode_w8_supported(int M, int N, int K, int geglu, int ln);
+int db1_linear_decode_w8(const void* x, int64_t ldx, const void* w8, const void* bias, int dtBias, void* y, int64_t ldy, int M, int N, int K,
+                         int geglu, const void* pre_res, int64_t ld_pre_res, float pre_alpha, const void* pre_gamma, const void* pre_beta,
+                         float pre_eps, void* pre_out, int64_t ld_pre_out, const void* res, int64_t ld_res, float alpha, const void* gamma,
+                         const void* beta, float eps, void* ln_out, int64_t ld_out, int dtParam, void* tickets, void* ws, int64_t ws_bytes,
+                         void* stream);
+int db1_linear_decode_attn_w8_supported(int B, int q, int H, int D, int nunit, int N);
+int db1_linear_decode_attn_w8(const float* attn_part, int nunit, int B, int q, int H, int D, const void* w8, void* y, int64_t ldy, int N, void* stream);
+
 /* ------------------------------------------------------------------ relative-position attention, materialised path
  * (fp32 parity gate, any head size).  Buffers S,T are float32 in [H][B][Lq][*] layout.
  * qu = q + u, qv = q + v_bias from the packed qkv activations [B, L, 3, H, D]  (transformer_xl.py:161,167). */

@@ -102,7 +102,20 @@ db1_relattn_decode_ring_kv8_fwd, in alternation in ONE process: q = 1, mlen = 10
 model's plain path launches) and, for B <= 2, the partials form; device time per call from events over 20 calls, the median of 7 rounds
 each, with the ring bytes a call reads and the rate they amount to.
 
-    python tools/bench_generate.py --kv8-kernels [B ...]"""
+    python tools/bench_generate.py --kv8-kernels [B ...]
+
+--decode-weights fp8 (with any mode): ``model.set_decode_weights("fp8")`` first -- the decode calls stream e4m3 copies of the layers' four
+linear maps, and the one-token call takes the per-layer launches instead of the persistent chain; every line carries "decode_weights".
+
+    python tools/bench_generate.py --decode-weights fp8 [M ...]
+
+--w8-kernels [M ...] (default 1 4 16 64): db1_linear_decode and db1_linear_decode_w8 alone at the model's four layer shapes (qkv_net, o_net,
+CoreNet.0 through GEGLU, CoreNet.2), in alternation in ONE process.  Each side is a captured graph of one launch over each of n copies of
+the weight (600 MB of bf16 copies: more bytes than the last-level cache holds, as the 24 layers of a decode step are), so a replay is device
+time without the host's launch cost; device time per launch from events over 5 replays, the median of 7 rounds with min .. max, the bytes of W a launch
+streams and the rate they amount to.
+
+    python tools/bench_generate.py --w8-kernels [M ...]"""
 import dataclasses
 import json
 import os
@@ -185,6 +198,47 @@ def kv8_kernels_us(B, mlen=1024, rounds=7, calls=20):
             rec[f"{k}_ring_MB"] = round(nbytes / 1e6, 2)
             rec[f"{k}_{form}_TBps"] = round(nbytes / (us * 1e-6) / 1e12, 3)
         rec[f"fp8_over_bf16_{form}"] = round(rec[f"fp8_{form}_us"] / rec[f"bf16_{form}_us"], 4)
+    return rec
+
+
+def w8_kernels_us(M, rounds=7, replays=5):
+    """db1_linear_decode and db1_linear_decode_w8 alone at the model's four layer shapes (the docstring above says how)"""
+    d, dff = model.d_model, model.d_ff
+    g = torch.Generator(device=dev).manual_seed(M)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, device=dev, generator=g) * sc).to(torch.bfloat16)
+    rec = {"M": M}
+    for name, N, K, geglu in (("qkv_net", 3 * d, d, False), ("o_net", d, d, False), ("CoreNet.0", dff, d, True), ("CoreNet.2", d, dff, False)):
+        rows = 2 * N if geglu else N
+        copies = -(-600_000_000 // (2 * rows * K))      # 600 MB of bf16 copies, 310 MB of fp8 ones: neither set stays in the 256 MB last-level cache
+        Ws = [rnd(rows, K, sc=0.02) for _ in range(copies)]
+        W8s = [ops.w8_quantize(w) for w in Ws]
+        bias = rnd(rows, sc=0.1) if name.startswith("CoreNet") else None
+        x, y = rnd(M, K), torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+        assert ops.linear_decode_w8_supported(M, N, K, geglu)
+        graphs = {}
+        for k, fn, ws in (("bf16", ops.linear_decode, Ws), ("fp8", ops.linear_decode_w8, W8s)):
+            fn(x, ws[0], bias, y, geglu=geglu)          # (workspace and tickets exist before the capture)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                for w in ws:
+                    fn(x, w, bias, y, geglu=geglu)
+            graphs[k] = gr
+        times = {k: [] for k in graphs}
+        for _ in range(rounds):
+            for k, gr in graphs.items():
+                times[k].append(device_us(gr.replay, replays) / copies)
+        for k, ws in (("bf16", Ws), ("fp8", W8s)):
+            us = float(np.median(times[k]))
+            nbytes = ws[0].numel() * ws[0].element_size()
+            rec[f"{name}_copies"] = copies
+            rec[f"{name}_{k}_us"] = round(us, 2)
+            rec[f"{name}_{k}_min_max_us"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+            rec[f"{name}_{k}_W_MB"] = round(nbytes / 1e6, 2)
+            rec[f"{name}_{k}_TBps"] = round(nbytes / (us * 1e-6) / 1e12, 3)
+        rec[f"{name}_fp8_over_bf16"] = round(rec[f"{name}_fp8_us"] / rec[f"{name}_bf16_us"], 4)
+        del Ws, W8s, graphs
+        torch.cuda.empty_cache()
     return rec
 
 
@@ -732,6 +786,16 @@ if "--ring-prefill" in args:   # the prompt prefills project only their own toke
     args = [a for a in args if a != "--ring-prefill"]
     _dumps = json.dumps
     json.dumps = lambda rec, **kw: _dumps(dict(rec, ring_prefill=True) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
+if "--w8-kernels" in args:
+    for M in [int(a) for a in args if a != "--w8-kernels"] or [1, 4, 16, 64]:
+        print(json.dumps(w8_kernels_us(M)), flush=True)
+    sys.exit(0)
+if "--decode-weights" in args:   # the decode calls stream fp8 copies of the layers' four linear maps (model.set_decode_weights)
+    i = args.index("--decode-weights")
+    model.set_decode_weights(args[i + 1])
+    args = args[:i] + args[i + 2:]
+    _dumps_dw = json.dumps
+    json.dumps = lambda rec, **kw: _dumps_dw(dict(rec, decode_weights=model.decode_weights) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
 TOP_N = None
 if "--top-logprobs" in args:
     i = args.index("--top-logprobs")
