@@ -27,6 +27,8 @@
 // M = 1 row: the products are VALU dot products (fp32 FMA, 8 bf16 of W per 16-byte load), the matrix pipe has nothing to gain at one row.
 // Arithmetic per element as the launches this replaces (db1_linear_decode_attn / db1_linear_decode): the merged attention row, the LayerNorm
 // inputs and outputs, z and act are rounded to bf16 where those store bf16; fp32 accumulation; results agree to fp32 summation order.
+// The same kernel over fp8 weights (db1_decode_chain_w8, template mode W8): the packed e4m3 copies of "fp8 decode weights" in place of the five
+// bf16 matrices; only the weight load sites and the widening differ ("fp8 weights" below), bit for bit this kernel over the dequantised weights.
 #include "ln_row.h"
 
 #define DC_D 2048
@@ -126,6 +128,50 @@ template <int NL> __device__ __forceinline__ float dc_dot(const DcRow<NL>& r, co
     return dc_wave_sum(acc);
 }
 
+// ---- fp8 weights (W8; include/db1_hip.h, "fp8 decode weights" / "fp8 weights in the persistent chain"): a weight [N, K] is N K payload bytes,
+// row-major, then N (K / 128) fp32 scales, row-major.  The lane-to-column map is the bf16 one: piece j of a row for this lane is columns
+// (j * 64 + lane) * 8 .. + 7 = the 8 payload bytes at row * K + (j * 64 + lane) * 8 (one 8-byte non-temporal load); all eight lie in block
+// (j * 64 + lane) >> 4 = j * 4 + lane / 16 of the row, whose scale is one dword load that 16 lanes share (4 addresses in one 64-byte line).  The
+// scales are requested WITH the row's payload, piece by piece (never behind a later stage's bulk requests).  A value is v_cvt_pk_f32_fp8 of
+// the payload times the scale in fp32 -- exact, and the bf16 value the dequantised weight holds (kv8_widen8_scaled keeps its upper half) -- and
+// enters the same fmaf chain in the same order: a launch is bit for bit the bf16 launch over the dequantised weights.
+typedef __attribute__((ext_vector_type(2))) unsigned dc_u32x2;
+typedef __attribute__((ext_vector_type(2))) float dc_f32x2;
+template <int NL> struct DcRow8 { dc_u32x2 w[NL]; float s[NL]; };
+template <bool W8, int NL> struct DcRowSel { typedef DcRow<NL> type; };
+template <int NL> struct DcRowSel<true, NL> { typedef DcRow8<NL> type; };
+// (pay, sc: the row's payload and its K / 128 scales)
+template <int NL> __device__ __forceinline__ void dc_load_row(DcRow8<NL>& r, const unsigned char* pay, const float* sc, int lane) {
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        r.w[j] = __builtin_nontemporal_load(reinterpret_cast<const dc_u32x2*>(pay + (j * 64 + lane) * 8));
+        r.s[j] = sc[j * 4 + (lane >> 4)];
+    }
+}
+__device__ __forceinline__ float dc_fma8(const dc_u32x2 w, const float sc, const dc_u32x4 x, float acc) {
+    const dc_f32x2 v[4] = {__builtin_amdgcn_cvt_pk_f32_fp8((int)w[0], false), __builtin_amdgcn_cvt_pk_f32_fp8((int)w[0], true),
+                           __builtin_amdgcn_cvt_pk_f32_fp8((int)w[1], false), __builtin_amdgcn_cvt_pk_f32_fp8((int)w[1], true)};
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        acc = fmaf(v[e][0] * sc, dc_lo(x[e]), acc);
+        acc = fmaf(v[e][1] * sc, dc_hi(x[e]), acc);
+    }
+    return acc;
+}
+template <int NL> __device__ __forceinline__ float dc_dot(const DcRow8<NL>& r, const bf16_t* xs, int lane) {
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < NL; j++) acc = dc_fma8(r.w[j], r.s[j], *reinterpret_cast<const dc_u32x4*>(xs + (j * 64 + lane) * 8), acc);
+    return dc_wave_sum(acc);
+}
+// row `row` of the packed [N, K] weight at `base` -> its payload and its scales
+template <int N, int K> __device__ __forceinline__ const unsigned char* dc_w8_pay(const bf16_t* base, int row) {
+    return reinterpret_cast<const unsigned char*>(base) + (int64_t)row * K;
+}
+template <int N, int K> __device__ __forceinline__ const float* dc_w8_sc(const bf16_t* base, int row) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(base) + (int64_t)N * K) + (int64_t)row * (K / 128);
+}
+
 // service wave: the words (k * 64 + lane) * 8 .. + 7 of a tagged row for two k, read past L1 / L2 (sc1)
 __device__ __forceinline__ void dc_read_pair(const unsigned* a, dc_u32x4& w0, dc_u32x4& w1, dc_u32x4& w2, dc_u32x4& w3) {
     asm volatile("global_load_dwordx4 %0, %4, off sc1\n\t"
@@ -167,11 +213,15 @@ template <int NP> __device__ __forceinline__ bool dc_poll_rest(const unsigned* r
     return false;
 }
 
-template <int NU>   // chunks of the attention partials the merge is unrolled for (>= att_nunit)
+// NU: chunks of the attention partials the merge is unrolled for (>= att_nunit).  W8: w_o, w1, w2, w_qkv and w_o_next are packed fp8 buffers
+// (above); only the weight load sites and the widening differ -- the merge, the stages, the barriers, the hand-off and the polls are one text.
+template <int NU, bool W8>
 __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChainArgs p) {
     // (separate LDS objects: the compiler then knows that reads of xs / res never touch the rows the LDS-DMA requests are still writing,
     //  and does not drain vmcnt before them)
     __shared__ __attribute__((aligned(16))) bf16_t xs[DC_DFF];
+    // (W8: 24 payload rows = 48 KB, then their 24 x 16 scales; the array keeps the bf16 size -- 104 KB of static LDS per workgroup, so that
+    //  a CU never takes a second workgroup of this grid, as the hand-off between 256 resident workgroups requires)
     __shared__ __attribute__((aligned(16))) char w3s[24 * DC_D * 2];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), bid = blockIdx.x;
     const bool last_layer = p.w_qkv == nullptr;
@@ -183,8 +233,9 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
 #pragma unroll
         for (int r = 0; r < 4; r++) bias1[r] = bf2f(p.b1[(r & 1 ? DC_DFF : 0) + bid * 16 + wave * 2 + (r >> 1)]);
         bias2 = bf2f(p.b2[bid * 8 + wave]);
-        DcRow<4> w0;                    // o_net: row bid * 8 + wave
-        dc_load_row(w0, p.w_o + (int64_t)(bid * 8 + wave) * DC_D, lane);
+        typename DcRowSel<W8, 4>::type w0;   // o_net: row bid * 8 + wave
+        if constexpr (W8) dc_load_row(w0, dc_w8_pay<DC_D, DC_D>(p.w_o, bid * 8 + wave), dc_w8_sc<DC_D, DC_D>(p.w_o, bid * 8 + wave), lane);
+        else dc_load_row(w0, p.w_o + (int64_t)(bid * 8 + wave) * DC_D, lane);
         DC_PIN();
         DC_TSW(0);
         // stage 0 input: the merge of the attention's chunk partials (worker thread t owns columns 4 t .. 4 t + 3 = head t / 32), the arithmetic
@@ -211,13 +262,18 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         }
         DC_PIN();
         DC_TSW(1);
-        DcRow<4> w1[4];                 // [0] value row pr0, [1] gate row pr0, [2] value row pr1, [3] gate row pr1
-        auto w1_row = [&](int r) { return p.w1 + (int64_t)((r & 1 ? DC_DFF : 0) + bid * 16 + wave * 2 + (r >> 1)) * DC_D; };
+        typename DcRowSel<W8, 4>::type w1[4];   // [0] value row pr0, [1] gate row pr0, [2] value row pr1, [3] gate row pr1
+        auto w1_load = [&](int r) {
+            const int row = (r & 1 ? DC_DFF : 0) + bid * 16 + wave * 2 + (r >> 1);
+            if constexpr (W8) dc_load_row(w1[r], dc_w8_pay<2 * DC_DFF, DC_D>(p.w1, row), dc_w8_sc<2 * DC_DFF, DC_D>(p.w1, row), lane);
+            else dc_load_row(w1[r], p.w1 + (int64_t)row * DC_D, lane);
+        };
 #pragma unroll
-        for (int r = 0; r < DC_W1_EARLY; r++) dc_load_row(w1[r], w1_row(r), lane);
+        for (int r = 0; r < DC_W1_EARLY; r++) w1_load(r);
         DC_PIN();
         DC_TSW(2);
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * DC_W1_EARLY) : "memory");   // W0 and the merge inputs have landed; the early W1 rows may be in flight
+        // W0 and the merge inputs have landed; the early W1 rows may be in flight (4 requests per row; W8: 4 payload + 4 scale requests)
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"((W8 ? 8 : 4) * DC_W1_EARLY) : "memory");
         {
             float mx = -1.0e30f;
 #pragma unroll
@@ -245,7 +301,7 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         // ---- stage 1: ff1 + GEGLU.  W2 requested now: a CU takes about 160 KB of requests before the requesting wave stalls in the issue
         // (W0 + W1 = 160 KB; with W2 on top the workers reached A0 at 5-7 us instead of 1.5 us)
 #pragma unroll
-        for (int r = DC_W1_EARLY; r < 4; r++) dc_load_row(w1[r], w1_row(r), lane);
+        for (int r = DC_W1_EARLY; r < 4; r++) w1_load(r);
         DC_PIN();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         DC_BARRIER();                                   // A1: LN1 row in LDS
@@ -259,8 +315,9 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         }
         DC_BARRIER();                                   // B1
         DC_BARRIER();                                   // C1
-        DcRow<8> w2;                    // ff2 row bid * 8 + wave (K = dff), requested behind the service wave's poll of the act row
-        dc_load_row(w2, p.w2 + (int64_t)(bid * 8 + wave) * DC_DFF, lane);
+        typename DcRowSel<W8, 8>::type w2;   // ff2 row bid * 8 + wave (K = dff), requested behind the service wave's poll of the act row
+        if constexpr (W8) dc_load_row(w2, dc_w8_pay<DC_D, DC_DFF>(p.w2, bid * 8 + wave), dc_w8_sc<DC_D, DC_DFF>(p.w2, bid * 8 + wave), lane);
+        else dc_load_row(w2, p.w2 + (int64_t)(bid * 8 + wave) * DC_DFF, lane);
         DC_PIN();
         // ---- stage 2: ff2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -281,9 +338,15 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         for (int j = 0; j < 3; j++) {
             float acc = 0.f;
 #pragma unroll
-            for (int i = 0; i < 4; i++)
-                acc = dc_fma8(*reinterpret_cast<const dc_u32x4*>(w3s + ((wave * 3 + j) * 4 + i) * 1024 + lane * 16),
-                              *reinterpret_cast<const dc_u32x4*>(xs + (i * 64 + lane) * 8), acc);
+            for (int i = 0; i < 4; i++) {
+                if constexpr (W8)   // the row is a straight copy of its 2048 payload bytes; its 16 scales follow the 24 rows
+                    acc = dc_fma8(*reinterpret_cast<const dc_u32x2*>(w3s + (wave * 3 + j) * DC_D + (i * 64 + lane) * 8),
+                                  *reinterpret_cast<const float*>(w3s + 24 * DC_D + ((wave * 3 + j) * 16 + i * 4 + (lane >> 4)) * 4),
+                                  *reinterpret_cast<const dc_u32x4*>(xs + (i * 64 + lane) * 8), acc);
+                else
+                    acc = dc_fma8(*reinterpret_cast<const dc_u32x4*>(w3s + ((wave * 3 + j) * 4 + i) * 1024 + lane * 16),
+                                  *reinterpret_cast<const dc_u32x4*>(xs + (i * 64 + lane) * 8), acc);
+            }
             const float s = dc_wave_sum(acc);
             if (lane == 0) p.qkv_next[bid * 24 + wave * 3 + j] = f2bf(s);   // (no bias; read by the NEXT launch: a plain store is enough)
         }
@@ -303,14 +366,33 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         // the next launch opens with a cold read of ITS o_net rows: ask for one dword of each of their 128-byte lines now -- same workgroup
         // index = same XCD = same L2 next time; the values are dropped
         unsigned touch0 = 0, touch1 = 0;
-        if (p.w_o_next) {
+        if constexpr (W8) {
+            if (p.w_o_next) {   // the payload of the workgroup's 8 rows: 16 KB = 128 lines, 64 per wave
+                touch0 = *reinterpret_cast<const unsigned*>(dc_w8_pay<DC_D, DC_D>(p.w_o_next, bid * 8 + v * 4) + lane * 128);
+            }
+        } else if (p.w_o_next) {
             const char* nx = reinterpret_cast<const char*>(p.w_o_next + (int64_t)(bid * 8 + v * 4) * DC_D) + lane * 128;   // this wave: 4 rows = 16 KB = 128 lines
             touch0 = *reinterpret_cast<const unsigned*>(nx); touch1 = *reinterpret_cast<const unsigned*>(nx + 8192);
         }
         DC_BARRIER();                                   // B1
         DC_BARRIER();                                   // C1
         DC_BARRIER();                                   // A2: W0, W1 and W2 have landed in every wave of the workgroup -- the CU's request queue is empty
-        if (!last_layer) {
+        if constexpr (W8) {
+            if (!last_layer) {
+                // this wave's 12 rows: their 192 scales first (contiguous: 3 dword requests of 256 bytes, lane-linear in LDS), then the payload,
+                // two 16-byte requests of 1 KiB per row
+                const float* sc = dc_w8_sc<3 * DC_D, DC_D>(p.w_qkv, bid * 24 + v * 12);
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+                    __builtin_amdgcn_global_load_lds(sc + k * 64 + lane, (__attribute__((address_space(3))) void*)(w3s + 24 * DC_D + v * 768 + k * 256), 4, 0, 0);
+#pragma unroll
+                for (int j = 0; j < 12; j++)
+#pragma unroll
+                    for (int i = 0; i < 2; i++)
+                        __builtin_amdgcn_global_load_lds(dc_w8_pay<3 * DC_D, DC_D>(p.w_qkv, bid * 24 + v * 12 + j) + i * 1024 + lane * 16,
+                                                         (__attribute__((address_space(3))) void*)(w3s + (v * 12 + j) * DC_D + i * 1024), 16, 0, 0);
+            }
+        } else if (!last_layer) {
 #pragma unroll
             for (int j = 0; j < 12; j++)
 #pragma unroll
@@ -454,14 +536,19 @@ extern "C" int db1_decode_chain_supported(int d, int dff, int H, int D, int nuni
 extern "C" int64_t db1_decode_chain_error_offset(void) { return (int64_t)(2 * DC_D + DC_DFF) * 4; }
 extern "C" int64_t db1_decode_chain_scratch_bytes(void) { return db1_decode_chain_error_offset() + 64; }
 
-extern "C" int db1_decode_chain(const float* att_part, int nunit, int H, const void* x_res, const void* w_o, const void* w1, const void* b1, const void* w2,
-                                const void* b2, const void* w_qkv_next, const void* w_o_next, const void* g1, const void* be1, const void* g2, const void* be2, float alpha, float eps,
-                                void* h1_out, void* f_out, void* x_next, void* qkv_next, void* scratch, int slot, int d, int dff, void* stream) {
+extern "C" int db1_decode_chain_w8_supported(int d, int dff, int H, int D, int nunit) { return db1_decode_chain_supported(d, dff, H, D, nunit); }
+
+// db1_decode_chain (w8 = false) and db1_decode_chain_w8 (w8 = true: w_o, w1, w2, w_qkv_next and w_o_next are packed fp8 buffers): one argument
+// check, one scratch, one slot rule
+static int dc_launch(bool w8, const float* att_part, int nunit, int H, const void* x_res, const void* w_o, const void* w1, const void* b1, const void* w2,
+                     const void* b2, const void* w_qkv_next, const void* w_o_next, const void* g1, const void* be1, const void* g2, const void* be2, float alpha, float eps,
+                     void* h1_out, void* f_out, void* x_next, void* qkv_next, void* scratch, int slot, int d, int dff, void* stream) {
     if (!db1_decode_chain_supported(d, dff, H, 128, nunit)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "decode_chain: d=%d dff=%d H=%d chunks=%d (built for d 2048, dff 4096, d_head 128, <= 12 chunks)", d, dff, H, nunit);
     if (slot < 0 || slot >= DC_SLOTS) DB1_FAIL(DB1_ERR_BAD_SHAPE, "decode_chain: slot %d", slot);
     if (!att_part || !x_res || !w_o || !w1 || !b1 || !w2 || !b2 || !g1 || !be1 || !g2 || !be2 || !scratch || (w_qkv_next && (!x_next || !qkv_next)) || (!w_qkv_next && (!h1_out || !f_out)))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "decode_chain: null operand");
     if (!db1_aligned16(x_res) || !db1_aligned16(w_o) || !db1_aligned16(w1) || !db1_aligned16(w2) || (w_qkv_next && !db1_aligned16(w_qkv_next)) || !db1_aligned16(scratch) ||
+        (w8 && w_o_next && !db1_aligned16(w_o_next)) ||
         !db1_aligned16(g1) || !db1_aligned16(be1) || !db1_aligned16(g2) || !db1_aligned16(be2) || (x_next && !db1_aligned16(x_next)) || (h1_out && !db1_aligned16(h1_out)) ||
         (qkv_next && ((uintptr_t)qkv_next & 7)) || (f_out && ((uintptr_t)f_out & 3)))
         DB1_FAIL(DB1_ERR_BAD_ALIGN, "decode_chain: operands must be 16-byte aligned");
@@ -476,8 +563,24 @@ extern "C" int db1_decode_chain(const float* att_part, int nunit, int H, const v
     a.tag = (unsigned)slot + 1u;
     a.ts = (g_dc_ts_slot < 0 || g_dc_ts_slot == slot) ? g_dc_ts : nullptr;
     a.h1_out = (bf16_t*)h1_out; a.f_out = (bf16_t*)f_out; a.x_next = (bf16_t*)x_next; a.qkv_next = (bf16_t*)qkv_next;
-    if (nunit <= 9) decode_chain_kernel<9><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);   // (mem_len 1024 + 1 token = 9 chunks)
-    else decode_chain_kernel<12><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);
+    if (w8) {
+        if (nunit <= 9) decode_chain_kernel<9, true><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);
+        else decode_chain_kernel<12, true><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);
+    } else {
+        if (nunit <= 9) decode_chain_kernel<9, false><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);   // (mem_len 1024 + 1 token = 9 chunks)
+        else decode_chain_kernel<12, false><<<DC_WG, DC_THREADS, 0, (hipStream_t)stream>>>(a);
+    }
     DB1_CHECK_LAUNCH("decode_chain");
     return DB1_OK;
+}
+
+extern "C" int db1_decode_chain(const float* att_part, int nunit, int H, const void* x_res, const void* w_o, const void* w1, const void* b1, const void* w2,
+                                const void* b2, const void* w_qkv_next, const void* w_o_next, const void* g1, const void* be1, const void* g2, const void* be2, float alpha, float eps,
+                                void* h1_out, void* f_out, void* x_next, void* qkv_next, void* scratch, int slot, int d, int dff, void* stream) {
+    return dc_launch(false, att_part, nunit, H, x_res, w_o, w1, b1, w2, b2, w_qkv_next, w_o_next, g1, be1, g2, be2, alpha, eps, h1_out, f_out, x_next, qkv_next, scratch, slot, d, dff, stream);
+}
+extern "C" int db1_decode_chain_w8(const float* att_part, int nunit, int H, const void* x_res, const void* w_o8, const void* w1_8, const void* b1, const void* w2_8,
+                                   const void* b2, const void* w_qkv_next8, const void* w_o_next8, const void* g1, const void* be1, const void* g2, const void* be2, float alpha, float eps,
+                                   void* h1_out, void* f_out, void* x_next, void* qkv_next, void* scratch, int slot, int d, int dff, void* stream) {
+    return dc_launch(true, att_part, nunit, H, x_res, w_o8, w1_8, b1, w2_8, b2, w_qkv_next8, w_o_next8, g1, be1, g2, be2, alpha, eps, h1_out, f_out, x_next, qkv_next, scratch, slot, d, dff, stream);
 }

@@ -336,6 +336,7 @@ class TransformerXL(nn.Module):
         self.use_decode_chain = os.environ.get("DB1_DECODE_CHAIN", "1") != "0"   # ... ONE token (ring memory): the linear maps between two attention launches as one persistent launch (db1_decode_chain)
         self._chain_watch = None         # (pinned copy of the chain's error flag, its scratch) of the last chain call: check_decode_chain()
         self.decode_weights = "bf16"     # "fp8": the fused decode branch streams e4m3 copies of the layers' four linear maps (set_decode_weights)
+        self._decode_chain_w8 = False    # ... and the one-token persistent chain does too (set_decode_weights("fp8", chain=True)): decode_chain_w8
         self._w8 = None                  # (version, {parameter name: packed buffer}) -- packed on the first fp8 decode call of a weight version
         self._wversion = 0               # bumped whenever the weights change (invalidates the inference caches)
         self._dec_state = None           # K/V cache of the memory returned by the last forward (see _decode_begin)
@@ -462,7 +463,12 @@ class TransformerXL(nn.Module):
     # ---- fp8 decode weights (include/db1_hip.h, "fp8 decode weights")
     W8_MAPS = ("dec_attn.qkv_net.weight", "dec_attn.o_net.weight", "pos_ff.CoreNet.0.weight", "pos_ff.CoreNet.2.weight")
 
-    def set_decode_weights(self, fmt: str):
+    @property
+    def decode_chain_w8(self) -> bool:
+        """does the one-token persistent chain stream the fp8 copies (``set_decode_weights("fp8", chain=True)``)?  Read-only."""
+        return self._decode_chain_w8
+
+    def set_decode_weights(self, fmt: str, *, chain: bool = False):
         """``"bf16"`` (the default) or ``"fp8"``: what the decode calls stream as the layers' linear maps.
 
         Under ``"fp8"`` every decode call -- at most 64 new tokens over a memory: generate, beam_search, sample_best_of, the streams, the
@@ -471,7 +477,12 @@ class TransformerXL(nn.Module):
         (db1_linear_decode_w8 / db1_linear_decode_attn_w8): 0.516 of the bf16 bytes per token, and bit for bit the bf16 launches over the
         dequantised copies.  The copies are packed on the first such call of a weight version (``mark_weights_changed`` drops them); that
         call must run eagerly -- GraphedRingStep's warm-up does -- and raises RuntimeError under a graph capture.  The one-token
-        persistent chain (``use_decode_chain``) is not taken under ``"fp8"``: the per-layer launches with the attention-merge prologue are.
+        persistent chain (``use_decode_chain``) is not taken under ``"fp8"`` alone: the per-layer launches with the attention-merge prologue
+        are.  ``chain=True`` (keyword, with ``"fp8"`` only; ``model.decode_chain_w8`` reads it back) keeps the one-token call on the chain:
+        db1_decode_chain_w8 streams the same packed copies, bit for bit the bf16 chain over the dequantised weights, and layer 0's own
+        projection runs as db1_linear_decode_w8 -- no bf16 copy of the four maps is streamed.  It needs what the chain needs (d_model 2048,
+        d_ff 4096, d_head 128, mem_len + 1 <= 1536 keys, n_layer >= 2, a device with 256 CUs: ValueError otherwise), and falls back to the
+        fp8 per-layer launches after a failed hand-off (``check_decode_chain``) like the bf16 chain falls back to its own.  Off by default.
         On bf16 stay: the head, the embedders, r_net, every call of more than 64 tokens (prefills, the ring prefill, PrefixCache.put) and
         any decode call that falls off the fused branch (``keep``, dropout, ``use_decode_fused = False``).
 
@@ -494,8 +505,15 @@ class TransformerXL(nn.Module):
                 why = "LayerNorm weights and biases of one dtype (the fused decode branch)"
             if why is not None:
                 raise ValueError(f"set_decode_weights('fp8') needs {why}")
-        if fmt != self.decode_weights:
-            self.decode_weights = fmt
+        chain = bool(chain)
+        if chain:
+            if fmt != "fp8":
+                raise ValueError("set_decode_weights: chain=True selects the fp8 persistent chain and needs fmt='fp8'")
+            if self.n_layer < 2 or not ops.decode_chain_w8_supported(self.d_model, self.d_ff, self.n_head, self.d_head, int(self.mem_len or 0) + 1):
+                raise ValueError("set_decode_weights('fp8', chain=True) needs the persistent chain's geometry (d_model 2048, d_ff 4096, d_head 128, "
+                                 "mem_len + 1 <= 1536), n_layer >= 2 and a device with at least 256 compute units")
+        if fmt != self.decode_weights or chain != self._decode_chain_w8:
+            self.decode_weights, self._decode_chain_w8 = fmt, chain
             self.mark_weights_changed()
 
     def W8(self, name: str) -> torch.Tensor:
@@ -1319,8 +1337,9 @@ class TransformerXL(nn.Module):
         self._win_on = False
         if self.bwd_window_ga > 1 and keep and self.training and mems is None and ring is None:
             R_in = self._window_begin(B, L, shift, R_in, dstep)      # (deferred backward: this micro-step's position table joins the window's)
-        # (the persistent chain streams the bf16 weights: under decode_weights == "fp8" the per-layer launches below run instead)
-        if (ring is not None and B * L == 1 and self.use_decode_chain and self.decode_weights != "fp8" and getattr(dec, "partials", False) and self.activation_fn == "geglu" and self.n_layer >= 2 and
+        # (the persistent chain streams the bf16 weights, or -- decode_chain_w8 -- the fp8 copies; under decode_weights == "fp8" alone the
+        #  per-layer launches below run instead)
+        if (ring is not None and B * L == 1 and self.use_decode_chain and (self.decode_weights != "fp8" or self._decode_chain_w8) and getattr(dec, "partials", False) and self.activation_fn == "geglu" and self.n_layer >= 2 and
                 ops.decode_chain_supported(d, self.d_ff, self.n_head, self.d_head, mlen + L)):
             x = self._decode_chain_layers(x, mlen, shift, dec)
             hids, lcs = [], []
@@ -1481,8 +1500,13 @@ class TransformerXL(nn.Module):
         d, H, D, n = self.d_model, self.n_head, self.d_head, self.n_layer
         a = 1.0 if self.deepnorm_alpha is None else self.deepnorm_alpha
         W = self.W
+        w8 = self.decode_weights == "fp8"      # (decode_chain_w8: the chain and layer 0's projection stream the packed fp8 copies)
+        Wm, chain = (self.W8, ops.decode_chain_w8) if w8 else (W, ops.decode_chain)
         qkv = self._new(1, 3 * d)
-        ops.gemm(x, W("h.0.dec_attn.qkv_net.weight").t(), qkv)
+        if w8:
+            ops.linear_decode_w8(x, Wm("h.0.dec_attn.qkv_net.weight"), None, qkv)
+        else:
+            ops.gemm(x, W("h.0.dec_attn.qkv_net.weight").t(), qkv)
         h1_out, f_out = self._new(1, d), self._new(1, d)
         for i in range(n):
             p = f"h.{i}."
@@ -1490,11 +1514,11 @@ class TransformerXL(nn.Module):
             last = i == n - 1
             x_next = None if last else self._new(1, d)
             qkv_next = None if last else self._new(1, 3 * d)
-            ops.decode_chain(part, mlen + 1, H, x, W(p + "dec_attn.o_net.weight"), W(p + "pos_ff.CoreNet.0.weight"), W(p + "pos_ff.CoreNet.0.bias"),
-                             W(p + "pos_ff.CoreNet.2.weight"), W(p + "pos_ff.CoreNet.2.bias"), None if last else W(f"h.{i + 1}.dec_attn.qkv_net.weight"),
-                             W(p + "dec_attn.layer_norm.weight"), W(p + "dec_attn.layer_norm.bias"), W(p + "pos_ff.layer_norm.weight"),
-                             W(p + "pos_ff.layer_norm.bias"), a, self.layer_norm_epsilon, h1_out if last else None, f_out if last else None, x_next, qkv_next, i,
-                             w_o_next=W(f"h.{(i + 1) % n}.dec_attn.o_net.weight"))
+            chain(part, mlen + 1, H, x, Wm(p + "dec_attn.o_net.weight"), Wm(p + "pos_ff.CoreNet.0.weight"), W(p + "pos_ff.CoreNet.0.bias"),
+                  Wm(p + "pos_ff.CoreNet.2.weight"), W(p + "pos_ff.CoreNet.2.bias"), None if last else Wm(f"h.{i + 1}.dec_attn.qkv_net.weight"),
+                  W(p + "dec_attn.layer_norm.weight"), W(p + "dec_attn.layer_norm.bias"), W(p + "pos_ff.layer_norm.weight"),
+                  W(p + "pos_ff.layer_norm.bias"), a, self.layer_norm_epsilon, h1_out if last else None, f_out if last else None, x_next, qkv_next, i,
+                  w_o_next=Wm(f"h.{(i + 1) % n}.dec_attn.o_net.weight"))
             if not last:
                 x, qkv = x_next, qkv_next
         # the chain's hand-off polls are bounded: if one ran out (a co-tenant kernel, a CU mask: not all 256 workgroups resident) the

@@ -1804,6 +1804,29 @@ def linear_decode_attn_w8(part, klen, B, q, H, D, W8, y):
     lib.call("db1_linear_decode_attn_w8", P(part), (int(klen) + 127) // 128, B, q, H, D, P(W8), P(y), y.stride(0), y.shape[1], stream())
 
 
+def decode_chain_w8_supported(d, dff, H, D, klen) -> bool:
+    return bool(lib.load().db1_decode_chain_w8_supported(int(d), int(dff), int(H), int(D), (int(klen) + 127) // 128))
+
+
+def decode_chain_w8(part, klen, H, x_res, w_o8, w1_8, b1, w2_8, b2, w_qkv_next8, g1, be1, g2, be2, alpha, eps, h1_out, f_out, x_next, qkv_next, slot, w_o_next=None):
+    """decode_chain with o_net, ff1, ff2, the next layer's qkv_net and ``w_o_next`` as packed fp8 buffers (w8_quantize of the [d, d],
+    [2 dff, d], [d, dff], [3 d, d] and [d, d] weights; db1_decode_chain_w8): bit for bit decode_chain over w8_unpack of them.  d and dff are
+    read from the bf16 operands (x_res, b1); the same scratch and slot rule as decode_chain."""
+    for t in (x_res, b1, b2, g1, be1, g2, be2):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError("decode_chain_w8: the input row, the biases and the LayerNorm parameters must be contiguous bf16 tensors")
+    d, dff, dev = x_res.numel(), b1.numel() // 2, x_res.device
+    for name, t, N, K in (("w_o8", w_o8, d, d), ("w1_8", w1_8, 2 * dff, d), ("w2_8", w2_8, d, dff), ("w_qkv_next8", w_qkv_next8, 3 * d, d), ("w_o_next", w_o_next, d, d)):
+        if t is None and name in ("w_qkv_next8", "w_o_next"):
+            continue
+        # (the size is the format's own rule, N K + 4 N K / 128: a wrong buffer is refused before the library is touched)
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.device != dev or K % 128 or
+                t.numel() != N * K + 4 * N * (K // 128)):
+            raise ValueError(f"decode_chain_w8: {name} must be the packed uint8 buffer of a [{N}, {K}] matrix on {dev} (w8_quantize; K % 128 == 0)")
+    lib.call("db1_decode_chain_w8", P(part), (int(klen) + 127) // 128, int(H), P(x_res), P(w_o8), P(w1_8), P(b1), P(w2_8), P(b2), P(w_qkv_next8), P(w_o_next), P(g1), P(be1),
+             P(g2), P(be2), float(alpha), float(eps), P(h1_out), P(f_out), P(x_next), P(qkv_next), P(decode_chain_scratch(x_res.device)), int(slot), int(d), int(dff), stream())
+
+
 def _w8_check(W8, N, K, device, who):
     if W8.dtype != torch.uint8 or W8.dim() != 1 or not W8.is_contiguous() or W8.device != device or K % 128 or W8.numel() != w8_bytes(N, K):
         raise ValueError(f"{who}: the weight must be the packed uint8 buffer of a [{N}, {K}] matrix on {device} (w8_quantize; K % 128 == 0)")

@@ -431,6 +431,23 @@ int db1_linear_decode_w8(const void* x, int64_t ldx, const void* w8, const void*
                          void* stream);
 int db1_linear_decode_attn_w8_supported(int B, int q, int H, int D, int nunit, int N);
 int db1_linear_decode_attn_w8(const float* attn_part, int nunit, int B, int q, int H, int D, const void* w8, void* y, int64_t ldy, int N, void* stream);
+/* fp8 weights in the persistent chain (csrc/decode_chain.hip; tests/w8_chain_rule.py restates the map in NumPy).
+ * db1_decode_chain_w8: the argument list of db1_decode_chain with w_o, w1, w2, w_qkv_next and w_o_next as packed buffers of the format above
+ * ([d, d], [2 dff, d], [d, dff], [3 d, d], [d, d]; the same copies the launches above read).  Biases and LayerNorm parameters stay bf16.  Same
+ * scratch (db1_decode_chain_scratch_bytes / _error_offset), same slot rule: a bf16 launch and an fp8 launch may follow each other on one
+ * scratch with different slots.  Only the weight load sites and the widening differ from the bf16 kernel.  The lane-to-column map is kept:
+ *     piece j of a row (K columns) for lane l (0 .. 63) = columns (64 j + l) 8 .. + 7 = the 8 payload bytes at row K + (64 j + l) 8,
+ *     all in scale block (64 j + l) >> 4 = 4 j + l / 16 of the row (K / 128 blocks: 16 for o_net, ff1 and qkv rows, 32 for ff2 rows).
+ * A value is v_cvt_pk_f32_fp8 of the payload times the block's scale in fp32 (exact) and enters the bf16 kernel's fmaf chain in its order
+ * (elements 0 .. 7 of piece 0, then piece 1, ...) and its wave sum: a launch is BIT FOR BIT db1_decode_chain over the dequantised weights
+ * (ops.w8_unpack), as long as no dequantised value is subnormal in bf16.
+ * _w8_supported: what db1_decode_chain_supported accepts.  Refused before anything is launched, with db1_decode_chain's codes: a geometry the
+ * query refuses (DB1_ERR_UNSUPPORTED), a slot out of range or a NULL operand (DB1_ERR_BAD_SHAPE), a buffer that is not 16-byte aligned
+ * (DB1_ERR_BAD_ALIGN; here w_o_next too: its payload is read as the launch's own rows are). */
+int db1_decode_chain_w8_supported(int d, int dff, int H, int D, int nunit);
+int db1_decode_chain_w8(const float* att_part, int nunit, int H, const void* x_res, const void* w_o8, const void* w1_8, const void* b1, const void* w2_8,
+                        const void* b2, const void* w_qkv_next8, const void* w_o_next8, const void* g1, const void* be1, const void* g2, const void* be2,
+                        float alpha, float eps, void* h1_out, void* f_out, void* x_next, void* qkv_next, void* scratch, int slot, int d, int dff, void* stream);
 
 /* ------------------------------------------------------------------ relative-position attention, materialised path
  * (fp32 parity gate, any head size).  Buffers S,T are float32 in [H][B][Lq][*] layout.

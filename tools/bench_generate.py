@@ -108,6 +108,17 @@ each, with the ring bytes a call reads and the rate they amount to.
 linear maps, and the one-token call takes the per-layer launches instead of the persistent chain; every line carries "decode_weights".
 
     python tools/bench_generate.py --decode-weights fp8 [M ...]
+    python tools/bench_generate.py --decode-weights fp8 --fp8-chain [M ...]   (``set_decode_weights("fp8", chain=True)``: the one-token call
+                                                                               stays on the persistent chain, db1_decode_chain_w8; every
+                                                                               line carries "decode_chain_w8": true)
+
+--chain-kernels: db1_decode_chain and db1_decode_chain_w8 alone, a layer's launch with the next layer's projection at mlen = 1024, in
+alternation in ONE process.  Each side is a captured graph of one launch over each of 12 distinct sets of the five weights (1 GB of bf16,
+520 MB of fp8: more than the last-level cache holds); device time per launch from events over 5 replays, the median of 7 rounds with
+min .. max, the bytes of W a launch streams, and workgroup 0's stage times (db1_test_decode_chain_timestamps) of the last launch of an eager
+sweep, the median of 3, so the record shows which stage the bytes came out of.
+
+    python tools/bench_generate.py --chain-kernels
 
 --w8-kernels [M ...] (default 1 4 16 64): db1_linear_decode and db1_linear_decode_w8 alone at the model's four layer shapes (qkv_net, o_net,
 CoreNet.0 through GEGLU, CoreNet.2), in alternation in ONE process.  Each side is a captured graph of one launch over each of n copies of
@@ -239,6 +250,76 @@ def w8_kernels_us(M, rounds=7, replays=5):
         rec[f"{name}_fp8_over_bf16"] = round(rec[f"{name}_fp8_us"] / rec[f"{name}_bf16_us"], 4)
         del Ws, W8s, graphs
         torch.cuda.empty_cache()
+    return rec
+
+
+CHAIN_STAMPS = ("start", "A0", "B0", "y_o polled", "LN1", "A1", "B1", "act polled", "act in LDS", "A2", "B2", "f polled", "LN2", "A3")
+
+
+def chain_kernels_us(copies=12, rounds=7, replays=5, mlen=1024):
+    """db1_decode_chain and db1_decode_chain_w8 alone: a layer's launch (with the next layer's projection) over ``copies`` distinct sets of the
+    five weights, bf16 against fp8 (the docstring above says how), and workgroup 0's stage times of one launch of each"""
+    import ctypes
+    d, dff, H, D = model.d_model, model.d_ff, model.n_head, model.d_head
+    assert ops.decode_chain_w8_supported(d, dff, H, D, mlen + 1)
+    nunit = (mlen + 1 + 127) // 128
+    g = torch.Generator(device=dev).manual_seed(1)
+    rnd = lambda *s, sc=1.0: (torch.randn(*s, device=dev, generator=g) * sc).to(torch.bfloat16)
+    shapes = (("o", d, d), ("w1", 2 * dff, d), ("w2", d, dff), ("qkv", 3 * d, d))
+    Ws = [{k: rnd(N, K, sc=0.02) for k, N, K in shapes} for _ in range(copies)]      # 84 MB of bf16 per copy, 43 MB of fp8
+    W8s = [{k: ops.w8_quantize(w) for k, w in ws.items()} for ws in Ws]
+    x, b1, b2 = rnd(1, d), rnd(2 * dff, sc=0.1), rnd(d, sc=0.1)
+    g1, be1, g2, be2 = 1 + rnd(d, sc=0.1), rnd(d, sc=0.1), 1 + rnd(d, sc=0.1), rnd(d, sc=0.1)
+    part = torch.zeros(H, nunit, 64, D + 2, device=dev)
+    part[:, :, 0, :D] = torch.randn(H, nunit, D, device=dev, generator=g)
+    part[:, :, 0, D] = torch.randn(H, nunit, device=dev, generator=g)
+    part[:, :, 0, D + 1] = torch.rand(H, nunit, device=dev, generator=g) + 0.5
+    xn, qn = torch.empty(1, d, device=dev, dtype=torch.bfloat16), torch.empty(1, 3 * d, device=dev, dtype=torch.bfloat16)
+    sides = {"bf16": (ops.decode_chain, Ws), "fp8": (ops.decode_chain_w8, W8s)}
+
+    def sweep(k):       # one launch per copy, consecutive slots; each touches the o_net rows of the next, as a model's layers do
+        fn, ws = sides[k]
+        for i, w in enumerate(ws):
+            fn(part, mlen + 1, H, x, w["o"], w["w1"], b1, w["w2"], b2, w["qkv"], g1, be1, g2, be2, 1.0, 1e-5, None, None, xn, qn, i, w_o_next=ws[(i + 1) % copies]["o"])
+    scratch = ops.new_chain_scratch(dev)
+    off = int(lib.load().db1_decode_chain_error_offset())
+    rec = {"copies": copies, "mlen": mlen}
+    with ops.chain_scratch_scope(*scratch):
+        graphs = {}
+        for k in sides:
+            sweep(k)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                sweep(k)
+            graphs[k] = gr
+        times = {k: [] for k in graphs}
+        for _ in range(rounds):
+            for k, gr in graphs.items():
+                times[k].append(device_us(gr.replay, replays) / copies)
+        # stage times: the last launch of an eager sweep (its weights were read a whole sweep ago), workgroup 0's service wave, us since its start
+        L = lib.load()
+        L.db1_test_decode_chain_timestamps.restype = None
+        ts = torch.zeros(16 + 2048, dtype=torch.int64, device=dev)
+        for k in sides:
+            stamps = []
+            for _ in range(3):
+                L.db1_test_decode_chain_timestamps(ctypes.c_void_p(ts.data_ptr()), copies - 1)
+                sweep(k)
+                torch.cuda.synchronize()
+                t = ts.cpu().numpy().astype(np.float64)
+                stamps.append((t[1:len(CHAIN_STAMPS)] - t[0]) / 100)
+            L.db1_test_decode_chain_timestamps(ctypes.c_void_p(0), -1)
+            rec[f"{k}_stage_us"] = dict(zip(CHAIN_STAMPS[1:], np.round(np.median(stamps, axis=0), 2).tolist()))
+    assert int(scratch[0][off:off + 4].view(torch.int32).item()) == 0, "a hand-off poll ran into its limit"
+    for k, (_, ws) in sides.items():
+        us = float(np.median(times[k]))
+        nbytes = sum(w.numel() * w.element_size() for w in ws[0].values())
+        rec[f"{k}_us"] = round(us, 2)
+        rec[f"{k}_min_max_us"] = [round(min(times[k]), 2), round(max(times[k]), 2)]
+        rec[f"{k}_W_MB"] = round(nbytes / 1e6, 2)
+        rec[f"{k}_TBps"] = round(nbytes / (us * 1e-6) / 1e12, 3)
+    rec["fp8_over_bf16"] = round(rec["fp8_us"] / rec["bf16_us"], 4)
     return rec
 
 
@@ -790,12 +871,17 @@ if "--w8-kernels" in args:
     for M in [int(a) for a in args if a != "--w8-kernels"] or [1, 4, 16, 64]:
         print(json.dumps(w8_kernels_us(M)), flush=True)
     sys.exit(0)
+if "--chain-kernels" in args:
+    print(json.dumps(chain_kernels_us()), flush=True)
+    sys.exit(0)
 if "--decode-weights" in args:   # the decode calls stream fp8 copies of the layers' four linear maps (model.set_decode_weights)
     i = args.index("--decode-weights")
-    model.set_decode_weights(args[i + 1])
-    args = args[:i] + args[i + 2:]
+    fp8_chain = "--fp8-chain" in args       # ... and the one-token call stays on the persistent chain (db1_decode_chain_w8)
+    model.set_decode_weights(args[i + 1], chain=fp8_chain)
+    args = [a for a in args[:i] + args[i + 2:] if a != "--fp8-chain"]
     _dumps_dw = json.dumps
-    json.dumps = lambda rec, **kw: _dumps_dw(dict(rec, decode_weights=model.decode_weights) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
+    _dw_fields = lambda: dict(decode_weights=model.decode_weights, **({"decode_chain_w8": True} if model.decode_chain_w8 else {}))
+    json.dumps = lambda rec, **kw: _dumps_dw(dict(rec, **_dw_fields()) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
 TOP_N = None
 if "--top-logprobs" in args:
     i = args.index("--top-logprobs")
