@@ -3,7 +3,7 @@
 Importing the package does not need a GPU; constructing a model or calling an op does, and raises
 if libdb1_hip.so or a gfx950 device is missing (there is no CPU fallback).
 """
-__all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "RingPrefill", "GraphedTrainStep",
+__all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRingStep", "RingMemory", "RingPrefill", "GroupedRingMemory", "GraphedTrainStep",
            "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
            "DecodingConstraints", "SamplingParams", "sample_best_of", "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers", "score_document", "document_segments",
            "generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler",
@@ -20,7 +20,7 @@ def __getattr__(name):
     if name == "GraphedMemoryStep":
         from .decode import GraphedMemoryStep
         return GraphedMemoryStep
-    if name in ("GraphedRingStep", "RingMemory", "RingPrefill"):
+    if name in ("GraphedRingStep", "RingMemory", "RingPrefill", "GroupedRingMemory"):
         from . import decode
         return getattr(decode, name)
     if name == "GraphedTrainStep":

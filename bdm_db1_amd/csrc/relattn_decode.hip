@@ -563,3 +563,244 @@ extern "C" int db1_relattn_decode_fwd(const void* qu, const void* qv, const void
     DB1_CHECK_LAUNCH("relattn_decode_merge");
     return DB1_OK;
 }
+
+// ======================================================================================= grouped variant (beam search / best-of-n sampling)
+// The M = G W rows of a beam search or a best-of-n sampling share their group's prompt: ONE base ring row per group [G, cap_b, 2, H, D]
+// (filled by the prefill, never moved while decoding) and a short tail ring per row [M, cap_t, 2, H, D] with the keys the row generated
+// itself (the rule: include/db1_hip.h, "grouped K/V ring"; tests/group_ring_rule.py).  One new token per row (q = 1), one launch of
+//   shared units  (128 base positions, head, group, 16-row tile of the group): the chunk's K / V are loaded ONCE, the MFMA's 16 query columns
+//                 are the rows g W + 16 tile + a (columns past W repeat the last row, never stored).  Every column is query 0, so a key's
+//                 distance is the same in all columns: the relative term is R[dist(key)] . (q + v) accumulated onto K . (q + u) by the same
+//                 accumulator -- 32 R rows per 32-key step, no LDS scratch, no skewed read-back.
+//   private units (128 tail positions, head, row): the ring kernel's q = 1 form over the row's own tail and the call's own key, which the
+//                 unit that holds tail position Lt appends.
+// A workgroup's four waves are its four 32-position steps, merged through LDS as in the ring kernel; a step outside [first, last] visible
+// position loads nothing.  Partials: [G][H][nunit][64][D + 2] with (G, W) in the place of (B, q) and the units in the order (shared chunks by
+// position, private chunks by position): relattn_decode_merge2_kernel merges them in that fixed order.
+struct DecodeGroupArgs {
+    const bf16_t* qkv; const bf16_t* u; const bf16_t* vb; const bf16_t* base; const int* state_b; bf16_t* tail; const int* state_t; const int* n_tail;
+    const bf16_t* R; float* part; int* status;
+    int G, W, mlen, Lt, H, shift, nd, nunit, nb, ntile, cap_b, cap_t;
+    float scale;
+};
+template <bool PRIV>
+__device__ __forceinline__ void decode_group_unit(const DecodeGroupArgs& p, char* smem, const int chunk, const int sub, const int sb, const int st_, const int ntl) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = blockIdx.y, grp = blockIdx.z;
+    const int a = lane & 15, lg = lane >> 4;
+    const int HD = p.H * DEC_D;
+    char* Vs = smem + wave * DEC_WAVE_LDS;
+    // PRIV: sub = the row inside the group, every column is that row.  Shared: sub = the 16-row tile, column a is row 16 sub + a (clamped)
+    const int wq = PRIV ? sub : (16 * sub + a < p.W ? 16 * sub + a : p.W - 1);
+    const int64_t row = (int64_t)grp * p.W + wq;
+    const bf16_t* qrow = p.qkv + row * 3 * HD + h * DEC_D + lg * 8;
+    bf16x8_t qraw[4], uraw[4], vraw[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ks++) {
+        qraw[ks] = *reinterpret_cast<const bf16x8_t*>(qrow + ks * 32);
+        uraw[ks] = *reinterpret_cast<const bf16x8_t*>(p.u + h * DEC_D + lg * 8 + ks * 32);
+        vraw[ks] = *reinterpret_cast<const bf16x8_t*>(p.vb + h * DEC_D + lg * 8 + ks * 32);
+    }
+    // positions: shared -- base position x in [ntl, mlen) is logical key x - ntl; private -- tail position x in [Lt - ntl, Lt] is logical key
+    // x - Lt + mlen (x == Lt: the call's own key).  lo .. hi are the positions inside the window; the distance of logical key j is mlen - j.
+    const int lo = PRIV ? p.Lt - ntl : ntl, hi = PRIV ? p.Lt : p.mlen - 1;
+    const int joff = PRIV ? p.mlen - p.Lt : -ntl;
+    const bf16_t* newkv = p.qkv + row * 3 * HD + HD + h * DEC_D;       // (private only) K of the call's own key, V at + HD
+    if (PRIV && chunk == p.Lt / DECR_KC && threadIdx.x < 32) {           // append: 16 sixteen-byte pieces of K, 16 of V
+        int r = st_ + p.Lt;
+        r = r >= p.cap_t ? r - p.cap_t : r;
+        const int pc = threadIdx.x;
+        *reinterpret_cast<uint4*>(p.tail + (row * p.cap_t + r) * 2 * HD + h * DEC_D + (pc >> 4) * HD + (pc & 15) * 8) =
+            *reinterpret_cast<const uint4*>(newkv + (pc >> 4) * HD + (pc & 15) * 8);
+    }
+    // K row of position x (V: + HD), x clamped into [lo, hi] by the caller: a slot outside the window is never read (it may hold anything).
+    // A select between the sources, not a branch (the ring kernel's comment records what the branch cost).
+    const bf16_t* ringrow = PRIV ? p.tail + row * p.cap_t * 2 * HD + h * DEC_D : p.base + (int64_t)grp * p.cap_b * 2 * HD + h * DEC_D;
+    const int origin = PRIV ? st_ : sb, cap = PRIV ? p.cap_t : p.cap_b;
+    auto krow = [&](int x) -> const bf16_t* {
+        int r = origin + x;
+        r = r >= cap ? r - cap : r;
+        const bf16_t* ringp = ringrow + (int64_t)r * 2 * HD;
+        return (PRIV && x == p.Lt) ? newkv : ringp;
+    };
+    const bf16_t* Rg = p.R + h * DEC_D;
+    f32x4 acc_o[8];
+#pragma unroll
+    for (int db = 0; db < 8; db++) acc_o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float m_i = -1.0e30f, l_i = 0.f;
+    const int x0 = chunk * DECR_KC + wave * 32;
+    if (lo <= hi && x0 <= hi && x0 + 31 >= lo) {   // (wave-uniform) a step outside the window loads nothing and contributes (0, -1e30, 0)
+        bf16x8_t fqu[4], fqv[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) {
+            fqu[ks] = dec_add_bias(qraw[ks], uraw[ks]);
+            fqv[ks] = dec_add_bias(qraw[ks], vraw[ks]);
+        }
+        // ---- every global load of the step is requested before the first use: 32 V rows, two 16-key K blocks, two 16-distance R blocks
+        uint4 vreg[8];
+        bf16x8_t kreg[2][4], rreg[2][4];
+#pragma unroll
+        for (int it = 0; it < 8; it++) {
+            int x = x0 + it * 4 + (lane >> 4);
+            x = x < lo ? lo : (x > hi ? hi : x);
+            vreg[it] = *reinterpret_cast<const uint4*>(krow(x) + HD + (lane & 15) * 8);
+        }
+#pragma unroll
+        for (int blk = 0; blk < 2; blk++) {
+            int x = x0 + 16 * blk + a;
+            x = x < lo ? lo : (x > hi ? hi : x);
+            const bf16_t* kr = krow(x) + lg * 8;
+            int dr = p.mlen - (x + joff);
+            dr = dr < 0 ? 0 : (dr > p.nd - 1 ? p.nd - 1 : dr);
+            const bf16_t* rr = Rg + (int64_t)dr * HD + lg * 8;
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) {
+                kreg[blk][ks] = *reinterpret_cast<const bf16x8_t*>(kr + ks * 32);
+                rreg[blk][ks] = *reinterpret_cast<const bf16x8_t*>(rr + ks * 32);
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < 8; it++) {
+            const int vrow = it * 4 + (lane >> 4), ch = lane & 15;
+            *reinterpret_cast<uint4*>(Vs + vrow * 256 + ch * 16) = vreg[it];
+        }
+        // ---- S^T[key][row] = K . (q + u)^T + R[dist(key)] . (q + v)^T for the two 16-key blocks, one fp32 accumulator
+        f32x4 acc_s[2];
+#pragma unroll
+        for (int blk = 0; blk < 2; blk++) {
+            acc_s[blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kreg[blk][ks], fqu[ks], acc_s[blk], 0, 0, 0);
+#pragma unroll
+            for (int ks = 0; ks < 4; ks++) acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rreg[blk][ks], fqv[ks], acc_s[blk], 0, 0, 0);
+        }
+        float s[8];
+#pragma unroll
+        for (int blk = 0; blk < 2; blk++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int x = x0 + 16 * blk + 4 * lg + r;
+                const bool vis = x >= lo && x <= hi && x + joff > -p.shift;
+                s[blk * 4 + r] = vis ? acc_s[blk][r] * p.scale : -1.0e30f;
+            }
+        float mb = s[0];
+#pragma unroll
+        for (int t = 1; t < 8; t++) mb = fmaxf(mb, s[t]);
+        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
+        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
+        m_i = mb;                      // (one step per wave: no running maximum to rescale)
+        float rs = 0.f;
+#pragma unroll
+        for (int t = 0; t < 8; t++) { s[t] = s[t] > -1.0e29f ? __expf(s[t] - m_i) : 0.f; rs += s[t]; }
+        rs += __shfl_xor(rs, 16, 64);
+        rs += __shfl_xor(rs, 32, 64);
+        l_i = rs;
+        union { unsigned u[4]; bf16x8_t v; } pb;
+#pragma unroll
+        for (int t = 0; t < 4; t++) pb.u[t] = dec_pk(s[2 * t], s[2 * t + 1]);
+        // ---- O^T[d][row] = V^T . P^T over the 32 keys (key permutation as in the header of this file)
+#pragma unroll
+        for (int db = 0; db < 8; db++) {
+            const int t16 = lane & 15;
+            const char* bs = Vs + (t16 >> 2) * 256 + (db * 16 + (t16 & 3) * 4) * 2;
+            const bf16x4_t vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(bs) + (4 * lg) * 256));
+            const bf16x4_t vhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(bs) + (16 + 4 * lg) * 256));
+            const bf16x8_t vt = __builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7);
+            acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
+        }
+    }
+    // ---- the four waves' partial results (one 32-position step each) merged through LDS into ONE unit, waves in order
+    constexpr int OLD = DEC_D + 4;                       // floats per row in LDS: O[128], m, l, pad
+    float* mine = reinterpret_cast<float*>(Vs);          // (the wave's own V stage: it is done with it)
+#pragma unroll
+    for (int db = 0; db < 8; db++) *reinterpret_cast<f32x4*>(mine + a * OLD + db * 16 + 4 * lg) = acc_o[db];
+    if (lg == 0) { mine[a * OLD + DEC_D] = m_i; mine[a * OLD + DEC_D + 1] = l_i; }
+    __syncthreads();
+    const int qi = threadIdx.x & 15, dg = (threadIdx.x >> 4) * 8;
+    const float* w0p = reinterpret_cast<const float*>(smem) + qi * OLD;
+    float mw[4], lw[4], mx = -1.0e30f;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        mw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D]; lw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D + 1];
+        mx = fmaxf(mx, mw[w]);
+    }
+    float lsum_ = 0.f, o8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const float wt = lw[w] > 0.f ? __expf(mw[w] - mx) : 0.f;
+        lsum_ += lw[w] * wt;
+        const f32x4 o_lo = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg), o_hi = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg + 4);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { o8[j] += o_lo[j] * wt; o8[4 + j] += o_hi[j] * wt; }
+    }
+    const int wrow = PRIV ? sub : 16 * sub + qi;          // the row inside the group this thread's column stands for
+    if (PRIV ? qi == 0 : wrow < p.W) {
+        const int unit = PRIV ? p.nb + chunk : chunk;
+        float* dst = p.part + ((((int64_t)grp * p.H + h) * p.nunit + unit) * 64 + wrow) * (DEC_D + 2);
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) *reinterpret_cast<float2*>(dst + dg + j) = make_float2(o8[j], o8[j + 1]);
+        if (dg == 0) { dst[DEC_D] = mx; dst[DEC_D + 1] = lsum_; }
+    }
+}
+// grid = (nb ntile shared units + nt W private units, heads, groups)
+__global__ __launch_bounds__(256) void relattn_decode_group_kernel(DecodeGroupArgs p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    // guard: a count or an origin out of range is clamped (every access stays in bounds) and reported by one thread
+    int ntl = p.n_tail[0], sb = p.state_b[0], st_ = p.state_t[0];
+    const int lim = p.Lt < p.mlen ? p.Lt : p.mlen;
+    const bool bad = ntl < 0 || ntl > lim || sb < 0 || sb >= p.cap_b || st_ < 0 || st_ >= p.cap_t;
+    ntl = ntl < 0 ? 0 : (ntl > lim ? lim : ntl);
+    sb = sb < 0 ? 0 : (sb >= p.cap_b ? p.cap_b - 1 : sb);
+    st_ = st_ < 0 ? 0 : (st_ >= p.cap_t ? p.cap_t - 1 : st_);
+    if (bad && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) atomicOr(p.status, 1);
+    const int nshared = p.nb * p.ntile, x = blockIdx.x;
+    if (x < nshared) decode_group_unit<false>(p, smem, x / p.ntile, x % p.ntile, sb, st_, ntl);
+    else decode_group_unit<true>(p, smem, (x - nshared) / p.W, (x - nshared) % p.W, sb, st_, ntl);
+}
+__global__ void group_ring_advance_kernel(int* state_t, int* n_tail, int cap_t, int lim) {
+    const int s = state_t[0] + 1, n = n_tail[0] + 1;
+    state_t[0] = s >= cap_t ? s - cap_t : s;
+    n_tail[0] = n > lim ? lim : n;
+}
+
+extern "C" int db1_relattn_decode_group_supported(int G, int W, int mlen, int Lt, int cap_b, int cap_t, int H, int D, int dt) {
+    return (dt == DB1_BF16 && D == DEC_D && G > 0 && G <= 65535 && H > 0 && H <= 65535 && W >= 1 && W <= 64 && mlen >= 1 && mlen + 1 <= 2048 && Lt >= 1 &&
+            Lt <= 4096 && cap_b >= mlen && cap_t >= Lt + 1) ? 1 : 0;
+}
+static inline int dec_group_units(int mlen, int Lt) { return (mlen + DECR_KC - 1) / DECR_KC + (Lt + 1 + DECR_KC - 1) / DECR_KC; }
+extern "C" int64_t db1_relattn_decode_group_workspace_bytes(int G, int W, int mlen, int Lt, int H) {
+    (void)W;
+    if (G <= 0 || H <= 0 || mlen < 1 || Lt < 1) return 0;
+    return (int64_t)G * H * dec_group_units(mlen, Lt) * 64 * (DEC_D + 2) * (int64_t)sizeof(float);
+}
+extern "C" int db1_relattn_decode_group_fwd(const void* qkv_new, const void* u, const void* vb, const void* base, const int32_t* state_b, int cap_b, void* tail,
+                                            const int32_t* state_t, int cap_t, const int32_t* n_tail, int Lt, const void* R, int nd, void* out, int G, int W,
+                                            int mlen, int H, int D, int shift, float scale, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
+    if (!db1_relattn_decode_group_supported(G, W, mlen, Lt, cap_b, cap_t, H, D, DB1_BF16))
+        DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_decode_group: needs bf16, d_head = 128, 1 <= W <= 64, 1 <= mlen <= 2047, 1 <= Lt <= 4096, cap_b >= mlen, cap_t > Lt "
+                 "(got W=%d mlen=%d Lt=%d cap_b=%d cap_t=%d D=%d)", W, mlen, Lt, cap_b, cap_t, D);
+    if (nd < 1 || shift < 0 || !qkv_new || !u || !vb || !base || !state_b || !tail || !state_t || !n_tail || !R || !out || !status)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_decode_group: null buffer, nd %d < 1 or shift %d < 0", nd, shift);
+    if (!db1_aligned16(qkv_new) || !db1_aligned16(u) || !db1_aligned16(vb) || !db1_aligned16(base) || !db1_aligned16(tail) || !db1_aligned16(R) || !db1_aligned16(out))
+        DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_decode_group: operands must be 16-byte aligned");
+    DecodeGroupArgs a;
+    a.qkv = (const bf16_t*)qkv_new; a.u = (const bf16_t*)u; a.vb = (const bf16_t*)vb; a.base = (const bf16_t*)base; a.state_b = state_b; a.tail = (bf16_t*)tail;
+    a.state_t = state_t; a.n_tail = n_tail; a.R = (const bf16_t*)R; a.status = status;
+    a.G = G; a.W = W; a.mlen = mlen; a.Lt = Lt; a.H = H; a.shift = shift; a.nd = nd; a.cap_b = cap_b; a.cap_t = cap_t; a.scale = scale;
+    a.nb = (mlen + DECR_KC - 1) / DECR_KC; a.ntile = (W + 15) / 16; a.nunit = dec_group_units(mlen, Lt);
+    DB1_NEED_WS(ws, ws_bytes, db1_relattn_decode_group_workspace_bytes(G, W, mlen, Lt, H), "relattn_decode_group");
+    a.part = (float*)ws;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nx = (unsigned)(a.nb * a.ntile + (a.nunit - a.nb) * W);
+    relattn_decode_group_kernel<<<dim3(nx, (unsigned)H, (unsigned)G), 256, 4 * DEC_WAVE_LDS, st>>>(a);
+    DB1_CHECK_LAUNCH("relattn_decode_group");
+    relattn_decode_merge2_kernel<<<dim3((unsigned)W, (unsigned)H, (unsigned)G), 128, 0, st>>>(a.part, (bf16_t*)out, W, H, a.nunit);
+    DB1_CHECK_LAUNCH("relattn_decode_group merge");
+    return DB1_OK;
+}
+extern "C" int db1_group_ring_advance(int32_t* state_t, int32_t* n_tail, int cap_t, int Lt, int mlen, void* stream) {
+    if (!state_t || !n_tail || cap_t <= 0 || Lt < 1 || mlen < 1 || cap_t < Lt + 1) DB1_FAIL(DB1_ERR_BAD_SHAPE, "group_ring_advance: cap_t=%d Lt=%d mlen=%d", cap_t, Lt, mlen);
+    group_ring_advance_kernel<<<1, 1, 0, (hipStream_t)stream>>>(state_t, n_tail, cap_t, Lt < mlen ? Lt : mlen);
+    DB1_CHECK_LAUNCH("group_ring_advance");
+    return DB1_OK;
+}

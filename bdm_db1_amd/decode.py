@@ -197,6 +197,75 @@ class RingMemory:
         ops.ring_reorder(self.kv, self._ptrs, self.state, mlen, t, mlen if max_t is None else int(max_t), parent, W=group, done=done)
 
 
+class GroupedRingMemory:
+    """The memory of G groups of W rows that share their group's prompt (beam search, best-of-n sampling; the rule: include/db1_hip.h,
+    "grouped K/V ring").  ``base``: a RingMemory of G rows -- ONE copy of every prompt's mem_len keys / values per layer, filled by a prefill
+    (``RingPrefill(memory.base, ...)`` or ``memory.base.load``) and only read while decoding.  ``tail``: per layer a ring [G W, cap_t, 2, H, D]
+    with the keys / values every row generated itself, at most ``tail_len`` of them; ``state`` (int32 [1]) is its origin and ``n_tail``
+    (int32 [1]) the number of valid tail keys.  Pass it as ``mems`` of a one-token call of G W rows: every layer's attention is
+    db1_relattn_decode_group_fwd, which reads the base once per group and appends the call's own keys to the tail; origin and count advance
+    after the last layer.  ``status`` (int32 [1]): bit 0 when a launch met a count or an origin out of range (``check`` raises)."""
+    is_group_ring = True
+    kv_dtype = "bf16"
+
+    def __init__(self, model, G: int, W: int, tail_len: int):
+        from . import ops
+        G, W, Lt = int(G), int(W), int(tail_len)
+        if model.compute_dtype != torch.bfloat16 or not model.use_decode or model.d_head != 128 or not model.mem_len:
+            raise ValueError("GroupedRingMemory needs the bf16 K/V-cached decode path (d_head 128, mem_len > 0)")
+        if G < 1 or W < 1 or G * W < 2:
+            raise ValueError(f"GroupedRingMemory: G = {G} groups of W = {W} rows (at least two rows in all; one row has nothing to share)")
+        mlen = int(model.mem_len)
+        self.cap_t = -(-(Lt + 1) // 8) * 8
+        if not ops.relattn_decode_group_supported(G, W, mlen, Lt, mlen + 64, self.cap_t, model.n_head, model.d_head, model.compute_dtype):
+            raise ValueError(f"GroupedRingMemory: db1_relattn_decode_group_fwd does not support W = {W}, mem_len = {mlen}, tail_len = {Lt} "
+                             f"(1 <= W <= {ops.GROUP_MAX_W}, mem_len <= {ops.GROUP_MAX_KLEN - 1}, 1 <= tail_len <= {ops.GROUP_MAX_TAIL})")
+        self.model, self.G, self.W, self.B, self.Lt = model, G, W, G * W, Lt
+        dev = model.dev
+        self.base = RingMemory(model, G)
+        self.kv = [torch.zeros(self.B, self.cap_t, 2, model.n_head, model.d_head, device=dev, dtype=torch.bfloat16) for _ in range(model.n_layer)]
+        self.state = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.n_tail = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ptrs = ops.ring_pointers(self.kv)   # (the tail rings' base pointers for reorder: made here, never under a capture)
+
+    def begin(self):
+        """a new run: an empty tail at origin 0 (the base is the prefill's to fill; the tail's slots need no clearing)"""
+        self.state.zero_()
+        self.n_tail.zero_()
+        self.status.zero_()
+
+    def reset(self):
+        self.base.reset()
+        self.begin()
+
+    def advance(self):
+        from . import ops
+        ops.group_ring_advance(self.state, self.n_tail, self.cap_t, self.Lt, int(self.model.mem_len))
+
+    def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
+        """beam search: ``RingMemory.reorder`` on the tail alone -- the last ``t`` tail keys of row b come from row ``parent[b]``
+        (db1_ring_reorder with the tail's window as its mlen); the base is the same for a group's rows and never moves"""
+        from . import ops
+        ops.ring_reorder(self.kv, self._ptrs, self.state, self.Lt, t, self.Lt if max_t is None else int(max_t), parent, W=group, done=done)
+
+    def snapshot(self):
+        """origin, count and tail as they are (the base is never written by a decode call)"""
+        return self.state.clone(), self.n_tail.clone(), [k.clone() for k in self.kv]
+
+    def restore(self, snap):
+        state, n_tail, kv = snap
+        self.state.copy_(state)
+        self.n_tail.copy_(n_tail)
+        for dst, src in zip(self.kv, kv):
+            dst.copy_(src)
+
+    def check(self):
+        """raise if a launch over this memory met a count or an origin out of range (a host read)"""
+        if int(self.status.cpu()) != 0:
+            raise RuntimeError("db1_relattn_decode_group_fwd: the tail count or a ring origin left its range")
+
+
 class RingPrefill:
     """A prompt prefill straight into a RingMemory: pass it as ``mems`` and the call's rows start from the zero memory (``model.init_mem``),
     project only their own tokens, attend over (the zero memory's keys / values, their own) with db1_relattn_mem_kv_fwd, and every layer's
@@ -277,7 +346,9 @@ class GraphedRingStep:
         self.x = (make_input or _token_input)(self.ids)
         from . import ops
         saved_state = self.memory.state.clone()
-        saved_kv = None if memory is None else [k.clone() for k in self.memory.kv]
+        grouped = getattr(self.memory, "is_group_ring", False)   # (GroupedRingMemory: origin, count and tail go back through its own snapshot)
+        snap = self.memory.snapshot() if grouped else None
+        saved_kv = None if (memory is None or grouped) else [k.clone() for k in self.memory.kv]
         # the persistent one-token launches of THIS step hand over through a scratch of its own, with its own pinned copy of the error
         # flag -- both created here, eagerly: a scratch first touched under capture would be allocated and zero-filled by a graph node, i.e.
         # every replay would wipe the sticky flag before anyone read it (and all steps captured on torch's capture stream would share it)
@@ -299,7 +370,9 @@ class GraphedRingStep:
         self._watch = watch            # the captured call's copy of the persistent launches' error flag (None: per-launch path)
         model._chain_watch = pending
         self._version = model._wversion
-        if saved_kv is None:
+        if grouped:
+            self.memory.restore(snap)
+        elif saved_kv is None:
             self.memory.reset()
         else:   # a shared memory keeps the state its owner left
             for dst, src in zip(self.memory.kv, saved_kv):

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .decode import GraphedRingStep, RingMemory, RingPrefill, _token_input  # noqa: F401  (scoring.py takes _token_input from here)
+from .decode import GraphedRingStep, GroupedRingMemory, RingMemory, RingPrefill, _token_input  # noqa: F401  (scoring.py takes _token_input from here)
 
 
 @dataclass(frozen=True)
@@ -281,6 +281,7 @@ class DecodeKey:
     per_request: bool = False
     caps: Optional[Tuple[int, int]] = None
     kv_cache = "bf16"        # (no field: the key of the default ring is what it was; ``DecodeKeyFp8`` carries the other value)
+    share_prompt = False     # (no field either: ``DecodeKeyShared`` carries the other value)
 
 
 @dataclass(frozen=True)
@@ -290,6 +291,14 @@ class DecodeKeyFp8(DecodeKey):
     validates the model and the path first: a ``DecodeKeyFp8(kv_cache="bf16")`` built by hand would name the default ring and still never
     equal the plain key."""
     kv_cache: str = "fp8"
+
+
+@dataclass(frozen=True)
+class DecodeKeyShared(DecodeKey):
+    """the key of a beam search or a best-of-n sampling whose rows share their group's prompt keys (``share_prompt=True``): a
+    ``GroupedRingMemory`` instead of a ``RingMemory``.  A class of its own for the reason ``DecodeKeyFp8`` is one: the default keys compare
+    equal to what they were, and a shared generator is never taken for a per-row one.  Created by ``_with_share_prompt`` ONLY."""
+    share_prompt: bool = True
 
 
 def clip_at_eos(ids, lengths) -> List[List[int]]:
@@ -667,6 +676,31 @@ def _with_kv_cache(who: str, model, key: DecodeKey, kv_cache: str, graphed: Opti
     return DecodeKeyFp8(**{f.name: getattr(key, f.name) for f in dataclasses.fields(key)})
 
 
+def _with_share_prompt(who: str, model, key: DecodeKey, share_prompt: bool, W: int, prompt, kv_cache: str, graphed: Optional[bool] = None) -> DecodeKey:
+    """``key`` for a call whose W rows per prompt share the prompt's keys / values: False -- the key itself; True -- a ``DecodeKeyShared`` of
+    the same fields, for a call that takes the graphed bf16 ring path on a model db1_relattn_decode_group_fwd supports.  Raises ValueError
+    before anything is launched."""
+    if not share_prompt:
+        return key
+    if model.compute_dtype != torch.bfloat16 or not _ring_ok(model):
+        raise ValueError(f"{who}: share_prompt=True needs the ring path (a bf16 model with use_decode, d_head 128 and mem_len > 0)")
+    if graphed is False:
+        raise ValueError(f"{who}: share_prompt=True needs the graphed ring path (not graphed=False)")
+    if kv_cache != "bf16":
+        raise ValueError(f"{who}: share_prompt=True keeps bf16 keys / values (kv_cache={kv_cache!r} is not supported)")
+    if isinstance(prompt, Prefixed):
+        raise ValueError(f"{who}: share_prompt=True does not take a Prefixed prompt (the prefix cache's continuations have rows of their own)")
+    mlen, mx = int(model.mem_len), int(key.cfg.max_new_tokens)
+    if mx > mlen:
+        raise ValueError(f"{who}: share_prompt=True with max_new_tokens {mx} above the model's mem_len {mlen}")
+    if key.rows * int(W) < 2:
+        raise ValueError(f"{who}: share_prompt=True over one row (G = W = 1) has nothing to share")
+    if not ops.relattn_decode_group_supported(key.rows, W, mlen, mx, mlen + 64, mx + 1, model.n_head, model.d_head, model.compute_dtype):
+        raise ValueError(f"{who}: share_prompt=True is not supported for this model (db1_relattn_decode_group_supported: 1 <= W <= {ops.GROUP_MAX_W}, "
+                         f"mem_len <= {ops.GROUP_MAX_KLEN - 1}, max_new_tokens <= {ops.GROUP_MAX_TAIL}; W = {W}, mem_len = {mlen}, max_new_tokens = {mx})")
+    return DecodeKeyShared(**{f.name: getattr(key, f.name) for f in dataclasses.fields(key)})
+
+
 # ----------------------------------------------------------------------------------------------------------------------- the device states
 # What ``_decode`` asks of a state: ``M`` rows, ``expand`` (None, or the rows per prompt), ``cache`` (the model attribute its ring generator
 # is kept under), ``start(...)``, ``epilogue(logits_last, next_ids, ring=None)`` -- select, reorder ``ring`` if beams, then t += 1 --,
@@ -888,7 +922,10 @@ class _RingGenerator:
 
     def __init__(self, model, state, key):
         self.model, self.key, self.state = model, key, state
-        self.ring = RingMemory(model, state.M, kv_dtype=key.kv_cache)
+        if key.share_prompt:     # one copy of every prompt's keys / values per group, the rows' own tokens in a tail of max_new_tokens
+            self.ring = GroupedRingMemory(model, key.rows, state.expand, key.cfg.max_new_tokens)
+        else:
+            self.ring = RingMemory(model, state.M, kv_dtype=key.kv_cache)
         self.step = GraphedRingStep(model, state.M, 1, memory=self.ring, epilogue=self.epilogue)
 
     def epilogue(self, step, logits):
@@ -938,18 +975,23 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
         st.start(*start)
         # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
         direct = ring and (_use_ring_prefill(model) or isinstance(prompt, Prefixed))
+        # (share_prompt) the prefill fills the G rows of the grouped memory's base ring, unexpanded; the tail starts empty
+        shared = ring and key.share_prompt
+        dst = gen.ring.base if shared else (gen.ring if ring else None)
+        if shared:
+            gen.ring.begin()
         if direct:      # (model.use_ring_prefill, or a Prefixed prompt) the prompt's keys / values go straight into every ring row, origin 0
-            gen.ring.state.zero_()
-            gen.ring.load_status.zero_()
-            logits, mems = _prefill_ring(model, prompt, gen.ring, None, st.expand), None
+            dst.state.zero_()
+            dst.load_status.zero_()
+            logits, mems = _prefill_ring(model, prompt, dst, None, None if shared else st.expand), None
         else:
-            logits, mems = _prefill(model, prompt, key.rows, st.expand)
+            logits, mems = _prefill(model, prompt, key.rows, None if shared else st.expand)
         last = logits[:, -1]
         st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids[:, 0])
         del logits, last
         calls = 0
         if ring and not direct:
-            gen.ring.load(mems)
+            dst.load(mems)
             del mems
         for i in range(1, st.cfg.max_new_tokens):
             if i % st.cfg.sync_every == 0 and st.all_done():
@@ -963,8 +1005,10 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             calls += 1
         if ring:
             gen.check(replay)
-            if direct and int(gen.ring.load_status.cpu()) != 0:
+            if direct and int(dst.load_status.cpu()) != 0:
                 raise RuntimeError("db1_ring_prefill_rows / db1_ring_fork_rows: the prefill skipped a ring row or read a cache row out of range")
+            if shared:
+                gen.ring.check()
         else:
             _check_chain(model)
         if stats is not None:
@@ -1101,7 +1145,7 @@ def question_suffixes(vqa_batch) -> List[Tuple[object, np.ndarray]]:
 @torch.no_grad()
 def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
                 replay: bool = True, constraints: Optional[DecodingConstraints] = None,
-                kv_cache: str = "bf16") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                kv_cache: str = "bf16", share_prompt: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Beam search after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of G prompts of one shape ->
     (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R = ``num_return_sequences``: each prompt's
     best hypotheses, best first.  ``ids[g, r, :lengths[g, r]]`` are the tokens before EOS (then EOS, then ``pad_id``); the score is the sum of
@@ -1112,7 +1156,10 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     run eagerly over the same ring instead of as a graph replay.  ``stats`` (a dict): receives the path taken, the number of per-token calls
     and ``parent_switches``, the number of (step, row) pairs (step > 0) whose parent was another row.  ``constraints`` (a
     ``DecodingConstraints``): applied to every step's logits on the device, over each beam's own tokens so far, before the beam step.
-    ``kv_cache``: as ``generate`` takes it (db1_ring_reorder copies fp8 slots as the bytes they are)."""
+    ``kv_cache``: as ``generate`` takes it (db1_ring_reorder copies fp8 slots as the bytes they are).  ``share_prompt`` True (graphed bf16
+    ring path only; ValueError otherwise, before anything is launched): the W beams of a group read ONE copy of their prompt's keys / values
+    (``GroupedRingMemory``, db1_relattn_decode_group_fwd) instead of W; the results are those of the default path up to the order of the
+    attention's partial sums.  False (default): everything is what it is without the keyword."""
     cfg = config or BeamSearchConfig()
     if not isinstance(cfg, BeamSearchConfig):
         raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
@@ -1128,6 +1175,7 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
     key = _constrained("beam_search", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
+    key = _with_share_prompt("beam_search", model, key, share_prompt, W, prompt, kv_cache, graphed)
     key = _with_kv_cache("beam_search", model, key, kv_cache, graphed)
     return _decode(model, prompt, _BeamState, key, graphed, replay, stats)
 
@@ -1172,7 +1220,8 @@ def _check_best_of(cfg, n, num_return_sequences, length_penalty):
 @torch.no_grad()
 def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, length_penalty: float = 1.0, num_return_sequences: int = 1,
                    stream_ids=None, graphed: Optional[bool] = None, stats: Optional[dict] = None,
-                   constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16") -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                   constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16",
+                   share_prompt: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Best-of-n sampling after ``prompt`` (G prompts of one shape): n sampled continuations of every prompt, ranked by their normalised
     log-probability -> (ids int32 [G, R, max_new_tokens], lengths int32 [G, R], scores float32 [G, R]) on the host, R =
     ``num_return_sequences``, best first: the triple ``beam_search`` returns.  ``config``: a sampling ``GenerationConfig`` (``greedy`` raises);
@@ -1180,7 +1229,8 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
     logits are expanded n-fold, as ``beam_search`` expands them to its beams, and row g * n + j samples from Philox stream g * n + j
     (``stream_ids`` of shape [G, n]: the streams to use instead).  score = sum_logprob / L^``length_penalty``, L = the tokens before EOS + 1
     for a row that ended with EOS, else its length; a row that met a step without a candidate scores -inf; ties go to the lower j.  The
-    ranking is NumPy on the host over [G, n].  ``graphed``, ``stats``, ``constraints`` and ``kv_cache`` as ``generate`` takes them."""
+    ranking is NumPy on the host over [G, n].  ``graphed``, ``stats``, ``constraints`` and ``kv_cache`` as ``generate`` takes them;
+    ``share_prompt`` as ``beam_search`` takes it (the n samples of a prompt read one copy of its keys / values)."""
     cfg = config or GenerationConfig(greedy=False)
     n, R = _check_best_of(cfg, n, num_return_sequences, length_penalty)
     cfg = dataclasses.replace(cfg, logprobs=True)
@@ -1196,6 +1246,7 @@ def sample_best_of(model, prompt, config: Optional[GenerationConfig], n: int, le
             raise ValueError(f"sample_best_of: stream_ids of shape [{G}, {n}] expected, got {tuple(stream_ids.shape)}")
         stream_ids = stream_ids.reshape(-1)
     key = _constrained("sample_best_of", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi, n=n), constraints, cfg.max_new_tokens)
+    key = _with_share_prompt("sample_best_of", model, key, share_prompt, n, prompt, kv_cache, graphed)
     key = _with_kv_cache("sample_best_of", model, key, kv_cache, graphed)
     out, lengths, _, sums, status = _decode(model, prompt, _BestOfState, key, graphed, True, stats, start=(stream_ids,))
     out, lengths = out.numpy().reshape(G, n, -1), lengths.numpy().reshape(G, n)

@@ -807,6 +807,12 @@ class TransformerXL(nn.Module):
     def _attention_decode(self, qkv, i, B, L, mlen, shift, dec):
         H, D = self.n_head, self.d_head
         u, vb = self._bias("r_w_bias", i), self._bias("r_r_bias", i)
+        if getattr(getattr(dec, "ring", None), "is_group_ring", False):   # one base row per group + one tail per row (decode.GroupedRingMemory)
+            mem = dec.ring
+            av = self._new(B, L, H, D)
+            ops.relattn_decode_group_fwd(qkv, u, vb, mem.base.kv[i], mem.base.state, mem.kv[i], mem.state, mem.n_tail, mem.Lt, dec.R[i], av, mem.G, mem.W,
+                                         mlen, H, D, shift, 1.0 / math.sqrt(D), mem.status)
+            return av
         if getattr(dec, "ring", None) is not None:   # K / V of the memory in a ring, appended in place by the attention launch (decode.RingMemory)
             ring_fwd = ops.relattn_decode_ring_kv8_fwd if getattr(dec.ring, "kv_dtype", "bf16") == "fp8" else ops.relattn_decode_ring_fwd
             if getattr(dec, "partials", False):       # one or two new tokens: the output projection merges the chunk partials itself
@@ -1323,10 +1329,13 @@ class TransformerXL(nn.Module):
         dec = self._decode_begin(mems, B, L, mlen) if (mems is not None and mlen > 0) else None
         if ring is not None:
             self.check_decode_chain()   # (a failed chain launch of an earlier call: raise before more tokens go into the same memory)
-            if not (self.use_decode and self.compute_dtype == torch.bfloat16 and ring.B == B and L <= 64 and mlen + L <= ring.cap):
+            grouped = getattr(ring, "is_group_ring", False)   # decode.GroupedRingMemory: one base row per group, one tail per row
+            if grouped and not (self.use_decode and self.compute_dtype == torch.bfloat16 and ring.model is self and ring.B == B and L == 1):
+                raise ValueError("GroupedRingMemory needs the bf16 decode path of its own model, its own batch size and one new token per call")
+            if not grouped and not (self.use_decode and self.compute_dtype == torch.bfloat16 and ring.B == B and L <= 64 and mlen + L <= ring.cap):
                 raise ValueError("RingMemory needs the bf16 decode path, its own batch size and at most 64 new tokens per call")
             dec = SimpleNamespace(ring=ring, R=self._decode_R(), kv=None, new_kv=[])
-            dec.partials = (self.use_decode_attn_partials and not self.pre_lnorm and self._decode_fused_ok(B * L, keep, dstep) and
+            dec.partials = (not grouped and self.use_decode_attn_partials and not self.pre_lnorm and self._decode_fused_ok(B * L, keep, dstep) and
                             self._decode_ln_prologue_ok(B * L) and ops.linear_decode_attn_supported(B, L, self.n_head, self.d_head, mlen + L, d))
         R_in = self._sinusoid(klen) if dec is None else None
         if dstep is not None and self.embd_pdrop > 0:   # the position table goes through the same nn.Dropout (:575); the cached table stays intact
@@ -1624,6 +1633,9 @@ class TransformerXL(nn.Module):
                     self._ctx = ctx
         res = (lm_logits, loss)
         if ring is not None:   # the ring was appended by the attention launches: only its origin moves
+            if getattr(ring, "is_group_ring", False):   # (the tail's origin and its count of valid keys)
+                ring.advance()
+                return res + (ring,)
             ops.ring_advance(ring.state, L, ring.cap)
             return res + (ring,)
         if mems is not None:  # _update_mem (:487-504)

@@ -1469,6 +1469,52 @@ def relattn_decode_ring_fwd(qkv_new, u, vb, kv_ring, state, R, out, B, q, mlen, 
              float(scale), ws, wsn, P(decode_tickets(qkv_new.device)) if (fused_merge and out is not None) else _vp(0), stream())
 
 
+# ---- the grouped K/V ring (include/db1_hip.h, "grouped K/V ring"): one base row per group, one short tail per row
+GROUP_MAX_W, GROUP_MAX_KLEN, GROUP_MAX_TAIL = 64, 2048, 4096
+
+
+def relattn_decode_group_supported(G, W, mlen, Lt, cap_b, cap_t, H, D, dtype) -> bool:
+    return bool(lib.load().db1_relattn_decode_group_supported(int(G), int(W), int(mlen), int(Lt), int(cap_b), int(cap_t), int(H), int(D), dt_code(dtype)))
+
+
+def relattn_decode_group_fwd(qkv_new, u, vb, base, state_b, tail, state_t, n_tail, Lt, R, out, G, W, mlen, H, D, shift, scale, status):
+    """one new token per row over a group's shared base ring and the row's own tail (db1_relattn_decode_group_fwd): qkv_new [G W, 1, 3, H, D]
+    (or [G W, 3 H D]), base [G, cap_b, 2, H, D], tail [G W, cap_t, 2, H, D], out [G W, 1, H, D], all bf16; state_b, state_t, n_tail, status
+    int32 [1] on the device.  The call's own key / value is appended to the tail.  Everything is checked here, on the host: ValueError
+    before the library is called."""
+    who = "relattn_decode_group_fwd"
+    G, W, mlen, Lt, H, D, shift = int(G), int(W), int(mlen), int(Lt), int(H), int(D), int(shift)
+    if D != 128 or not 1 <= W <= GROUP_MAX_W or G < 1 or H < 1 or not 1 <= mlen < GROUP_MAX_KLEN or not 1 <= Lt <= GROUP_MAX_TAIL or shift < 0:
+        raise ValueError(f"{who}: needs d_head 128, 1 <= W <= {GROUP_MAX_W}, 1 <= mlen <= {GROUP_MAX_KLEN - 1}, 1 <= Lt <= {GROUP_MAX_TAIL} and shift >= 0 "
+                         f"(got G={G}, W={W}, mlen={mlen}, Lt={Lt}, H={H}, D={D}, shift={shift})")
+    M, dev = G * W, qkv_new.device
+    for name, x, lead in (("base", base, G), ("tail", tail, M)):
+        if x.dim() != 5 or x.shape[0] != lead or tuple(x.shape[2:]) != (2, H, D) or x.dtype != torch.bfloat16 or not x.is_contiguous() or x.device != dev:
+            raise ValueError(f"{who}: {name} must be a contiguous bf16 [{lead}, cap, 2, {H}, {D}] tensor on {dev}")
+    cap_b, cap_t = int(base.shape[1]), int(tail.shape[1])
+    if cap_b < mlen or cap_t < Lt + 1:
+        raise ValueError(f"{who}: the base ring needs mlen ({mlen}) slots and the tail ring Lt + 1 ({Lt + 1}) (got {cap_b} and {cap_t})")
+    if qkv_new.dtype != torch.bfloat16 or not qkv_new.is_contiguous() or qkv_new.numel() != M * 3 * H * D:
+        raise ValueError(f"{who}: qkv_new must be a contiguous bf16 tensor of {M} x 3 x {H} x {D} elements")
+    if out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() != M * H * D or out.device != dev:
+        raise ValueError(f"{who}: out must be a contiguous bf16 tensor of {M} x {H} x {D} elements on {dev}")
+    for name, x in (("u", u), ("vb", vb)):
+        _check_tensor(who, name, x, torch.bfloat16, H * D, dev)
+    if R.dim() < 2 or R.shape[0] < 1 or R.dtype != torch.bfloat16 or not R.is_contiguous() or R.numel() != R.shape[0] * H * D or R.device != dev:
+        raise ValueError(f"{who}: R must be a contiguous bf16 [nd, {H}, {D}] tensor on {dev}")
+    for name, x in (("state_b", state_b), ("state_t", state_t), ("n_tail", n_tail), ("status", status)):
+        _check_tensor(who, name, x, torch.int32, 1, dev)
+    if any(x.data_ptr() % 16 for x in (qkv_new, u, vb, base, tail, R, out)):
+        raise ValueError(f"{who}: operands must be 16-byte aligned")
+    ws, wsn = _ws("db1_relattn_decode_group_workspace_bytes", (G, W, mlen, Lt, H), dev)
+    lib.call("db1_relattn_decode_group_fwd", P(qkv_new), P(u), P(vb), P(base), P(state_b), cap_b, P(tail), P(state_t), cap_t, P(n_tail), Lt, P(R),
+             int(R.shape[0]), P(out), G, W, mlen, H, D, shift, float(scale), P(status), ws, wsn, stream())
+
+
+def group_ring_advance(state_t, n_tail, cap_t, Lt, mlen):
+    lib.call("db1_group_ring_advance", P(state_t), P(n_tail), int(cap_t), int(Lt), int(mlen), stream())
+
+
 def relattn_decode_ring_part_numel(B, q, klen, H) -> int:
     return int(lib.load().db1_relattn_decode_ring_workspace_bytes(int(B), int(q), int(klen), int(H))) // 4
 

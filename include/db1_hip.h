@@ -349,6 +349,34 @@ int db1_ring_advance(int* state, int q, int cap, void* stream);
  * With it (and q <= 16) the key chunk that finishes last for a (batch, head) merges the partial results inside the attention launch.
  * out == NULL (q <= 16): no merge at all, the per-chunk partial results stay in ws for db1_linear_decode_attn. */
 
+/* ------------------------------------------------------------------ grouped K/V ring (tests/group_ring_rule.py restates the rule in NumPy).
+ * Beam search and best-of-n sampling decode M = G W rows whose W rows per group share one prompt.  Per layer the memory is
+ *   a BASE ring  [G, cap_b, 2, H, D] bf16, origin state_b[0], cap_b >= mlen: the prompt's mlen keys / values, one row per group, only read;
+ *   a TAIL ring  [M, cap_t, 2, H, D] bf16, origin state_t[0], window Lt, cap_t >= Lt + 1: the keys / values every row generated itself, and
+ *   n_tail[0], the number of valid tail keys, 0 <= n_tail <= min(Lt, mlen).
+ * Row r belongs to group g = r / W.  Its logical memory is the last mlen positions of cat(base window of g, its n_tail tail keys):
+ *   logical key j <  mlen - n_tail          base slot (state_b[0] + n_tail + j) % cap_b of base row g
+ *   mlen - n_tail <= j < mlen               tail slot (state_t[0] + Lt - mlen + j) % cap_t of tail row r
+ *   j == mlen                               the call's own key / value from qkv_new [M, 1, 3, H, D]; the same launch appends it at tail slot
+ *                                           (state_t[0] + Lt) % cap_t of row r.  No other byte of either ring changes.
+ * Scores, distances (mlen - j for the one query), visibility (j > -shift), u / vb, scale and the rounding points are those of
+ * db1_relattn_decode_ring_fwd at q = 1: fp32 scores from bf16 MFMA, P rounded to bf16 before P.V, one normalisation, one bf16 store.  Only the
+ * grouping of the partial sums differs (chunks of 128 base POSITIONS read once per group, then chunks of 128 tail positions per row), so
+ * the result is not bit-equal to the per-row ring kernel's; it is deterministic: the partials are merged in that fixed order, without
+ * atomics, and two launches give the same bits.  out [M, 1, H, D] bf16.
+ * Guard: an n_tail outside [0, min(Lt, mlen)] or an origin outside its ring is clamped into range (every access stays in bounds) and one
+ * thread ORs bit 0 into *status (int32 [1]; the launch's only atomic).
+ * Supported (_supported; DB1_ERR_UNSUPPORTED otherwise): bf16, D == 128, 1 <= W <= 64, 1 <= mlen <= 2047, 1 <= Lt <= 4096, cap_b >= mlen,
+ * cap_t >= Lt + 1.  DB1_ERR_BAD_SHAPE: a NULL buffer, nd < 1, shift < 0; DB1_ERR_BAD_ALIGN: an operand that is not 16-byte aligned;
+ * DB1_ERR_WORKSPACE_TOO_SMALL: fewer than _workspace_bytes.  db1_group_ring_advance, after the last layer of a call: state_t[0] = (state_t[0] + 1) %
+ * cap_t and n_tail[0] = min(n_tail[0] + 1, Lt, mlen).  db1_ring_reorder serves the tail as it is: rings = the tail rings, mlen = Lt. */
+int db1_relattn_decode_group_supported(int G, int W, int mlen, int Lt, int cap_b, int cap_t, int H, int D, int dt);
+int64_t db1_relattn_decode_group_workspace_bytes(int G, int W, int mlen, int Lt, int H);
+int db1_relattn_decode_group_fwd(const void* qkv_new, const void* u, const void* vb, const void* base, const int32_t* state_b, int cap_b, void* tail,
+                                 const int32_t* state_t, int cap_t, const int32_t* n_tail, int Lt, const void* R, int nd, void* out, int G, int W,
+                                 int mlen, int H, int D, int shift, float scale, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+int db1_group_ring_advance(int32_t* state_t, int32_t* n_tail, int cap_t, int Lt, int mlen, void* stream);
+
 /* ------------------------------------------------------------------ fp8 K/V ring (tests/kv8_rule.py restates the format in NumPy).
  * The same ring with half the bytes per key: kv_ring is [B, cap, slot] BYTES, one slot = one key position of one batch row:
  *     H * 128 bytes of K payload, H * 128 bytes of V payload, H fp32 K scales, H fp32 V scales     (264 H bytes; D == 128, H even)

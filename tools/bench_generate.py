@@ -97,6 +97,19 @@ every line carries "kv_cache" and the ring's bytes at that M.
 
     python tools/bench_generate.py --kv-cache fp8 [M ...]
 
+--share-prompt (with --num-beams or --best-of): ``share_prompt=True`` -- the rows of a group read ONE copy of their prompt's keys / values
+(``GroupedRingMemory``, db1_relattn_decode_group_fwd); every line carries "share_prompt": true and the bytes of the memory.
+
+    python tools/bench_generate.py --num-beams 4 --share-prompt [G ...]
+    python tools/bench_generate.py --best-of 4 --share-prompt [G ...]
+
+--group-kernels [G W [n_tail ...]] (default 16 4 0 29): db1_relattn_decode_group_fwd alone against db1_relattn_decode_ring_fwd at B = G W
+(q = 1, mlen = 1024, 16 heads, tail window 30), in alternation in ONE process.  Each side is a captured graph of one launch over each of
+n distinct memories (more bytes than the last-level cache holds); device time per launch from events over 5 replays, the median of 7
+rounds with min .. max, and the key / value bytes a launch reads.
+
+    python tools/bench_generate.py --group-kernels [G W [n_tail ...]]
+
 --kv8-kernels [B ...] (default 1 16 64): the two attention entry points alone, db1_relattn_decode_ring_fwd and
 db1_relattn_decode_ring_kv8_fwd, in alternation in ONE process: q = 1, mlen = 1024, 16 heads, the merge as a second launch (what the
 model's plain path launches) and, for B <= 2, the partials form; device time per call from events over 20 calls, the median of 7 rounds
@@ -177,6 +190,66 @@ def gen_ms_per_token(M, cfg, short=10, **kw):
 
 
 KV_CACHE = "bf16"      # --kv-cache
+SHARE_KW = {}          # --share-prompt: dict(share_prompt=True)
+
+
+def _memory_bytes(gen):
+    """the bytes of a ring generator's memory: the rings of a RingMemory, or base + tail of a GroupedRingMemory"""
+    mem = gen.ring
+    rings = list(mem.kv) + (list(mem.base.kv) if getattr(mem, "is_group_ring", False) else [])
+    return sum(k.numel() * k.element_size() for k in rings)
+
+
+def group_kernels_us(G, W, n_tail, mlen=1024, Lt=N_NEW, rounds=7, replays=5, n=8):
+    """the grouped attention and the per-row ring attention alone at q = 1 (the docstring above says how)"""
+    H, D, M = model.n_head, model.d_head, G * W
+    cap_b, cap_t = mlen + 64, -(-(Lt + 1) // 8) * 8
+    slot = 2 * H * D * 2
+    # n memories a side: at G = 16, W = 4 that is 8 x 570 MB of per-row rings and 8 x 143 MB of base rings, both beyond the last-level cache
+    g = torch.Generator(device=dev).manual_seed(G * 100 + W)
+    rnd = lambda *s: torch.randn(*s, device=dev, generator=g).to(torch.bfloat16)
+    qkv, u, vb, R = rnd(M, 1, 3, H, D), rnd(H, D), rnd(H, D), rnd(cap_b, H * D)
+    rings = [rnd(M, cap_b, 2, H, D) for _ in range(n)]
+    bases = [rnd(G, cap_b, 2, H, D) for _ in range(n)]
+    tails = [rnd(M, cap_t, 2, H, D) for _ in range(n)]
+    i32 = lambda v: torch.tensor([v], dtype=torch.int32, device=dev)
+    state, state_b, state_t, nt, status = i32(0), i32(0), i32(3), i32(n_tail), i32(0)
+    out = torch.empty(M, 1, H, D, device=dev, dtype=torch.bfloat16)
+    scale = 1.0 / D ** 0.5
+    sides = {"ring": lambda i: ops.relattn_decode_ring_fwd(qkv, u, vb, rings[i], state, R, out, M, 1, mlen, H, D, mlen + 1, scale),
+             "group": lambda i: ops.relattn_decode_group_fwd(qkv, u, vb, bases[i], state_b, tails[i], state_t, nt, Lt, R, out, G, W, mlen, H, D, mlen + 1,
+                                                             scale, status)}
+    graphs = {}
+    for name, fn in sides.items():
+        fn(0)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for i in range(n):
+                fn(i)
+        graphs[name] = gr
+    times = {name: [] for name in sides}
+    for _ in range(rounds):
+        for name, gr in graphs.items():
+            gr.replay()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(replays):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / (replays * n) * 1e3)
+    assert int(status.cpu()) == 0
+    rec = {"G": G, "W": W, "M": M, "mlen": mlen, "H": H, "tail_len": Lt, "n_tail": n_tail, "memories": n}
+    read = {"ring": M * mlen * slot, "group": (G * (mlen - n_tail) + M * n_tail) * slot}
+    for name in sides:
+        t = sorted(times[name])
+        rec[f"{name}_us"] = round(t[len(t) // 2], 2)
+        rec[f"{name}_us_min_max"] = [round(t[0], 2), round(t[-1], 2)]
+        rec[f"{name}_read_MB"] = round(read[name] / 1e6, 1)
+        rec[f"{name}_TBps"] = round(read[name] / (t[len(t) // 2] * 1e-6) / 1e12, 3)
+    rec["group_over_ring"] = round(rec["group_us"] / rec["ring_us"], 4)
+    return rec
 
 
 def kv8_kernels_us(B, mlen=1024, rounds=7, calls=20):
@@ -385,7 +458,11 @@ def beam_kernels_us(G, W, t_reorder=N_NEW - 1):
         st.select(logits, ids[:, 0])
     restore = device_us(lambda: [dst.copy_(src) for dst, src in zip((st.beam_score, st.parent, st.tokens, st.pool_count, st.done), state0)])
     step_us = device_us(step) - restore
-    ring = RingMemory(model, M)
+    if SHARE_KW:     # (share_prompt: the reorder runs on the grouped memory's tail)
+        from bdm_db1_amd.decode import GroupedRingMemory
+        ring = GroupedRingMemory(model, G, W, N_NEW)
+    else:
+        ring = RingMemory(model, M)
     parent = torch.tensor([(b // W) * W + (b + 1) % W for b in range(M)], dtype=torch.int32, device=dev)
     t = torch.tensor([t_reorder], dtype=torch.int32, device=dev)
     done = torch.zeros(G, dtype=torch.int32, device=dev)
@@ -400,7 +477,8 @@ def beam_main(W, Gs):
     for G in Gs:
         M = G * W
         rec = {"G": G, "num_beams": W, "M": M, "new_tokens": N_NEW}
-        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW)), 4)
+        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW), **SHARE_KW), 4)
+        rec["memory_bytes"] = _memory_bytes(model._beam_generator)
         model._beam_generator = None
         torch.cuda.empty_cache()
         bare, ring = bare_replay_ms(M)
@@ -848,10 +926,11 @@ def best_of_main(N, Gs):
     for G in Gs:
         rec = {"G": G, "n": N, "M": G * N, "new_tokens": N_NEW}
         cfg = GenerationConfig(max_new_tokens=N_NEW, greedy=False, top_p=0.9, seed=1)
-        rec["best_of_ms_per_token"] = round(gen_ms_per_token(G, cfg, n=N), 4)
+        rec["best_of_ms_per_token"] = round(gen_ms_per_token(G, cfg, n=N, **SHARE_KW), 4)
+        rec["memory_bytes"] = _memory_bytes(model._best_of_generator)
         model._best_of_generator = None
         torch.cuda.empty_cache()
-        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=N, max_new_tokens=N_NEW)), 4)
+        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=N, max_new_tokens=N_NEW), **SHARE_KW), 4)
         model._beam_generator = None
         torch.cuda.empty_cache()
         rec["best_of_over_beam"] = round(rec["best_of_ms_per_token"] / rec["beam_ms_per_token"], 4)
@@ -867,6 +946,19 @@ if "--ring-prefill" in args:   # the prompt prefills project only their own toke
     args = [a for a in args if a != "--ring-prefill"]
     _dumps = json.dumps
     json.dumps = lambda rec, **kw: _dumps(dict(rec, ring_prefill=True) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
+if "--share-prompt" in args:   # beam search and best-of-n read one copy of a group's prompt keys / values (share_prompt=True)
+    if "--num-beams" not in args and "--best-of" not in args:
+        sys.exit("--share-prompt goes with --num-beams or --best-of")
+    SHARE_KW = dict(share_prompt=True)
+    args = [a for a in args if a != "--share-prompt"]
+    _dumps_sp = json.dumps
+    json.dumps = lambda rec, **kw: _dumps_sp(dict(rec, share_prompt=True) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
+if "--group-kernels" in args:
+    rest = [int(a) for a in args if a != "--group-kernels"]
+    G_, W_ = (rest + [16, 4])[:2] if len(rest) >= 2 else (16, 4)
+    for n_tail in rest[2:] or [0, 29]:
+        print(json.dumps(group_kernels_us(G_, W_, n_tail)), flush=True)
+    sys.exit(0)
 if "--w8-kernels" in args:
     for M in [int(a) for a in args if a != "--w8-kernels"] or [1, 4, 16, 64]:
         print(json.dumps(w8_kernels_us(M)), flush=True)
