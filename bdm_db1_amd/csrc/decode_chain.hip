@@ -30,6 +30,7 @@
 // The same kernel over fp8 weights (db1_decode_chain_w8, template mode W8): the packed e4m3 copies of "fp8 decode weights" in place of the five
 // bf16 matrices; only the weight load sites and the widening differ ("fp8 weights" below), bit for bit this kernel over the dequantised weights.
 #include "ln_row.h"
+#include "relattn_decode_step.h"   // the layout of the attention partials
 
 #define DC_D 2048
 #define DC_DFF 4096
@@ -239,7 +240,7 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         DC_PIN();
         DC_TSW(0);
         // stage 0 input: the merge of the attention's chunk partials (worker thread t owns columns 4 t .. 4 t + 3 = head t / 32), the arithmetic
-        // of relattn_decode_merge2_kernel / db1_linear_decode_attn.  Its inputs are requested, then W1, and only then are they waited for:
+        // of relattn_decode_merge2_kernel (relattn_decode.hip) / db1_linear_decode_attn.  Its inputs are requested, then W1, and only then are they waited for:
         //   ff1 rows of this wave: pairs pr = bid * 16 + wave * 2 + {0, 1}: value row pr, gate row dff + pr          (16 pieces)
         //   (ff2's row follows after B0: a CU takes about 160 KB of requests before the requesting wave stalls in the issue -- with W2 up
         //    here the workers reached A0 at 5-7 us instead of 1.5 us; the next layer's qkv rows go to LDS, requested by the DMA waves after A1)
@@ -248,11 +249,11 @@ __global__ __launch_bounds__(DC_THREADS, 1) void decode_chain_kernel(DecodeChain
         float4 ov[NU];
         float2 ml[NU];
         {
-            const float* src = p.att_part + ((int64_t)hh * p.att_nunit * 64) * (DD + 2);
+            const float* src = p.att_part + ((int64_t)hh * p.att_nunit * DEC_PART_ROWS) * DEC_PART_LD;
 #pragma unroll
             for (int c = 0; c < NU; c++) {     // (row 0 of a unit starts 16-byte aligned: 64 * 130 floats per unit)
                 if (c < p.att_nunit) {
-                    const float* u = src + (int64_t)c * 64 * (DD + 2);
+                    const float* u = src + (int64_t)c * DEC_PART_ROWS * DEC_PART_LD;
                     ml[c] = *reinterpret_cast<const float2*>(u + DD);
                     ov[c] = *reinterpret_cast<const float4*>(u + d0);
                 } else {

@@ -10,6 +10,7 @@
 #include "gemm_tile.h"
 #include "ln_row.h"
 #include "kv8_format.h"
+#include "relattn_decode_step.h"   // the layout of the attention partials
 
 struct GemmSkinnyArgs {
     const bf16_t* x; const bf16_t* w; void* y; const void* bias;
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
     if constexpr (PRO < 0) {
         // The input rows (M <= 2) are the merge of the decode attention's chunk partials
         // (relattn_decode.hip: O, max, sum per 128-key chunk; rows m = b * q + i): thread t owns columns 8 t .. 8 t + 7 = head t / 16, and weights the <= 12 units
-        // in chunk order -- the arithmetic of relattn_decode_merge2_kernel, in the shadow of the W stream instead of at the end of the
+        // in chunk order -- the arithmetic of relattn_decode_merge2_kernel (relattn_decode.hip), in the shadow of the W stream instead of at the end of the
         // attention launch behind a ticket (drain + atomic + two dependent reads: ~3 us per layer).
         static_assert(MT == 1, "attention-merge prologue: one 16-row tile");
         constexpr int MR = -PRO, XLD = 2048 + 8, NU = 12, DD = 128;
@@ -276,10 +277,10 @@ __global__ __launch_bounds__(256) void gemm_skinny_fused_kernel(SkinnyFusedArgs 
 #pragma unroll
         for (int m = 0; m < MR; m++) {
             const int bq = m < p.M ? m : 0, bb = bq / p.att_q, qi = bq % p.att_q;
-            const float* src = p.att_part + ((((int64_t)bb * p.att_H + hh) * p.att_nunit) * 64 + qi) * (DD + 2);
+            const float* src = p.att_part + ((((int64_t)bb * p.att_H + hh) * p.att_nunit) * DEC_PART_ROWS + qi) * DEC_PART_LD;
 #pragma unroll
             for (int c = 0; c < NU; c++) {
-                const float* u = src + (int64_t)(c < p.att_nunit ? c : p.att_nunit - 1) * 64 * (DD + 2);
+                const float* u = src + (int64_t)(c < p.att_nunit ? c : p.att_nunit - 1) * DEC_PART_ROWS * DEC_PART_LD;
                 ml[m][c] = *reinterpret_cast<const float2*>(u + DD);
                 const float2 a0 = *reinterpret_cast<const float2*>(u + d0), a1 = *reinterpret_cast<const float2*>(u + d0 + 2);
                 const float2 a2 = *reinterpret_cast<const float2*>(u + d0 + 4), a3 = *reinterpret_cast<const float2*>(u + d0 + 6);

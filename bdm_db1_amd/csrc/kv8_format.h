@@ -1,6 +1,7 @@
-// The quantising half of the fp8 K/V slot format (include/db1_hip.h, "fp8 K/V ring"; tests/kv8_rule.py): one definition for every kernel
-// that writes slots -- the ring attention's append and db1_kv8_quantize (relattn_decode_kv8.hip), the prefill's slot writers (ring_prefill.hip)
-// -- and, at the end, the widening of a slot's payload to VALUES for the attention over a ring-resident memory (relattn_mem.hip).
+// The fp8 K/V slot format (include/db1_hip.h, "fp8 K/V ring"; tests/kv8_rule.py).  The quantising half: one definition for every kernel
+// that writes slots -- the ring attention's append and db1_kv8_quantize (relattn_decode_kv8.hip), the prefill's slot writers (ring_prefill.hip).
+// The widening half, at the end: a slot's payload to unscaled bf16 for the ring attention (relattn_decode_kv8.hip, which applies the scales
+// to scores and probabilities) and to VALUES for the attention over a ring-resident memory (relattn_mem.hip).
 #pragma once
 #include "db1_common.h"
 
@@ -57,9 +58,24 @@ __device__ __forceinline__ void kv8_quant_block(const bf16_t* src, unsigned char
     }
 }
 
-// The widening half, for a kernel that wants VALUES: 8 payload bytes times the block's scale -> 8 bf16 (v_cvt_pk_f32_fp8, the product in fp32,
-// then the upper halves: a power of two times a 4-bit significand is exact in bf16 unless it is subnormal there; a NaN byte stays NaN)
+// ---- the widening half
 typedef __attribute__((ext_vector_type(2))) float kv8fmt_f32x2;
+typedef __attribute__((ext_vector_type(4))) unsigned kv8fmt_u32x4;
+typedef __attribute__((ext_vector_type(8))) short kv8fmt_bf16x8;
+// four e4m3 bytes -> four bf16 (two dwords): v_cvt_pk_f32_fp8, then the upper halves of the two floats (the low 16 bits are zero)
+__device__ __forceinline__ void kv8_widen4(unsigned w, unsigned& d0, unsigned& d1) {
+    const kv8fmt_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    d0 = __builtin_amdgcn_perm(__float_as_uint(lo[1]), __float_as_uint(lo[0]), 0x07060302u);
+    d1 = __builtin_amdgcn_perm(__float_as_uint(hi[1]), __float_as_uint(hi[0]), 0x07060302u);
+}
+__device__ __forceinline__ kv8fmt_bf16x8 kv8_widen8(uint2 w) {
+    unsigned d0, d1, d2, d3;
+    kv8_widen4(w.x, d0, d1);
+    kv8_widen4(w.y, d2, d3);
+    return __builtin_bit_cast(kv8fmt_bf16x8, (kv8fmt_u32x4){d0, d1, d2, d3});
+}
+// for a kernel that wants VALUES: 8 payload bytes times the block's scale -> 8 bf16 (v_cvt_pk_f32_fp8, the product in fp32,
+// then the upper halves: a power of two times a 4-bit significand is exact in bf16 unless it is subnormal there; a NaN byte stays NaN)
 __device__ __forceinline__ uint4 kv8_widen8_scaled(uint2 w, float sc) {
     const kv8fmt_f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.x, true);
     const kv8fmt_f32x2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, false), d = __builtin_amdgcn_cvt_pk_f32_fp8((int)w.y, true);

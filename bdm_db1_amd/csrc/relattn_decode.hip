@@ -11,33 +11,19 @@
 //   (8 MFMA; V^T via ds_read_b64_tr_b16 from the staged rows, with the key permutation that makes the S registers directly
 //   the B operand: slots 0-3 = keys 4g..4g+3 of the first 16-key block, slots 4-7 = the same keys of the second).
 //   Partials (m, l, O) per chunk go to a workspace; relattn_decode_merge_kernel combines them in chunk order.
-#include "db1_common.h"
+// The step's arithmetic, shared with the fp8 ring kernel and the memory kernel, and the layout of the partials: relattn_decode_step.h.
+#include "relattn_decode_step.h"
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short bf16x4_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-#define LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
-
-#define DEC_D 128
 #define DEC_KC 64                        // keys per workgroup (two 32-key steps: the chunks, not the loop, provide the parallelism)
-#define DEC_WAVE_LDS (32 * 256 + 48 * 16 * 4)  // V tile [32][128] bf16 + T scratch [48][16] f32
 
 struct DecodeArgs {
     const bf16_t* qu; const bf16_t* qv; const bf16_t* k; const bf16_t* v; const bf16_t* R;
-    float* part;   // [B][H][nchunk][64 queries][D + 2]: O (unnormalised), m, l
+    float* part;   // [B][H][nchunk] units (relattn_decode_step.h)
     bf16_t* out;
     int64_t kv_rs, kv_bs;
     int B, q, klen, mlen, H, shift, nd, nchunk;
     float scale;
 };
-
-typedef __attribute__((ext_vector_type(2))) float dec_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 dec_bf16x2;
-__device__ __forceinline__ unsigned dec_pk(float lo, float hi) {
-    dec_f32x2 v = {lo, hi};
-    dec_bf16x2 r = __builtin_convertvector(v, dec_bf16x2);
-    return *reinterpret_cast<unsigned*>(&r);
-}
 
 __global__ __launch_bounds__(256) void relattn_decode_kernel(DecodeArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -91,65 +77,28 @@ __global__ __launch_bounds__(256) void relattn_decode_kernel(DecodeArgs p) {
             for (int ks = 0; ks < 4; ks++)
                 acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(kr + ks * 32), fqu[ks], acc_s[blk], 0, 0, 0);
         }
-        // ---- relative term: distances d_lo .. d_lo+47 with d_lo = mlen + i0 - j0 - 31  ->  Tw[dist][query]
+        // ---- relative term: distances d_lo .. d_lo+47 with d_lo = mlen + i0 - j0 - 31  ->  Tw[dist][query], R rows straight from global
         const int d_lo = p.mlen + i0 - j0 - 31;
-#pragma unroll
-        for (int tb = 0; tb < 3; tb++) {
+        dec_rel_term(Tw, fqv, a, g, [&](int tb, int ks) {
             int dr = d_lo + 16 * tb + a;
             dr = dr < 0 ? 0 : (dr > p.nd - 1 ? p.nd - 1 : dr);  // out-of-range distances belong to masked pairs
-            const bf16_t* rr = Rg + (int64_t)dr * HD + g * 8;
-            f32x4 acc_t = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++)
-                acc_t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8_t*>(rr + ks * 32), fqv[ks], acc_t, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; r++) Tw[(16 * tb + 4 * g + r) * 16 + a] = acc_t[r];
-        }
-        // (same wave wrote and reads the scratch; LDS operations of a wave complete in order)
+            return *reinterpret_cast<const bf16x8_t*>(Rg + (int64_t)dr * HD + g * 8 + ks * 32);
+        });
         float s[8];
 #pragma unroll
         for (int blk = 0; blk < 2; blk++)
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int bcol = 16 * blk + 4 * g + r;  // key j0 + bcol
-                const int j = j0 + bcol;
-                const float v = (acc_s[blk][r] + Tw[(a - bcol + 31) * 16 + a]) * p.scale;
-                const bool vis = (j < p.klen) && (j <= i + p.mlen) && (j > i - p.shift) && (i < p.q);
-                s[blk * 4 + r] = vis ? v : -1.0e30f;
+                const float v = (acc_s[blk][r] + dec_rel_read(Tw, a, bcol)) * p.scale;
+                s[blk * 4 + r] = dec_visible(i, j0 + bcol, p.q, p.klen, p.mlen, p.shift) ? v : -1.0e30f;
             }
-        float mb = s[0];
-#pragma unroll
-        for (int t = 1; t < 8; t++) mb = fmaxf(mb, s[t]);
-        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-        const float m_new = fmaxf(m_i, mb);
-        const float alpha = __expf(m_i - m_new);
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < 8; t++) { s[t] = s[t] > -1.0e29f ? __expf(s[t] - m_new) : 0.f; rs += s[t]; }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_i = l_i * alpha + rs;
-        m_i = m_new;
-        union { unsigned u[4]; bf16x8_t v; } pb;
-#pragma unroll
-        for (int t = 0; t < 4; t++) pb.u[t] = dec_pk(s[2 * t], s[2 * t + 1]);
-        // ---- O^T[d][query] += V^T . P^T over the 32 keys (key permutation as described in the header)
-#pragma unroll
-        for (int db = 0; db < 8; db++) {
-            const int t16 = lane & 15;
-            const char* base = Vs + (t16 >> 2) * 256 + (db * 16 + (t16 & 3) * 4) * 2;
-            const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(base) + (4 * g) * 256));
-            const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(base) + (16 + 4 * g) * 256));
-            const bf16x8_t vt = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-            for (int r = 0; r < 4; r++) acc_o[db][r] *= alpha;
-            acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
-        }
+        const float alpha = dec_softmax_update(s, m_i, l_i);
+        dec_pv(acc_o, Vs, dec_pack_p(s), alpha, a, g);
     }
     // ---- partial results of this chunk: lane holds query a, d = db*16 + 4g + r
     if (i < p.q) {
-        float* dst = p.part + ((((int64_t)b * p.H + h) * p.nchunk + chunk) * 64 + i) * (DEC_D + 2);
+        float* dst = p.part + dec_part_off(b, p.H, h, p.nchunk, chunk, i);
 #pragma unroll
         for (int db = 0; db < 8; db++)
             *reinterpret_cast<float2*>(dst + db * 16 + 4 * g) = make_float2(acc_o[db][0], acc_o[db][1]),
@@ -161,8 +110,8 @@ __global__ __launch_bounds__(256) void relattn_decode_kernel(DecodeArgs p) {
 // one 128-thread block per (query, head, batch): combine the chunk partials in chunk order
 __global__ __launch_bounds__(128) void relattn_decode_merge_kernel(DecodeArgs p) {
     const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* src = p.part + ((((int64_t)b * p.H + h) * p.nchunk) * 64 + i) * (DEC_D + 2);
-    const int64_t cs = (int64_t)64 * (DEC_D + 2);
+    const float* src = p.part + dec_part_off(b, p.H, h, p.nchunk, 0, i);
+    const int64_t cs = DEC_PART_UNIT;
     float m = -1.0e30f;
     for (int c = 0; c < p.nchunk; c++) m = fmaxf(m, src[c * cs + DEC_D]);
     float l = 0.f, o = 0.f;
@@ -183,42 +132,17 @@ __global__ __launch_bounds__(128) void relattn_decode_merge_kernel(DecodeArgs p)
 // (start + mlen + i) % cap by the workgroups that visit them -- so a call appends in place instead of concatenating 8 MB per layer, and
 // `start` is a DEVICE scalar (advanced by db1_ring_advance after the last layer): the same captured graph serves every call.
 // q + u and q + v are formed here from qkv_new (rounded to bf16 like db1_relattn_add_head_bias does).
-// SPLIT (what the host launches): a workgroup = one 16-query tile x one 128-key chunk, its four waves are the chunk's four 32-key steps,
-// merged through LDS into one partial per (tile, chunk).  (The other form -- a wave is one of four 16-query tiles and walks the chunk's
-// steps itself -- took 38.6 us per launch at q = 22 against 8.8 us at q = 1: four dependent rounds of loads per wave.)
+// A workgroup = one 16-query tile x one 128-key chunk, its four waves are the chunk's four 32-key steps, merged through LDS into one
+// partial per (tile, chunk).  (An earlier form -- a wave is one of four 16-query tiles and walks the chunk's steps itself -- took 38.6 us
+// per launch at q = 22 against 8.8 us at q = 1: four dependent rounds of loads per wave.)
 #define DECR_KC 128
-struct DecodeRingArgs {
-    const bf16_t* qkv; const bf16_t* u; const bf16_t* vb; bf16_t* ring; const int* state; const bf16_t* R;
-    float* part; bf16_t* out; unsigned* tickets;
-    int B, q, klen, mlen, H, shift, nd, nunit, cap;
-    float scale;
-};
-__device__ __forceinline__ bf16x8_t dec_add_bias(const bf16x8_t a, const bf16x8_t b) {
-    union { unsigned u[4]; bf16x8_t v; } o;
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        const float x0 = __uint_as_float((unsigned)(unsigned short)a[2 * t] << 16) + __uint_as_float((unsigned)(unsigned short)b[2 * t] << 16);
-        const float x1 = __uint_as_float((unsigned)(unsigned short)a[2 * t + 1] << 16) + __uint_as_float((unsigned)(unsigned short)b[2 * t + 1] << 16);
-        o.u[t] = dec_pk(x0, x1);
-    }
-    return o.v;
-}
-__device__ __forceinline__ void dec_st_agent(float* p, float a, float b) {   // 8 bytes, write-through (sc1)
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), ((unsigned long long)__float_as_uint(b) << 32) | __float_as_uint(a), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void dec_ld_agent2(const float* p, float& a, float& b) {   // 8 bytes, L1-bypassing (sc1)
-    const unsigned long long v = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    a = __uint_as_float((unsigned)v); b = __uint_as_float((unsigned)(v >> 32));
-}
-template <bool SPLIT>
 __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // SPLIT: blockIdx.x = chunk * (number of 16-query tiles) + tile -- every workgroup is ONE query tile against ONE 128-key chunk
-    const int nqt = SPLIT ? (p.q + 15) / 16 : 1;
-    const int i0 = SPLIT ? ((int)blockIdx.x % nqt) * 16 : wave * 16;
-    const int chunk = SPLIT ? (int)blockIdx.x / nqt : (int)blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    // blockIdx.x = chunk * (number of 16-query tiles) + tile -- every workgroup is ONE query tile against ONE 128-key chunk
+    const int nqt = (p.q + 15) / 16;
+    const int i0 = ((int)blockIdx.x % nqt) * 16;
+    const int chunk = (int)blockIdx.x / nqt, h = blockIdx.y, b = blockIdx.z;
     const int a = lane & 15, g = lane >> 4;
     const int HD = p.H * DEC_D;
     char* Vs = smem + wave * DEC_WAVE_LDS;
@@ -237,8 +161,8 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
         const int start_ = p.state[0];
         const int ja = chunk * DECR_KC > p.mlen ? chunk * DECR_KC : p.mlen, jb = (chunk + 1) * DECR_KC < p.klen ? (chunk + 1) * DECR_KC : p.klen;
         const bf16_t* nk = p.qkv + (int64_t)b * p.q * 3 * HD + HD + h * DEC_D;
-        bf16_t* rg = p.ring + (int64_t)b * p.cap * 2 * HD + h * DEC_D;
-        for (int idx = threadIdx.x; idx < ((!SPLIT || i0 == 0) ? (jb - ja) * 32 : 0); idx += 256) {   // (one query tile of the chunk copies)
+        bf16_t* rg = reinterpret_cast<bf16_t*>(p.ring) + (int64_t)b * p.cap * 2 * HD + h * DEC_D;
+        for (int idx = threadIdx.x; idx < (i0 == 0 ? (jb - ja) * 32 : 0); idx += 256) {   // (one query tile of the chunk copies)
             const int j = ja + (idx >> 5), pc = idx & 31;          // piece 0..15: K, 16..31: V
             int r = start_ + j;
             r = r >= p.cap ? r - p.cap : r;
@@ -246,7 +170,7 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
                 *reinterpret_cast<const uint4*>(nk + (int64_t)(j - p.mlen) * 3 * HD + (pc >> 4) * HD + (pc & 15) * 8);
         }
     }
-    if (i0 >= p.q) return;  // waves are independent: no workgroup barrier below
+    if (i0 >= p.q) return;  // (never taken: i0 = 16 tile < q; a workgroup-uniform exit, so the barriers below stay whole)
     bf16x8_t fqu[4], fqv[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
@@ -254,7 +178,7 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
         fqv[ks] = dec_add_bias(qraw[ks], vraw[ks]);
     }
     const int start = p.state[0];
-    bf16_t* ring = p.ring + (int64_t)b * p.cap * 2 * HD + h * DEC_D;        // row r: K at r * 2 HD, V at r * 2 HD + HD
+    const bf16_t* ring = reinterpret_cast<const bf16_t*>(p.ring) + (int64_t)b * p.cap * 2 * HD + h * DEC_D;   // row r: K at r * 2 HD, V at r * 2 HD + HD
     const bf16_t* newkv = p.qkv + (int64_t)b * p.q * 3 * HD + HD + h * DEC_D;  // new row i: K at i * 3 HD, V at i * 3 HD + HD
     // K row of logical key j (V: + HD); j clamped by the caller.  A select, not a branch: with a divergent if / else around them the
     // compiler issued the 28 loads of a step one round trip at a time (14.6 us per launch at q = 1, almost all of it memory latency)
@@ -272,7 +196,9 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
     float m_i = -1.0e30f, l_i = 0.f;
     const int i = i0 + a;  // this lane's query
     const int jc0 = chunk * DECR_KC;
-    for (int st = SPLIT ? wave : 0; st < (SPLIT ? wave + 1 : DECR_KC / 32); st++) {
+    // (one step per wave, st = wave.  Kept in the shape of a loop: as one `if` the compiler schedules the step's prologue differently and a
+    // launch at q = 1 took 6.9 us instead of 6.7 us)
+    for (int st = wave; st < wave + 1; st++) {
         const int j0 = jc0 + st * 32;
         if (j0 >= p.klen) break;
         if (j0 > i0 + 15 + p.mlen || j0 + 31 <= i0 - p.shift) continue;   // whole step outside the window of every query of the tile (wave-uniform)
@@ -315,7 +241,9 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
 #pragma unroll
             for (int ks = 0; ks < 4; ks++) acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kreg[blk][ks], fqu[ks], acc_s[blk], 0, 0, 0);
         }
-        // ---- relative term  ->  Tw[dist][query]
+        // ---- relative term  ->  Tw[dist][query].  From here to the end of the step this kernel keeps its OWN COPY of dec_rel_term, dec_visible,
+        // dec_softmax_update and dec_pv (relattn_decode_step.h; the fp8 kernel calls them): through the functions the compiler scheduled the
+        // step differently and generation at 16 and 64 rows took 2 - 4 % longer per token.  Keep the order of operations equal to theirs.
 #pragma unroll
         for (int tb = 0; tb < 3; tb++) {
             f32x4 acc_t = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -351,7 +279,7 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
         m_i = m_new;
         union { unsigned u[4]; bf16x8_t v; } pb;
 #pragma unroll
-        for (int t = 0; t < 4; t++) pb.u[t] = dec_pk(s[2 * t], s[2 * t + 1]);
+        for (int t = 0; t < 4; t++) pb.u[t] = f2bf_pk(s[2 * t], s[2 * t + 1]);
 #pragma unroll
         for (int db = 0; db < 8; db++) {
             const int t16 = lane & 15;
@@ -364,112 +292,22 @@ __global__ __launch_bounds__(256) void relattn_decode_ring_kernel(DecodeRingArgs
             acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
         }
     }
-    if (!SPLIT) {
-        if (i < p.q) {
-            float* dst = p.part + ((((int64_t)b * p.H + h) * p.nunit + chunk) * 64 + i) * (DEC_D + 2);
-#pragma unroll
-            for (int db = 0; db < 8; db++)
-                *reinterpret_cast<float2*>(dst + db * 16 + 4 * g) = make_float2(acc_o[db][0], acc_o[db][1]),
-                *reinterpret_cast<float2*>(dst + db * 16 + 4 * g + 2) = make_float2(acc_o[db][2], acc_o[db][3]);
-            if (g == 0) { dst[DEC_D] = m_i; dst[DEC_D + 1] = l_i; }
-        }
-        return;
-    }
-    // ---- SPLIT: the four waves' partial results (one 32-key step each) are merged here, through LDS, into ONE unit per chunk (every wave
-    // reaches this point: i0 = 0 < q, and break / continue above only skip the step)
-    constexpr int OLD = DEC_D + 4;                       // floats per query row in LDS: O[128], m, l, pad
-    float* mine = reinterpret_cast<float*>(Vs);          // (the wave's own V stage / T scratch, 11 KB >= 16 rows x 132 floats: it is done with them)
-#pragma unroll
-    for (int db = 0; db < 8; db++) *reinterpret_cast<f32x4*>(mine + a * OLD + db * 16 + 4 * g) = acc_o[db];
-    if (g == 0) { mine[a * OLD + DEC_D] = m_i; mine[a * OLD + DEC_D + 1] = l_i; }
-    __syncthreads();
+    // ---- the four waves' partial results (one 32-key step each) are merged here, through LDS, into ONE unit per chunk (every wave reaches
+    // this point: a skipped step contributes (0, -1e30, 0))
+    float o8[8], mx, lsum;
+    dec_merge_waves<DEC_WAVE_LDS>(smem, acc_o, m_i, l_i, o8, mx, lsum);
     const bool inlaunch = p.tickets != nullptr;   // the merge over the chunks happens in this launch too: partials as write-through stores
-    {
-        const int qi = threadIdx.x & 15, dg = (threadIdx.x >> 4) * 8;
-        const float* w0p = reinterpret_cast<const float*>(smem) + qi * OLD;
-        float mw[4], lw[4], mx = -1.0e30f;
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            mw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D]; lw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D + 1];
-            mx = fmaxf(mx, mw[w]);
-        }
-        float lsum_ = 0.f, o8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < 4; w++) {   // (waves in order: deterministic)
-            const float wt = lw[w] > 0.f ? __expf(mw[w] - mx) : 0.f;
-            lsum_ += lw[w] * wt;
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg), hi = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg + 4);
-#pragma unroll
-            for (int j = 0; j < 4; j++) { o8[j] += lo[j] * wt; o8[4 + j] += hi[j] * wt; }
-        }
-        if (i0 + qi < p.q) {
-            float* dst = p.part + ((((int64_t)b * p.H + h) * p.nunit + chunk) * 64 + i0 + qi) * (DEC_D + 2);
-            if (inlaunch) {
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) dec_st_agent(dst + dg + j, o8[j], o8[j + 1]);
-                if (dg == 0) dec_st_agent(dst + DEC_D, mx, lsum_);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) *reinterpret_cast<float2*>(dst + dg + j) = make_float2(o8[j], o8[j + 1]);
-                if (dg == 0) { dst[DEC_D] = mx; dst[DEC_D + 1] = lsum_; }
-            }
-        }
-    }
-    if (!inlaunch) return;
-    // ---- the chunk that finishes last for this (batch, head) merges the units (ticket counter, zero on entry and left zero): one launch less
-    // per layer.  Same arithmetic as relattn_decode_merge2_kernel, two queries at a time (128 threads each).
-    // Hand-off (per-XCD L2s are not coherent, L1s never refreshed): write-through 8-byte stores above, every wave drains them, one relaxed
-    // agent-scope ticket per workgroup, and the merging workgroup reads the partials with L1-bypassing (sc1) loads.
-    __shared__ unsigned ticket_s;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    unsigned* tk = p.tickets + ((int64_t)b * p.H + h) * nqt + i0 / 16;
-    if (threadIdx.x == 0) ticket_s = __hip_atomic_fetch_add(tk, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (ticket_s != gridDim.x / nqt - 1) return;
-    if (threadIdx.x == 0) __hip_atomic_store(tk, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    {   // thread = (query qi of the tile, 8 output columns): all units' pieces are requested at once (<= 16 chunks: klen <= 2048), weighted in
-        // chunk order -- the arithmetic of relattn_decode_merge2_kernel, one round trip instead of one per row pair
-        constexpr int NU = 16;
-        const int qi = threadIdx.x & 15, dg = (threadIdx.x >> 4) * 8;
-        const bool valid = i0 + qi < p.q;
-        const float* src = p.part + ((((int64_t)b * p.H + h) * p.nunit) * 64 + (valid ? i0 + qi : i0)) * (DEC_D + 2);
-        const int64_t cs = (int64_t)64 * (DEC_D + 2);
-        float mlm[NU], mll[NU], ov[NU][8];
-#pragma unroll
-        for (int c = 0; c < NU; c++) {
-            const float* u = src + (c < p.nunit ? c : p.nunit - 1) * cs;
-            dec_ld_agent2(u + DEC_D, mlm[c], mll[c]);
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) dec_ld_agent2(u + dg + j, ov[c][j], ov[c][j + 1]);
-        }
-        float mx = -1.0e30f;
-#pragma unroll
-        for (int c = 0; c < NU; c++) mx = fmaxf(mx, c < p.nunit ? mlm[c] : -1.0e30f);
-        float l = 0.f, o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NU; c++) {
-            const float lc = c < p.nunit ? mll[c] : 0.f;
-            const float wt = lc > 0.f ? __expf(mlm[c] - mx) : 0.f;
-            l += lc * wt;
-#pragma unroll
-            for (int j = 0; j < 8; j++) o[j] += ov[c][j] * wt;
-        }
-        if (valid) {
-            uint4 w;
-            w.x = f2bf_pk(l > 0.f ? o[0] / l : 0.f, l > 0.f ? o[1] / l : 0.f); w.y = f2bf_pk(l > 0.f ? o[2] / l : 0.f, l > 0.f ? o[3] / l : 0.f);
-            w.z = f2bf_pk(l > 0.f ? o[4] / l : 0.f, l > 0.f ? o[5] / l : 0.f); w.w = f2bf_pk(l > 0.f ? o[6] / l : 0.f, l > 0.f ? o[7] / l : 0.f);
-            *reinterpret_cast<uint4*>(p.out + ((int64_t)b * p.q + i0 + qi) * p.H * DEC_D + h * DEC_D + dg) = w;
-        }
-    }
+    const int qt = threadIdx.x & 15, dg = (threadIdx.x >> 4) * 8;
+    if (i0 + qt < p.q) dec_store_unit(p.part + dec_part_off(b, p.H, h, p.nunit, chunk, i0 + qt), dg, o8, mx, lsum, inlaunch);
+    if (inlaunch) dec_inlaunch_merge(p, b, h, nqt, i0);
 }
 // one 128-thread block per (query, head, batch): the units' (m, l) first (independent loads, weights through LDS), then the weighted sum
 __global__ __launch_bounds__(128) void relattn_decode_merge2_kernel(const float* __restrict__ part, bf16_t* __restrict__ out, int q, int H, int nunit) {
     __shared__ float wgt[64];
     __shared__ float red[2];
     const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, d = threadIdx.x;
-    const float* src = part + ((((int64_t)b * H + h) * nunit) * 64 + i) * (DEC_D + 2);
-    const int64_t cs = (int64_t)64 * (DEC_D + 2);
+    const float* src = part + dec_part_off(b, H, h, nunit, 0, i);
+    const int64_t cs = DEC_PART_UNIT;
     if (d < 64) {   // first wave: nunit <= 64 units
         const float m = d < nunit ? src[d * cs + DEC_D] : -1.0e30f;
         const float l = d < nunit ? src[d * cs + DEC_D + 1] : 0.f;
@@ -490,6 +328,11 @@ __global__ __launch_bounds__(128) void relattn_decode_merge2_kernel(const float*
     const float l = red[0];
     out[((int64_t)b * q + i) * H * DEC_D + h * DEC_D + d] = f2bf(l > 0.f ? o / l : 0.f);
 }
+int dec_launch_merge2(const float* part, bf16_t* out, int B, int q, int H, int nunit, hipStream_t st) {
+    relattn_decode_merge2_kernel<<<dim3((unsigned)q, (unsigned)H, (unsigned)B), 128, 0, st>>>(part, out, q, H, nunit);
+    DB1_CHECK_LAUNCH("relattn_decode_merge2");
+    return DB1_OK;
+}
 __global__ void ring_advance_kernel(int* state, int q, int cap) { int s = state[0] + q; state[0] = s >= cap ? s - cap : s; }
 
 extern "C" int db1_ring_advance(int* state, int q, int cap, void* stream) {
@@ -500,7 +343,7 @@ extern "C" int db1_ring_advance(int* state, int q, int cap, void* stream) {
 }
 extern "C" int64_t db1_relattn_decode_ring_workspace_bytes(int B, int q, int klen, int H) {
     (void)q;
-    return (int64_t)B * H * ((klen + 31) / 32) * 64 * (DEC_D + 2) * (int64_t)sizeof(float);
+    return (int64_t)B * H * ((klen + 31) / 32) * DEC_PART_UNIT * (int64_t)sizeof(float);
 }
 extern "C" int db1_relattn_decode_ring_fwd(const void* qkv_new, const void* u, const void* vb, void* kv_ring, const int* ring_state, int cap, const void* R,
                                            int nd, void* out, int B, int q, int mlen, int H, int D, int shift, float scale, void* ws, int64_t ws_bytes,
@@ -512,21 +355,17 @@ extern "C" int db1_relattn_decode_ring_fwd(const void* qkv_new, const void* u, c
     if (!db1_aligned16(qkv_new) || !db1_aligned16(kv_ring) || !db1_aligned16(R) || (out && !db1_aligned16(out)) || !db1_aligned16(u) || !db1_aligned16(vb))
         DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_decode_ring: operands must be 16-byte aligned");
     DecodeRingArgs a;
-    a.qkv = (const bf16_t*)qkv_new; a.u = (const bf16_t*)u; a.vb = (const bf16_t*)vb; a.ring = (bf16_t*)kv_ring; a.state = ring_state; a.R = (const bf16_t*)R;
+    a.qkv = (const bf16_t*)qkv_new; a.u = (const bf16_t*)u; a.vb = (const bf16_t*)vb; a.ring = (unsigned char*)kv_ring; a.state = ring_state; a.R = (const bf16_t*)R;
     a.out = (bf16_t*)out; a.B = B; a.q = q; a.klen = klen; a.mlen = mlen; a.H = H; a.shift = shift; a.nd = nd; a.cap = cap; a.scale = scale;
-    const bool split = true;   // (one workgroup per (query tile, chunk) for every q: the tile-per-wave form walked a chunk's four steps in sequence)
     const int nchunk = (klen + DECR_KC - 1) / DECR_KC, nqt = (q + 15) / 16;
     a.tickets = ((int64_t)B * H * nqt <= 2048 && out) ? (unsigned*)tickets : nullptr;   // (the ticket buffer of db1_linear_decode_tickets_bytes)
     a.nunit = nchunk;   // (the four waves of a workgroup are merged inside it)
     DB1_NEED_WS(ws, ws_bytes, db1_relattn_decode_ring_workspace_bytes(B, q, klen, H), "relattn_decode_ring");
     a.part = (float*)ws;
     hipStream_t st = (hipStream_t)stream;
-    relattn_decode_ring_kernel<true><<<dim3((unsigned)(nchunk * nqt), (unsigned)H, (unsigned)B), 256, 4 * DEC_WAVE_LDS, st>>>(a);
+    relattn_decode_ring_kernel<<<dim3((unsigned)(nchunk * nqt), (unsigned)H, (unsigned)B), 256, 4 * DEC_WAVE_LDS, st>>>(a);
     DB1_CHECK_LAUNCH("relattn_decode_ring");
-    if (out && !(split && a.tickets)) {
-        relattn_decode_merge2_kernel<<<dim3((unsigned)q, (unsigned)H, (unsigned)B), 128, 0, st>>>(a.part, a.out, q, H, a.nunit);
-        DB1_CHECK_LAUNCH("relattn_decode_merge2");
-    }
+    if (out && !a.tickets) return dec_launch_merge2(a.part, a.out, B, q, H, a.nunit, st);
     return DB1_OK;
 }
 
@@ -536,7 +375,7 @@ extern "C" int db1_relattn_decode_supported(int B, int q, int klen, int H, int D
 
 extern "C" int64_t db1_relattn_decode_workspace_bytes(int B, int q, int klen, int H) {  // per (b, h, key chunk): 64 rows x (out, max, sum)
     (void)q;
-    return (int64_t)B * H * ((klen + DEC_KC - 1) / DEC_KC) * 64 * (DEC_D + 2) * (int64_t)sizeof(float);
+    return (int64_t)B * H * ((klen + DEC_KC - 1) / DEC_KC) * DEC_PART_UNIT * (int64_t)sizeof(float);
 }
 
 extern "C" int db1_relattn_decode_fwd(const void* qu, const void* qv, const void* k, const void* v, int64_t kv_row_stride,
@@ -683,64 +522,16 @@ __device__ __forceinline__ void decode_group_unit(const DecodeGroupArgs& p, char
                 const bool vis = x >= lo && x <= hi && x + joff > -p.shift;
                 s[blk * 4 + r] = vis ? acc_s[blk][r] * p.scale : -1.0e30f;
             }
-        float mb = s[0];
-#pragma unroll
-        for (int t = 1; t < 8; t++) mb = fmaxf(mb, s[t]);
-        mb = fmaxf(mb, __shfl_xor(mb, 16, 64));
-        mb = fmaxf(mb, __shfl_xor(mb, 32, 64));
-        m_i = mb;                      // (one step per wave: no running maximum to rescale)
-        float rs = 0.f;
-#pragma unroll
-        for (int t = 0; t < 8; t++) { s[t] = s[t] > -1.0e29f ? __expf(s[t] - m_i) : 0.f; rs += s[t]; }
-        rs += __shfl_xor(rs, 16, 64);
-        rs += __shfl_xor(rs, 32, 64);
-        l_i = rs;
-        union { unsigned u[4]; bf16x8_t v; } pb;
-#pragma unroll
-        for (int t = 0; t < 4; t++) pb.u[t] = dec_pk(s[2 * t], s[2 * t + 1]);
-        // ---- O^T[d][row] = V^T . P^T over the 32 keys (key permutation as in the header of this file)
-#pragma unroll
-        for (int db = 0; db < 8; db++) {
-            const int t16 = lane & 15;
-            const char* bs = Vs + (t16 >> 2) * 256 + (db * 16 + (t16 & 3) * 4) * 2;
-            const bf16x4_t vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(bs) + (4 * lg) * 256));
-            const bf16x4_t vhi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(bs) + (16 + 4 * lg) * 256));
-            const bf16x8_t vt = __builtin_shufflevector(vlo, vhi, 0, 1, 2, 3, 4, 5, 6, 7);
-            acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
-        }
+        m_i = dec_tile_max(s);         // (one step per wave: no running maximum, nothing accumulated to rescale)
+        l_i = dec_tile_exp(s, m_i);
+        dec_pv(acc_o, Vs, dec_pack_p(s), 1.f, a, lg);
     }
     // ---- the four waves' partial results (one 32-position step each) merged through LDS into ONE unit, waves in order
-    constexpr int OLD = DEC_D + 4;                       // floats per row in LDS: O[128], m, l, pad
-    float* mine = reinterpret_cast<float*>(Vs);          // (the wave's own V stage: it is done with it)
-#pragma unroll
-    for (int db = 0; db < 8; db++) *reinterpret_cast<f32x4*>(mine + a * OLD + db * 16 + 4 * lg) = acc_o[db];
-    if (lg == 0) { mine[a * OLD + DEC_D] = m_i; mine[a * OLD + DEC_D + 1] = l_i; }
-    __syncthreads();
+    float o8[8], mx, lsum;
+    dec_merge_waves<DEC_WAVE_LDS>(smem, acc_o, m_i, l_i, o8, mx, lsum);
     const int qi = threadIdx.x & 15, dg = (threadIdx.x >> 4) * 8;
-    const float* w0p = reinterpret_cast<const float*>(smem) + qi * OLD;
-    float mw[4], lw[4], mx = -1.0e30f;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        mw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D]; lw[w] = w0p[w * (DEC_WAVE_LDS / 4) + DEC_D + 1];
-        mx = fmaxf(mx, mw[w]);
-    }
-    float lsum_ = 0.f, o8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const float wt = lw[w] > 0.f ? __expf(mw[w] - mx) : 0.f;
-        lsum_ += lw[w] * wt;
-        const f32x4 o_lo = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg), o_hi = *reinterpret_cast<const f32x4*>(w0p + w * (DEC_WAVE_LDS / 4) + dg + 4);
-#pragma unroll
-        for (int j = 0; j < 4; j++) { o8[j] += o_lo[j] * wt; o8[4 + j] += o_hi[j] * wt; }
-    }
     const int wrow = PRIV ? sub : 16 * sub + qi;          // the row inside the group this thread's column stands for
-    if (PRIV ? qi == 0 : wrow < p.W) {
-        const int unit = PRIV ? p.nb + chunk : chunk;
-        float* dst = p.part + ((((int64_t)grp * p.H + h) * p.nunit + unit) * 64 + wrow) * (DEC_D + 2);
-#pragma unroll
-        for (int j = 0; j < 8; j += 2) *reinterpret_cast<float2*>(dst + dg + j) = make_float2(o8[j], o8[j + 1]);
-        if (dg == 0) { dst[DEC_D] = mx; dst[DEC_D + 1] = lsum_; }
-    }
+    if (PRIV ? qi == 0 : wrow < p.W) dec_store_unit(p.part + dec_part_off(grp, p.H, h, p.nunit, PRIV ? p.nb + chunk : chunk, wrow), dg, o8, mx, lsum, false);
 }
 // grid = (nb ntile shared units + nt W private units, heads, groups)
 __global__ __launch_bounds__(256) void relattn_decode_group_kernel(DecodeGroupArgs p) {
@@ -771,7 +562,7 @@ static inline int dec_group_units(int mlen, int Lt) { return (mlen + DECR_KC - 1
 extern "C" int64_t db1_relattn_decode_group_workspace_bytes(int G, int W, int mlen, int Lt, int H) {
     (void)W;
     if (G <= 0 || H <= 0 || mlen < 1 || Lt < 1) return 0;
-    return (int64_t)G * H * dec_group_units(mlen, Lt) * 64 * (DEC_D + 2) * (int64_t)sizeof(float);
+    return (int64_t)G * H * dec_group_units(mlen, Lt) * DEC_PART_UNIT * (int64_t)sizeof(float);
 }
 extern "C" int db1_relattn_decode_group_fwd(const void* qkv_new, const void* u, const void* vb, const void* base, const int32_t* state_b, int cap_b, void* tail,
                                             const int32_t* state_t, int cap_t, const int32_t* n_tail, int Lt, const void* R, int nd, void* out, int G, int W,
@@ -794,9 +585,7 @@ extern "C" int db1_relattn_decode_group_fwd(const void* qkv_new, const void* u, 
     const unsigned nx = (unsigned)(a.nb * a.ntile + (a.nunit - a.nb) * W);
     relattn_decode_group_kernel<<<dim3(nx, (unsigned)H, (unsigned)G), 256, 4 * DEC_WAVE_LDS, st>>>(a);
     DB1_CHECK_LAUNCH("relattn_decode_group");
-    relattn_decode_merge2_kernel<<<dim3((unsigned)W, (unsigned)H, (unsigned)G), 128, 0, st>>>(a.part, (bf16_t*)out, W, H, a.nunit);
-    DB1_CHECK_LAUNCH("relattn_decode_group merge");
-    return DB1_OK;
+    return dec_launch_merge2(a.part, (bf16_t*)out, G, W, H, a.nunit, st);
 }
 extern "C" int db1_group_ring_advance(int32_t* state_t, int32_t* n_tail, int cap_t, int Lt, int mlen, void* stream) {
     if (!state_t || !n_tail || cap_t <= 0 || Lt < 1 || mlen < 1 || cap_t < Lt + 1) DB1_FAIL(DB1_ERR_BAD_SHAPE, "group_ring_advance: cap_t=%d Lt=%d mlen=%d", cap_t, Lt, mlen);

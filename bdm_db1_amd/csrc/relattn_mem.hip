@@ -17,17 +17,12 @@
 //   distances the 16 x 32 block touches (3 x 4 MFMA against R rows) through the wave's LDS scratch [48 dist][16 q]
 //   and the skewed read-back, online softmax, P rounded to bf16, O^T += V^T.P^T (8 MFMA).  Then ONE normalisation, one bf16 store, and
 //   lse = m + log(l) (the sum over the fp32 probabilities).
-#include "db1_common.h"
+//   The step is this kernel's OWN COPY of what relattn_decode_step.h holds for the decode kernels (only the types and constants come from
+//   there): through that header's functions -- even the mask predicate alone -- the compiler scheduled this loop differently, and the
+//   launch took 693 us instead of 581 us at the caption prompt's shape.  Keep the order of operations equal to the header's.
+#include "relattn_decode_step.h"
 #include "kv8_format.h"
 
-typedef __attribute__((ext_vector_type(8))) short mem_bf16x8;
-typedef __attribute__((ext_vector_type(4))) short mem_bf16x4;
-typedef __attribute__((ext_vector_type(4))) float mem_f32x4;
-typedef __attribute__((ext_vector_type(2))) float mem_f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 mem_bf16x2;
-#define MEM_LDS_PTR(T, p) ((__attribute__((address_space(3))) T*)(p))
-
-#define MEM_D 128
 #define MEM_QB 64                       // queries per workgroup
 #define MEM_TILE (32 * 256)             // one 32-key tile of K or V: [32][128] bf16
 #define MEM_TW (48 * 16 * 4)            // the wave's distance scratch [48][16] f32
@@ -49,12 +44,6 @@ struct MemArgs {
     int M_base, cap_base;
 };
 
-__device__ __forceinline__ unsigned mem_pk(float lo, float hi) {
-    mem_f32x2 v = {lo, hi};
-    mem_bf16x2 r = __builtin_convertvector(v, mem_bf16x2);
-    return *reinterpret_cast<unsigned*>(&r);
-}
-
 // KV = false: k, v hold all klen rows.  KV = true (db1_relattn_mem_kv_fwd): logical key j < mlen is row j of km / vm, key j >= mlen row
 // j - mlen of k / v -- only the staged rows' addresses differ, so the result is bit for bit that of KV = false over the concatenation.
 // RING (with KV; db1_relattn_mem_ring_fwd): logical key j < mlen is slot (origin + j) % cap_base of ring row base_rows[b] of a K/V ring --
@@ -68,24 +57,24 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     const int ib0 = blockIdx.x * MEM_QB, h = blockIdx.y, b = blockIdx.z;
     const int i0 = ib0 + wave * 16;
     const int a = lane & 15, g = lane >> 4;
-    const int HD = p.H * MEM_D;
+    const int HD = p.H * DEC_D;
     char* Rr = smem + 4 * MEM_TILE;
     float* Tw = reinterpret_cast<float*>(smem + 4 * MEM_TILE + MEM_RING + wave * MEM_TW);
     const int i = i0 + a;                                  // this lane's query
     const int qi = i < p.q ? i : p.q - 1;                  // rows beyond q repeat the last query (never stored)
-    const bf16_t* qu = p.qu + ((int64_t)b * p.q + qi) * HD + h * MEM_D + g * 8;
-    const bf16_t* qv = p.qv + ((int64_t)b * p.q + qi) * HD + h * MEM_D + g * 8;
-    mem_bf16x8 fqu[4], fqv[4];
+    const bf16_t* qu = p.qu + ((int64_t)b * p.q + qi) * HD + h * DEC_D + g * 8;
+    const bf16_t* qv = p.qv + ((int64_t)b * p.q + qi) * HD + h * DEC_D + g * 8;
+    bf16x8_t fqu[4], fqv[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {
-        fqu[ks] = *reinterpret_cast<const mem_bf16x8*>(qu + ks * 32);
-        fqv[ks] = *reinterpret_cast<const mem_bf16x8*>(qv + ks * 32);
+        fqu[ks] = *reinterpret_cast<const bf16x8_t*>(qu + ks * 32);
+        fqv[ks] = *reinterpret_cast<const bf16x8_t*>(qv + ks * 32);
     }
-    const bf16_t* kg = p.k + (int64_t)b * p.kv_bs + h * MEM_D;
-    const bf16_t* vg = p.v + (int64_t)b * p.kv_bs + h * MEM_D;
-    const bf16_t* Rg = p.R + h * MEM_D;
-    const bf16_t* kmg = KV ? p.km + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
-    const bf16_t* vmg = KV ? p.vm + (int64_t)b * p.m_bs + h * MEM_D : nullptr;
+    const bf16_t* kg = p.k + (int64_t)b * p.kv_bs + h * DEC_D;
+    const bf16_t* vg = p.v + (int64_t)b * p.kv_bs + h * DEC_D;
+    const bf16_t* Rg = p.R + h * DEC_D;
+    const bf16_t* kmg = KV ? p.km + (int64_t)b * p.m_bs + h * DEC_D : nullptr;
+    const bf16_t* vmg = KV ? p.vm + (int64_t)b * p.m_bs + h * DEC_D : nullptr;
     // RING: the call row's ring row and the origin, clamped into range -- every read stays in bounds, one thread per call row reports it
     const unsigned char* ringb = nullptr;
     int rs0 = 0;
@@ -114,14 +103,14 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
         const int r_ = rs0 + j_ >= p.cap_base ? rs0 + j_ - p.cap_base : rs0 + j_;
         const unsigned char* sl_ = ringb + (int64_t)r_ * rslot;
         if (RING == 2) {
-            const uint2 kp_ = *reinterpret_cast<const uint2*>(sl_ + h * MEM_D + sch * 8), vp_ = *reinterpret_cast<const uint2*>(sl_ + HD + h * MEM_D + sch * 8);
+            const uint2 kp_ = *reinterpret_cast<const uint2*>(sl_ + h * DEC_D + sch * 8), vp_ = *reinterpret_cast<const uint2*>(sl_ + HD + h * DEC_D + sch * 8);
             kx_ = make_uint4(kp_.x, kp_.y, 0u, 0u);
             vx_ = make_uint4(vp_.x, vp_.y, 0u, 0u);
             ks_ = reinterpret_cast<const float*>(sl_ + 2 * HD)[h];
             vs_ = reinterpret_cast<const float*>(sl_ + 2 * HD)[p.H + h];
         } else {
-            kx_ = *reinterpret_cast<const uint4*>(sl_ + (h * MEM_D + sch * 8) * 2);
-            vx_ = *reinterpret_cast<const uint4*>(sl_ + (HD + h * MEM_D + sch * 8) * 2);
+            kx_ = *reinterpret_cast<const uint4*>(sl_ + (h * DEC_D + sch * 8) * 2);
+            vx_ = *reinterpret_cast<const uint4*>(sl_ + (HD + h * DEC_D + sch * 8) * 2);
         }
     };
     // rows past klen are clamped: their probabilities are exactly zero
@@ -207,9 +196,9 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
         *reinterpret_cast<uint4*>(Rr + (ub_ & 127) * 256 + ((sch ^ (ub_ & 15)) << 4)) = rst1;                 \
     }
     const int DL0 = p.mlen + ib0 - 31;           // the block's lowest distance at step st is DL0 - 32 st
-    mem_f32x4 acc_o[8];
+    f32x4 acc_o[8];
 #pragma unroll
-    for (int db = 0; db < 8; db++) acc_o[db] = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int db = 0; db < 8; db++) acc_o[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
     float m_i = -1.0e30f, l_i = 0.f;
     MEM_STAGE_LOAD(st_lo)
 #pragma unroll
@@ -235,10 +224,10 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
             for (int tb = 0; tb < 3; tb++) {
                 const int u = d_lo + 16 * tb + a;
                 const char* rrow = Rr + (u & 127) * 256;
-                mem_f32x4 acc_t = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+                f32x4 acc_t = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {
-                    const mem_bf16x8 rf = *reinterpret_cast<const mem_bf16x8*>(rrow + (((ks * 4 + g) ^ (u & 15)) << 4));
+                    const bf16x8_t rf = *reinterpret_cast<const bf16x8_t*>(rrow + (((ks * 4 + g) ^ (u & 15)) << 4));
                     acc_t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rf, fqv[ks], acc_t, 0, 0, 0);
                 }
 #pragma unroll
@@ -247,18 +236,17 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
             const char* Ks = smem + cur * MEM_TILE;
             const char* Vs = smem + (2 + cur) * MEM_TILE;
             // ---- S^T[key][query] for the two 16-key blocks
-            mem_f32x4 acc_s[2];
+            f32x4 acc_s[2];
 #pragma unroll
             for (int blk = 0; blk < 2; blk++) {
-                acc_s[blk] = (mem_f32x4){0.f, 0.f, 0.f, 0.f};
+                acc_s[blk] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 const int row = 16 * blk + a;
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) {
-                    const mem_bf16x8 kf = *reinterpret_cast<const mem_bf16x8*>(Ks + row * 256 + (((ks * 4 + g) ^ (row & 15)) << 4));
+                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Ks + row * 256 + (((ks * 4 + g) ^ (row & 15)) << 4));
                     acc_s[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, fqu[ks], acc_s[blk], 0, 0, 0);
                 }
             }
-            // (same wave wrote and reads the scratch; LDS operations of a wave complete in order)
             float s[8];
 #pragma unroll
             for (int blk = 0; blk < 2; blk++)
@@ -284,9 +272,9 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
             rs += __shfl_xor(rs, 32, 64);
             l_i = l_i * alpha + rs;
             m_i = m_new;
-            union { unsigned u[4]; mem_bf16x8 v; } pb;
+            union { unsigned u[4]; bf16x8_t v; } pb;
 #pragma unroll
-            for (int t = 0; t < 4; t++) pb.u[t] = mem_pk(s[2 * t], s[2 * t + 1]);
+            for (int t = 0; t < 4; t++) pb.u[t] = f2bf_pk(s[2 * t], s[2 * t + 1]);
             // ---- O^T[d][query] += V^T . P^T over the 32 keys (key permutation of relattn_decode_kernel: slots 0-3 = keys 4g..4g+3 of the
             // first 16-key block, slots 4-7 = the same keys of the second); lane reads 8 bytes of row 4g + (a >> 2) (+ 16), columns db*16 + (a & 3)*4
             const int vrow = 4 * g + (a >> 2);                       // (vrow & 7) == ((vrow + 16) & 7): one swizzle for both reads
@@ -295,9 +283,9 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
             for (int db = 0; db < 8; db++) {
                 const int slot = (db * 2 + ((a & 3) >> 1)) ^ vsw;
                 const char* base = Vs + vrow * 256 + (slot << 4) + ((a & 1) << 3);
-                const mem_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(MEM_LDS_PTR(mem_bf16x4, const_cast<char*>(base)));
-                const mem_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(MEM_LDS_PTR(mem_bf16x4, const_cast<char*>(base) + 16 * 256));
-                const mem_bf16x8 vt = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+                const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(base)));
+                const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(bf16x4_t, const_cast<char*>(base) + 16 * 256));
+                const bf16x8_t vt = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 #pragma unroll
                 for (int r = 0; r < 4; r++) acc_o[db][r] *= alpha;
                 acc_o[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pb.v, acc_o[db], 0, 0, 0);
@@ -312,7 +300,7 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
     // ---- one normalisation, one store: lane holds query a, d = db*16 + 4g + r.  Every row i < q saw at least one key (shift + mlen >= 1)
     if (i < p.q) {
         const float inv = l_i > 0.f ? 1.0f / l_i : 0.f;
-        bf16_t* dst = p.out + ((int64_t)b * p.q + i) * HD + h * MEM_D + 4 * g;
+        bf16_t* dst = p.out + ((int64_t)b * p.q + i) * HD + h * DEC_D + 4 * g;
 #pragma unroll
         for (int db = 0; db < 8; db++) {
             uint2 w;
@@ -325,7 +313,7 @@ __global__ __launch_bounds__(256) void relattn_mem_kernel(MemArgs p) {
 }
 
 extern "C" int db1_relattn_mem_supported(int B, int q, int klen, int mlen, int H, int D, int shift, int dt) {
-    return (dt == DB1_BF16 && D == MEM_D && B > 0 && H > 0 && B <= 65535 && H <= 65535 && q >= 1 && q <= MEM_MAX_Q && mlen >= 0 &&
+    return (dt == DB1_BF16 && D == DEC_D && B > 0 && H > 0 && B <= 65535 && H <= 65535 && q >= 1 && q <= MEM_MAX_Q && mlen >= 0 &&
             klen == mlen + q && klen <= MEM_MAX_KLEN && shift >= 0 && (int64_t)shift + mlen >= 1) ? 1 : 0;
 }
 
@@ -343,7 +331,7 @@ extern "C" int db1_relattn_mem_fwd(const void* qu, const void* qv, const void* k
         DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_mem: needs bf16, d_head = 128, 1 <= q <= 8192, klen = mlen + q <= 16384, shift >= 0, shift + mlen >= 1 "
                                       "(got q=%d klen=%d mlen=%d D=%d shift=%d)", q, klen, mlen, D, shift);
     if (nd < 1 || !R || !qu || !qv || !k || !v || !out) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: R rows (%d) or a null operand", nd);
-    if (kv_row_stride < (int64_t)H * MEM_D || kv_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: key / value row stride below H * D");
+    if (kv_row_stride < (int64_t)H * DEC_D || kv_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem: key / value row stride below H * D");
     if ((kv_row_stride % 8) || (kv_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) || !db1_aligned16(k) || !db1_aligned16(v) ||
         !db1_aligned16(R) || !db1_aligned16(out) || (((uintptr_t)lse) & 3))
         DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_mem: operands must be 16-byte aligned, strides multiples of 8 elements");
@@ -378,7 +366,7 @@ extern "C" int db1_relattn_mem_kv_fwd(const void* qu, const void* qv, const void
         DB1_FAIL(DB1_ERR_UNSUPPORTED, "relattn_mem_kv: needs bf16, d_head = 128, 1 <= q <= 8192, mlen >= 1, mlen + q <= 16384, shift >= 0 "
                                       "(got q=%d mlen=%d D=%d shift=%d)", q, mlen, D, shift);
     if (nd < 1 || !R || !qu || !qv || !k_new || !v_new || !k_mem || !v_mem || !out) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_kv: R rows (%d) or a null operand", nd);
-    if (new_row_stride < (int64_t)H * MEM_D || new_batch_stride < 0 || mem_batch_stride < 0 || (mem_row_stride != 0 && mem_row_stride < (int64_t)H * MEM_D))
+    if (new_row_stride < (int64_t)H * DEC_D || new_batch_stride < 0 || mem_batch_stride < 0 || (mem_row_stride != 0 && mem_row_stride < (int64_t)H * DEC_D))
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_kv: a key / value row stride below H * D (the memory's may be 0)");
     if ((new_row_stride % 8) || (new_batch_stride % 8) || (mem_row_stride % 8) || (mem_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) ||
         !db1_aligned16(k_new) || !db1_aligned16(v_new) || !db1_aligned16(k_mem) || !db1_aligned16(v_mem) || !db1_aligned16(R) || !db1_aligned16(out) ||
@@ -417,7 +405,7 @@ extern "C" int db1_relattn_mem_ring_fwd(const void* qu, const void* qv, const vo
     if (nd < 1 || !R || !qu || !qv || !k_new || !v_new || !base || !state_base || !status || !out)
         DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: R rows (%d) or a null operand", nd);
     if (M_base < 1 || (!base_rows && B > M_base)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: %d call rows over a base ring of %d rows need base_rows", B, M_base);
-    if (new_row_stride < (int64_t)H * MEM_D || new_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: key / value row stride below H * D");
+    if (new_row_stride < (int64_t)H * DEC_D || new_batch_stride < 0) DB1_FAIL(DB1_ERR_BAD_SHAPE, "relattn_mem_ring: key / value row stride below H * D");
     if ((new_row_stride % 8) || (new_batch_stride % 8) || !db1_aligned16(qu) || !db1_aligned16(qv) || !db1_aligned16(k_new) || !db1_aligned16(v_new) ||
         !db1_aligned16(base) || !db1_aligned16(R) || !db1_aligned16(out) || (((uintptr_t)lse | (uintptr_t)state_base | (uintptr_t)base_rows | (uintptr_t)status) & 3))
         DB1_FAIL(DB1_ERR_BAD_ALIGN, "relattn_mem_ring: operands must be 16-byte aligned, strides multiples of 8 elements");

@@ -3,7 +3,7 @@
 kernels round (it only sizes the tolerance), and mutants of the closed form (never of a kernel) that the CPU test uses to prove that a
 one-off index or mask error moves the result by at least ten tolerances.  numpy only: neither torch nor the library is imported here.
 
-Geometry (relattn_decode.hip, oracle.db1_oracle.attention_mask_dense):
+Geometry (relattn_decode.hip and relattn_decode_step.h, oracle.db1_oracle.attention_mask_dense):
     score[i, j] = ((q_i + u).k_j + (q_i + v).R[clip(mlen + i - j, 0, nd - 1)]) * scale,   visible iff  i - shift < j <= i + mlen
 so the oldest visible key of row i is max(0, i - shift + 1) and the window holds up to shift + mlen keys (`shift` is the kernels' argument).
 
@@ -398,6 +398,7 @@ DECODE_CASES = [
     (16, 0, 16, None), (16, 31, 32, None), (16, 32, 48, None), (16, 128, 129, None), (16, 127, 143, None),
     (17, 0, 17, None), (17, 1, 2, None), (17, 31, 32, None), (17, 127, 1, 130), (17, 128, 145, None), (17, 300, 1, None),
     (64, 0, 64, None), (64, 32, 33, None), (64, 127, 1, 128), (64, 128, 192, None), (64, 129, 32, None), (64, 300, 364, None), (64, 300, 301, None),
+    (1, 2047, 2048, None), (17, 2031, 2048, None),   # klen = 2048: 16 units, every slot of the ring kernels' in-launch merge
 ]
 
 
