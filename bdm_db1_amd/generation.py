@@ -15,8 +15,9 @@ device state (``_State``, ``_BeamState``), and a generation is
 
 Sampling's epilogue is ``db1_select_tokens`` (greedy / temperature / top-k / top-p, Gumbel-max draws from Philox); beam search's is
 ``db1_beam_step`` (lse, per-row top-2W, the group walk, the hypothesis pool, the next ids) and ``db1_ring_reorder`` (the last t keys of every
-beam whose parent is another row), after a prefill whose memory and last logits are expanded to the W beams of each prompt.  Both rules are
-stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py and tests/beam_rule.py.  With ``constraints=`` (a
+beam whose parent is another row), after a prefill whose memory and last logits are expanded to the W beams of each prompt; with
+``BeamSearchConfig.num_beam_groups`` > 1 the step is ``db1_beam_step_diverse`` (sub-groups that choose in turn under a Hamming penalty).  The
+rules are stated in include/db1_hip.h and restated in NumPy in tests/select_rule.py, tests/beam_rule.py and tests/diverse_beam_rule.py.  With ``constraints=`` (a
 ``DecodingConstraints``) either epilogue is preceded by ``db1_constrain_logits``, which edits the step's logits in place over each row's own
 generated tokens (tests/constraint_rule.py; with a frequency / presence penalty or a logit bias ``db1_constrain_logits_pen``,
 tests/penalty_rule.py), and with stop sequences the sampling epilogue is followed by ``db1_stop_match`` (tests/stop_rule.py), which ends a row
@@ -118,7 +119,11 @@ class BeamSearchConfig:
     """Beam search with ``num_beams`` beams per prompt (1 .. 16), ``max_new_tokens`` new tokens (at most the model's ``mem_len``), scores
     normalised by (length)^``length_penalty``; the best ``num_return_sequences`` (<= num_beams) hypotheses of each prompt come back.
     ``eos_id`` None: no end-of-sequence token (every hypothesis runs ``max_new_tokens``).  Tokens are chosen in ``[vocab_lo, vocab_hi)``
-    (``vocab_hi`` None as in ``GenerationConfig``).  The host checks whether every prompt is done each ``sync_every`` tokens."""
+    (``vocab_hi`` None as in ``GenerationConfig``).  The host checks whether every prompt is done each ``sync_every`` tokens.
+    ``num_beam_groups`` D > 1: diverse beam search (Vijayakumar et al., 2016; rule in include/db1_hip.h) -- the beams are split into D
+    sub-groups of num_beams / D that choose in turn at every step; a token an earlier sub-group chose in this step costs a later one
+    ``diversity_penalty`` per earlier choice in its ranking.  The scores that come back stay the model's length-normalised log-probabilities;
+    the results are the best of the D merged pools.  D must divide ``num_beams``; the penalty is finite, >= 0, and 0 when D = 1."""
     num_beams: int = 4
     max_new_tokens: int = 30
     length_penalty: float = 1.0
@@ -128,10 +133,19 @@ class BeamSearchConfig:
     vocab_lo: int = 0
     vocab_hi: Optional[int] = None
     sync_every: int = 8
+    num_beam_groups: int = 1
+    diversity_penalty: float = 0.0
 
     def __post_init__(self):
         if not 1 <= int(self.num_beams) <= 16:
             raise ValueError(f"num_beams {self.num_beams} must lie in [1, 16]")
+        D, lam = self.num_beam_groups, self.diversity_penalty
+        if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or not 1 <= int(D) <= int(self.num_beams) or int(self.num_beams) % int(D):
+            raise ValueError(f"num_beam_groups {D!r} must be an integer in [1, num_beams = {self.num_beams}] that divides num_beams")
+        if isinstance(lam, bool) or not isinstance(lam, (int, float, np.integer, np.floating)) or not 0 <= float(lam) < float("inf"):
+            raise ValueError(f"diversity_penalty {lam!r} must be finite and >= 0")
+        if int(D) == 1 and float(lam) != 0:
+            raise ValueError(f"diversity_penalty {lam} needs num_beam_groups > 1 (one group has no earlier group to differ from)")
         if int(self.max_new_tokens) < 1:
             raise ValueError(f"max_new_tokens {self.max_new_tokens} must be >= 1")
         if not abs(float(self.length_penalty)) < float("inf"):
@@ -839,28 +853,36 @@ class _BestOfState(_State):
 
 
 class _BeamState:
-    """the device state of one beam search over G groups of W beams (include/db1_hip.h, db1_beam_step)"""
+    """the device state of one beam search over G prompts of W beams (include/db1_hip.h, db1_beam_step); with ``cfg.num_beam_groups`` D > 1
+    the state of G * D sub-groups of W / D beams, stepped by db1_beam_step_diverse"""
     cache = "_beam_generator"
 
     def __init__(self, model, key: DecodeKey):
         G, cfg, V, hi, dev = key.rows, key.cfg, key.V, key.hi, model.dev
-        W, mx = int(cfg.num_beams), int(cfg.max_new_tokens)
+        W, mx, D = int(cfg.num_beams), int(cfg.max_new_tokens), int(cfg.num_beam_groups)
+        Q, Wg = G * D, W // D                    # (D = 1: the G groups of W beams of the plain search)
         i32 = dict(dtype=torch.int32, device=dev)
         self.G, self.W, self.M, self.cfg, self.V, self.hi = G, W, G * W, cfg, V, hi
+        self.D, self.Q, self.Wg = D, Q, Wg
         self.expand = W
         self.t = torch.zeros(1, **i32)
         self.beam_score = torch.zeros(G * W, dtype=torch.float32, device=dev)
         self.parent = torch.zeros(G * W, **i32)
         self.tokens = torch.zeros(G * W, mx, **i32)
-        self.pool_tokens = torch.zeros(G, W, mx, **i32)
-        self.pool_len = torch.zeros(G, W, **i32)
-        self.pool_score = torch.zeros(G, W, dtype=torch.float32, device=dev)
-        self.pool_slot = torch.zeros(G, W, **i32)
-        self.pool_count = torch.zeros(G, **i32)
-        self.done = torch.zeros(G, **i32)
-        self.switches = torch.zeros(G, **i32)
-        self.status = torch.zeros(G, **i32)
+        self.pool_tokens = torch.zeros(Q, Wg, mx, **i32)
+        self.pool_len = torch.zeros(Q, Wg, **i32)
+        self.pool_score = torch.zeros(Q, Wg, dtype=torch.float32, device=dev)
+        self.pool_slot = torch.zeros(Q, Wg, **i32)
+        self.pool_count = torch.zeros(Q, **i32)
+        self.done = torch.zeros(Q, **i32)
+        self.switches = torch.zeros(Q, **i32)
+        self.status = torch.zeros(Q, **i32)
         self.con = _constrain_args(key.constraints, cfg, V, dev)
+        # the step, bound ONCE: db1_beam_step, or with sub-groups db1_beam_step_diverse
+        kw = dict(W=Wg, V=V, vocab_lo=cfg.vocab_lo, vocab_hi=hi, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id,
+                  length_penalty=cfg.length_penalty)
+        self._step = partial(ops.beam_step, **kw) if D == 1 else \
+            partial(ops.beam_step_diverse, D=D, diversity_penalty=float(cfg.diversity_penalty), **kw)
 
     def start(self):
         pad = self.cfg.pad_id
@@ -870,22 +892,20 @@ class _BeamState:
         self.tokens.fill_(pad)
         self.pool_tokens.fill_(pad)
         self.pool_score.fill_(float("-inf"))
-        self.pool_slot.copy_(torch.arange(self.W, dtype=torch.int32).expand(self.G, self.W))
+        self.pool_slot.copy_(torch.arange(self.Wg, dtype=torch.int32).expand(self.Q, self.Wg))
 
     def select(self, logits2d, next_ids):
-        """db1_beam_step on the last-position logits [M, V] of step t; the next ids go to ``next_ids`` (int64 [M])"""
-        c = self.cfg
+        """db1_beam_step (db1_beam_step_diverse) on the last-position logits [M, V] of step t; the next ids go to ``next_ids`` (int64 [M])"""
         if self.con is not None:     # (``tokens``: db1_beam_step has reordered it into every new beam's own history)
             ops.constrain_logits(logits2d, self.t, self.tokens, **self.con)
-        ops.beam_step(logits2d, self.t, self.beam_score, self.parent, self.tokens, self.pool_tokens, self.pool_len, self.pool_score, self.pool_slot,
-                      self.pool_count, self.done, self.switches, next_ids, self.status, W=self.W, V=self.V, vocab_lo=c.vocab_lo, vocab_hi=self.hi,
-                      eos_id=-1 if c.eos_id is None else c.eos_id, pad_id=c.pad_id, length_penalty=c.length_penalty)
+        self._step(logits2d, self.t, self.beam_score, self.parent, self.tokens, self.pool_tokens, self.pool_len, self.pool_score, self.pool_slot,
+                   self.pool_count, self.done, self.switches, next_ids, self.status)
 
     def epilogue(self, logits2d, next_ids, ring=None):
         """``ring`` None: step 0 (every beam descends from the same prefill, nothing to reorder), or the list-form memory (``reorder_list``)"""
         self.select(logits2d, next_ids)
         if ring is not None:
-            ring.reorder(self.parent, self.t, max_t=self.cfg.max_new_tokens, group=self.W, done=self.done)
+            ring.reorder(self.parent, self.t, max_t=self.cfg.max_new_tokens, group=self.Wg, done=self.done)
         self.t.add_(1)
 
     def reorder_list(self, mems):
@@ -903,6 +923,8 @@ class _BeamState:
         ids = torch.full((self.G, R, mx), self.cfg.pad_id, dtype=torch.int32)
         lengths = torch.zeros(self.G, R, dtype=torch.int32)
         scores = torch.full((self.G, R), float("-inf"), dtype=torch.float32)
+        if self.D > 1:
+            return self._merged(ids, lengths, scores, toks, slot, n, sc, count)
         for g in range(self.G):
             k = min(R, int(count[g]))           # (fewer hypotheses than R only when every beam of a group ran out of candidates)
             ids[g, :k] = toks[g, slot[g, :k].long()]
@@ -910,8 +932,37 @@ class _BeamState:
             scores[g, :k] = sc[g, :k]
         return ids, lengths, scores
 
+    def _merged(self, ids, lengths, scores, toks, slot, n, sc, count):
+        """step 8 of the diverse rule: a prompt's D pools merged by (score descending, sub-group ascending, position in its pool ascending),
+        the first R"""
+        for g, ent in enumerate(self._merge_order(sc, count)):
+            for r, (d, k) in enumerate(ent):
+                q = g * self.D + d
+                ids[g, r] = toks[q, int(slot[q, k])]
+                lengths[g, r] = n[q, k]
+                scores[g, r] = sc[q, k]
+        return ids, lengths, scores
+
+    def _merge_order(self, sc, count):
+        """per prompt the (sub-group, pool position) of its first R merged results (``sc`` [G D, W'] / ``count`` [G D] on the host)"""
+        D, R = self.D, int(self.cfg.num_return_sequences)
+        out = []
+        for g in range(self.G):
+            ent = sorted((-float(sc[g * D + d, k]), d, k) for d in range(D) for k in range(int(count[g * D + d])))
+            out.append([(d, k) for _, d, k in ent[:R]])
+        return out
+
     def stats(self) -> dict:
-        return dict(parent_switches=int(self.switches.sum()))
+        """``parent_switches``; with sub-groups also ``result_groups`` (int32 [G, R]): the sub-group every result came from, -1 where
+        there is none"""
+        st = dict(parent_switches=int(self.switches.sum()))
+        if self.D > 1:
+            groups = torch.full((self.G, int(self.cfg.num_return_sequences)), -1, dtype=torch.int32)
+            for g, ent in enumerate(self._merge_order(self.pool_score.cpu(), self.pool_count.cpu())):
+                for r, (d, _) in enumerate(ent):
+                    groups[g, r] = d
+            st["result_groups"] = groups
+        return st
 
 
 # ------------------------------------------------------------------------------------------------------------------------------ the driver
@@ -1159,7 +1210,10 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
     ``kv_cache``: as ``generate`` takes it (db1_ring_reorder copies fp8 slots as the bytes they are).  ``share_prompt`` True (graphed bf16
     ring path only; ValueError otherwise, before anything is launched): the W beams of a group read ONE copy of their prompt's keys / values
     (``GroupedRingMemory``, db1_relattn_decode_group_fwd) instead of W; the results are those of the default path up to the order of the
-    attention's partial sums.  False (default): everything is what it is without the keyword."""
+    attention's partial sums.  False (default): everything is what it is without the keyword.  With ``config.num_beam_groups`` D > 1
+    (diverse beam search, db1_beam_step_diverse): the same paths and keywords; a prompt's results are the best R of its D sub-groups' pools
+    (equal scores: the lower sub-group first), the scores stay unpenalised, and ``stats`` also receives ``result_groups`` (int32 [G, R]:
+    the sub-group every result came from).  D = 1 (default): everything is what it is without the two fields."""
     cfg = config or BeamSearchConfig()
     if not isinstance(cfg, BeamSearchConfig):
         raise TypeError(f"beam_search: BeamSearchConfig expected, got {type(cfg).__name__}")
@@ -1174,6 +1228,9 @@ def beam_search(model, prompt, config: Optional[BeamSearchConfig] = None, graphe
         raise ValueError(f"eos_id {cfg.eos_id} lies outside the model's vocabulary ({V})")
     if not ops.beam_step_supported(V, V, W, model.compute_dtype):
         raise ValueError(f"db1_beam_step does not support a vocabulary of {V} with {W} beams")
+    D = int(cfg.num_beam_groups)
+    if D > 1 and not ops.beam_step_diverse_supported(V, V, W // D, D, model.compute_dtype):
+        raise ValueError(f"db1_beam_step_diverse does not support a vocabulary of {V} with {D} sub-groups of {W // D} beams")
     key = _constrained("beam_search", model, DecodeKey(rows=G, cfg=cfg, V=V, hi=hi), constraints, cfg.max_new_tokens)
     key = _with_share_prompt("beam_search", model, key, share_prompt, W, prompt, kv_cache, graphed)
     key = _with_kv_cache("beam_search", model, key, kv_cache, graphed)

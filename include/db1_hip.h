@@ -828,6 +828,41 @@ int db1_beam_step(const void* logits, int G, int W, int V, int64_t ld, int dt, i
                   float length_penalty, const int32_t* t, int max_new, float* beam_score, int32_t* parent, int32_t* tokens,
                   int32_t* pool_tokens, int32_t* pool_len, float* pool_score, int32_t* pool_slot, int32_t* pool_count, int32_t* done,
                   int32_t* switches, int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
+/* Diverse (group) beam search (Vijayakumar et al., 2016; tests/diverse_beam_rule.py restates the rule in NumPy on tests/beam_rule.py).
+ * The W beams of each of G prompts are split into D sub-groups of W' = W / D beams (D >= 1, D * W' <= 16); row b = (g * D + d) * W' + j for
+ * prompt g, sub-group d, beam j, and EVERY state array has the layout of db1_beam_step for G * D groups of W' beams (beam_score / parent /
+ * tokens [G * W, ...], the pool arrays [G * D, W', ...], pool_count / done / switches / status [G * D]).  At step t, for each prompt, the
+ * sub-groups d = 0 .. D - 1 choose in turn over a list `chosen` that starts empty:
+ *   1. a sub-group that is done, or a counter outside [0, max_new): as in the plain rule (pad_id to next_ids, status bit 1 for the counter);
+ *      it adds nothing to `chosen`;
+ *   2. candidates: steps 1-2 of the plain rule over the sub-group's W' rows, s = beam_score + (l - lse), lse in fp32; at t = 0 only beam
+ *      j = 0 of EACH sub-group is live;
+ *   3. n(c) = the number of entries of `chosen` equal to c; sel = s - fp32(n) * diversity_penalty in fp32 (no lower than -FLT_MAX); the
+ *      sub-group's candidates sorted by sel descending, ties by the lower (j, c); the first 2W' are walked;
+ *   4. the walk is step 4 of the plain rule with W' for W: EOS at rank < W' becomes a hypothesis, later EOS are dropped, other candidates
+ *      fill the W' new beams in sel order.  Every STORED score is the unpenalised s (beam scores, pool scores s / (t + 1)^length_penalty):
+ *      the penalty only ranks, the model's log-probability stays what the plain search and the scoring report;
+ *   5. the sub-group is done when no beam was filled, or when its pool holds W' entries and the worst one >= (the LARGEST s among the new
+ *      beams) / (t + 1)^length_penalty;
+ *   6. at t = max_new - 1 the new beams are offered as in the plain rule;
+ *   7. a sub-group that is not done after this step appends the tokens of its filled beams to `chosen`, in beam order (EOS never fills a
+ *      beam and is never counted);
+ *   8. output, on the host: a prompt's D pools merged, sorted by (score descending, d ascending, position in its pool ascending), the
+ *      first R (1 <= R <= W).
+ * A later sub-group sees at most W - W' distinct penalised tokens, so a row's raw top W' + W (by logit descending, column ascending)
+ * holds its share of the penalised top 2W': launch 1 is db1_beam_step's rows kernel over G * D groups of W' with K = W' + W (<= 32), and
+ * the workspace depends on that K.  Launch 2: one workgroup per PROMPT loops over its sub-groups, `chosen` in LDS.  Fixed order, no
+ * atomics, no communication between workgroups: the same inputs give the same bits; at D = 1, diversity_penalty = 0 the bits of
+ * db1_beam_step, at D > 1, diversity_penalty = 0 those of db1_beam_step over G * D groups of W'.  *t is only READ.  `W` below is W', the
+ * beams of ONE sub-group.  Refused before a launch, with db1_beam_step's codes: a NULL buffer, D < 1, D * W' > 16, G * D * W' > 65535, an
+ * empty window, a diversity_penalty that is negative or not finite, a short workspace. */
+int db1_beam_step_diverse_supported(int V, int64_t ld, int W, int D, int dt);
+int64_t db1_beam_step_diverse_workspace_bytes(int M, int V, int W, int D, int max_new, int dt);
+int db1_beam_step_diverse(const void* logits, int G, int D, int W, float diversity_penalty, int V, int64_t ld, int dt, int vocab_lo,
+                          int vocab_hi, int eos_id, int pad_id, float length_penalty, const int32_t* t, int max_new, float* beam_score,
+                          int32_t* parent, int32_t* tokens, int32_t* pool_tokens, int32_t* pool_len, float* pool_score,
+                          int32_t* pool_slot, int32_t* pool_count, int32_t* done, int32_t* switches, int64_t* next_ids,
+                          int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream);
 /* Beam K/V history of a RingMemory: rings = a DEVICE array of n_layers pointers to rings [M, cap, slot] (slot = 2 * H * D bf16 =
  * slot_bytes, a multiple of 16).  After the forward of step t (state = the ring origin after that call's advance) the last t logical keys
  * of every row, slots (state + mlen - t + i) % cap for i < t, are copied from row parent[b] to row b in every layer; rows with parent[b] == b

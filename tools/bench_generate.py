@@ -17,6 +17,11 @@ With --num-beams W the arguments are group counts G (default 1 16), and per G (M
     history: 2 x M x 29 x n_layer slots read and written), device time per call from events over 50 calls.
 
     python tools/bench_generate.py --num-beams 4 [G ...]
+With --beam-groups D --diversity LAMBDA (diverse beam search: D sub-groups of W / D beams, db1_beam_step_diverse) the same lines, each with
+"beam_groups" and "diversity"; beam_step_us is then the diverse step's.
+    python tools/bench_generate.py --num-beams 4 --beam-groups 2 --diversity 0.5 [G ...]
+With --num-beams W --diversity-report [--diversity LAMBDA] (default 0.5): one line per divisor D of W with the mean pairwise Hamming
+distance between a prompt's W results, the mean number of distinct first tokens and the mean best score against D = 1.
 
 With --stream: continuous batching (serving.caption_stream) against lockstep batches.  256 one-image requests, 64 slots, per-request token
 limits drawn once from a seeded uniform 5 .. 30 (random weights never emit EOS); one JSON line with
@@ -191,6 +196,7 @@ def gen_ms_per_token(M, cfg, short=10, **kw):
 
 KV_CACHE = "bf16"      # --kv-cache
 SHARE_KW = {}          # --share-prompt: dict(share_prompt=True)
+BEAM_KW = {}           # --beam-groups D --diversity lambda: dict(num_beam_groups=D, diversity_penalty=lambda)
 
 
 def _memory_bytes(gen):
@@ -440,11 +446,12 @@ def device_us(fn, calls=50):
 
 
 def beam_kernels_us(G, W, t_reorder=N_NEW - 1):
-    """db1_beam_step on random bf16 logits at step 1 (every beam live) and db1_ring_reorder at t = t_reorder over a ring of M rows"""
+    """db1_beam_step (with --beam-groups: db1_beam_step_diverse) on random bf16 logits at step 1 (every beam live) and db1_ring_reorder at
+    t = t_reorder over a ring of M rows"""
     from bdm_db1_amd.decode import RingMemory
     from bdm_db1_amd.generation import DecodeKey, _BeamState
     M, V, hi = G * W, int(model.total_vocab_size), int(model.text_vocab_size)
-    st = _BeamState(model, DecodeKey(rows=G, cfg=BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, vocab_hi=hi), V=V, hi=hi))
+    st = _BeamState(model, DecodeKey(rows=G, cfg=BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, vocab_hi=hi, **BEAM_KW), V=V, hi=hi))
     logits = torch.randn(M, V, device=dev).to(torch.bfloat16)
     ids = torch.zeros(M, 1, dtype=torch.long, device=dev)
     st.start()
@@ -463,11 +470,12 @@ def beam_kernels_us(G, W, t_reorder=N_NEW - 1):
         ring = GroupedRingMemory(model, G, W, N_NEW)
     else:
         ring = RingMemory(model, M)
-    parent = torch.tensor([(b // W) * W + (b + 1) % W for b in range(M)], dtype=torch.int32, device=dev)
+    Wg = st.Wg             # (the rows a parent may come from: W, with --beam-groups W / D)
+    parent = torch.tensor([(b // Wg) * Wg + (b + 1) % Wg for b in range(M)], dtype=torch.int32, device=dev)
     t = torch.tensor([t_reorder], dtype=torch.int32, device=dev)
-    done = torch.zeros(G, dtype=torch.int32, device=dev)
-    reorder_us = device_us(lambda: ring.reorder(parent, t, max_t=N_NEW, group=W, done=done))
-    moved = (M if W > 1 else 0) * t_reorder * model.n_layer * ring.kv[0][0, 0].numel() * 2 * 4   # gather + write-back, read + write each
+    done = torch.zeros(M // Wg, dtype=torch.int32, device=dev)
+    reorder_us = device_us(lambda: ring.reorder(parent, t, max_t=N_NEW, group=Wg, done=done))
+    moved = (M if Wg > 1 else 0) * t_reorder * model.n_layer * ring.kv[0][0, 0].numel() * 2 * 4   # gather + write-back, read + write each
     del ring
     torch.cuda.empty_cache()
     return step_us, reorder_us, moved
@@ -477,7 +485,9 @@ def beam_main(W, Gs):
     for G in Gs:
         M = G * W
         rec = {"G": G, "num_beams": W, "M": M, "new_tokens": N_NEW}
-        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW), **SHARE_KW), 4)
+        if BEAM_KW:
+            rec.update(beam_groups=BEAM_KW["num_beam_groups"], diversity=BEAM_KW["diversity_penalty"])
+        rec["beam_ms_per_token"] = round(gen_ms_per_token(G, BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, **BEAM_KW), **SHARE_KW), 4)
         rec["memory_bytes"] = _memory_bytes(model._beam_generator)
         model._beam_generator = None
         torch.cuda.empty_cache()
@@ -492,6 +502,29 @@ def beam_main(W, Gs):
         rec["ring_reorder_t29_traffic_MB"] = round(moved / 1e6, 1)
         rec["ring_reorder_t29_TBps"] = round(moved / (reorder_us * 1e-6) / 1e12, 3) if moved else 0.0
         print(json.dumps(rec), flush=True)
+
+
+def diversity_report_main(W, Gs, lam):
+    """what the sub-groups buy, on this model's random weights: per D in the divisors of W, over the G caption prompts with R = W results
+    each, the mean pairwise Hamming distance between a prompt's results (positions that differ, of N_NEW), the mean number of distinct first
+    tokens, and the mean score of the best result minus that of D = 1 (scores are unpenalised length-normalised log-probabilities)"""
+    for G in Gs:
+        b = batch(G)
+        best1 = None
+        for D in [d for d in range(1, W + 1) if W % d == 0]:
+            cfg = BeamSearchConfig(num_beams=W, max_new_tokens=N_NEW, num_return_sequences=W, num_beam_groups=D,
+                                   diversity_penalty=lam if D > 1 else 0.0)
+            ids, _, scores = generate_captions(model, b, cfg, **SHARE_KW)
+            ids = ids.numpy()
+            ham = [float((ids[g, i] != ids[g, j]).sum()) for g in range(G) for i in range(W) for j in range(i + 1, W)]
+            first = [len(set(ids[g, :, 0].tolist())) for g in range(G)]
+            best = float(scores[:, 0].mean())
+            best1 = best if D == 1 else best1
+            print(json.dumps({"G": G, "num_beams": W, "beam_groups": D, "diversity": cfg.diversity_penalty, "new_tokens": N_NEW,
+                              "mean_pairwise_hamming": round(float(np.mean(ham)), 3), "mean_distinct_first_tokens": round(float(np.mean(first)), 3),
+                              "mean_best_score": round(best, 5), "best_score_minus_D1": round(best - best1, 5)}), flush=True)
+        model._beam_generator = None
+        torch.cuda.empty_cache()
 
 
 def stream_main(n_req=256, slots=64):
@@ -1000,6 +1033,25 @@ if "--stream" in args:
     (stream_per_request_constraints_main if "--per-request-constraints" in args else
      stream_per_request_main if "--per-request" in args else stream_main)(*rest[:2])
     sys.exit(0)
+if "--diversity-report" in args:   # --num-beams W --diversity-report [--diversity LAMBDA] [G ...]: what the sub-groups buy, per divisor D of W
+    rest = [a for a in args if a != "--diversity-report"]
+    lam = 0.5
+    if "--diversity" in rest:
+        i = rest.index("--diversity")
+        lam, rest = float(rest[i + 1]), rest[:i] + rest[i + 2:]
+    i = rest.index("--num-beams")
+    diversity_report_main(int(rest[i + 1]), [int(a) for a in rest[:i] + rest[i + 2:]] or [16], lam)
+    sys.exit(0)
+if "--beam-groups" in args or "--diversity" in args:      # diverse beam search: D sub-groups, a Hamming penalty between them
+    if "--num-beams" not in args:
+        sys.exit("--beam-groups / --diversity go with --num-beams")
+    for flag, name, conv in (("--beam-groups", "num_beam_groups", int), ("--diversity", "diversity_penalty", float)):
+        if flag in args:
+            i = args.index(flag)
+            BEAM_KW[name] = conv(args[i + 1])
+            args = args[:i] + args[i + 2:]
+    BEAM_KW.setdefault("num_beam_groups", 1)
+    BEAM_KW.setdefault("diversity_penalty", 0.0)
 if "--num-beams" in args:
     i = args.index("--num-beams")
     W = int(args[i + 1])
