@@ -1,18 +1,20 @@
-// Beam search on the device (db1_beam_step, db1_ring_reorder; the rule is stated in include/db1_hip.h and restated in NumPy in
-// tests/beam_rule.py).  The reference evaluates captions and answers by generating text (train.py:140-170, evaluate_ic / evaluate_vqa,
-// not released); captioning is normally scored with beam search.
+// Beam search on the device (db1_beam_step, db1_beam_step_diverse, db1_ring_reorder; the rules are stated in include/db1_hip.h and restated
+// in NumPy in tests/beam_rule.py).  The reference evaluates captions and answers by generating text (train.py:140-170, evaluate_ic /
+// evaluate_vqa, not released); captioning is normally scored with beam search.
 //
-// db1_beam_step, two launches, both only READ the token counter *t (the step can live in a captured graph):
+// Both steps are one launcher (beam_step_launch) and one group step (beam_group_step<DIVERSE>); the plain step is the case of one sub-group
+// per prompt and no penalty.  Two launches, both only READ the token counter *t (the step can live in a captured graph):
 //   1. rows:  (nb chunks of the vocabulary window) x (M rows), 256 threads.  A chunk computes its max logit m_c, sum exp(l - m_c) and its
-//             top-K (K = 2W) candidates by (logit desc, column asc) as packed (order-preserving key << 32 | ~column) words: K rounds of a
-//             block arg-max; after each round only the thread that owned the winner rescans its own columns.  Done groups and dead beams
-//             exit at once.
-//   2. groups: one 256-thread workgroup per group.  A wave per beam row merges the nb chunk lists (K rounds of a wave arg-max over the nb
-//             list heads) and the fp32 lse (wave max / butterfly sum over the chunks); every candidate gets s = beam_score + (l - lse) and
-//             a group key (key(s) << 32 | ~(j << 16 | c)); the group's top-2W come from exact ranks (count of larger keys), so the order is
-//             (s desc, j asc, c asc) whatever the rounding did inside a row.  One thread walks them (pool offers, new beams), then the
-//             workgroup writes the histories (staged through the workspace: the permutation is in place), the pool rows it touched, the
-//             beam scores, the parents and the next input ids.
+//             top-K (K = 2W; diverse: W' + W) candidates by (logit desc, column asc) as packed (order-preserving key << 32 | ~column)
+//             words: K rounds of a block arg-max; after each round only the thread that owned the winner rescans its own columns.  Done
+//             groups and dead beams exit at once.
+//   2. groups: one 256-thread workgroup per group (beam_group_kernel) or per prompt, walking its D sub-groups in turn
+//             (beam_group_diverse_kernel).  A wave per beam row merges the nb chunk lists (K rounds of a wave arg-max over the nb list
+//             heads) and the fp32 lse (wave max / butterfly sum over the chunks); every candidate gets s = beam_score + (l - lse) and a
+//             group key (key(s) << 32 | ~(j << 16 | c); diverse: the key of sel = s - n(c) * lambda, s kept beside it); the group's top-2W
+//             come from exact ranks (count of larger keys), so the order is (s desc, j asc, c asc) whatever the rounding did inside a row.
+//             One thread walks them (pool offers, new beams), then the workgroup writes the histories (staged through the workspace: the
+//             permutation is in place), the pool rows it touched, the beam scores, the parents and the next input ids.
 // db1_ring_reorder, two launches (gather into the workspace, write back): the last t keys of every row whose parent is another row.
 // Every reduction runs in a fixed order; no atomics, no communication between workgroups inside a launch.
 #include <cfloat>
@@ -51,7 +53,8 @@ struct BeamArgs {
     int* hist;                  // [M, max_new] staged histories
 };
 
-__device__ __forceinline__ bool beam_live(const BeamArgs& a, int t, int row, int j) {
+template <typename Args>      // (BeamArgs, by value or in the kernarg segment)
+__device__ __forceinline__ bool beam_live(const Args& a, int t, int row, int j) {
     return t == 0 ? j == 0 : a.beam_score[row] > -INFINITY;
 }
 
@@ -123,32 +126,47 @@ __device__ void beam_offer(float h, int src, int last, int n, int W, int& count,
     slast[slot] = last;
 }
 
-__global__ __launch_bounds__(BEAM_THREADS) void beam_group_kernel(BeamArgs a) {
-    __shared__ unsigned long long gk[BEAM_MAX_W * BEAM_MAX_K];
-    __shared__ unsigned long long top[BEAM_MAX_K];
-    __shared__ float ps[BEAM_MAX_W], nb_sc[BEAM_MAX_W];
-    __shared__ int pl[BEAM_MAX_W], pslot[BEAM_MAX_W], srow[BEAM_MAX_W], slast[BEAM_MAX_W], nb_par[BEAM_MAX_W], nb_tok[BEAM_MAX_W], nocand[BEAM_MAX_W];
-    __shared__ int s_filled, s_done;
-    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int W = a.W, K = a.K, b0 = g * W, mx = a.max_new;
+// The LDS of one group step.  DIVERSE adds the unpenalised s beside every sel key (gs, tops) and the list of the tokens that the earlier
+// sub-groups of the prompt chose; the plain step carries one element of each.
+template <bool DIVERSE>
+struct BeamGroupLds {
+    unsigned long long gk[BEAM_MAX_W * BEAM_MAX_K];
+    unsigned long long top[BEAM_MAX_K];
+    float gs[DIVERSE ? BEAM_MAX_W * BEAM_MAX_K : 1];
+    float tops[DIVERSE ? BEAM_MAX_K : 1];
+    float ps[BEAM_MAX_W], nb_sc[BEAM_MAX_W];
+    int pl[BEAM_MAX_W], pslot[BEAM_MAX_W], srow[BEAM_MAX_W], slast[BEAM_MAX_W], nb_par[BEAM_MAX_W], nb_tok[BEAM_MAX_W], nocand[BEAM_MAX_W];
+    int chosen[DIVERSE ? BEAM_MAX_W : 1];
+    int filled, done, n_chosen;
+};
+
+// One (sub-)group g of W = a.W beams at step t, by the whole workgroup.  The plain step: a.K = 2W candidates per row, ranked by s.  DIVERSE:
+// a.K = W' + W per row; every candidate gets s and, ONCE, sel = s - n(c) * lam (n(c): one ballot over the at most 16 tokens in sh.chosen);
+// the top-2W' come from exact ranks on the sel keys with s kept beside the key; the walk uses the unpenalised s and appends the new beams'
+// tokens to sh.chosen.  Args: BeamArgs, by value or in the kernarg segment.
+template <bool DIVERSE, typename Args>
+__device__ __forceinline__ void beam_group_step(const Args& a, int g, float lam, BeamGroupLds<DIVERSE>& sh) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = a.W, K = a.K, K2 = DIVERSE ? 2 * a.W : a.K, b0 = g * W, mx = a.max_new;
     const int t = *a.t;
     const int was_done = a.done[g];
-    if (was_done || t < 0 || t >= mx) {
+    if (was_done || t < 0 || t >= mx) {      // (block-uniform)
         if (tid < W) a.next_ids[(int64_t)(b0 + tid) * a.ids_stride] = a.pad;
         if (tid == 0 && !was_done) a.status[g] |= 2;
         return;
     }
-    // 1. per beam row: lse over the chunks, the row's top-K as group keys
+    const int nch = DIVERSE ? sh.n_chosen : 0;
+    // 1. per beam row: lse over the chunks, the row's top-K as group keys (DIVERSE: sel keys, with their s)
     for (int j = wv; j < W; j += BEAM_WAVES) {
         const int row = b0 + j;
-        if (lane < K) gk[j * BEAM_MAX_K + lane] = 0ull;
-        if (lane == 0) nocand[j] = 0;
+        if (lane < K) sh.gk[j * BEAM_MAX_K + lane] = 0ull;
+        if (lane == 0) sh.nocand[j] = 0;
         if (!beam_live(a, t, row, j)) continue;
         const float base = t == 0 ? 0.f : a.beam_score[row];
         const float2 ms = lane < a.nb ? a.ms[(int64_t)row * a.nb + lane] : make_float2(-INFINITY, 0.f);
         const float m = wave_max(ms.x);
         if (!(m > -INFINITY)) {
-            if (lane == 0) nocand[j] = 1;
+            if (lane == 0) sh.nocand[j] = 1;
             continue;
         }
         const float lse = m + logf(wave_sum(ms.x > -INFINITY ? ms.y * expf(ms.x - m) : 0.f));
@@ -161,58 +179,82 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_group_kernel(BeamArgs a) {
             if (h == w) idx++;
             const int c = (int)~(unsigned)w;
             const float s = base + (sel_unkey((unsigned)(w >> 32)) - lse);
-            const unsigned sk = sel_key(s);
-            if (lane == 0) gk[j * BEAM_MAX_K + r] = sk ? (((unsigned long long)sk << 32) | (unsigned)~(((unsigned)j << 16) | (unsigned)c)) : 0ull;
+            unsigned sk = sel_key(s);
+            if constexpr (DIVERSE) {
+                const int n = __popcll(__ballot(lane < nch && sh.chosen[lane & (BEAM_MAX_W - 1)] == c));   // (one lane per entry of the list)
+                if (lane == 0) {
+                    sk = sk ? sel_key(fmaxf(s - (float)n * lam, -FLT_MAX)) : 0u;
+                    sh.gs[j * BEAM_MAX_K + r] = s;
+                }
+            }
+            if (lane == 0) sh.gk[j * BEAM_MAX_K + r] = sk ? (((unsigned long long)sk << 32) | (unsigned)~(((unsigned)j << 16) | (unsigned)c)) : 0ull;
         }
     }
-    if (tid < K) top[tid] = 0ull;
+    if (tid < K2) sh.top[tid] = 0ull;
     if (tid < W) {
-        ps[tid] = a.pool_score[b0 + tid];
-        pl[tid] = a.pool_len[b0 + tid];
-        pslot[tid] = a.pool_slot[b0 + tid];
-        srow[tid] = -1;
+        sh.ps[tid] = a.pool_score[b0 + tid];
+        sh.pl[tid] = a.pool_len[b0 + tid];
+        sh.pslot[tid] = a.pool_slot[b0 + tid];
+        sh.srow[tid] = -1;
     }
     __syncthreads();
-    // 2. the group's top-2W by exact rank (group keys are unique: (j, c) pairs differ)
+    // 2. the group's top-K2 by exact rank (group keys are unique: (j, c) pairs differ)
     for (int e = tid; e < W * K; e += BEAM_THREADS) {
-        const unsigned long long x = gk[(e / K) * BEAM_MAX_K + e % K];
+        const int at = (e / K) * BEAM_MAX_K + e % K;
+        const unsigned long long x = sh.gk[at];
         if (x == 0) continue;
         int rank = 0;
-        for (int f = 0; f < W * K && rank < K; f++) rank += gk[(f / K) * BEAM_MAX_K + f % K] > x;
-        if (rank < K) top[rank] = x;
+        for (int f = 0; f < W * K && rank < K2; f++) rank += sh.gk[(f / K) * BEAM_MAX_K + f % K] > x;
+        if (rank < K2) {
+            sh.top[rank] = x;
+            if constexpr (DIVERSE) sh.tops[rank] = sh.gs[at];
+        }
     }
     __syncthreads();
-    // 3. the walk (one thread, LDS only)
+    // 3. the walk (one thread, LDS only); DIVERSE: the order is sel's, every score is the unpenalised s
     if (tid == 0) {
         const float den = powf((float)(t + 1), a.alpha);
         int count = a.pool_count[g], filled = 0;
-        for (int r = 0; r < K && filled < W; r++) {
-            const unsigned long long p = top[r];
+        for (int r = 0; r < K2 && filled < W; r++) {
+            const unsigned long long p = sh.top[r];
             if (!p) break;
             const unsigned low = ~(unsigned)p;
             const int j = (int)(low >> 16), c = (int)(low & 0xffffu);
-            const float s = sel_unkey((unsigned)(p >> 32));
+            float s;
+            if constexpr (DIVERSE) s = sh.tops[r];
+            else s = sel_unkey((unsigned)(p >> 32));
             if (c == a.eos) {
-                if (r < W) beam_offer(s / den, b0 + j, c, t, W, count, ps, pl, pslot, srow, slast);
+                if (r < W) beam_offer(s / den, b0 + j, c, t, W, count, sh.ps, sh.pl, sh.pslot, sh.srow, sh.slast);
                 continue;
             }
-            nb_par[filled] = j;
-            nb_tok[filled] = c;
-            nb_sc[filled] = s;
+            sh.nb_par[filled] = j;
+            sh.nb_tok[filled] = c;
+            sh.nb_sc[filled] = s;
             filled++;
         }
         if (t == mx - 1)
-            for (int k = 0; k < filled; k++) beam_offer(nb_sc[k] / den, b0 + nb_par[k], nb_tok[k], t + 1, W, count, ps, pl, pslot, srow, slast);
-        const int done = filled == 0 || (count == W && ps[W - 1] >= nb_sc[0] / den);
+            for (int k = 0; k < filled; k++)
+                beam_offer(sh.nb_sc[k] / den, b0 + sh.nb_par[k], sh.nb_tok[k], t + 1, W, count, sh.ps, sh.pl, sh.pslot, sh.srow, sh.slast);
+        float best = -INFINITY;        // the largest new score: the first (the new beams are in s order), DIVERSE (sel order) the maximum
+        if constexpr (DIVERSE)
+            for (int k = 0; k < filled; k++) best = fmaxf(best, sh.nb_sc[k]);
+        else best = sh.nb_sc[0];
+        const int done = filled == 0 || (count == W && sh.ps[W - 1] >= best / den);
         int bits = 0, sw = 0;
-        for (int j = 0; j < W; j++) bits |= nocand[j];
-        for (int k = 0; k < filled && t > 0; k++) sw += nb_par[k] != k;   // (t = 0: every beam descends from beam 0 of one prefill)
+        for (int j = 0; j < W; j++) bits |= sh.nocand[j];
+        for (int k = 0; k < filled && t > 0; k++) sw += sh.nb_par[k] != k;   // (t = 0: every beam descends from beam 0 of one prefill)
         a.pool_count[g] = count;
         a.done[g] = done;
         a.switches[g] += sw;
         if (bits) a.status[g] |= bits;
-        s_filled = filled;
-        s_done = done;
+        sh.filled = filled;
+        sh.done = done;
+        if constexpr (DIVERSE) {
+            if (!done) {       // (nch + filled <= D * W' <= 16)
+                for (int k = 0; k < filled && nch + k < BEAM_MAX_W; k++) sh.chosen[nch + k] = sh.nb_tok[k];
+                sh.n_chosen = min(nch + filled, BEAM_MAX_W);
+            }
+        }
     }
     // 4. stage the histories (the new beams and the pool read the OLD rows)
     for (int e = tid; e < W * t; e += BEAM_THREADS) {
@@ -220,36 +262,38 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_group_kernel(BeamArgs a) {
         a.hist[o] = a.tokens[o];
     }
     __syncthreads();
-    const int filled = s_filled;
+    const int filled = sh.filled;
     for (int e = tid; e < W * (t + 1); e += BEAM_THREADS) {
         const int j = e / (t + 1), i = e % (t + 1);
         const int64_t o = (int64_t)(b0 + j) * mx + i;
-        if (j < filled) a.tokens[o] = i < t ? a.hist[(int64_t)(b0 + nb_par[j]) * mx + i] : nb_tok[j];
+        if (j < filled) a.tokens[o] = i < t ? a.hist[(int64_t)(b0 + sh.nb_par[j]) * mx + i] : sh.nb_tok[j];
         else if (i == t) a.tokens[o] = a.pad;
     }
     for (int e = tid; e < W * mx; e += BEAM_THREADS) {
-        const int k = e / mx, i = e % mx, src = srow[k];
+        const int k = e / mx, i = e % mx, src = sh.srow[k];
         if (src < 0) continue;
-        a.pool_tokens[(int64_t)(b0 + k) * mx + i] = i < t ? a.hist[(int64_t)src * mx + i] : (i == t ? slast[k] : a.pad);
+        a.pool_tokens[(int64_t)(b0 + k) * mx + i] = i < t ? a.hist[(int64_t)src * mx + i] : (i == t ? sh.slast[k] : a.pad);
     }
     if (tid < W) {
         const int b = b0 + tid;
         const bool alive = tid < filled;
-        a.beam_score[b] = alive ? nb_sc[tid] : -INFINITY;
-        a.parent[b] = alive ? b0 + nb_par[tid] : b;
-        a.next_ids[(int64_t)b * a.ids_stride] = (alive && !s_done) ? nb_tok[tid] : a.pad;
-        a.pool_score[b] = ps[tid];
-        a.pool_len[b] = pl[tid];
-        a.pool_slot[b] = pslot[tid];
+        a.beam_score[b] = alive ? sh.nb_sc[tid] : -INFINITY;
+        a.parent[b] = alive ? b0 + sh.nb_par[tid] : b;
+        a.next_ids[(int64_t)b * a.ids_stride] = (alive && !sh.done) ? sh.nb_tok[tid] : a.pad;
+        a.pool_score[b] = sh.ps[tid];
+        a.pool_len[b] = sh.pl[tid];
+        a.pool_slot[b] = sh.pslot[tid];
     }
 }
 
+__global__ __launch_bounds__(BEAM_THREADS) void beam_group_kernel(BeamArgs a) {
+    __shared__ BeamGroupLds<false> sh;
+    beam_group_step<false>(a, blockIdx.x, 0.f, sh);
+}
+
 // Diverse beam search (db1_beam_step_diverse; the rule is stated in include/db1_hip.h and restated in tests/diverse_beam_rule.py): one
-// workgroup per PROMPT walks its D sub-groups of W' = a.W beams in order (a.G = prompts * D sub-groups, a.K = W' + W candidates per row from
-// launch 1).  Per sub-group: the chunk merge and the lse per row as in beam_group_kernel; every candidate gets s and, ONCE,
-// sel = s - n(c) * lambda (n(c): one ballot over the at most 16 tokens the earlier sub-groups chose, in LDS); the sub-group's top-2W' come
-// from exact ranks on the sel keys with s kept beside the key; one thread walks them with the unpenalised s and appends the new beams' tokens
-// to the list.  Barriers separate the sub-groups; nothing leaves the workgroup.
+// workgroup per PROMPT walks its D sub-groups of W' = a.W beams in order (a.G = prompts * D sub-groups).  Barriers separate the sub-groups;
+// nothing leaves the workgroup.
 #define BEAM_KERNARG __attribute__((address_space(4)))      // the constant address space of the kernel's own arguments
 struct BeamDivArgs {
     BeamArgs a;
@@ -258,157 +302,19 @@ struct BeamDivArgs {
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void beam_group_diverse_kernel(BeamDivArgs) {
-    __shared__ unsigned long long gk[BEAM_MAX_W * BEAM_MAX_K];
-    __shared__ float gs[BEAM_MAX_W * BEAM_MAX_K];
-    __shared__ unsigned long long top[BEAM_MAX_K];
-    __shared__ float tops[BEAM_MAX_K];
-    __shared__ float ps[BEAM_MAX_W], nb_sc[BEAM_MAX_W];
-    __shared__ int pl[BEAM_MAX_W], pslot[BEAM_MAX_W], srow[BEAM_MAX_W], slast[BEAM_MAX_W], nb_par[BEAM_MAX_W], nb_tok[BEAM_MAX_W], nocand[BEAM_MAX_W];
-    __shared__ int chosen[BEAM_MAX_W];
-    __shared__ int s_filled, s_done, s_chosen;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ BeamGroupLds<true> sh;
     // The arguments (the kernel's only parameter: offset 0 of the kernarg segment) are read through a pointer that every trip of the
     // sub-group loop takes as new.  Read as a by-value parameter, all 15 pointers and every loop-invariant condition stay live across the
     // loop, which costs 52 SGPR spills; read again per trip they are scalar loads from the constant segment and nothing spills.
     const BEAM_KERNARG BeamDivArgs* kp = (const BEAM_KERNARG BeamDivArgs*)__builtin_amdgcn_kernarg_segment_ptr();
     const int nD = kp->D;
-    if (tid == 0) s_chosen = 0;
+    if (threadIdx.x == 0) sh.n_chosen = 0;
     __syncthreads();
 #pragma unroll 1
     for (int d = 0; d < nD; d++) {
         asm volatile("" : "+s"(kp));
-        const BEAM_KERNARG BeamDivArgs& da = *kp;
-        const BEAM_KERNARG BeamArgs& a = da.a;
-        const int W = a.W, K = a.K, K2 = 2 * a.W, mx = a.max_new;
-        const int t = *a.t;
-        const int g = blockIdx.x * da.D + d, b0 = g * W;
-        const int was_done = a.done[g];
-        if (was_done || t < 0 || t >= mx) {      // (block-uniform)
-            if (tid < W) a.next_ids[(int64_t)(b0 + tid) * a.ids_stride] = a.pad;
-            if (tid == 0 && !was_done) a.status[g] |= 2;
-            continue;
-        }
-        const int nch = s_chosen;
-        // 1. per beam row: lse over the chunks, the row's top-K with their s and their sel keys
-        for (int j = wv; j < W; j += BEAM_WAVES) {
-            const int row = b0 + j;
-            if (lane < K) gk[j * BEAM_MAX_K + lane] = 0ull;
-            if (lane == 0) nocand[j] = 0;
-            if (!(t == 0 ? j == 0 : a.beam_score[row] > -INFINITY)) continue;      // (beam_live)
-            const float base = t == 0 ? 0.f : a.beam_score[row];
-            const float2 ms = lane < a.nb ? a.ms[(int64_t)row * a.nb + lane] : make_float2(-INFINITY, 0.f);
-            const float m = wave_max(ms.x);
-            if (!(m > -INFINITY)) {
-                if (lane == 0) nocand[j] = 1;
-                continue;
-            }
-            const float lse = m + logf(wave_sum(ms.x > -INFINITY ? ms.y * expf(ms.x - m) : 0.f));
-            const unsigned long long* lst = a.cand + ((int64_t)row * a.nb + lane) * K;
-            int idx = 0;
-            for (int r = 0; r < K; r++) {
-                const unsigned long long h = (lane < a.nb && idx < K) ? lst[idx] : 0ull;
-                const unsigned long long w = wave_max_u64(h);
-                if (w == 0) break;
-                if (h == w) idx++;
-                const int c = (int)~(unsigned)w;
-                const float s = base + (sel_unkey((unsigned)(w >> 32)) - lse);
-                const int n = __popcll(__ballot(lane < nch && chosen[lane & (BEAM_MAX_W - 1)] == c));   // (one lane per entry of the list)
-                if (lane == 0) {
-                    const float sel = fmaxf(s - (float)n * da.lam, -FLT_MAX);
-                    const unsigned sk = sel_key(s) ? sel_key(sel) : 0u;
-                    gk[j * BEAM_MAX_K + r] = sk ? (((unsigned long long)sk << 32) | (unsigned)~(((unsigned)j << 16) | (unsigned)c)) : 0ull;
-                    gs[j * BEAM_MAX_K + r] = s;
-                }
-            }
-        }
-        if (tid < K2) top[tid] = 0ull;
-        if (tid < W) {
-            ps[tid] = a.pool_score[b0 + tid];
-            pl[tid] = a.pool_len[b0 + tid];
-            pslot[tid] = a.pool_slot[b0 + tid];
-            srow[tid] = -1;
-        }
-        __syncthreads();
-        // 2. the sub-group's top-2W' by exact rank on the sel keys (unique: (j, c) pairs differ)
-        for (int e = tid; e < W * K; e += BEAM_THREADS) {
-            const int at = (e / K) * BEAM_MAX_K + e % K;
-            const unsigned long long x = gk[at];
-            if (x == 0) continue;
-            int rank = 0;
-            for (int f = 0; f < W * K && rank < K2; f++) rank += gk[(f / K) * BEAM_MAX_K + f % K] > x;
-            if (rank < K2) {
-                top[rank] = x;
-                tops[rank] = gs[at];
-            }
-        }
-        __syncthreads();
-        // 3. the walk (one thread, LDS only): the order is sel's, every score is the unpenalised s
-        if (tid == 0) {
-            const float den = powf((float)(t + 1), a.alpha);
-            int count = a.pool_count[g], filled = 0;
-            for (int r = 0; r < K2 && filled < W; r++) {
-                const unsigned long long p = top[r];
-                if (!p) break;
-                const unsigned low = ~(unsigned)p;
-                const int j = (int)(low >> 16), c = (int)(low & 0xffffu);
-                const float s = tops[r];
-                if (c == a.eos) {
-                    if (r < W) beam_offer(s / den, b0 + j, c, t, W, count, ps, pl, pslot, srow, slast);
-                    continue;
-                }
-                nb_par[filled] = j;
-                nb_tok[filled] = c;
-                nb_sc[filled] = s;
-                filled++;
-            }
-            if (t == mx - 1)
-                for (int k = 0; k < filled; k++) beam_offer(nb_sc[k] / den, b0 + nb_par[k], nb_tok[k], t + 1, W, count, ps, pl, pslot, srow, slast);
-            float best = -INFINITY;
-            for (int k = 0; k < filled; k++) best = fmaxf(best, nb_sc[k]);
-            const int done = filled == 0 || (count == W && ps[W - 1] >= best / den);
-            int bits = 0, sw = 0;
-            for (int j = 0; j < W; j++) bits |= nocand[j];
-            for (int k = 0; k < filled && t > 0; k++) sw += nb_par[k] != k;
-            a.pool_count[g] = count;
-            a.done[g] = done;
-            a.switches[g] += sw;
-            if (bits) a.status[g] |= bits;
-            s_filled = filled;
-            s_done = done;
-            if (!done) {       // (nch + filled <= D * W' <= 16)
-                for (int k = 0; k < filled && nch + k < BEAM_MAX_W; k++) chosen[nch + k] = nb_tok[k];
-                s_chosen = min(nch + filled, BEAM_MAX_W);
-            }
-        }
-        // 4. stage the sub-group's histories (the new beams and the pool read the OLD rows)
-        for (int e = tid; e < W * t; e += BEAM_THREADS) {
-            const int64_t o = (int64_t)(b0 + e / t) * mx + e % t;
-            a.hist[o] = a.tokens[o];
-        }
-        __syncthreads();
-        const int filled = s_filled;
-        for (int e = tid; e < W * (t + 1); e += BEAM_THREADS) {
-            const int j = e / (t + 1), i = e % (t + 1);
-            const int64_t o = (int64_t)(b0 + j) * mx + i;
-            if (j < filled) a.tokens[o] = i < t ? a.hist[(int64_t)(b0 + nb_par[j]) * mx + i] : nb_tok[j];
-            else if (i == t) a.tokens[o] = a.pad;
-        }
-        for (int e = tid; e < W * mx; e += BEAM_THREADS) {
-            const int k = e / mx, i = e % mx, src = srow[k];
-            if (src < 0) continue;
-            a.pool_tokens[(int64_t)(b0 + k) * mx + i] = i < t ? a.hist[(int64_t)src * mx + i] : (i == t ? slast[k] : a.pad);
-        }
-        if (tid < W) {
-            const int b = b0 + tid;
-            const bool alive = tid < filled;
-            a.beam_score[b] = alive ? nb_sc[tid] : -INFINITY;
-            a.parent[b] = alive ? b0 + nb_par[tid] : b;
-            a.next_ids[(int64_t)b * a.ids_stride] = (alive && !s_done) ? nb_tok[tid] : a.pad;
-            a.pool_score[b] = ps[tid];
-            a.pool_len[b] = pl[tid];
-            a.pool_slot[b] = pslot[tid];
-        }
-        __syncthreads();     // (the next sub-group rewrites every LDS array above)
+        beam_group_step<true>(kp->a, blockIdx.x * kp->D + d, kp->lam, sh);
+        __syncthreads();     // (the next sub-group rewrites every LDS array)
     }
 }
 
@@ -417,7 +323,7 @@ static int beam_nb(int M, int width) {
     nb = min(nb, (width + 1023) / 1024);
     return max(1, min(nb, BEAM_MAX_NB));
 }
-// K: the candidates a chunk keeps per row (2W for the plain step)
+// K: the candidates a chunk keeps per row (W' + D W'; 2W for the plain step)
 static int64_t beam_ws_layout_k(int M, int V, int K, int max_new, int64_t* off_cand, int64_t* off_hist) {
     const int nb = beam_nb(M, V);
     const int64_t ms = ((int64_t)M * nb * 8 + 15) / 16 * 16;
@@ -425,56 +331,6 @@ static int64_t beam_ws_layout_k(int M, int V, int K, int max_new, int64_t* off_c
     if (off_cand) *off_cand = ms;
     if (off_hist) *off_hist = ms + cand;
     return ms + cand + (int64_t)M * max_new * 4;
-}
-static int64_t beam_ws_layout(int M, int V, int W, int max_new, int64_t* off_cand, int64_t* off_hist) {
-    return beam_ws_layout_k(M, V, 2 * W, max_new, off_cand, off_hist);
-}
-
-extern "C" int db1_beam_step_supported(int V, int64_t ld, int W, int dt) {
-    return db1_dt_ok(dt) && V > 0 && V <= BEAM_MAX_V && ld >= V && W >= 1 && W <= BEAM_MAX_W;
-}
-
-extern "C" int64_t db1_beam_step_workspace_bytes(int M, int V, int W, int max_new, int dt) {
-    (void)dt;
-    if (M <= 0 || V <= 0 || W <= 0 || max_new <= 0) return 0;
-    return beam_ws_layout(M, V, W, max_new, nullptr, nullptr);
-}
-
-extern "C" int db1_beam_step(const void* logits, int G, int W, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, int eos_id, int pad_id,
-                             float length_penalty, const int32_t* t, int max_new, float* beam_score, int32_t* parent, int32_t* tokens,
-                             int32_t* pool_tokens, int32_t* pool_len, float* pool_score, int32_t* pool_slot, int32_t* pool_count, int32_t* done,
-                             int32_t* switches, int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
-    if (!db1_beam_step_supported(V, ld, W, dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "beam_step: V=%d ld=%lld W=%d dt=%d", V, (long long)ld, W, dt);
-    if (G <= 0 || (int64_t)G * W > 65535 || max_new <= 0 || ids_stride < 0)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step: G=%d W=%d max_new=%d ids_stride=%lld", G, W, max_new, (long long)ids_stride);
-    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
-    if (!(length_penalty > -INFINITY && length_penalty < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step: length_penalty %g", (double)length_penalty);
-    if (!logits || !t || !beam_score || !parent || !tokens || !pool_tokens || !pool_len || !pool_score || !pool_slot || !pool_count || !done ||
-        !switches || !next_ids || !status)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step: null buffer");
-    const int M = G * W;
-    int64_t off_cand = 0, off_hist = 0;
-    const int64_t need = beam_ws_layout(M, V, W, max_new, &off_cand, &off_hist);
-    DB1_NEED_WS(ws, ws_bytes, need, "beam_step");
-    BeamArgs a;
-    a.logits = logits; a.ld = ld; a.G = G; a.W = W; a.K = 2 * W; a.M = M; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
-    a.nb = beam_nb(M, vocab_hi - vocab_lo);
-    a.span = (vocab_hi - vocab_lo + a.nb - 1) / a.nb;
-    a.eos = eos_id; a.pad = pad_id; a.max_new = max_new; a.alpha = length_penalty; a.t = t;
-    a.beam_score = beam_score; a.parent = parent; a.tokens = tokens; a.pool_tokens = pool_tokens; a.pool_len = pool_len; a.pool_score = pool_score;
-    a.pool_slot = pool_slot; a.pool_count = pool_count; a.done = done; a.switches = switches;
-    a.next_ids = reinterpret_cast<long long*>(next_ids); a.ids_stride = ids_stride; a.status = status;
-    char* w = static_cast<char*>(ws);
-    a.ms = reinterpret_cast<float2*>(w);
-    a.cand = reinterpret_cast<unsigned long long*>(w + off_cand);
-    a.hist = reinterpret_cast<int*>(w + off_hist);
-    hipStream_t st = (hipStream_t)stream;
-    DB1_DISPATCH_DT(dt, T, { beam_rows_kernel<T><<<dim3(a.nb, M), BEAM_THREADS, 0, st>>>(a); });
-    DB1_CHECK_LAUNCH("beam_step rows");
-    beam_group_kernel<<<G, BEAM_THREADS, 0, st>>>(a);
-    DB1_CHECK_LAUNCH("beam_step groups");
-    return DB1_OK;
 }
 
 // W: the beams of ONE sub-group (W'), D sub-groups per prompt
@@ -488,31 +344,37 @@ extern "C" int64_t db1_beam_step_diverse_workspace_bytes(int M, int V, int W, in
     return beam_ws_layout_k(M, V, W + D * W, max_new, nullptr, nullptr);
 }
 
-extern "C" int db1_beam_step_diverse(const void* logits, int G, int D, int W, float diversity_penalty, int V, int64_t ld, int dt, int vocab_lo,
-                                     int vocab_hi, int eos_id, int pad_id, float length_penalty, const int32_t* t, int max_new, float* beam_score,
-                                     int32_t* parent, int32_t* tokens, int32_t* pool_tokens, int32_t* pool_len, float* pool_score,
-                                     int32_t* pool_slot, int32_t* pool_count, int32_t* done, int32_t* switches, int64_t* next_ids,
-                                     int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
-    if (!db1_beam_step_diverse_supported(V, ld, W, D, dt))
-        DB1_FAIL(DB1_ERR_UNSUPPORTED, "beam_step_diverse: V=%d ld=%lld W'=%d D=%d dt=%d", V, (long long)ld, W, D, dt);
+extern "C" int db1_beam_step_supported(int V, int64_t ld, int W, int dt) { return db1_beam_step_diverse_supported(V, ld, W, 1, dt); }
+
+extern "C" int64_t db1_beam_step_workspace_bytes(int M, int V, int W, int max_new, int dt) {
+    (void)dt;
+    if (M <= 0 || V <= 0 || W <= 0 || max_new <= 0) return 0;
+    return beam_ws_layout_k(M, V, 2 * W, max_new, nullptr, nullptr);
+}
+
+// Both steps: G prompts of D sub-groups of W beams (the plain step: D = 1, lam = 0, `diverse` false: beam_group_kernel on G workgroups).
+static int beam_step_launch(const char* who, bool diverse, const void* logits, int G, int D, int W, float lam, int V, int64_t ld, int dt, int vocab_lo,
+                            int vocab_hi, int eos_id, int pad_id, float length_penalty, const int32_t* t, int max_new, float* beam_score,
+                            int32_t* parent, int32_t* tokens, int32_t* pool_tokens, int32_t* pool_len, float* pool_score, int32_t* pool_slot,
+                            int32_t* pool_count, int32_t* done, int32_t* switches, int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws,
+                            int64_t ws_bytes, void* stream) {
+    if (!db1_beam_step_diverse_supported(V, ld, W, D, dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d ld=%lld W=%d D=%d dt=%d", who, V, (long long)ld, W, D, dt);
     if (G <= 0 || (int64_t)G * D * W > 65535 || max_new <= 0 || ids_stride < 0)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step_diverse: G=%d D=%d W'=%d max_new=%d ids_stride=%lld", G, D, W, max_new, (long long)ids_stride);
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: G=%d D=%d W=%d max_new=%d ids_stride=%lld", who, G, D, W, max_new, (long long)ids_stride);
     if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step_diverse: window [%d, %d) is empty or outside [0, %d)", vocab_lo, vocab_hi, V);
-    if (!(length_penalty > -INFINITY && length_penalty < INFINITY))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step_diverse: length_penalty %g", (double)length_penalty);
-    if (!(diversity_penalty >= 0.f && diversity_penalty < INFINITY))
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step_diverse: diversity_penalty %g must be finite and >= 0", (double)diversity_penalty);
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, vocab_lo, vocab_hi, V);
+    if (!(length_penalty > -INFINITY && length_penalty < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: length_penalty %g", who, (double)length_penalty);
+    if (!(lam >= 0.f && lam < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: diversity_penalty %g must be finite and >= 0", who, (double)lam);
     if (!logits || !t || !beam_score || !parent || !tokens || !pool_tokens || !pool_len || !pool_score || !pool_slot || !pool_count || !done ||
         !switches || !next_ids || !status)
-        DB1_FAIL(DB1_ERR_BAD_SHAPE, "beam_step_diverse: null buffer");
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
     const int M = G * D * W;
     int64_t off_cand = 0, off_hist = 0;
     const int64_t need = beam_ws_layout_k(M, V, W + D * W, max_new, &off_cand, &off_hist);
-    DB1_NEED_WS(ws, ws_bytes, need, "beam_step_diverse");
+    DB1_NEED_WS(ws, ws_bytes, need, who);
     BeamDivArgs da;
     BeamArgs& a = da.a;
-    da.D = D; da.lam = diversity_penalty;
+    da.D = D; da.lam = lam;
     a.logits = logits; a.ld = ld; a.G = G * D; a.W = W; a.K = W + D * W; a.M = M; a.V = V; a.vlo = vocab_lo; a.vhi = vocab_hi;
     a.nb = beam_nb(M, vocab_hi - vocab_lo);
     a.span = (vocab_hi - vocab_lo + a.nb - 1) / a.nb;
@@ -526,10 +388,32 @@ extern "C" int db1_beam_step_diverse(const void* logits, int G, int D, int W, fl
     a.hist = reinterpret_cast<int*>(w + off_hist);
     hipStream_t st = (hipStream_t)stream;
     DB1_DISPATCH_DT(dt, T, { beam_rows_kernel<T><<<dim3(a.nb, M), BEAM_THREADS, 0, st>>>(a); });
-    DB1_CHECK_LAUNCH("beam_step_diverse rows");
-    beam_group_diverse_kernel<<<G, BEAM_THREADS, 0, st>>>(da);
-    DB1_CHECK_LAUNCH("beam_step_diverse groups");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) DB1_FAIL(DB1_ERR_HIP, "%s rows: %s", who, hipGetErrorString(e));
+    if (diverse) beam_group_diverse_kernel<<<G, BEAM_THREADS, 0, st>>>(da);
+    else beam_group_kernel<<<G, BEAM_THREADS, 0, st>>>(a);
+    e = hipGetLastError();
+    if (e != hipSuccess) DB1_FAIL(DB1_ERR_HIP, "%s groups: %s", who, hipGetErrorString(e));
     return DB1_OK;
+}
+
+extern "C" int db1_beam_step(const void* logits, int G, int W, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, int eos_id, int pad_id,
+                             float length_penalty, const int32_t* t, int max_new, float* beam_score, int32_t* parent, int32_t* tokens,
+                             int32_t* pool_tokens, int32_t* pool_len, float* pool_score, int32_t* pool_slot, int32_t* pool_count, int32_t* done,
+                             int32_t* switches, int64_t* next_ids, int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
+    return beam_step_launch("beam_step", false, logits, G, 1, W, 0.f, V, ld, dt, vocab_lo, vocab_hi, eos_id, pad_id, length_penalty, t, max_new,
+                            beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches, next_ids,
+                            ids_stride, status, ws, ws_bytes, stream);
+}
+
+extern "C" int db1_beam_step_diverse(const void* logits, int G, int D, int W, float diversity_penalty, int V, int64_t ld, int dt, int vocab_lo,
+                                     int vocab_hi, int eos_id, int pad_id, float length_penalty, const int32_t* t, int max_new, float* beam_score,
+                                     int32_t* parent, int32_t* tokens, int32_t* pool_tokens, int32_t* pool_len, float* pool_score,
+                                     int32_t* pool_slot, int32_t* pool_count, int32_t* done, int32_t* switches, int64_t* next_ids,
+                                     int64_t ids_stride, int32_t* status, void* ws, int64_t ws_bytes, void* stream) {
+    return beam_step_launch("beam_step_diverse", true, logits, G, D, W, diversity_penalty, V, ld, dt, vocab_lo, vocab_hi, eos_id, pad_id,
+                            length_penalty, t, max_new, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done,
+                            switches, next_ids, ids_stride, status, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------ ring reorder

@@ -923,18 +923,9 @@ class _BeamState:
         ids = torch.full((self.G, R, mx), self.cfg.pad_id, dtype=torch.int32)
         lengths = torch.zeros(self.G, R, dtype=torch.int32)
         scores = torch.full((self.G, R), float("-inf"), dtype=torch.float32)
-        if self.D > 1:
-            return self._merged(ids, lengths, scores, toks, slot, n, sc, count)
-        for g in range(self.G):
-            k = min(R, int(count[g]))           # (fewer hypotheses than R only when every beam of a group ran out of candidates)
-            ids[g, :k] = toks[g, slot[g, :k].long()]
-            lengths[g, :k] = n[g, :k]
-            scores[g, :k] = sc[g, :k]
-        return ids, lengths, scores
-
-    def _merged(self, ids, lengths, scores, toks, slot, n, sc, count):
-        """step 8 of the diverse rule: a prompt's D pools merged by (score descending, sub-group ascending, position in its pool ascending),
-        the first R"""
+        # step 8 of the diverse rule: a prompt's D pools merged by (score descending, sub-group ascending, position in its pool ascending),
+        # the first R (fewer only when its beams ran out of candidates).  D = 1: the pool's own order -- it is sorted, and on equal scores
+        # the earlier offer stays ahead
         for g, ent in enumerate(self._merge_order(sc, count)):
             for r, (d, k) in enumerate(ent):
                 q = g * self.D + d

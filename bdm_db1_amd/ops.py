@@ -1055,6 +1055,50 @@ def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:
     return bool(lib.load().db1_beam_step_supported(int(V), int(ld), int(W), dt_code(dtype)))
 
 
+def beam_step_diverse_supported(V: int, ld: int, W: int, D: int, dtype) -> bool:
+    """``W``: the beams of ONE sub-group (W'), ``D`` sub-groups per prompt"""
+    return bool(lib.load().db1_beam_step_diverse_supported(int(V), int(ld), int(W), int(D), dt_code(dtype)))
+
+
+def _beam_step(who, logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches, next_ids,
+               status, W, D, lam, V, vocab_lo, vocab_hi, eos_id, pad_id, length_penalty):
+    """``beam_step`` (D = 1, lam = 0) and ``beam_step_diverse``: every host check over the Q = M / W (sub-)groups of W beams, then the
+    library's own predicate, then db1_<who> (the diverse symbols take D, and lambda, next to W)"""
+    dev, W, D, lam, i32, f32 = logits2d.device, int(W), int(D), float(lam), torch.int32, torch.float32
+    d = (D,) if who == "beam_step_diverse" else ()
+    if W < 1 or D < 1 or D * W > 16:
+        raise ValueError(f"{who}: W={W} beams in each of D={D} sub-groups: both must be >= 1 and D * W <= 16")
+    if not 0 <= lam < float("inf"):
+        raise ValueError(f"{who}: diversity_penalty {lam} must be finite and >= 0")
+    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi, lambda V, ld: True)      # (the library's predicate: below)
+    if M % (D * W) != 0 or M == 0:
+        raise ValueError(f"{who}: D * W = {D * W} must divide the {M} rows")
+    G, Q = M // (D * W), M // W
+    lp = float(length_penalty)
+    if not abs(lp) < float("inf"):
+        raise ValueError(f"{who}: length_penalty {length_penalty} must be finite")
+    _check_tensor(who, "tokens", tokens, i32, (M, -1), dev)
+    mx = tokens.shape[1]
+    if mx < 1:
+        raise ValueError(f"{who}: max_new must be >= 1")
+    for name, x, shape, dt in (("t", t, (1,), i32), ("beam_score", beam_score, (M,), f32), ("parent", parent, (M,), i32),
+                               ("pool_tokens", pool_tokens, (Q, W, mx), i32), ("pool_len", pool_len, (Q, W), i32),
+                               ("pool_score", pool_score, (Q, W), f32), ("pool_slot", pool_slot, (Q, W), i32),
+                               ("pool_count", pool_count, (Q,), i32), ("done", done, (Q,), i32), ("switches", switches, (Q,), i32),
+                               ("status", status, (Q,), i32)):
+        _check_tensor(who, name, x, dt, shape, dev)
+    _check_next_ids(who, next_ids, M, dev)
+    if M > 65535:
+        raise ValueError(f"{who}: {M} rows (at most 65535)")
+    sym, code, ld = "db1_" + who, dt_code(logits2d), max(ld, V)
+    if not getattr(lib.load(), sym + "_supported")(V, ld, W, *d, code):      # (the library's own predicate, after every host check)
+        raise ValueError(f"{who}: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {logits2d.stride(0)}")
+    ws, wsn = _ws(sym + "_workspace_bytes", (M, V, W, *d, mx, code), dev)
+    lib.call(sym, P(logits2d), G, *((D, W, lam) if d else (W,)), V, ld, code, vocab_lo, vocab_hi, int(eos_id), int(pad_id), lp, P(t), mx,
+             P(beam_score), P(parent), P(tokens), P(pool_tokens), P(pool_len), P(pool_score), P(pool_slot), P(pool_count), P(done), P(switches),
+             P(next_ids), next_ids.stride(0), P(status), ws, wsn, stream())
+
+
 def beam_step(logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches, next_ids, status,
               *, W, V=None, vocab_lo=0, vocab_hi=None, eos_id=-1, pad_id=0, length_penalty=1.0):
     """one beam-search step over ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid, M = G * W rows) on the device
@@ -1062,37 +1106,8 @@ def beam_step(logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, po
     [M, max_new]), the pool (pool_tokens int32 [G, W, max_new], pool_len / pool_slot int32 [G, W], pool_score float32 [G, W]) and pool_count /
     done / switches / status (int32 [G]) updated; the next ids go to ``next_ids`` (int64, [M] or a column of [M, q]).  Capturable; raises
     ValueError on bad arguments before anything is launched."""
-    who, dev, W, i32, f32 = "beam_step", logits2d.device, int(W), torch.int32, torch.float32
-    if not 1 <= W <= 16:
-        raise ValueError(f"beam_step: W={W} must lie in [1, 16]")
-    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi,
-                                                 lambda V, ld: beam_step_supported(V, max(ld, V), W, logits2d.dtype))
-    if M % W != 0 or M == 0:
-        raise ValueError(f"beam_step: W={W} must divide the {M} rows")
-    G = M // W
-    lp = float(length_penalty)
-    if not abs(lp) < float("inf"):
-        raise ValueError(f"beam_step: length_penalty {length_penalty} must be finite")
-    _check_tensor(who, "tokens", tokens, i32, (M, -1), dev)
-    mx = tokens.shape[1]
-    if mx < 1:
-        raise ValueError("beam_step: max_new must be >= 1")
-    for name, x, shape, dt in (("t", t, (1,), i32), ("beam_score", beam_score, (M,), f32), ("parent", parent, (M,), i32),
-                               ("pool_tokens", pool_tokens, (G, W, mx), i32), ("pool_len", pool_len, (G, W), i32),
-                               ("pool_score", pool_score, (G, W), f32), ("pool_slot", pool_slot, (G, W), i32),
-                               ("pool_count", pool_count, (G,), i32), ("done", done, (G,), i32), ("switches", switches, (G,), i32),
-                               ("status", status, (G,), i32)):
-        _check_tensor(who, name, x, dt, shape, dev)
-    _check_next_ids(who, next_ids, M, dev)
-    ws, wsn = _ws("db1_beam_step_workspace_bytes", (M, V, W, mx, dt_code(logits2d)), dev)
-    lib.call("db1_beam_step", P(logits2d), G, W, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, int(eos_id), int(pad_id), lp, P(t), mx,
-             P(beam_score), P(parent), P(tokens), P(pool_tokens), P(pool_len), P(pool_score), P(pool_slot), P(pool_count), P(done), P(switches),
-             P(next_ids), next_ids.stride(0), P(status), ws, wsn, stream())
-
-
-def beam_step_diverse_supported(V: int, ld: int, W: int, D: int, dtype) -> bool:
-    """``W``: the beams of ONE sub-group (W'), ``D`` sub-groups per prompt"""
-    return bool(lib.load().db1_beam_step_diverse_supported(int(V), int(ld), int(W), int(D), dt_code(dtype)))
+    _beam_step("beam_step", logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches,
+               next_ids, status, W, 1, 0.0, V, vocab_lo, vocab_hi, eos_id, pad_id, length_penalty)
 
 
 def beam_step_diverse(logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done, switches, next_ids,
@@ -1102,38 +1117,8 @@ def beam_step_diverse(logits2d, t, beam_score, parent, tokens, pool_tokens, pool
     for G * D groups of ``W`` beams; a token chosen by an earlier sub-group of the prompt in this step costs a later one
     ``diversity_penalty`` per earlier choice in the ranking, never in a stored score.  Capturable; raises ValueError on bad arguments before
     anything is launched."""
-    who, dev, W, D, i32, f32 = "beam_step_diverse", logits2d.device, int(W), int(D), torch.int32, torch.float32
-    if W < 1 or D < 1 or D * W > 16:
-        raise ValueError(f"beam_step_diverse: W={W} beams in each of D={D} sub-groups: both must be >= 1 and D * W <= 16")
-    lam = float(diversity_penalty)
-    if not 0 <= lam < float("inf"):
-        raise ValueError(f"beam_step_diverse: diversity_penalty {diversity_penalty} must be finite and >= 0")
-    M, ld, V, vocab_lo, vocab_hi = _check_logits(who, logits2d, V, vocab_lo, vocab_hi, lambda V, ld: True)      # (the library's predicate: below)
-    if M % (D * W) != 0 or M == 0:
-        raise ValueError(f"beam_step_diverse: D * W = {D * W} must divide the {M} rows")
-    G, Q = M // (D * W), M // W
-    lp = float(length_penalty)
-    if not abs(lp) < float("inf"):
-        raise ValueError(f"beam_step_diverse: length_penalty {length_penalty} must be finite")
-    _check_tensor(who, "tokens", tokens, i32, (M, -1), dev)
-    mx = tokens.shape[1]
-    if mx < 1:
-        raise ValueError("beam_step_diverse: max_new must be >= 1")
-    for name, x, shape, dt in (("t", t, (1,), i32), ("beam_score", beam_score, (M,), f32), ("parent", parent, (M,), i32),
-                               ("pool_tokens", pool_tokens, (Q, W, mx), i32), ("pool_len", pool_len, (Q, W), i32),
-                               ("pool_score", pool_score, (Q, W), f32), ("pool_slot", pool_slot, (Q, W), i32),
-                               ("pool_count", pool_count, (Q,), i32), ("done", done, (Q,), i32), ("switches", switches, (Q,), i32),
-                               ("status", status, (Q,), i32)):
-        _check_tensor(who, name, x, dt, shape, dev)
-    _check_next_ids(who, next_ids, M, dev)
-    if M > 65535:
-        raise ValueError(f"beam_step_diverse: {M} rows (at most 65535)")
-    if not beam_step_diverse_supported(V, max(ld, V), W, D, logits2d.dtype):      # (the library's own predicate, after every host check)
-        raise ValueError(f"beam_step_diverse: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {ld}")
-    ws, wsn = _ws("db1_beam_step_diverse_workspace_bytes", (M, V, W, D, mx, dt_code(logits2d)), dev)
-    lib.call("db1_beam_step_diverse", P(logits2d), G, D, W, lam, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, int(eos_id), int(pad_id),
-             lp, P(t), mx, P(beam_score), P(parent), P(tokens), P(pool_tokens), P(pool_len), P(pool_score), P(pool_slot), P(pool_count), P(done),
-             P(switches), P(next_ids), next_ids.stride(0), P(status), ws, wsn, stream())
+    _beam_step("beam_step_diverse", logits2d, t, beam_score, parent, tokens, pool_tokens, pool_len, pool_score, pool_slot, pool_count, done,
+               switches, next_ids, status, W, D, diversity_penalty, V, vocab_lo, vocab_hi, eos_id, pad_id, length_penalty)
 
 
 def ring_pointers(rings) -> torch.Tensor:

@@ -37,8 +37,8 @@ def _lse32(x) -> np.float32:
     return np.float32(m + np.log(np.exp(x - m).sum()))
 
 
-def row_candidates(l, lo, hi, base, k):
-    """-> (s float32 [<= k], c int [<= k]): the row's best k candidates by (logit desc, column asc) and their scores"""
+def row_candidates(l, lo, hi, base, k=None):
+    """-> (s float32 [<= k], c int [<= k]): the row's best k candidates (None: all of them) by (logit desc, column asc) and their scores"""
     l = np.asarray(l, np.float32)
     cols = np.arange(lo, hi)
     lw = l[lo:hi]
@@ -52,105 +52,119 @@ def row_candidates(l, lo, hi, base, k):
     return s, cols[order]
 
 
-def step(S: dict, logits, t: int, W: int, lo: int, hi: int, eos: int = -1, pad: int = 0, alpha: float = 1.0, tol: float = 1e-5):
-    """one step on a copy of the state ``S`` (new_state layout) and logits [M, V] (fp32; bf16 widened) -> (new state, ambiguous bool [G])"""
+def step(S: dict, logits, t: int, W: int, lo: int, hi: int, eos: int = -1, pad: int = 0, alpha: float = 1.0, tol: float = 1e-5, D: int = 1,
+         lam: float = 0.0, k_row=None, walked=None):
+    """one step on a copy of the state ``S`` (new_state layout) and logits [M, V] (fp32; bf16 widened) -> (new state, ambiguous bool [G D]).
+    The only restatement of the step: with ``D`` > 1 and ``lam`` the rule of tests/diverse_beam_rule.py over D sub-groups of W / D beams per
+    prompt (``S``: G * D groups of W / D beams), of which the plain rule above is the case D = 1, lam = 0 (sel = s; the largest new score is
+    the first).  ``k_row``: None ranks every candidate of a row, an int only the row's best k_row; ``walked`` (a dict) receives, per
+    (sub-)group that chose, the (j, c) pairs of the first 2 W / D candidates in sel order"""
     S = {k: np.array(v, copy=True) for k, v in S.items()}
     M, mx = S["tokens"].shape
-    G = M // W
-    amb = np.zeros(G, bool)
+    Wp = W // D
+    Q = M // Wp                                           # (sub-)groups
+    amb = np.zeros(Q, bool)
     logits = np.asarray(logits, np.float32)
+    lam32 = np.float32(lam)
     if not 0 <= t < mx:
-        for g in range(G):
-            S["next_ids"][g * W:(g + 1) * W] = pad
-            if not S["done"][g]:
-                S["status"][g] |= 2
+        for q in range(Q):
+            S["next_ids"][q * Wp:(q + 1) * Wp] = pad
+            if not S["done"][q]:
+                S["status"][q] |= 2
         return S, amb
     den = np.float32(np.float32(t + 1) ** np.float32(alpha))
     old_tokens = S["tokens"].copy()
-    for g in range(G):
-        b0 = g * W
-        if S["done"][g]:
-            S["next_ids"][b0:b0 + W] = pad
+    chosen = []
+    for q in range(Q):
+        if q % D == 0:
+            chosen = []                                   # the tokens the earlier sub-groups of this prompt chose
+        b0 = q * Wp
+        if S["done"][q]:
+            S["next_ids"][b0:b0 + Wp] = pad
             continue
         cs, cj, cc = [], [], []
-        for j in range(W):
+        for j in range(Wp):
             b = b0 + j
             live = (j == 0) if t == 0 else S["beam_score"][b] > -np.inf
             if not live:
                 continue
             base = np.float32(0.0) if t == 0 else S["beam_score"][b]
-            rc = row_candidates(logits[b], lo, hi, base, 2 * W + 1)
+            rc = row_candidates(logits[b], lo, hi, base, k_row)
             if rc is None:
-                S["status"][g] |= 1
+                S["status"][q] |= 1
                 continue
             cs.append(rc[0])
             cc.append(rc[1])
             cj.append(np.full(rc[0].size, j))
-        ps = [float(x) for x in S["pool_score"][g]]
-        pl = [int(x) for x in S["pool_len"][g]]
-        pslot = [int(x) for x in S["pool_slot"][g]]
-        count = int(S["pool_count"][g])
-        src = {}                                      # slot -> (old row, last token)
+        ps = [float(x) for x in S["pool_score"][q]]
+        pl = [int(x) for x in S["pool_len"][q]]
+        pslot = [int(x) for x in S["pool_slot"][q]]
+        count = int(S["pool_count"][q])
+        src = {}                                          # slot -> (old row, last token)
         if cs:
             s, j_, c_ = np.concatenate(cs), np.concatenate(cj), np.concatenate(cc)
-            order = np.lexsort((c_, j_, -s.astype(np.float64)))
-            s, j_, c_ = s[order], j_[order], c_[order]
-            scale = max(1.0, float(np.abs(s[:2 * W + 1]).max()))
-            gaps = np.abs(np.diff(s[:2 * W + 1].astype(np.float64)))
+            n = np.zeros(s.size, np.float32)
+            for c in chosen:
+                n += (c_ == c)
+            with np.errstate(over="ignore"):
+                sel = np.maximum((s - n * lam32).astype(np.float32), -np.finfo(np.float32).max)
+            order = np.lexsort((c_, j_, -sel.astype(np.float64)))
+            s, sel, j_, c_ = s[order], sel[order], j_[order], c_[order]
+            scale = max(1.0, float(np.abs(sel[:2 * Wp + 1]).max()))
+            gaps = np.abs(np.diff(sel[:2 * Wp + 1].astype(np.float64)))
             if ((gaps > 0) & (gaps <= tol * scale)).any():
-                amb[g] = True
-            s, j_, c_ = s[:2 * W], j_[:2 * W], c_[:2 * W]
+                amb[q] = True
+            s, j_, c_ = s[:2 * Wp], j_[:2 * Wp], c_[:2 * Wp]
         else:
             s = j_ = c_ = np.zeros(0)
             scale = 1.0
+        if walked is not None:
+            walked[q] = [(int(j), int(c)) for j, c in zip(j_, c_)]
 
-        def offer(h, row, last):
+        def offer(h, row, last, n_tok):
             nonlocal count
             h = float(h)
             if any(0 < abs(h - p) <= tol * scale for p in ps[:count]):
-                amb[g] = True
+                amb[q] = True
             pos = count
             while pos > 0 and ps[pos - 1] < h:
                 pos -= 1
-            if pos >= W:
+            if pos >= Wp:
                 return
-            if count < W:
+            if count < Wp:
                 slot = count
                 count += 1
             else:
-                slot = pslot[W - 1]
+                slot = pslot[Wp - 1]
             for k in range(count - 1, pos, -1):
                 ps[k], pl[k], pslot[k] = ps[k - 1], pl[k - 1], pslot[k - 1]
-            ps[pos], pl[pos], pslot[pos] = h, n_of[0], slot
+            ps[pos], pl[pos], pslot[pos] = h, n_tok, slot
             src[slot] = (row, last)
 
-        n_of = [0]
-        new = []                                      # (j, c, s)
+        new = []                                          # (j, c, s)
         for r in range(len(s)):
-            if len(new) == W:
+            if len(new) == Wp:
                 break
             if int(c_[r]) == eos:
-                if r < W:
-                    n_of[0] = t
-                    offer(np.float32(s[r] / den), b0 + int(j_[r]), eos)
+                if r < Wp:
+                    offer(np.float32(s[r] / den), b0 + int(j_[r]), eos, t)
                 continue
             new.append((int(j_[r]), int(c_[r]), np.float32(s[r])))
         if t == mx - 1:
-            n_of[0] = t + 1
             for j, c, sc in new:
-                offer(np.float32(sc / den), b0 + j, c)
+                offer(np.float32(sc / den), b0 + j, c, t + 1)
         if new:
-            best = float(np.float32(new[0][2] / den))
-            if count == W and 0 < abs(ps[W - 1] - best) <= tol * scale:
-                amb[g] = True
-            done = count == W and ps[W - 1] >= best
+            best = float(np.float32(max(sc for _, _, sc in new) / den))
+            if count == Wp and 0 < abs(ps[Wp - 1] - best) <= tol * scale:
+                amb[q] = True
+            done = count == Wp and ps[Wp - 1] >= best
         else:
             done = True
-        S["pool_count"][g] = count
-        S["done"][g] = int(done)
+        S["pool_count"][q] = count
+        S["done"][q] = int(done)
         if t > 0:
-            S["switches"][g] += sum(1 for k, (j, _, _) in enumerate(new) if j != k)
-        for k in range(W):
+            S["switches"][q] += sum(1 for k, (j, _, _) in enumerate(new) if j != k)
+        for k in range(Wp):
             b = b0 + k
             if k < len(new):
                 j, c, sc = new[k]
@@ -164,13 +178,15 @@ def step(S: dict, logits, t: int, W: int, lo: int, hi: int, eos: int = -1, pad: 
                 S["parent"][b] = b
                 S["tokens"][b, t] = pad
                 S["next_ids"][b] = pad
-        S["pool_score"][g] = ps
-        S["pool_len"][g] = pl
-        S["pool_slot"][g] = pslot
+        S["pool_score"][q] = ps
+        S["pool_len"][q] = pl
+        S["pool_slot"][q] = pslot
         for slot, (row, last) in src.items():
-            S["pool_tokens"][g, slot] = pad
-            S["pool_tokens"][g, slot, :t] = old_tokens[row, :t]
-            S["pool_tokens"][g, slot, t] = last
+            S["pool_tokens"][q, slot] = pad
+            S["pool_tokens"][q, slot, :t] = old_tokens[row, :t]
+            S["pool_tokens"][q, slot, t] = last
+        if not done:
+            chosen.extend(c for _, c, _ in new)
     return S, amb
 
 

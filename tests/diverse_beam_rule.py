@@ -34,136 +34,7 @@ def step(S: dict, logits, t: int, W: int, D: int, lam: float, lo: int, hi: int, 
          tol: float = 1e-5, k_row=None, walked=None):
     """one step on a copy of ``S`` (new_state layout) and logits [G * W, V] -> (new state, ambiguous bool [G * D]); ``walked`` (a dict):
     receives, per sub-group that chose, the (j, c) pairs of the first 2W' candidates in sel order"""
-    S = {k: np.array(v, copy=True) for k, v in S.items()}
-    M, mx = S["tokens"].shape
-    Wp = W // D
-    Q = M // Wp                                           # sub-groups
-    G = Q // D
-    amb = np.zeros(Q, bool)
-    logits = np.asarray(logits, np.float32)
-    lam32 = np.float32(lam)
-    if not 0 <= t < mx:
-        for q in range(Q):
-            S["next_ids"][q * Wp:(q + 1) * Wp] = pad
-            if not S["done"][q]:
-                S["status"][q] |= 2
-        return S, amb
-    den = np.float32(np.float32(t + 1) ** np.float32(alpha))
-    old_tokens = S["tokens"].copy()
-    for g in range(G):
-        chosen = []
-        for d in range(D):
-            q = g * D + d
-            b0 = q * Wp
-            if S["done"][q]:
-                S["next_ids"][b0:b0 + Wp] = pad
-                continue
-            cs, cj, cc = [], [], []
-            for j in range(Wp):
-                b = b0 + j
-                live = (j == 0) if t == 0 else S["beam_score"][b] > -np.inf
-                if not live:
-                    continue
-                base = np.float32(0.0) if t == 0 else S["beam_score"][b]
-                rc = B.row_candidates(logits[b], lo, hi, base, k_row)
-                if rc is None:
-                    S["status"][q] |= 1
-                    continue
-                cs.append(rc[0])
-                cc.append(rc[1])
-                cj.append(np.full(rc[0].size, j))
-            ps = [float(x) for x in S["pool_score"][q]]
-            pl = [int(x) for x in S["pool_len"][q]]
-            pslot = [int(x) for x in S["pool_slot"][q]]
-            count = int(S["pool_count"][q])
-            src = {}                                      # slot -> (old row, last token)
-            if cs:
-                s, j_, c_ = np.concatenate(cs), np.concatenate(cj), np.concatenate(cc)
-                n = np.zeros(s.size, np.float32)
-                for c in chosen:
-                    n += (c_ == c)
-                with np.errstate(over="ignore"):
-                    sel = np.maximum((s - n * lam32).astype(np.float32), -np.finfo(np.float32).max)
-                order = np.lexsort((c_, j_, -sel.astype(np.float64)))
-                s, sel, j_, c_ = s[order], sel[order], j_[order], c_[order]
-                scale = max(1.0, float(np.abs(sel[:2 * Wp + 1]).max()))
-                gaps = np.abs(np.diff(sel[:2 * Wp + 1].astype(np.float64)))
-                if ((gaps > 0) & (gaps <= tol * scale)).any():
-                    amb[q] = True
-                s, j_, c_ = s[:2 * Wp], j_[:2 * Wp], c_[:2 * Wp]
-            else:
-                s = j_ = c_ = np.zeros(0)
-                scale = 1.0
-            if walked is not None:
-                walked[q] = [(int(j), int(c)) for j, c in zip(j_, c_)]
-
-            def offer(h, row, last, n_tok):
-                nonlocal count
-                h = float(h)
-                if any(0 < abs(h - p) <= tol * scale for p in ps[:count]):
-                    amb[q] = True
-                pos = count
-                while pos > 0 and ps[pos - 1] < h:
-                    pos -= 1
-                if pos >= Wp:
-                    return
-                if count < Wp:
-                    slot = count
-                    count += 1
-                else:
-                    slot = pslot[Wp - 1]
-                for k in range(count - 1, pos, -1):
-                    ps[k], pl[k], pslot[k] = ps[k - 1], pl[k - 1], pslot[k - 1]
-                ps[pos], pl[pos], pslot[pos] = h, n_tok, slot
-                src[slot] = (row, last)
-
-            new = []                                      # (j, c, s)
-            for r in range(len(s)):
-                if len(new) == Wp:
-                    break
-                if int(c_[r]) == eos:
-                    if r < Wp:
-                        offer(np.float32(s[r] / den), b0 + int(j_[r]), eos, t)
-                    continue
-                new.append((int(j_[r]), int(c_[r]), np.float32(s[r])))
-            if t == mx - 1:
-                for j, c, sc in new:
-                    offer(np.float32(sc / den), b0 + j, c, t + 1)
-            if new:
-                best = float(np.float32(max(sc for _, _, sc in new) / den))
-                if count == Wp and 0 < abs(ps[Wp - 1] - best) <= tol * scale:
-                    amb[q] = True
-                done = count == Wp and ps[Wp - 1] >= best
-            else:
-                done = True
-            S["pool_count"][q] = count
-            S["done"][q] = int(done)
-            if t > 0:
-                S["switches"][q] += sum(1 for k, (j, _, _) in enumerate(new) if j != k)
-            for k in range(Wp):
-                b = b0 + k
-                if k < len(new):
-                    j, c, sc = new[k]
-                    S["beam_score"][b] = sc
-                    S["parent"][b] = b0 + j
-                    S["tokens"][b, :t] = old_tokens[b0 + j, :t]
-                    S["tokens"][b, t] = c
-                    S["next_ids"][b] = pad if done else c
-                else:
-                    S["beam_score"][b] = -np.inf
-                    S["parent"][b] = b
-                    S["tokens"][b, t] = pad
-                    S["next_ids"][b] = pad
-            S["pool_score"][q] = ps
-            S["pool_len"][q] = pl
-            S["pool_slot"][q] = pslot
-            for slot, (row, last) in src.items():
-                S["pool_tokens"][q, slot] = pad
-                S["pool_tokens"][q, slot, :t] = old_tokens[row, :t]
-                S["pool_tokens"][q, slot, t] = last
-            if not done:
-                chosen.extend(c for _, c, _ in new)
-    return S, amb
+    return B.step(S, logits, t, W, lo, hi, eos, pad, alpha, tol, D, lam, k_row, walked)
 
 
 def merge_order(scores, counts):

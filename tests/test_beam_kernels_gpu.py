@@ -14,60 +14,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 import beam_rule as B  # noqa: E402
+from beam_kernel_common import _bits_equal, _compare, _launch, _upload  # noqa: E402
 from gpu_common import _need_gpu  # noqa: E402,F401
-
-DEV_KEYS = ("beam_score", "parent", "tokens", "pool_tokens", "pool_len", "pool_score", "pool_slot", "pool_count", "done", "switches", "status")
-
-
-def _upload(S):
-    return {k: torch.from_numpy(np.ascontiguousarray(S[k])).to(DEV) for k in DEV_KEYS}
-
-
-def _download(D, ids):
-    S = {k: v.cpu().numpy() for k, v in D.items()}
-    S["next_ids"] = ids[:, 0].cpu().numpy().astype(np.int64)
-    return S
-
-
-def _launch(S, logits, t, W, lo, hi, eos, pad, alpha, V):
-    D = _upload(S)
-    ids = torch.full((logits.shape[0], 2), -5, dtype=torch.long, device=DEV)     # (column 0 of [M, 2]: the row stride is 2)
-    tt = torch.tensor([t], dtype=torch.int32, device=DEV)
-    from bdm_db1_amd import ops
-    ops.beam_step(logits, tt, D["beam_score"], D["parent"], D["tokens"], D["pool_tokens"], D["pool_len"], D["pool_score"], D["pool_slot"],
-                  D["pool_count"], D["done"], D["switches"], ids[:, 0], D["status"], W=W, V=V, vocab_lo=lo, vocab_hi=hi, eos_id=eos, pad_id=pad,
-                  length_penalty=alpha)
-    torch.cuda.synchronize()
-    assert (ids[:, 1] == -5).all()
-    return _download(D, ids)
-
-
-def _close(a, b, rtol=1e-5):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    same_inf = (np.isinf(a) & np.isinf(b) & (np.sign(a) == np.sign(b)))
-    return bool(np.all(same_inf | (np.abs(a - b) <= rtol * np.maximum(1.0, np.abs(b)))))
-
-
-def _compare(got, want, amb, W, t):
-    G = len(want["done"])
-    for g in range(G):
-        rows = slice(g * W, (g + 1) * W)
-        assert got["status"][g] == want["status"][g], g
-        if amb[g]:
-            continue
-        assert got["done"][g] == want["done"][g], (g, t)
-        assert (got["parent"][rows] == want["parent"][rows]).all(), (g, t)
-        assert (got["next_ids"][rows] == want["next_ids"][rows]).all(), (g, t)
-        assert (got["tokens"][rows, :t + 1] == want["tokens"][rows, :t + 1]).all(), (g, t)
-        assert _close(got["beam_score"][rows], want["beam_score"][rows]), (g, t)
-        assert got["switches"][g] == want["switches"][g], (g, t)
-        n = int(want["pool_count"][g])
-        assert got["pool_count"][g] == n, (g, t)
-        assert (got["pool_len"][g, :n] == want["pool_len"][g, :n]).all(), (g, t)
-        assert _close(got["pool_score"][g, :n], want["pool_score"][g, :n]), (g, t)
-        gt = got["pool_tokens"][g, got["pool_slot"][g, :n]]
-        wt = want["pool_tokens"][g, want["pool_slot"][g, :n]]
-        assert (gt == wt).all(), (g, t)
 
 
 def _logits(rng, M, V, W, t, eos, case):
@@ -110,12 +58,10 @@ def test_beam_step_follows_the_rule(W, G, V):
         lt = torch.from_numpy(l).to(DEV).to(dt)
         lw = lt.float().cpu().numpy()                      # (bf16: the widened values the kernel sees)
         want, amb = B.step(S, lw, t, W, lo, hi, eos, pad, alpha)
-        got = _launch(S, lt, t, W, lo, hi, eos, pad, alpha, V)
-        _compare(got, want, amb, W, t)
+        got = _launch(S, lt, t, W, 1, 0.0, lo, hi, eos, pad, alpha, V, plain=True)
+        _compare(got, want, amb, W, 1, t)
         if t == 1:      # the same inputs give the same bits
-            again = _launch(S, lt, t, W, lo, hi, eos, pad, alpha, V)
-            for k in DEV_KEYS + ("next_ids",):
-                assert np.array_equal(got[k].view(np.uint8), again[k].view(np.uint8)), k
+            _bits_equal(got, _launch(S, lt, t, W, 1, 0.0, lo, hi, eos, pad, alpha, V, plain=True))
         n_amb += int(amb.sum())
         n_groups += G
         S = got                                            # the next step starts from the device's state
@@ -127,7 +73,7 @@ def test_beam_step_counter_out_of_range_and_bad_arguments():
     W, G, V, mx = 2, 2, 300, 4
     S = B.new_state(G, W, mx, 0)
     l = torch.randn(G * W, V, device=DEV)
-    got = _launch(S, l, mx, W, 0, V, -1, 7, 1.0, V)
+    got = _launch(S, l, mx, W, 1, 0.0, 0, V, -1, 7, 1.0, V, plain=True)
     assert (got["status"] & 2).all() and (got["next_ids"] == 7).all() and (got["pool_count"] == 0).all()
     D = _upload(S)
     ids = torch.zeros(G * W, dtype=torch.long, device=DEV)

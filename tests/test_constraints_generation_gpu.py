@@ -236,7 +236,7 @@ def test_beam_search_keeps_the_constraints(model):
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_one_constrained_beam_step_equals_the_two_rules(dt):
     from bdm_db1_amd import ops
-    from test_beam_kernels_gpu import _compare, _download, _upload
+    from beam_kernel_common import _compare, _download, _upload
     G, W, V, mx, t, lo, hi, eos, pad = 3, 3, 500, 8, 4, 2, 480, 5, 479
     M = G * W
     rng = np.random.default_rng(9)
@@ -266,7 +266,7 @@ def test_one_constrained_beam_step_equals_the_two_rules(dt):
                   length_penalty=0.8)
     torch.cuda.synchronize()
     assert not amb.all()
-    _compare(_download(D, ids), want, amb, W, t)
+    _compare(_download(D, ids), want, amb, W, 1, t)
 
 
 def test_stream_requests_equal_generate_alone(model):
