@@ -7,7 +7,7 @@ __all__ = ["TransformerXL", "initialize", "mpu", "GraphedMemoryStep", "GraphedRi
            "GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
            "DecodingConstraints", "SamplingParams", "sample_best_of", "ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers", "score_document", "document_segments",
            "generate_stream", "generate_many", "caption_stream", "answer_stream", "question_prompts", "SlotScheduler",
-           "PrefixCache", "Prefixed", "image_prefix", "question_suffixes"]
+           "PrefixCache", "Prefixed", "image_prefix", "question_suffixes", "SpeculativeConfig"]
 
 
 def __getattr__(name):
@@ -27,7 +27,7 @@ def __getattr__(name):
         from .graphed_train import GraphedTrainStep
         return GraphedTrainStep
     if name in ("GenerationConfig", "generate", "generate_captions", "answer_questions", "clip_at_eos", "BeamSearchConfig", "beam_search",
-                "DecodingConstraints", "SamplingParams", "sample_best_of", "PrefixCache", "Prefixed", "image_prefix", "question_suffixes"):
+                "DecodingConstraints", "SamplingParams", "sample_best_of", "PrefixCache", "Prefixed", "image_prefix", "question_suffixes", "SpeculativeConfig"):
         from . import generation
         return getattr(generation, name)
     if name in ("ScoreConfig", "ScoreResult", "score", "validation_report", "rank_candidates", "rank_captions", "rank_answers", "score_document", "document_segments"):

@@ -65,6 +65,11 @@ struct SelArgs {
     int* top_ids;
     float* top_logprob;
     const int* params;          // the per-slot form (PER, db1_select_tokens_slots_per): [n_slots, 8], the record of include/db1_hip.h; NULL otherwise
+    int q_in, Q;                // the verify form (SPEC, db1_spec_pick): positions per row in this launch, row stride of the four arrays below
+    const long long* spec_ids;  // [rows, Q] the step's input ids (column i + 1: the draft for position i), READ only
+    int* spec_sel;              // [rows, Q] the pick of every position (-1: no candidate, -2: skipped)
+    int* spec_hit;              // [rows, Q] 1 where the next column's draft is the pick
+    float* spec_lp;             // [rows, Q] the pick's log-probability (LP); NULL otherwise
 };
 
 // the unused entries [from, top_n) of one (row, t) of the _top buffers: -1 / -inf
@@ -85,9 +90,15 @@ __device__ __forceinline__ void sel_top_fill(const SelArgs& a, int64_t at, int f
 // the slot's own, eight block-uniform words read from params[slot] once the slot is known to be live and its counter in range; a record no
 // launch would have accepted as scalars closes the slot with status bit 2 the way a counter out of range closes it with bit 1.  The other
 // instantiations take the same values from SelArgs and hold no trace of this mode.
-template <typename T, int NG, bool SLOTS, bool LP, bool TOP, bool PER>
+// SPEC (db1_spec_pick; lockstep only, with or without LP): the verify launch of speculative decoding.  Workgroup blockIdx.x looks at
+// position i = blockIdx.x % q_in of row blockIdx.x / q_in, i.e. at token index *t + i, and chooses exactly as the plain form chooses there
+// (the code from the keys to `tok` is shared, the Philox step is step_base + *t + i); it keeps NO books: the owner thread writes the pick,
+// whether the next column's draft equals it and (LP) its log-probability into [row, i] of the scratch arrays and nothing else, so that
+// db1_spec_accept can derive the accepted count from those arrays alone.  The other instantiations hold no trace of this mode either.
+template <typename T, int NG, bool SLOTS, bool LP, bool TOP, bool PER, bool SPEC>
 __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
     static_assert(SLOTS || !PER, "the per-slot parameters belong to the slot form");
+    static_assert(!SPEC || (!SLOTS && !TOP), "the verify form is a lockstep form without alternatives");
     __shared__ SelShared sh;
     const int tid = threadIdx.x;
     int row = blockIdx.x, t;
@@ -130,6 +141,20 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
                 }
                 return;
             }
+        }
+    } else if constexpr (SPEC) {
+        const int i = (int)(blockIdx.x % (unsigned)a.q_in);
+        row = (int)(blockIdx.x / (unsigned)a.q_in);
+        t = *a.t + i;
+        t_ok = true;
+        if (a.finished[row] || t < 0 || t >= a.max_new) {     // (block-uniform) nothing to verify here: SKIP
+            if (tid == 0) {
+                const int64_t at = (int64_t)row * a.Q + i;
+                a.spec_sel[at] = -2;
+                a.spec_hit[at] = 0;
+                if constexpr (LP) a.spec_lp[at] = 0.f;
+            }
+            return;
         }
     } else {
         t = *a.t;
@@ -270,6 +295,17 @@ __global__ __launch_bounds__(SEL_THREADS) void select_tokens_kernel(SelArgs a) {
             if (tid == 0) sel_top_fill(a, at, got);
         }
     }
+    if constexpr (SPEC) {
+        if (tid == 0) {
+            const int i = (int)(blockIdx.x % (unsigned)a.q_in);
+            const int64_t at = (int64_t)row * a.Q + i;
+            const int s = (bits & 1) ? -1 : tok;
+            a.spec_sel[at] = s;
+            a.spec_hit[at] = (i + 1 < a.q_in && a.spec_ids[at + 1] == (long long)s) ? 1 : 0;
+            if constexpr (LP) a.spec_lp[at] = kmax != 0 ? (ldf<T>(lg + tok) - sel_unkey(kmax)) - lz : 0.f;
+        }
+        return;
+    }
     if (tid == 0) {
         int fin = 0;
         if (bits & 1) fin = 1;
@@ -307,11 +343,11 @@ extern "C" int64_t db1_select_tokens_workspace_bytes(int M, int V, int dt) {
     return 0;
 }
 
-template <typename T, bool SLOTS, bool LP, bool TOP, bool PER = false>
+template <typename T, bool SLOTS, bool LP, bool TOP, bool PER = false, bool SPEC = false>
 static void sel_dispatch(int ng, const SelArgs& a, int M, hipStream_t st) {
-    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
-    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
-    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP, TOP, PER><<<M, SEL_THREADS, 0, st>>>(a);
+    if (ng == 1) select_tokens_kernel<T, 1, SLOTS, LP, TOP, PER, SPEC><<<M, SEL_THREADS, 0, st>>>(a);
+    else if (ng == 3) select_tokens_kernel<T, 3, SLOTS, LP, TOP, PER, SPEC><<<M, SEL_THREADS, 0, st>>>(a);
+    else select_tokens_kernel<T, SEL_MAX_NG, SLOTS, LP, TOP, PER, SPEC><<<M, SEL_THREADS, 0, st>>>(a);
 }
 
 // The host side both entry points share: `a` arrives filled; validation (in one order for both, so an argument list that is wrong in two ways
@@ -491,4 +527,43 @@ extern "C" int db1_select_tokens_slots_per(const void* logits, int M, int V, int
     a.t_slot = t; a.limit = limit; a.row_map = row_map; a.n_slots = n_slots; a.logprob = logprob; a.sum_logprob = sum_logprob;
     a.top_n = top_n; a.top_ids = top_ids; a.top_logprob = top_logprob; a.params = params;
     return sel_launch("select_tokens_slots_per", true, lp, top, true, a, M, dt, 1.f, stream);
+}
+
+// ------------------------------------------------------------------ the verify form (speculative decoding, generation.py; csrc/spec.hip)
+#define SPEC_MAX_Q 16
+
+extern "C" int db1_spec_pick_supported(int V, int64_t ld, int dt, int Q) {
+    return db1_select_tokens_supported(V, ld, dt) && Q >= 2 && Q <= SPEC_MAX_Q;
+}
+
+// db1_spec_pick: the SPEC instantiations over M * q_in workgroups (lp == NULL: without the log-prob sweep).  Its refusals are sel_launch's,
+// in sel_launch's order and with its codes, for the arguments the two share; nothing is launched after one.
+extern "C" int db1_spec_pick(const void* logits, int M, int q_in, int Q, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature,
+                             int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int pad_id, int step_base, const int32_t* t,
+                             const int32_t* stream_id, const int32_t* finished, int max_new, const int64_t* ids, int32_t* sel, int32_t* hit,
+                             float* lp, void* stream) {
+    const char* who = "spec_pick";
+    if (!db1_dt_ok(dt)) DB1_FAIL(DB1_ERR_UNSUPPORTED_DTYPE, "%s: dtype %d", who, dt);
+    if (M <= 0 || Q < 2 || Q > SPEC_MAX_Q || q_in < 1 || q_in > Q || (int64_t)M * Q > 65535 || V <= 0 || ld < V || max_new <= 0)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: M=%d q_in=%d Q=%d V=%d ld=%lld max_new=%d (1 <= q_in <= Q, 2 <= Q <= %d, M * Q <= 65535)", who, M, q_in, Q, V,
+                 (long long)ld, max_new, SPEC_MAX_Q);
+    const int ng = sel_ng(V);
+    if (!ng) DB1_FAIL(DB1_ERR_UNSUPPORTED, "%s: V=%d (at most %d)", who, V, SEL_MAX_NG * 4096);
+    if (!logits || !t || !finished || !ids || !sel || !hit) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: null buffer", who);
+    if (vocab_lo < 0 || vocab_hi > V || vocab_lo >= vocab_hi)
+        DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: window [%d, %d) is empty or outside [0, %d)", who, vocab_lo, vocab_hi, V);
+    if (!greedy && !(temperature > 0.f && temperature < INFINITY)) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: temperature %g", who, (double)temperature);
+    if (!greedy && (top_k < 0 || !(top_p > 0.f && top_p <= 1.f))) DB1_FAIL(DB1_ERR_BAD_SHAPE, "%s: top_k %d top_p %g", who, top_k, (double)top_p);
+    SelArgs a = sel_args(logits, V, ld, vocab_lo, vocab_hi, top_k, top_p, greedy, seed_lo, seed_hi, -1, pad_id, step_base, stream_id,
+                         const_cast<int32_t*>(finished), nullptr, nullptr, max_new, nullptr, 0, nullptr);     // (the SPEC code only reads finished)
+    a.inv_t = greedy ? 1.f : 1.f / temperature;
+    a.t = t; a.n_slots = M; a.q_in = q_in; a.Q = Q;
+    a.spec_ids = reinterpret_cast<const long long*>(ids); a.spec_sel = sel; a.spec_hit = hit; a.spec_lp = lp;
+    hipStream_t st = (hipStream_t)stream;
+    DB1_DISPATCH_DT(dt, T, {
+        if (lp) sel_dispatch<T, false, true, false, false, true>(ng, a, M * q_in, st);
+        else sel_dispatch<T, false, false, false, false, true>(ng, a, M * q_in, st);
+    });
+    DB1_CHECK_LAUNCH(who);
+    return DB1_OK;
 }

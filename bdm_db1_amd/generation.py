@@ -21,7 +21,9 @@ rules are stated in include/db1_hip.h and restated in NumPy in tests/select_rule
 ``DecodingConstraints``) either epilogue is preceded by ``db1_constrain_logits``, which edits the step's logits in place over each row's own
 generated tokens (tests/constraint_rule.py; with a frequency / presence penalty or a logit bias ``db1_constrain_logits_pen``,
 tests/penalty_rule.py), and with stop sequences the sampling epilogue is followed by ``db1_stop_match`` (tests/stop_rule.py), which ends a row
-whose tokens spell one and removes them; without, nothing is launched.  scoring.py takes its prefill, its eval-mode switch and its
+whose tokens spell one and removes them; without, nothing is launched.  With ``speculative=`` (a ``SpeculativeConfig``) a token call
+carries 1 + k tokens per row, k of them drafts, and the sampling epilogue is ``db1_spec_pick`` / ``db1_spec_accept`` / ``db1_spec_commit``
+(``_SpecState``, tests/spec_rule.py): the same tokens in fewer calls where the drafts are right.  scoring.py takes its prefill, its eval-mode switch and its
 vocabulary checks from here.
 """
 from __future__ import annotations
@@ -160,6 +162,41 @@ class BeamSearchConfig:
             raise ValueError(f"sync_every {self.sync_every} must be >= 1")
 
 
+@dataclass(frozen=True)
+class SpeculativeConfig:
+    """Speculative decoding for ``generate`` (``speculative=``): every call feeds a row its last token and ``num_draft_tokens`` k guessed
+    next tokens (1 .. 15; Q = 1 + k positions per call) and keeps the model's own choices up to the first wrong guess.  The selection rule is the
+    one-token loop's, greedy or sampled (include/db1_hip.h, db1_spec_pick / _accept / _commit): the results are the same in exact arithmetic
+    and in fp32 up to the order of the GEMMs' sums; in bf16 the wider call's logits differ in their last bits, and a row can part from the
+    one-token loop's at a near tie (``generate`` says more).  The
+    guesses come from an n-gram lookup over the row's history on the device: the longest n-gram, ``ngram_max`` down to ``ngram_min`` (1 .. 8),
+    that ends the history and occurred before, continued from its latest occurrence; ``use_prompt``: the history starts with the prompt's
+    text tokens (``NLPTaskInput`` prompts), not only with the generated ones.  ``draft_script=`` of ``generate`` replaces the lookup."""
+    num_draft_tokens: int = 4
+    ngram_max: int = 3
+    ngram_min: int = 1
+    use_prompt: bool = True
+
+    def __post_init__(self):
+        for name, lo, hi in (("num_draft_tokens", 1, ops.SPEC_MAX_Q - 1), ("ngram_max", 1, ops.SPEC_MAX_NGRAM), ("ngram_min", 1, ops.SPEC_MAX_NGRAM)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise ValueError(f"{name} {v!r} must be an integer in [{lo}, {hi}]")
+            object.__setattr__(self, name, int(v))
+        if self.ngram_min > self.ngram_max:
+            raise ValueError(f"ngram_min {self.ngram_min} exceeds ngram_max {self.ngram_max}")
+        object.__setattr__(self, "use_prompt", bool(self.use_prompt))
+
+
+@dataclass(frozen=True)
+class _SpecPlan:
+    """what a speculative decoding state is built from besides the config: whether the drafts come from a script, and the row stride of the
+    prompt-text buffer (0: none).  The ``speculative`` field of a ``DecodeKey``."""
+    config: SpeculativeConfig
+    scripted: bool
+    ctx_cap: int
+
+
 MAX_BAD_TOKEN_IDS = 1024
 MAX_LOGIT_BIAS = 1024
 MAX_STOP_SEQUENCES, MAX_STOP_LEN = ops.MAX_STOP_SEQUENCES, ops.MAX_STOP_LEN
@@ -296,6 +333,7 @@ class DecodeKey:
     caps: Optional[Tuple[int, int]] = None
     kv_cache = "bf16"        # (no field: the key of the default ring is what it was; ``DecodeKeyFp8`` carries the other value)
     share_prompt = False     # (no field either: ``DecodeKeyShared`` carries the other value)
+    speculative = None       # (nor this: ``DecodeKeySpec`` carries a plan)
 
 
 @dataclass(frozen=True)
@@ -313,6 +351,15 @@ class DecodeKeyShared(DecodeKey):
     ``GroupedRingMemory`` instead of a ``RingMemory``.  A class of its own for the reason ``DecodeKeyFp8`` is one: the default keys compare
     equal to what they were, and a shared generator is never taken for a per-row one.  Created by ``_with_share_prompt`` ONLY."""
     share_prompt: bool = True
+
+
+@dataclass(frozen=True)
+class DecodeKeySpec(DecodeKey):
+    """the key of a speculative ``generate`` (``speculative=``): the ``_SpecPlan`` and the K/V format as the last fields.  A class of its own
+    for the reason ``DecodeKeyFp8`` is one: the default keys keep their fields and compare equal to what they were.  Created by
+    ``_generate_speculative`` ONLY, after ``_with_kv_cache`` has validated the format."""
+    speculative: Optional[_SpecPlan] = None
+    kv_cache: str = "bf16"
 
 
 def clip_at_eos(ids, lengths) -> List[List[int]]:
@@ -718,7 +765,8 @@ def _with_share_prompt(who: str, model, key: DecodeKey, share_prompt: bool, W: i
 # ----------------------------------------------------------------------------------------------------------------------- the device states
 # What ``_decode`` asks of a state: ``M`` rows, ``expand`` (None, or the rows per prompt), ``cache`` (the model attribute its ring generator
 # is kept under), ``start(...)``, ``epilogue(logits_last, next_ids, ring=None)`` -- select, reorder ``ring`` if beams, then t += 1 --,
-# ``reorder_list(mems)``, ``all_done()`` (a host read), ``result()`` and ``stats()``.  The stream (serving.py) asks its ``_SlotState`` for
+# ``reorder_list(mems, old)``, ``all_done()`` (a host read), ``result()`` and ``stats()``; ``width`` (default 1): the tokens per row of a
+# token call -- a wider state's epilogue takes the logits of all positions [M * width, V] and the whole input ids [M, width].  The stream (serving.py) asks its ``_SlotState`` for
 # ``M``, ``expand``, ``cache``, ``start()`` and ``epilogue``.
 _no_launch = lambda *args, **kw: None      # the step of an epilogue that has nothing to do
 
@@ -786,6 +834,7 @@ class _SamplingState:
 class _State(_SamplingState):
     """the device state of one generation: token counter, per-row flags, the output and the stream ids"""
     cache = "_generator"
+    width = 1
 
     def __init__(self, model, key: DecodeKey):
         M = key.rows if key.n is None else key.rows * key.n      # (best-of-n: n rows per prompt)
@@ -819,7 +868,7 @@ class _State(_SamplingState):
         self.stop_match(next_ids)
         self.t.add_(1)
 
-    def reorder_list(self, mems):
+    def reorder_list(self, mems, old=None):
         return mems
 
     def all_done(self) -> bool:
@@ -852,10 +901,88 @@ class _BestOfState(_State):
         return super().result() + (self.status.cpu(),)
 
 
+class _SpecState(_State):
+    """``_State`` for speculative decoding (``SpeculativeConfig``; include/db1_hip.h, db1_spec_pick / _accept / _commit): a token call
+    carries ``width`` Q = 1 + k tokens per row, and the epilogue is the three launches -- pick every position's token, accept the run the
+    drafts allow (the books, the next input ids and the next drafts), commit (``t += n_acc``, the ring's origin back over what was not
+    kept).  The outputs and ``result()`` are ``_State``'s.  Next to its buffers: the scratch ``sel`` / ``hit`` / ``lp`` [M, Q], ``n_acc`` [1],
+    ``hist`` [Q + 1] (steps by accepted count), the prompt's text ``ctx`` [M, ctx_cap] / ``ctx_len`` [M] and the draft ``script`` [M, max_new]."""
+    cache = "_spec_generator"
+
+    def __init__(self, model, key: DecodeKey):
+        super().__init__(model, key)
+        plan, cfg, i32, dev = key.speculative, key.cfg, self.i32, model.dev
+        sc = plan.config
+        self.width = Q = 1 + sc.num_draft_tokens
+        M, mx = self.M, int(cfg.max_new_tokens)
+        self.spec_sel, self.spec_hit = torch.zeros(M, Q, **i32), torch.zeros(M, Q, **i32)
+        self.spec_lp = torch.zeros(M, Q, dtype=torch.float32, device=dev) if cfg.logprobs else None
+        self.n_acc, self.hist = torch.zeros(1, **i32), torch.zeros(Q + 1, **i32)
+        self.ctx = torch.zeros(M, plan.ctx_cap, **i32) if plan.ctx_cap else None
+        self.ctx_len = torch.zeros(M, **i32) if plan.ctx_cap else None
+        self.script = torch.zeros(M, mx, **i32) if plan.scripted else None
+        self._mem_idx = None
+        self._pick = partial(ops.spec_pick, t=self.t, finished=self.finished, sel=self.spec_sel, hit=self.spec_hit, lp=self.spec_lp, max_new=mx,
+                             V=self.V, vocab_lo=cfg.vocab_lo, vocab_hi=key.hi, greedy=cfg.greedy, temperature=cfg.temperature, top_k=cfg.top_k,
+                             top_p=cfg.top_p, seed=cfg.seed, pad_id=cfg.pad_id, stream_id=self.stream_id)
+        self._accept = partial(ops.spec_accept, self.t, self.spec_sel, self.spec_hit, self.finished, self.lengths, self.out, self.status,
+                               n_acc=self.n_acc, V=self.V, eos_id=-1 if cfg.eos_id is None else cfg.eos_id, pad_id=cfg.pad_id, lp=self.spec_lp,
+                               logprob=self.logprob, sum_logprob=self.sum_logprob, ctx=self.ctx, ctx_len=self.ctx_len, script=self.script,
+                               ngram_min=sc.ngram_min, ngram_max=sc.ngram_max)
+
+    def start(self, stream_ids=None, ctx=None, script=None):
+        """``ctx``: the prompt's text tokens (int array [M, L]) or None; ``script``: the draft script (int32 array [M, max_new]) or None"""
+        super().start(stream_ids)
+        self.n_acc.zero_()
+        self.hist.zero_()
+        if self.ctx is not None:
+            self.ctx_len.zero_()
+            if ctx is not None and ctx.shape[1]:
+                self.ctx[:, :ctx.shape[1]].copy_(torch.as_tensor(np.ascontiguousarray(ctx, dtype=np.int32)))
+                self.ctx_len.fill_(int(ctx.shape[1]))
+        if self.script is not None:
+            self.script.copy_(torch.as_tensor(np.ascontiguousarray(script, dtype=np.int32)))
+
+    def epilogue(self, logits2d, ids, ring=None):
+        """``logits2d`` [M * q_in, V]: q_in = 1 after the prefill (token 0: nothing to verify, nothing to take back, not counted), else Q;
+        ``ids`` int64 [M, Q]: the step's input, rewritten for the next one"""
+        q_in = logits2d.shape[0] // self.M
+        self._pick(logits2d, ids=ids, q_in=q_in)
+        self._accept(ids, q_in=q_in)
+        ops.spec_commit(self.t, self.n_acc, q_in=q_in, Q=self.width, hist=self.hist if q_in > 1 else None,
+                        ring_state=None if ring is None else ring.state, cap=0 if ring is None else ring.cap)
+
+    def reorder_list(self, mems, old=None):
+        """the list-form memory after a call of Q tokens of which n_acc were kept: rows [n_acc, n_acc + mem_len) of cat(old[:, :Q], returned)
+        per layer -- the old memory without its n_acc oldest rows, then the kept tokens' hidden states; the index is a device tensor"""
+        Q, mlen = self.width, int(mems[0].shape[1])
+        if self._mem_idx is None or self._mem_idx.numel() != mlen:
+            self._mem_idx = torch.arange(mlen, dtype=torch.long, device=self.dev)
+        idx = self._mem_idx + self.n_acc.long()
+        return [torch.cat([o[:, :Q].to(m.dtype), m], 1).index_select(1, idx) for o, m in zip(old, mems)]
+
+    def all_done(self) -> bool:
+        """also notes ``left``, the tokens still to come, from which ``_decode`` works out its next look"""
+        self.left = int(self.cfg.max_new_tokens) - int(self.t)
+        return self.left <= 0 or bool(self.finished.all())
+
+    def result(self):
+        if (self.status.cpu() & 2).any():
+            raise RuntimeError("db1_spec_accept: the token counter left [0, max_new_tokens]")
+        return super().result()
+
+    def stats(self) -> dict:
+        """``accepted``: per accepted count 0 .. Q the number of token calls that committed that many tokens; ``tokens_per_call``"""
+        hist = [int(v) for v in self.hist.cpu()]
+        calls = sum(hist)
+        return dict(super().stats(), accepted=hist, tokens_per_call=(sum(i * n for i, n in enumerate(hist)) / calls) if calls else 0.0)
+
+
 class _BeamState:
     """the device state of one beam search over G prompts of W beams (include/db1_hip.h, db1_beam_step); with ``cfg.num_beam_groups`` D > 1
     the state of G * D sub-groups of W / D beams, stepped by db1_beam_step_diverse"""
     cache = "_beam_generator"
+    width = 1
 
     def __init__(self, model, key: DecodeKey):
         G, cfg, V, hi, dev = key.rows, key.cfg, key.V, key.hi, model.dev
@@ -908,7 +1035,7 @@ class _BeamState:
             ring.reorder(self.parent, self.t, max_t=self.cfg.max_new_tokens, group=self.Wg, done=self.done)
         self.t.add_(1)
 
-    def reorder_list(self, mems):
+    def reorder_list(self, mems, old=None):
         parent = self.parent.long()
         return [m.index_select(0, parent) for m in mems]
 
@@ -968,10 +1095,14 @@ class _RingGenerator:
             self.ring = GroupedRingMemory(model, key.rows, state.expand, key.cfg.max_new_tokens)
         else:
             self.ring = RingMemory(model, state.M, kv_dtype=key.kv_cache)
-        self.step = GraphedRingStep(model, state.M, 1, memory=self.ring, epilogue=self.epilogue)
+        self.q = int(getattr(state, "width", 1))     # the tokens per row of a token call (a speculative state: 1 + its draft tokens)
+        self.step = GraphedRingStep(model, state.M, self.q, memory=self.ring, epilogue=self.epilogue)
 
     def epilogue(self, step, logits):
-        self.state.epilogue(logits[:, -1], step.ids[:, 0], self.ring)
+        if self.q == 1:
+            self.state.epilogue(logits[:, -1], step.ids[:, 0], self.ring)
+        else:       # every position's logits [M * q, V] (a view: the rows keep their padded stride) and the whole input ids
+            self.state.epilogue(logits.view(self.state.M * self.q, logits.shape[-1]), step.ids, self.ring)
 
     def token(self, replay: bool):
         """one token step on the ids the last one left in ``step.ids``: a graph replay, or the same forward and epilogue launched eagerly over
@@ -1013,7 +1144,8 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
             st, ids = gen.state, gen.step.ids
         else:
             st = State(model, key)
-            ids = torch.zeros(st.M, 1, dtype=torch.long, device=model.dev)
+            ids = torch.zeros(st.M, st.width, dtype=torch.long, device=model.dev)
+        wide = st.width > 1
         st.start(*start)
         # prefill: the whole prompt through the list-form memory path; its last position (expanded like the memory) picks token 0
         direct = ring and (_use_ring_prefill(model) or isinstance(prompt, Prefixed))
@@ -1029,21 +1161,32 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
         else:
             logits, mems = _prefill(model, prompt, key.rows, None if shared else st.expand)
         last = logits[:, -1]
-        st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids[:, 0])
+        st.epilogue(last if st.expand is None else last.repeat_interleave(st.expand, 0), ids if wide else ids[:, 0])
         del logits, last
         calls = 0
         if ring and not direct:
             dst.load(mems)
             del mems
+        # (a wide state may reach the end in fewer calls, and a call past the end is a whole forward that commits nothing: the host also
+        #  looks after the fewest calls that can get there, and from the counter it reads then, after the fewest that can get there now)
+        look = -(-(st.cfg.max_new_tokens - 1) // st.width)
         for i in range(1, st.cfg.max_new_tokens):
-            if i % st.cfg.sync_every == 0 and st.all_done():
-                break
+            if i % st.cfg.sync_every == 0 or (wide and i - 1 >= look):
+                if st.all_done():
+                    break
+                if wide:
+                    look = i - 1 + max(1, -(-st.left // st.width))
             if ring:
                 gen.token(replay)
             else:
+                old = mems
                 logits, _, mems = model([_token_input(ids)], compute_loss=False, mems=mems)
-                st.epilogue(logits[:, -1], ids[:, 0])
-                mems = st.reorder_list(mems)
+                if wide:
+                    st.epilogue(logits.view(st.M * st.width, logits.shape[-1]), ids)
+                else:
+                    st.epilogue(logits[:, -1], ids[:, 0])
+                mems = st.reorder_list(mems, old)
+                del old
             calls += 1
         if ring:
             gen.check(replay)
@@ -1061,7 +1204,8 @@ def _decode(model, prompt, State, key, graphed: Optional[bool], replay: bool, st
 @torch.no_grad()
 def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_ids=None, graphed: Optional[bool] = None,
              stats: Optional[dict] = None, replay: bool = True,
-             constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16"):
+             constraints: Optional[DecodingConstraints] = None, kv_cache: str = "bf16",
+             speculative: Optional[SpeculativeConfig] = None, draft_script=None):
     """Generate ``config.max_new_tokens`` tokens after ``prompt`` -- ONE ``NLPTaskInput`` / ``ICTaskInput`` / ``VQATaskInput`` batch of M rows
     of one shape -> (ids int32 [M, max_new_tokens], lengths int32 [M]) on the host.  ``ids[r, :lengths[r]]`` are the tokens before EOS;
     after EOS a row holds ``pad_id``.  ``stream_ids`` (M ints, default 0 .. M-1): the Philox stream of every row -- a row's draws depend only
@@ -1082,8 +1226,21 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     the memory's keys / values are held as e4m3 with a power-of-two scale per (row, position, K or V, head) -- half the bytes per token
     step and per slot, results within the e4m3 rounding of the keys / values; "bf16" (default): everything is what it is without it.
     ``prompt`` may also be a ``Prefixed`` (``PrefixCache``): its rows continue cached prefixes, only the suffix is projected; ring path
-    only, with the cache's own ``kv_cache`` (ValueError otherwise, before anything is launched)."""
+    only, with the cache's own ``kv_cache`` (ValueError otherwise, before anything is launched).  ``speculative`` (a
+    ``SpeculativeConfig``): every token call carries 1 + k tokens per row, k of them drafts that the call itself verifies on the device; what
+    comes back follows the same rule as without the keyword, token by token, in fewer calls where the drafts are right: in exact arithmetic the
+    same ids, lengths and log-probs; in fp32 the same up to the order of the GEMMs' sums; in bf16 the logits of a (1 + k)-token call differ
+    from the one-token call's in their last bits (other launches, other partial sums), so where two logits are nearly tied a token, and with
+    it the rest of that row, can differ -- as between graphed and eager list-form generation.  ``stats`` also receives
+    ``accepted`` (int list [k + 2]: the token calls that committed 0 .. k + 1 tokens, counted on the device) and ``tokens_per_call``.  The
+    drafts: an n-gram lookup over the prompt's text and the row's output, or ``draft_script`` (an int array [M, max_new_tokens]: the proposal
+    for every token index; what a draft model would supply).  Not with constraints, ``top_logprobs`` or more than 64 / (k + 1) rows
+    (ValueError).  None (default): every launch, graph and cached generator is what it is without the keyword."""
     cfg = config or GenerationConfig()
+    if speculative is None and draft_script is not None:
+        raise ValueError("generate: draft_script needs speculative= (a SpeculativeConfig)")
+    if speculative is not None:
+        return _generate_speculative(model, prompt, cfg, speculative, draft_script, stream_ids, graphed, stats, replay, constraints, kv_cache)
     _need_memory(model, "generate")
     M = _batch_size(prompt, prefixed_ok=True)
     _check_prompt("generate", model, prompt, kv_cache, graphed)
@@ -1095,7 +1252,72 @@ def generate(model, prompt, config: Optional[GenerationConfig] = None, stream_id
     return _decode(model, prompt, _State, key, graphed, replay, stats, start=(stream_ids,))
 
 
+def _prompt_text(prompt, M: int) -> Optional[np.ndarray]:
+    """the text tokens of an ``NLPTaskInput`` prompt batch as int64 [M, L] on the host (any other prompt: None)"""
+    from .data import NLPTaskInput
+    if isinstance(prompt, Prefixed) or not isinstance(prompt, NLPTaskInput):
+        return None
+    seq = prompt.text_seq
+    arr = np.asarray(seq.cpu() if torch.is_tensor(seq) else seq).astype(np.int64)
+    return arr.reshape(M, -1)
+
+
+def _generate_speculative(model, prompt, cfg, spec, draft_script, stream_ids, graphed, stats, replay, constraints, kv_cache):
+    """``generate`` with ``speculative=``: every refusal first (ValueError before any launch), then ``_decode`` over a ``_SpecState``"""
+    who = "generate(speculative=)"
+    if not isinstance(spec, SpeculativeConfig):
+        raise ValueError(f"{who}: a SpeculativeConfig expected, got {type(spec).__name__}")
+    if not isinstance(cfg, GenerationConfig):
+        raise ValueError(f"{who}: a GenerationConfig expected, got {type(cfg).__name__} (beam search has no speculative form)")
+    if constraints is not None:
+        raise ValueError(f"{who}: constraints and stop sequences are not supported (their history would have to include the drafts)")
+    if cfg.top_logprobs:
+        raise ValueError(f"{who}: top_logprobs is not supported")
+    mlen = _need_memory(model, "generate")
+    M = _batch_size(prompt, prefixed_ok=True)
+    Q, mx = 1 + spec.num_draft_tokens, int(cfg.max_new_tokens)
+    if M * Q > 64:
+        raise ValueError(f"{who}: {M} rows of {Q} tokens per call ({M * Q} > 64, where the fused decode path of a token call ends)")
+    if Q > mlen:
+        raise ValueError(f"{who}: {Q} tokens per call exceed the model's mem_len {mlen}")
+    text = _prompt_text(prompt, M) if spec.use_prompt else None
+    if mx > ops.SPEC_MAX_HIST or (text is not None and text.shape[1] + mx > ops.SPEC_MAX_HIST):
+        raise ValueError(f"{who}: the prompt's text ({0 if text is None else text.shape[1]} tokens) plus max_new_tokens {mx} exceeds "
+                         f"{ops.SPEC_MAX_HIST}, the history a row's draft lookup can hold")
+    script = None
+    if draft_script is not None:
+        script = draft_script.cpu().numpy() if torch.is_tensor(draft_script) else np.asarray(draft_script)
+        if script.shape != (M, mx) or script.dtype.kind not in "iu":
+            raise ValueError(f"{who}: draft_script must be an integer array of shape [{M}, {mx}] (got {script.dtype} {tuple(script.shape)})")
+        script = np.clip(script.astype(np.int64), -1, 2 ** 31 - 1).astype(np.int32)     # (a value outside [0, V) is no proposal)
+    _check_prompt("generate", model, prompt, kv_cache, graphed)
+    V, hi = _vocab_window(model, cfg)
+    _with_kv_cache("generate", model, DecodeKey(rows=M, cfg=cfg, V=V, hi=hi), kv_cache, graphed)     # (its refusals; the key below names the format)
+    ctx_cap = (ops.SPEC_MAX_HIST - mx) if spec.use_prompt else 0
+    ring = _ring_ok(model) if graphed is None else bool(graphed)
+    cap = mlen + 64 if ring else 1
+    if not ops.spec_supported(V, V, model.compute_dtype, Q, ctx_cap, mx, spec.ngram_min, spec.ngram_max, cap):
+        raise ValueError(f"{who}: db1_spec_pick / db1_spec_accept do not support a vocabulary of {V} with {Q} tokens per call")
+    if ring and _ring_ok(model):
+        ok = (ops.relattn_decode_ring_kv8_supported(M, Q, mlen + Q, model.n_head, model.d_head) if kv_cache == "fp8" else
+              ops.relattn_decode_supported(M, Q, mlen + Q, model.n_head, model.d_head, model.compute_dtype))
+        if not ok:
+            raise ValueError(f"{who}: the ring attention does not support {Q} tokens per call over mem_len {mlen} (kv_cache={kv_cache!r})")
+    key = DecodeKeySpec(rows=M, cfg=cfg, V=V, hi=hi, speculative=_SpecPlan(config=spec, scripted=script is not None, ctx_cap=ctx_cap),
+                        kv_cache=kv_cache)
+    return _decode(model, prompt, _SpecState, key, graphed, replay, stats, start=(stream_ids, text, script))
+
+
 def _run(model, x, cfg, n=None, **kw):
+    for name in ("speculative", "draft_script"):      # (None is the call without the keyword, whichever function it goes to)
+        if name in kw and kw[name] is None:
+            del kw[name]
+    if kw.get("speculative") is not None and (isinstance(cfg, BeamSearchConfig) or n is not None):
+        raise ValueError("speculative= applies to generate under a GenerationConfig (not to beam search or best-of-n sampling)")
+    if kw.get("speculative") is not None and kw.get("share_prompt"):
+        raise ValueError("speculative= does not take share_prompt (a grouped memory has one token per call)")
+    if kw.get("speculative") is not None:
+        kw.pop("share_prompt", None)
     if isinstance(cfg, BeamSearchConfig):
         if n is not None:
             raise ValueError("n= (best-of-n sampling) takes a GenerationConfig, not a BeamSearchConfig")

@@ -1051,6 +1051,141 @@ def stop_match_per(stop_tok, stop_len, lengths, checked, finished, stop_hit, out
                 sum_logprob, top_n, top_ids, top_logprob)
 
 
+SPEC_MAX_Q = 16           # 1 + the most draft tokens of a speculative step (db1_spec_pick)
+SPEC_MAX_HIST = 4096      # the prompt text + max_new tokens a row's draft lookup can stage (db1_spec_accept)
+SPEC_MAX_NGRAM = 8
+
+
+def _check_spec_width(who, M, q_in, Q):
+    """the widths every speculative launch shares (pure Python: nothing is loaded): 2 <= Q <= 16, 1 <= q_in <= Q, M * Q <= 65535"""
+    for name, v in (("Q", Q), ("q_in", q_in)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{who}: {name} {v!r} must be an integer")
+    if not 2 <= int(Q) <= SPEC_MAX_Q:
+        raise ValueError(f"{who}: Q {Q} must lie in [2, {SPEC_MAX_Q}] (1 + the number of draft tokens)")
+    if not 1 <= int(q_in) <= int(Q):
+        raise ValueError(f"{who}: q_in {q_in} must lie in [1, Q = {Q}]")
+    if not 1 <= int(M) or int(M) * int(Q) > 65535:
+        raise ValueError(f"{who}: {M} rows of Q = {Q} positions (1 <= M, M * Q <= 65535)")
+
+
+def spec_supported(V: int, ld: int, dtype, Q: int, ctx_cap: int, max_new: int, ngram_min: int = 1, ngram_max: int = 3, cap: int = 1) -> bool:
+    """whether the three launches of a speculative step (db1_spec_pick / _accept / _commit) take these sizes"""
+    L = lib.load()
+    return bool(L.db1_spec_pick_supported(int(V), int(ld), dt_code(dtype), int(Q)) and
+                L.db1_spec_accept_supported(int(Q), int(ctx_cap), int(max_new), int(ngram_min), int(ngram_max)) and
+                L.db1_spec_commit_supported(int(Q), int(cap)))
+
+
+def spec_pick(logits2d, t, finished, ids, sel, hit, *, q_in, V=None, vocab_lo=0, vocab_hi=None, greedy=True, temperature=1.0, top_k=0, top_p=1.0,
+              seed=0, pad_id=0, step_base=0, stream_id=None, lp=None, max_new):
+    """launch 1 of a speculative step (db1_spec_pick, rule in include/db1_hip.h): for row r and position i < ``q_in``, logits row r * q_in + i
+    of ``logits2d`` [M * q_in, ld], the token ``select_tokens`` would pick at token index ``t`` + i goes to ``sel`` [M, Q] (int32; -1: no
+    candidate, -2: the row is finished or the index is past ``max_new``), ``hit`` [M, Q] says whether column i + 1 of ``ids`` (int64 [M, Q],
+    contiguous; READ only) holds that token, and ``lp`` (float32 [M, Q], optional) receives its log-probability.  ``t`` int32 [1] and
+    ``finished`` int32 [M] are only read.  Capturable; raises ValueError on bad arguments before the library is loaded."""
+    who, dev = "spec_pick", logits2d.device
+    if not torch.is_tensor(ids) or ids.dim() != 2:
+        raise ValueError(f"{who}: ids must be a contiguous {torch.int64} tensor of shape (rows, Q)")
+    M, Q = int(ids.shape[0]), int(ids.shape[1])
+    _check_spec_width(who, M, q_in, Q)
+    q_in = int(q_in)
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1 or logits2d.shape[0] != M * q_in:
+        raise ValueError(f"{who}: logits must be a 2-D tensor of {M} * {q_in} rows with unit column stride")
+    if logits2d.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{who}: logits dtype {logits2d.dtype} (float32 / bfloat16)")
+    if int(max_new) < 1:
+        raise ValueError(f"{who}: max_new {max_new} must be >= 1")
+    ld = logits2d.stride(0)
+    V = logits2d.shape[1] if V is None else int(V)
+    if not 0 < V <= logits2d.shape[1]:
+        raise ValueError(f"{who}: V={V} for logits of shape {tuple(logits2d.shape)}")
+    vocab_lo, vocab_hi = _check_window(who, V, vocab_lo, vocab_hi)
+    _check_sampling(who, greedy, temperature, top_k, top_p)
+    _check_tensor(who, "ids", ids, torch.int64, (M, Q), dev)
+    _check_vectors(who, dev, M, finished=finished)
+    _check_vectors(who, dev, 1, t=t)
+    _check_vectors(who, dev, M, optional=("stream_id",), stream_id=stream_id)
+    _check_tensor(who, "sel", sel, torch.int32, (M, Q), dev)
+    _check_tensor(who, "hit", hit, torch.int32, (M, Q), dev)
+    if lp is not None:
+        _check_tensor(who, "lp", lp, torch.float32, (M, Q), dev)
+    if not lib.load().db1_spec_pick_supported(V, max(ld, V), dt_code(logits2d), Q):
+        raise ValueError(f"{who}: V={V} unsupported for logits of shape {tuple(logits2d.shape)}, row stride {ld}")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lib.call("db1_spec_pick", P(logits2d), M, q_in, Q, V, max(ld, V), dt_code(logits2d), vocab_lo, vocab_hi, float(temperature), int(top_k),
+             float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(pad_id), int(step_base), P(t), P(stream_id), P(finished),
+             int(max_new), P(ids), P(sel), P(hit), P(lp), stream())
+
+
+def spec_accept(t, sel, hit, finished, lengths, out, status, ids, n_acc, *, q_in, V, eos_id=-1, pad_id=0, lp=None, logprob=None, sum_logprob=None,
+                ctx=None, ctx_len=None, script=None, ngram_min=1, ngram_max=3):
+    """launch 2 of a speculative step (db1_spec_accept): from ``sel`` / ``hit`` [M, Q] the accepted count goes to ``n_acc`` (int32 [1]), every
+    row commits that many tokens into ``out`` [M, max_new] at column ``t`` on (``lengths`` / ``finished`` / ``status`` int32 [M] and, with
+    ``lp`` [M, Q], ``logprob`` [M, max_new] / ``sum_logprob`` [M] updated), its last token goes to column 0 of ``ids`` (int64 [M, Q]) and the
+    next Q - 1 drafts to the other columns: from ``script`` (int32 [M, max_new]) if given, else by n-gram lookup (``ngram_max`` down to
+    ``ngram_min``) over ``ctx`` (int32 [M, ctx_cap], ``ctx_len`` int32 [M]; both or neither) followed by the row's output.  ``t`` is only read.
+    Capturable; raises ValueError on bad arguments before the library is loaded."""
+    who = "spec_accept"
+    i32 = torch.int32
+    if not torch.is_tensor(ids) or ids.dim() != 2:
+        raise ValueError(f"{who}: ids must be a contiguous {torch.int64} tensor of shape (rows, Q)")
+    if not torch.is_tensor(out) or out.dim() != 2:
+        raise ValueError(f"{who}: out must be a contiguous {i32} tensor of shape (rows, max_new)")
+    dev, (M, Q), mx = out.device, (int(ids.shape[0]), int(ids.shape[1])), int(out.shape[1])
+    _check_spec_width(who, M, q_in, Q)
+    for name, v in (("ngram_min", ngram_min), ("ngram_max", ngram_max)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= SPEC_MAX_NGRAM:
+            raise ValueError(f"{who}: {name} {v!r} must be an integer in [1, {SPEC_MAX_NGRAM}]")
+    if int(ngram_min) > int(ngram_max):
+        raise ValueError(f"{who}: ngram_min {ngram_min} exceeds ngram_max {ngram_max}")
+    if int(V) < 1 or mx < 1:
+        raise ValueError(f"{who}: V={V}, max_new={mx}")
+    if (ctx is None) != (ctx_len is None):
+        raise ValueError(f"{who}: ctx and ctx_len go together (one of them is None)")
+    ctx_cap = 0
+    if ctx is not None:
+        if not torch.is_tensor(ctx) or ctx.dim() != 2 or ctx.shape[1] < 1:
+            raise ValueError(f"{who}: ctx must be a contiguous {i32} tensor of shape (rows, ctx_cap >= 1)")
+        ctx_cap = int(ctx.shape[1])
+    if ctx_cap + mx > SPEC_MAX_HIST:
+        raise ValueError(f"{who}: ctx_cap {ctx_cap} + max_new {mx} exceeds {SPEC_MAX_HIST}, the history a row's lookup can stage")
+    if (lp is None) != (logprob is None) or (logprob is None) != (sum_logprob is None):
+        raise ValueError(f"{who}: lp, logprob and sum_logprob go together (all or none)")
+    _check_tensor(who, "ids", ids, torch.int64, (M, Q), dev)
+    _check_tensor(who, "out", out, i32, (M, mx), dev)
+    _check_tensor(who, "sel", sel, i32, (M, Q), dev)
+    _check_tensor(who, "hit", hit, i32, (M, Q), dev)
+    _check_vectors(who, dev, M, finished=finished, lengths=lengths, status=status)
+    _check_vectors(who, dev, 1, t=t, n_acc=n_acc)
+    if lp is not None:
+        _check_tensor(who, "lp", lp, torch.float32, (M, Q), dev)
+        _check_logprobs(who, logprob, sum_logprob, M, mx, dev)
+    if ctx is not None:
+        _check_tensor(who, "ctx", ctx, i32, (M, ctx_cap), dev)
+        _check_vectors(who, dev, M, ctx_len=ctx_len)
+    if script is not None:
+        _check_tensor(who, "script", script, i32, (M, mx), dev)
+    lib.call("db1_spec_accept", M, int(q_in), Q, int(eos_id), int(pad_id), int(V), mx, P(t), P(sel), P(hit), P(lp), P(finished), P(lengths), P(out),
+             P(status), P(logprob), P(sum_logprob), P(ids), P(ctx), P(ctx_len), ctx_cap, P(script), int(ngram_min), int(ngram_max), P(n_acc), stream())
+
+
+def spec_commit(t, n_acc, *, q_in, Q, hist=None, ring_state=None, cap=0):
+    """launch 3 of a speculative step (db1_spec_commit, one thread): ``t`` += ``n_acc`` (both int32 [1]); ``ring_state`` (int32 [1], optional)
+    goes back by the ``q_in`` - n_acc positions that were not kept, modulo ``cap``; ``hist`` (int32 [Q + 1], optional) counts the step under
+    its accepted count.  Capturable; raises ValueError on bad arguments before the library is loaded."""
+    who, dev = "spec_commit", t.device
+    _check_spec_width(who, 1, q_in, Q)
+    _check_vectors(who, dev, 1, t=t, n_acc=n_acc)
+    if hist is not None:
+        _check_tensor(who, "hist", hist, torch.int32, (int(Q) + 1,), dev)
+    if ring_state is not None:
+        _check_vectors(who, dev, 1, ring_state=ring_state)
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or int(cap) <= 0 or int(cap) < int(q_in):
+            raise ValueError(f"{who}: cap {cap!r} must be a positive integer, at least q_in = {q_in}")
+    lib.call("db1_spec_commit", P(t), P(n_acc), P(hist), int(q_in), int(Q), P(ring_state), int(cap), stream())
+
+
 def beam_step_supported(V: int, ld: int, W: int, dtype) -> bool:
     return bool(lib.load().db1_beam_step_supported(int(V), int(ld), int(W), dt_code(dtype)))
 

@@ -1046,6 +1046,56 @@ int db1_stop_match_per(const int32_t* stop_tok, const int32_t* stop_len, int pad
                        int32_t* stop_hit, int32_t* out, int max_new, int64_t* next_ids, int64_t ids_stride, const int32_t* row_map, int M,
                        int n_slots, float* logprob, float* sum_logprob, int top_n, int32_t* top_ids, float* top_logprob, void* stream);
 
+/* ------------------------------------------------------------------ speculative decoding (tests/spec_rule.py restates the rule in NumPy).
+ * A one-token call streams every weight once; a call of Q = 1 + k tokens costs little more.  So a step feeds every row its last emitted token
+ * and k GUESSED next tokens, and keeps as many of the model's own choices as the guesses allow.  The choice at a position is a pure function
+ * of (that position's logits, stream id, seed, token index) -- db1_select_tokens' rule -- and under same_length attention a q-token call
+ * over the ring equals q one-token calls, so the tokens that come out are exactly those of the one-token loop, sampled or greedy: a guess
+ * is kept only if it IS the token the selection picks.  No rejection sampling.
+ * State: t [1], finished / lengths / status [M], out [M, max_new] and optionally logprob [M, max_new] / sum_logprob [M], as db1_select_tokens
+ * has them; ids int64 [M, Q], the step's input (column 0: the last emitted token, not yet in the ring; column 1 + j: the guess for token
+ * index t + j); scratch sel, hit int32 [M, Q], lp float [M, Q], n_acc int32 [1], hist int32 [Q + 1].  A step verifies q_in positions
+ * (1 <= q_in <= Q) over logits [M * q_in, ld], row r's position i at logits row r * q_in + i, in three launches:
+ *   1. db1_spec_pick, M * q_in workgroups.  Token index tau = *t + i.  sel[r, i] = SKIP (-2) if finished[r] or tau outside [0, max_new);
+ *      NONE (-1) if the window holds no finite logit; else the token db1_select_tokens picks from that logits row with the Philox counter
+ *      (col / 4, stream_id[r] (NULL: r), step_base + tau, 0xE0000100).  hit[r, i] = 1 iff i + 1 < q_in and ids[r, i + 1] == sel[r, i], else
+ *      0.  With lp: lp[r, i] = the _lp rule's value for the pick, 0 for NONE and SKIP.  The launch writes nothing else and only reads ids.
+ *   2. db1_spec_accept, one workgroup per row.  *t outside [0, max_new]: status[r] |= 2 on every row, n_acc = 0, nothing else.
+ *      *t == max_new: n_acc = 0 and nothing else (no status bit: the host may replay past the end until its next look).  Otherwise a row
+ *      is LIVE iff sel[r, 0] != SKIP.  A live row walks i = 0, 1, ...; it emits position i and stops after it if sel[r, i] is NONE or
+ *      eos_id (the row ends), tau + 1 == max_new, i == q_in - 1, or hit[r, i] == 0; a_row = its emissions.  n_acc = the minimum of a_row
+ *      over the live rows, 0 if there is none.  Every live row commits exactly its first n_acc emissions (there is one t and one ring
+ *      origin, so the rows are cut to the shortest).  Per emission i: out[r, t + i] = sel[r, i] (pad_id for NONE); lengths[r] += 1 unless EOS
+ *      or NONE; logprob[r, t + i] = lp[r, i] and sum_logprob[r] += lp[r, i], one fp32 add per token in token order (NONE: 0 and no add);
+ *      finished[r] = 1 on EOS or NONE; status[r] |= 1 on NONE.  A row that was not live writes pad_id (and 0) at the n_acc positions.
+ *      n_acc > 0: ids[r, 0] = the last committed token, pad_id if the row is finished by now.  Then the k guesses with t' = t + n_acc over
+ *      the history h = cat(ctx[r, :ctx_len[r]], out[r, :t']) of n tokens (ctx int32 [M, ctx_cap], ctx_len clamped to [0, ctx_cap]; NULL: none;
+ *      ctx_cap + max_new <= 4096):  a finished row, or n == 0: ids[r, 1 + j] = pad_id.  script (int32 [M, max_new]) non-NULL: d_j =
+ *      script[r, t' + j] if t' + j < max_new and the value lies in [0, V), else h[n - 1].  Else the n-gram lookup: for g = ngram_max down to
+ *      ngram_min with n > g, the largest p <= n - g - 1 with h[p .. p + g) == h[n - g .. n); the first g with such a p wins and d_j =
+ *      h[p + g + (j mod L)], L = n - (p + g) (a loop goes on periodically); no match at any g: d_j = h[n - 1].  ids[r, 1 + j] = d_j, j < k.
+ *   3. db1_spec_commit, one thread: *t += n_acc; *ring_state = (*ring_state + cap - (q_in - n_acc)) % cap where ring_state is given (the
+ *      forward has advanced the origin by q_in with db1_ring_advance; the keys of the positions that were not kept fall outside the
+ *      window and are overwritten by the next call); hist[n_acc] += 1 where hist is given.
+ * The pick of token 0 after a prefill is the same three launches with q_in = 1 (nothing to verify, no ring_state, no hist).
+ * Every workgroup of launch 2 derives n_acc from sel, hit and *t only, which no workgroup of that launch writes: no atomics, no
+ * communication between workgroups, fixed-order reductions -- two runs give the same bits; nothing is read back: capturable.
+ * DB1_ERR_BAD_SHAPE before any launch: a NULL required buffer, q_in outside 1 .. Q, Q outside 2 .. 16, M * Q > 65535, an empty window, lp /
+ * logprob / sum_logprob not all or none, ctx without ctx_len, an n-gram range outside 1 <= min <= max <= 8, cap <= 0 with a ring_state;
+ * DB1_ERR_UNSUPPORTED: V above db1_select_tokens' limit, ctx_cap + max_new > 4096. */
+int db1_spec_pick_supported(int V, int64_t ld, int dt, int Q);
+int db1_spec_pick(const void* logits, int M, int q_in, int Q, int V, int64_t ld, int dt, int vocab_lo, int vocab_hi, float temperature, int top_k,
+                  float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int pad_id, int step_base, const int32_t* t,
+                  const int32_t* stream_id, const int32_t* finished, int max_new, const int64_t* ids, int32_t* sel, int32_t* hit, float* lp,
+                  void* stream);
+int db1_spec_accept_supported(int Q, int ctx_cap, int max_new, int ngram_min, int ngram_max);
+int db1_spec_accept(int M, int q_in, int Q, int eos_id, int pad_id, int V, int max_new, const int32_t* t, const int32_t* sel,
+                    const int32_t* hit, const float* lp, int32_t* finished, int32_t* lengths, int32_t* out, int32_t* status, float* logprob,
+                    float* sum_logprob, int64_t* ids, const int32_t* ctx, const int32_t* ctx_len, int ctx_cap, const int32_t* script,
+                    int ngram_min, int ngram_max, int32_t* n_acc, void* stream);
+int db1_spec_commit_supported(int Q, int cap);
+int db1_spec_commit(int32_t* t, const int32_t* n_acc, int32_t* hist, int q_in, int Q, int32_t* ring_state, int cap, void* stream);
+
 /* ------------------------------------------------------------------ scoring given text (tests/score_rule.py restates the rule in NumPy).
  * For a row of logits l[0 .. V) (fp32 / bf16 read as stored and widened to fp32; columns >= V are padding), a label y and a window
  * [vocab_lo, vocab_hi) with 0 <= vocab_lo < vocab_hi <= V:

@@ -144,7 +144,23 @@ the weight (600 MB of bf16 copies: more bytes than the last-level cache holds, a
 time without the host's launch cost; device time per launch from events over 5 replays, the median of 7 rounds with min .. max, the bytes of W a launch
 streams and the rate they amount to.
 
-    python tools/bench_generate.py --w8-kernels [M ...]"""
+    python tools/bench_generate.py --w8-kernels [M ...]
+
+--speculative K [--draft-script perfect|wrong] [--text-prompt] [M ...] (default M = 1 4): ``generate(..., speculative=SpeculativeConfig(
+num_draft_tokens=K))`` against plain ``generate`` on the same prompt in ONE process, greedy, ms per generated token by the difference
+method of the default mode (30 tokens minus 10); every line carries "speculative", the draft source, the accepted histogram and the
+tokens per call of the 30-token run.  Drafts: the n-gram lookup (default), the tokens of a speculative run that never accepts (perfect: the
+ceiling) or an id outside the window (wrong: the cost of never accepting).  The prompt: the caption prompt, or with --text-prompt 64 text tokens that repeat an
+8-token pattern.
+
+    python tools/bench_generate.py --speculative 4 [--draft-script perfect|wrong] [--text-prompt] [M ...]
+
+--spec-replay [B:n ...] (default 1:1 1:2 1:5 1:8 4:5): the bare ``GraphedRingStep`` replay of a call of n new tokens for B rows, ms per call.
+--spec-logits: the same 22 tokens through the ring one per call, five per call, and five per call behind a first call of two: the largest
+and the root-mean-square distance between the three paths' text-window logits relative to the largest logit, the relative gap between a
+position's two largest logits, and how many positions' arg-max agree; each path also against an fp32 model on the same parameters.
+--spec-kernels [rows ...] (default 5 64): db1_spec_pick / db1_spec_accept / db1_spec_commit at V = 33 025 over that many logits rows (Q = 5 for
+5 rows, 16 otherwise) and db1_select_tokens over the same number of rows, device time from events, the median of 7 rounds."""
 import dataclasses
 import json
 import os
@@ -192,6 +208,157 @@ def gen_ms_per_token(M, cfg, short=10, **kw):
     full = best(cfg)
     part = best(dataclasses.replace(cfg, max_new_tokens=short))
     return (full - part) / (N_NEW - short) * 1e3
+
+
+def text_batch(M, n=64, period=8):
+    rng = np.random.default_rng(100 + M)
+    pat = rng.integers(0, 32000, (M, period))
+    return NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None,
+                        text_seq=torch.from_numpy(np.tile(pat, (1, n // period))).to(dev), text_len=None)
+
+
+def spec_main(K, script_mode, Ms, text):
+    from bdm_db1_amd import SpeculativeConfig, generate
+    from bdm_db1_amd.generation import _text_window, caption_prompt
+    sc = SpeculativeConfig(num_draft_tokens=K)
+    for M in Ms:
+        x = text_batch(M) if text else caption_prompt(batch(M))
+        cfg = _text_window(model, GenerationConfig(max_new_tokens=N_NEW))
+        short = dataclasses.replace(cfg, max_new_tokens=10)
+        plain_ids = generate(model, x, cfg)[0].numpy()
+        wrong = np.full((M, N_NEW), int(model.text_vocab_size), np.int32)
+        # perfect: the tokens of the Q-token call itself, from a run that never accepts (on random weights the logits are near ties, and
+        # the bf16 rounding of the one-row chain and of the Q-row launches can part the two paths' arg-max)
+        own_ids = generate(model, x, cfg, speculative=sc, draft_script=wrong)[0].numpy() if script_mode == "perfect" else None
+
+        def script(c):
+            if script_mode is None:
+                return {}
+            n = c.max_new_tokens
+            return dict(draft_script=own_ids[:, :n] if script_mode == "perfect" else wrong[:, :n])
+
+        def best(c, **kw):
+            generate(model, x, c, **kw)            # capture + warm-up
+            t = 1e30
+            for _ in range(REPS):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                generate(model, x, c, **kw)
+                t = min(t, time.perf_counter() - t0)
+            return t
+
+        rec = {"M": M, "new_tokens": N_NEW, "speculative": K, "drafts": script_mode or "lookup", "prompt": "text" if text else "caption"}
+        rec["plain_ms_per_token"] = round((best(cfg) - best(short)) / (N_NEW - 10) * 1e3, 4)
+        rec["speculative_ms_per_token"] = round((best(cfg, speculative=sc, **script(cfg)) - best(short, speculative=sc, **script(short))) / (N_NEW - 10) * 1e3, 4)
+        st = {}
+        ids = generate(model, x, cfg, speculative=sc, stats=st, **script(cfg))[0].numpy()
+        rec.update(accepted=st["accepted"], tokens_per_call=round(st["tokens_per_call"], 3), token_calls=st["token_calls"],
+                   same_tokens_as_plain=bool((ids == plain_ids).all()), tokens_equal_to_plain=int((ids == plain_ids).sum()),
+                   **({"same_tokens_as_script": bool((ids == own_ids).all())} if own_ids is not None else {}), speculative_over_plain=round(rec["speculative_ms_per_token"] / rec["plain_ms_per_token"], 4))
+        print(json.dumps(rec), flush=True)
+        model._generator = model._spec_generator = None
+        torch.cuda.empty_cache()
+
+
+def spec_replay_main(pairs, calls=N_NEW):
+    for B, n in pairs:
+        step = GraphedRingStep(model, batch_size=B, n_new=n)
+        for _ in range(5):
+            step(step.ids)
+        ts = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                step(step.ids)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / calls * 1e3)
+        step.check(synchronize=True)
+        del step
+        torch.cuda.empty_cache()
+        print(json.dumps({"B": B, "n_new": n, "bare_ring_replay_ms": round(float(np.median(ts)), 4), "min": round(min(ts), 4), "max": round(max(ts), 4)}),
+              flush=True)
+
+
+def spec_logits_main(Q=5, n=22):
+    """the same n tokens through the K/V ring cut into calls in three ways -- one token per call (the persistent chain), Q per call, and Q per
+    call behind a first call of 2 (every token at another position of its call) -- and how far the text-window logits of the three lie apart,
+    next to the gap between the two largest logits of a position: what decides whether the arg-max of two paths can differ"""
+    from bdm_db1_amd.decode import RingMemory
+    toks = torch.from_numpy(np.random.default_rng(7).integers(0, 32000, (1, n))).to(dev)
+    V = int(model.text_vocab_size)
+
+    def run(cuts):
+        ring, out, at = RingMemory(model, 1), [], 0
+        with torch.no_grad():
+            for L in cuts:
+                x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=toks[:, at:at + L], text_len=None)
+                logits, _, _ = model([x], compute_loss=False, mems=ring)
+                out.append(logits[0, :, :V].float().cpu().numpy())
+                at += L
+        assert at == n
+        return np.concatenate(out)
+
+    wide = [Q] * (n // Q) + ([n % Q] if n % Q else [])
+    a, b, c = run([1] * n), run(wide), run([2] + [Q] * ((n - 2) // Q) + ([(n - 2) % Q] if (n - 2) % Q else []))
+    # the reference: an fp32 model on the same parameters, the n tokens in ONE list-form call after the zero memory (under same_length the
+    # same function of the tokens, however they are cut into calls)
+    ref_model = TransformerXL(synth.db1_config("1.3B"), device=dev, compute_dtype=torch.float32)
+    ref_model.load_state_dict(model.state_dict(), strict=False)
+    ref_model.eval()
+    with torch.no_grad():
+        x = NLPTaskInput(position_id=None, attention_mask=None, loss_mask=None, label=None, text_seq=toks, text_len=None)
+        ref = ref_model([x], compute_loss=False, mems=ref_model.init_mem(1))[0][0, :, :V].float().cpu().numpy()
+    del ref_model
+    top = np.sort(ref, axis=1)[:, -2:]
+    gap = (top[:, 1] - top[:, 0]) / np.abs(ref).max(axis=1)
+    rel = lambda u, v: float((np.abs(u - v).max(axis=1) / np.abs(u).max(axis=1)).max())
+    rms = lambda u, v: float(np.sqrt(((u - v) ** 2).mean()) / np.abs(u).max())
+    rec = {"Q": Q, "positions": n, "mem_len": int(model.mem_len), "max_abs_logit": round(float(np.abs(ref).max()), 4)}
+    for name, u in (("one", a), ("wide", b), ("shifted", c)):      # every bf16 path against the fp32 reference
+        rec.update({f"{name}_vs_fp32_max_rel": rel(ref, u), f"{name}_vs_fp32_rms_rel": rms(ref, u),
+                    f"argmax_equal_{name}_vs_fp32": int((ref.argmax(1) == u.argmax(1)).sum())})
+    rec.update({"one_vs_wide_max_rel": rel(a, b), "one_vs_wide_rms_rel": rms(a, b), "wide_vs_shifted_max_rel": rel(b, c), "wide_vs_shifted_rms_rel": rms(b, c),
+           "top2_gap_rel_median": float(np.median(gap)), "top2_gap_rel_min": float(gap.min()), "positions_with_tied_top2": int((gap == 0).sum()),
+           "argmax_equal_one_vs_wide": int((a.argmax(1) == b.argmax(1)).sum()), "argmax_equal_wide_vs_shifted": int((b.argmax(1) == c.argmax(1)).sum())})
+    print(json.dumps(rec), flush=True)
+
+
+def spec_kernels_us(rows, rounds=7):
+    V, ld, hi, mx = int(model.total_vocab_size), int(model.vocab_pad), int(model.text_vocab_size), 64
+    Q = 5 if rows <= 5 else 16
+    M = rows // Q
+    i32 = dict(dtype=torch.int32, device=dev)
+    lg = (torch.randn(M * Q, ld, device=dev) * 3).to(torch.bfloat16)
+    t, fin, lens, status, n_acc, hist, ring = (torch.zeros(n, **i32) for n in (1, M, M, M, 1, Q + 1, 1))
+    out, sel, hit = torch.zeros(M, mx, **i32), torch.zeros(M, Q, **i32), torch.zeros(M, Q, **i32)
+    ids = torch.zeros(M, Q, dtype=torch.long, device=dev)
+    ctx, ctx_len = torch.zeros(M, 4096 - mx, **i32), torch.full((M,), 64, **i32)
+    nxt, t1 = torch.zeros(M * Q, dtype=torch.long, device=dev), torch.zeros(1, **i32)
+    f2, l2, s2, o2 = torch.zeros(M * Q, **i32), torch.zeros(M * Q, **i32), torch.zeros(M * Q, **i32), torch.zeros(M * Q, mx, **i32)
+
+    def reset():
+        t.zero_(); fin.zero_(); f2.zero_()
+    fns = dict(spec_pick=lambda: ops.spec_pick(lg, t, fin, ids, sel, hit, q_in=Q, V=V, vocab_hi=hi, max_new=mx),
+               spec_accept=lambda: ops.spec_accept(t, sel, hit, fin, lens, out, status, ids, n_acc, q_in=Q, V=V, ctx=ctx, ctx_len=ctx_len),
+               spec_commit=lambda: ops.spec_commit(t, n_acc, q_in=Q, Q=Q, hist=hist, ring_state=ring, cap=1088),
+               select_tokens=lambda: ops.select_tokens(lg, t1, f2, l2, o2, nxt, s2, V=V, vocab_hi=hi))
+    rec = {"rows": rows, "M": M, "Q": Q, "V": V}
+    for name, fn in fns.items():
+        us = []
+        for _ in range(rounds):
+            reset()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            fn()
+            reset()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3)
+        rec[f"{name}_us"] = round(float(np.median(us)), 2)
+        rec[f"{name}_min_max_us"] = [round(min(us), 2), round(max(us), 2)]
+    return rec
 
 
 KV_CACHE = "bf16"      # --kv-cache
@@ -986,6 +1153,27 @@ if "--share-prompt" in args:   # beam search and best-of-n read one copy of a gr
     args = [a for a in args if a != "--share-prompt"]
     _dumps_sp = json.dumps
     json.dumps = lambda rec, **kw: _dumps_sp(dict(rec, share_prompt=True) if isinstance(rec, dict) else rec, **kw)   # every line of this run says so
+if "--speculative" in args:
+    i = args.index("--speculative")
+    K_, rest = int(args[i + 1]), args[:i] + args[i + 2:]
+    mode_ = None
+    if "--draft-script" in rest:
+        j = rest.index("--draft-script")
+        mode_, rest = rest[j + 1], rest[:j] + rest[j + 2:]
+        if mode_ not in ("perfect", "wrong"):
+            sys.exit("--draft-script perfect|wrong")
+    spec_main(K_, mode_, [int(a) for a in rest if a != "--text-prompt"] or [1, 4], "--text-prompt" in rest)
+    sys.exit(0)
+if "--spec-replay" in args:
+    spec_replay_main([tuple(int(v) for v in a.split(":")) for a in args if a != "--spec-replay"] or [(1, 1), (1, 2), (1, 5), (1, 8), (4, 5)])
+    sys.exit(0)
+if "--spec-logits" in args:
+    spec_logits_main()
+    sys.exit(0)
+if "--spec-kernels" in args:
+    for rows_ in [int(a) for a in args if a != "--spec-kernels"] or [5, 64]:
+        print(json.dumps(spec_kernels_us(rows_)), flush=True)
+    sys.exit(0)
 if "--group-kernels" in args:
     rest = [int(a) for a in args if a != "--group-kernels"]
     G_, W_ = (rest + [16, 4])[:2] if len(rest) >= 2 else (16, 4)
