@@ -255,11 +255,17 @@ def relattn_dqr_supported(B, L, H, D, dtype) -> bool:
     return bool(lib.load().db1_relattn_dqr_supported(B, L, H, D, dt_code(dtype)))
 
 
+def _dqr_bf16_only(who, *tensors):
+    if any(t.dtype != torch.bfloat16 for t in tensors):
+        raise lib.Db1Error(f"{who}: bf16 operands only")     # (the entry point takes no dtype: refused here, nothing launched)
+
+
 def relattn_dqr(dT, R, dqv):
     """dqv[b, i, h, :] = sum_dist dT[h, b, i, dist] R[dist, h, :]  (dT [H,B,L,L] bf16 zero above the causal diagonal, R [L, H*D], dqv [B,L,H,D])"""
     H, B, L, _ = dT.shape
     D = dqv.shape[-1]
     assert dT.is_contiguous() and R.stride(1) == 1 and dqv.stride(3) == 1 and dqv.stride(2) == D
+    _dqr_bf16_only("relattn_dqr", dT, R, dqv)
     ws, wsn = _ws("db1_relattn_dqr_workspace_bytes", (L, H), dT.device)
     # algorithmic bytes: the causal half of dT read once + the output written
     _timed("relattn_dqr", 2.0 * (H * B * L * (L + 1) / 2 + dqv.numel()),
@@ -295,6 +301,7 @@ def relattn_dqr_fused(dT, R, dq, du_acc, dv_acc):
     D = dq.shape[-1]
     assert dT.is_contiguous() and R.stride(1) == 1 and dq.stride(3) == 1 and dq.stride(2) == D and dq.shape == (B, L, H, D)
     assert du_acc.dtype == torch.float32 and dv_acc.dtype == torch.float32 and du_acc.numel() == H * D == dv_acc.numel()
+    _dqr_bf16_only("relattn_dqr_fused", dT, R, dq)
     ws, wsn = _ws("db1_relattn_dqr_workspace_bytes", (L, H), dT.device)
     # algorithmic bytes: the causal half of dT read once, dq read and written
     _timed("relattn_dqr", 2.0 * (H * B * L * (L + 1) / 2 + 2 * dq.numel()),
@@ -314,6 +321,7 @@ def relattn_dqr_fused_groups(dT, Rg, dq, du_acc, dv_acc):
     ng = Rg.shape[0]
     assert dT.is_contiguous() and Rg.dim() == 3 and Rg.stride(2) == 1 and dq.stride(3) == 1 and dq.stride(2) == D and dq.shape == (B, L, H, D)
     assert du_acc.dtype == torch.float32 and dv_acc.dtype == torch.float32 and du_acc.numel() == H * D == dv_acc.numel()
+    _dqr_bf16_only("relattn_dqr_fused_groups", dT, Rg, dq)
     ws, wsn = _ws("db1_relattn_dqr_groups_workspace_bytes", (L, H, ng), dT.device)
     _timed("relattn_dqr", 2.0 * (H * B * L * (L + 1) / 2 + 2 * dq.numel()),
            lambda: lib.call("db1_relattn_dqr_fused_groups", P(dT), P(Rg), Rg.stride(1), Rg.stride(0), ng, P(dq), dq.stride(1), dq.stride(0), P(du_acc), P(dv_acc),
@@ -329,6 +337,7 @@ def relattn_dqr_fused_parts(dT, R, dq, parts):
     H, B, L, _ = dT.shape
     D = dq.shape[-1]
     assert dT.is_contiguous() and R.stride(1) == 1 and dq.stride(3) == 1 and dq.stride(2) == D and dq.shape == (B, L, H, D)
+    _dqr_bf16_only("relattn_dqr_fused_parts", dT, R, dq)
     assert parts.dtype == torch.float32 and parts.is_contiguous() and parts.shape == (2, relattn_dqr_parts_rows(H), H * D)
     ws, wsn = _ws("db1_relattn_dqr_workspace_bytes", (L, H), dT.device)
     _timed("relattn_dqr", 2.0 * (H * B * L * (L + 1) / 2 + 2 * dq.numel()),

@@ -170,9 +170,11 @@ def _to_dist(dS, vis, dist, mlen, nd):
     return dT
 
 
-def backward(p, dout, fwd, cache, rounded=False):
+def backward(p, dout, fwd, cache, rounded=False, round_dq=False):
     """dq, dk, dv, dR, du, dv_bias, delta (and dT) of the closed form.  rounded: P and dS (= dT) rounded to bf16 before their products, delta
-    from the bf16 output, dq_k / dk / dv stored as bf16, and dq, dR, du, dv_bias assembled from those stores as the GPU test assembles them."""
+    from the bf16 output, dq_k / dk / dv stored as bf16, and dq, dR, du, dv_bias assembled from those stores as the GPU test assembles them.
+    round_dq (with rounded): one more rounding point, dq = bf16(dq_k + dq_r), which is what the kernels that finish the query gradient store
+    (relattn_dqr_fused, add2d_colsums); off by default, so every tolerance derived without it is unchanged."""
     r = bf16 if rounded else (lambda x: x)
     P, vis, dist, qu, qv = cache
     k, v, R = p["k"], p["v"], p["R"]
@@ -187,14 +189,51 @@ def backward(p, dout, fwd, cache, rounded=False):
     dT = _to_dist(dSr, vis, dist, p["mlen"], R.shape[0])
     dqr = _T(dT @ R.transpose(1, 0, 2)[None])
     dR = (dT.transpose(0, 1, 3, 2) @ qv).sum(0).transpose(1, 0, 2)                # [nd,H,D]
-    return dict(dq=dqk + dqr, dk=dk, dv=dv, dR=dR, du=dqk.sum((0, 1)), dv_bias=dqr.sum((0, 1)), delta=delta, dT=dT)
+    return dict(dq=r(dqk + dqr) if round_dq else dqk + dqr, dk=dk, dv=dv, dR=dR, du=dqk.sum((0, 1)), dv_bias=dqr.sum((0, 1)), delta=delta, dT=dT)
 
 
-def reference(p, dout=None, geo=None, rounded=False):
+def reference(p, dout=None, geo=None, rounded=False, round_dq=False):
     fwd, cache = forward(p, geo, rounded)
     if dout is not None:
-        fwd.update(backward(p, dout, fwd, cache, rounded))
+        fwd.update(backward(p, dout, fwd, cache, rounded, round_dq))
     return fwd
+
+
+def materialised(AC, T, dP, mlen, shift, scale, rounded=False):
+    """relattn_softmax_fwd + relattn_softmax_bwd (relattn_mat.hip, the fp32 parity path) in closed form: AC [H,B,Lq,Lk], T [H,B,Lq,nd], dP like AC.
+    Returns P, lse [H,B,Lq], dS and dT [H,B,Lq,nd] with dT[.., mlen + i - j] = dS[.., j] on the visible pairs and 0 elsewhere; `written` is that
+    set.  A row without a visible key is uniform, P = 1 / Lk and lse = -1e30 + log Lk, and passes no gradient.
+    rounded: float32 at every value the kernels hold or store -- the scaled score, the difference to the row maximum, exp evaluated as the
+    kernel's __expf evaluates it (exp2 of the float32 product with log2 e), the row sum, its reciprocal, P, lse, the row dot and dS."""
+    f = (lambda x: np.asarray(x, np.float32)) if rounded else (lambda x: np.asarray(x, np.float64))
+    Lq, Lk, nd = AC.shape[2], AC.shape[3], T.shape[3]
+    i, j = np.arange(Lq)[:, None], np.arange(Lk)[None, :]
+    vis = (j > i - shift) & (j <= i + mlen)
+    ridx = np.clip(mlen + i - j, 0, nd - 1)
+    assert ((mlen + i - j)[vis] >= 0).all() and ((mlen + i - j)[vis] < nd).all()
+    BD = np.take_along_axis(f(T), np.broadcast_to(ridx[None, None], AC.shape), axis=3)
+    s = f(f(f(AC) + BD) * f(scale))
+    s = np.where(vis, s, -np.inf)
+    empty = ~vis.any(1)
+    m = np.where(empty[None, None, :, None], 0.0, s.max(-1, keepdims=True)).astype(s.dtype)
+    x = f(s - m)
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        e = np.exp2(f(x * np.float32(1.4426950408889634))) if rounded else np.exp(x)
+    e = np.where(vis, e, 0.0).astype(s.dtype)
+    tot = e.sum(-1, keepdims=True, dtype=s.dtype)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        P = f(e * f(1.0 / tot))
+        lse = f(m[..., 0] + f(np.log(tot[..., 0])))
+    P = np.where(empty[None, None, :, None], f(1.0 / Lk), P).astype(s.dtype)
+    lse = np.where(empty[None, None, :], f(-1e30) + f(np.log(f(Lk))), lse).astype(s.dtype)
+    dot = np.where(vis, f(P * f(dP)), 0.0).sum(-1, keepdims=True, dtype=s.dtype)
+    dS = np.where(vis, f(f(P * f(f(dP) - dot)) * f(scale)), 0.0).astype(s.dtype)
+    dT = np.zeros(T.shape, s.dtype)
+    written = np.zeros((Lq, nd), bool)
+    ii, jj = np.nonzero(vis)
+    dT[:, :, ii, mlen + ii - jj] = dS[:, :, ii, jj]
+    written[ii, mlen + ii - jj] = True
+    return dict(P=P.astype(np.float64), lse=lse.astype(np.float64), dS=dS.astype(np.float64), dT=dT.astype(np.float64)), written
 
 
 def mutants(p, dout=None, names=MASK_MUTANTS):

@@ -137,6 +137,9 @@ def test_flash_backward_probe(L, shift, mode):
         check("du", g[:, :, 0].sum((0, 1)), ref["du"], tol["du"], case)
         check("dv_bias", dqr.sum((0, 1)), ref["dv_bias"], tol["dv_bias"], case)
         check("delta", delta, ref["delta"], tol["delta"], case)
+        ii, dd = np.arange(L)[:, None], np.arange(L)[None, :]
+        seen = (dd <= ii) & (dd < shift)                                       # the visible keys j = i - dist: the producer judged directly
+        check("dT", dTn[:, :, seen], ref["dT"].transpose(1, 0, 2, 3)[:, :, seen], tol["dT"], case)
 
 
 @pytest.mark.parametrize("q,mlen,shift,nd", A.DECODE_CASES)
