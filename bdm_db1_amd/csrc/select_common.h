@@ -1,4 +1,5 @@
-// Order-preserving logit keys and fixed-order block reductions shared by next-token selection (select.hip) and beam search (beam.hip).
+// Order-preserving logit keys and fixed-order block reductions shared by next-token selection (select.hip), beam search (beam.hip), scoring
+// (score.hip) and action decoding (action.hip).
 //
 // sel_key maps a float to a uint32 whose unsigned order is the float order (0 = not a candidate: NaN, +-inf), so max / arg-max are integer
 // reductions; packing (key << 32) | ~column into a uint64 makes the arg-max pick the lowest column on ties.  Block reductions: every wave
@@ -84,6 +85,17 @@ __device__ __forceinline__ float block_sum_f(float x, SelSharedT<NW>& sh, int& p
     for (int w = 1; w < NW; w++) r += sh.f[ph][w];
     ph ^= 1;
     return r;
+}
+
+// The threshold search of top-k / top-p: the largest x in [l, h] with ok(x), for a block-uniform, monotone ok (true up to some x, false above)
+// that holds at l.  ok may reduce over the block: every thread walks the same midpoints.
+template <typename Ok>
+__device__ __forceinline__ unsigned sel_bisect_max(unsigned l, unsigned h, Ok ok) {
+    while (l < h) {
+        const unsigned mid = l + ((h - l) >> 1) + ((h - l) & 1);
+        if (ok(mid)) l = mid; else h = mid - 1;
+    }
+    return l;
 }
 
 // the packed pair of a candidate (0: not a candidate)

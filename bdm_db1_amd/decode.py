@@ -186,6 +186,40 @@ class RingMemory:
                 src = slots
             ops.ring_load_rows(self.kv, self._ptrs, src, self.state, mlen, rows, self.load_status)
 
+    def reset_rows(self, rows):
+        """new episodes in rows ``rows`` (distinct ints in [0, B), or an int32 vector of them on the device) while the others go on: those
+        rows go back to the zero memory (``reset``'s keys / values) relative to the CURRENT origin through db1_ring_load_rows; no bit of
+        another row changes.  The zero memory of one row is projected (and, on an fp8 ring, quantised) once per weight version and kept
+        as many times as the largest reset so far had rows: a later reset of no more rows is the one launch, with no projection and no copy."""
+        from . import ops
+        model, mlen = self.model, int(self.model.mem_len)
+        if not torch.is_tensor(rows):
+            rows = [int(r) for r in rows]
+            if len(set(rows)) != len(rows) or any(not 0 <= r < self.B for r in rows):
+                raise ValueError(f"RingMemory.reset_rows: rows {rows} must be distinct and lie in [0, {self.B})")
+            rows = torch.tensor(rows, dtype=torch.int32).to(model.dev)
+        n = int(rows.numel())
+        if n > self.B:
+            raise ValueError(f"RingMemory.reset_rows: {n} rows for a ring of {self.B}")
+        if n == 0:
+            return
+        z = getattr(self, "_zero_rows", None)
+        if z is None or z[0] != model._wversion:
+            with torch.no_grad():
+                src = [kv.contiguous() for kv in self._project(model.init_mem(1), 1)]
+                if self.kv_dtype == "fp8":
+                    slots = [torch.empty(1, mlen, self.kv[0].shape[2], device=model.dev, dtype=torch.uint8) for _ in src]
+                    for kv, sl in zip(src, slots):
+                        ops.kv8_quantize(kv, sl)
+                    src = slots
+            z = self._zero_rows = [model._wversion, src]
+        with torch.no_grad():
+            # db1_ring_load_rows reads one source row per target row: the cached source holds the zero memory as many times as the largest
+            # reset so far asked for (it grows, and is copied, only then); a smaller reset reads its first n rows
+            if z[1][0].shape[0] < n:
+                z[1] = [s[:1].expand(n, *s.shape[1:]).contiguous() for s in z[1]]
+            ops.ring_load_rows(self.kv, self._ptrs, [s[:n] for s in z[1]], self.state, mlen, rows, self.load_status)
+
     def reorder(self, parent: torch.Tensor, t: torch.Tensor, max_t: int = None, group: int = 1, done: torch.Tensor = None):
         """beam search: after the call that appended token t - 1, give row b the keys / values of the last ``t`` tokens of row
         ``parent[b]`` in every layer (db1_ring_reorder; ``t`` a device int32 [1], read by the launch, so this can be captured).  The older

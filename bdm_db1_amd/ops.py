@@ -2228,6 +2228,68 @@ def mulaw_decode(ids, out, is_action, num_bins=1024, mu=100.0, M=256.0, oob_flag
              float(M), P(oob_flag), stream())
 
 
+ACT_MAX_WINDOW, ACT_MAX_LEN = 4096, 64     # db1_select_actions: the widest action window, the longest action
+
+
+def select_actions_supported(V: int, ld: int, dtype, act_lo: int, act_hi: int) -> bool:
+    return bool(lib.load().db1_select_actions_supported(int(V), int(ld), dt_code(dtype), int(act_lo), int(act_hi)))
+
+
+def select_actions(logits2d, ctr, bins, next_ids, status, *, act_lo, act_hi, V=None, mask=None, values=None, num_bins=1024, greedy=True,
+                   temperature=1.0, top_k=0, top_p=1.0, seed=0, step_base=0, stream_id=None):
+    """one action token per row of ``logits2d`` [M, ld] (fp32 / bf16, the first V columns valid) on the device (db1_select_actions, rule in
+    include/db1_hip.h): ``select_tokens``' choice over the columns [act_lo, act_hi) (at most 4096) that ``mask`` (uint8 [M, n_mask], 1 =
+    allowed, the columns from act_lo on; None: all) leaves.  ``ctr`` (int32 [2], device) = {env_step, i}, READ only; for i < act_len =
+    ``bins.shape[1]``: the bin token - act_lo goes to ``bins`` [M, act_len] (int32) at column i, its decoded action value to ``values``
+    (float32 [M, act_len] or None) and the token to ``next_ids`` (int64, [M] or a column of [M, q]); i == act_len writes nothing; ``status``
+    (int32 [M]) |= 1 for a row without a candidate, |= 2 for i out of range.  Capturable; raises ValueError on bad arguments before anything
+    is launched."""
+    who, dev = "select_actions", logits2d.device
+    M, ld, V, act_lo, act_hi = _check_logits(who, logits2d, V, act_lo, act_hi, lambda V, ld: True)
+    if act_hi - act_lo > ACT_MAX_WINDOW:
+        raise ValueError(f"{who}: the window [{act_lo}, {act_hi}) is wider than {ACT_MAX_WINDOW} columns")
+    _check_sampling(who, greedy, temperature, top_k, top_p)
+    if not torch.is_tensor(bins) or bins.dim() != 2 or not 1 <= bins.shape[1] <= ACT_MAX_LEN:
+        raise ValueError(f"{who}: bins must be a contiguous {torch.int32} tensor of shape ({M}, act_len) with act_len in [1, {ACT_MAX_LEN}] on {dev}")
+    act_len = bins.shape[1]
+    _check_tensor(who, "bins", bins, torch.int32, (M, act_len), dev)
+    if values is not None:
+        _check_tensor(who, "values", values, torch.float32, (M, act_len), dev)
+    _check_vectors(who, dev, 2, ctr=ctr)
+    _check_vectors(who, dev, M, status=status)
+    _check_vectors(who, dev, M, optional=("stream_id",), stream_id=stream_id)
+    _check_next_ids(who, next_ids, M, dev)
+    n_mask = 0
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dim() != 2 or not 1 <= mask.shape[1] <= act_hi - act_lo:
+            raise ValueError(f"{who}: mask must be a contiguous {torch.uint8} tensor of shape ({M}, n) with 1 <= n <= {act_hi - act_lo} on {dev}")
+        n_mask = mask.shape[1]
+        _check_tensor(who, "mask", mask, torch.uint8, (M, n_mask), dev)
+    if int(num_bins) < 1:
+        raise ValueError(f"{who}: num_bins {num_bins} must be >= 1")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lib.call("db1_select_actions", P(logits2d), M, V, max(ld, V), dt_code(logits2d), act_lo, act_hi, P(mask), n_mask, float(temperature), int(top_k),
+             float(top_p), int(bool(greedy)), seed & 0xFFFFFFFF, seed >> 32, int(step_base), P(ctr), P(stream_id), act_len, int(num_bins), P(bins),
+             P(values), P(next_ids), next_ids.stride(0), P(status), stream())
+
+
+def obs_tokens(x, ids, *, bin_base, sep_id, num_bins=1024, mu=100.0, M=256.0):
+    """float observations ``x`` [rows, obs_dim] (float32, contiguous) -> ``ids`` [rows, >= obs_dim + 1] (int64, unit column stride; a view of
+    the observation call's static input ids): column j < obs_dim = ``bin_base`` + the tokenizer's observation bin of x[:, j]
+    (``mulaw_discretize(is_action=False)``, the same ids), column obs_dim = ``sep_id`` (db1_obs_tokens).  Capturable; raises ValueError on bad
+    arguments before anything is launched."""
+    who = "obs_tokens"
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{who}: x must be a contiguous {torch.float32} tensor of shape (rows, obs_dim)")
+    rows, obs_dim = x.shape
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.dtype != torch.int64 or ids.shape[0] != rows or ids.shape[1] < obs_dim + 1 or \
+            ids.stride(1) != 1 or ids.stride(0) < obs_dim + 1 or ids.device != x.device:
+        raise ValueError(f"{who}: ids must be an {torch.int64} tensor of shape ({rows}, >= {obs_dim + 1}) with unit column stride on {x.device}")
+    if int(num_bins) < 1 or int(bin_base) < 0 or int(sep_id) < 0:
+        raise ValueError(f"{who}: num_bins {num_bins} must be >= 1, bin_base {bin_base} and sep_id {sep_id} >= 0")
+    lib.call("db1_obs_tokens", P(x), rows, obs_dim, P(ids), ids.stride(0), int(bin_base), int(sep_id), int(num_bins), float(mu), float(M), stream())
+
+
 GEMM_KERNELS = {0: "strided-fp32", 1: "tile128", 2: "tile256", 3: "pp-k64", 4: "pp-k32", 5: "w4", 6: "skinny", 7: "w4n"}
 
 

@@ -1143,6 +1143,41 @@ int db1_lmhead_score_top(const void* h, const void* W, const int64_t* labels, fl
 int db1_score_segments(const float* logprob, const int32_t* rank, const int64_t* labels, const float* mask, float* out, int64_t n_seg,
                        int64_t seg_len, int V, void* stream);
 
+/* ------------------------------------------------------------------ action decoding for RL rollouts (tests/action_rule.py restates the rule
+ * in NumPy).  The reference restricts the logits to the action vocabulary, subtracts the environment's action mask, takes the argmax, maps the
+ * id back to a tokenizer bin and copies it to the host once per action token (evaluate_rl.py:96-138,157-266).  db1_select_actions: ONE launch
+ * picks one action token for each of the M environments from logits [M, ld] (fp32 / bf16; columns >= V are padding):
+ *   - candidates: the FINITE logits of the columns [act_lo, act_hi), 0 <= act_lo < act_hi <= V, at most 4096 columns; mask (uint8 [M, n_mask],
+ *     1 = allowed; NULL with n_mask 0: none) covers the columns act_lo .. act_lo + n_mask, n_mask <= act_hi - act_lo: a column whose mask
+ *     byte is 0 is not a candidate; NaN and +-inf are never chosen;
+ *   - the choice is exactly db1_select_tokens' over the window [act_lo, act_hi) of a row in which every masked column holds -inf: greedy (or
+ *     top_k == 1) the largest logit, lowest column on ties; else top-k, top-p and the Gumbel-max draw of that rule with its Philox layout
+ *     (counter (col / 4, stream_id[row] (NULL: row), step, 0xE0000100), word col % 4, key (seed_lo, seed_hi)) and the fp32 sums of top-p added
+ *     in that kernel's order: the same token, bit for bit.  step = step_base + ctr[0] * act_len + ctr[1];
+ *   - ctr (device int32 [2]) = {env_step, i}, only READ (the caller advances it, e.g. with a captured ctr[1] += 1): capturable.
+ *     i == act_len is the memorising call of the reference's protocol (the last action token enters the memory, nothing is chosen): NOTHING
+ *     is written, no status bit.  i outside [0, act_len]: status[row] |= 2 and nothing else is written;
+ *   - for 0 <= i < act_len: bins[row, i] = token - act_lo (int32 [M, act_len]); values[row, i] (float [M, act_len], nullable) = the action
+ *     branch of db1_mulaw_decode on that bin with num_bins (bin / num_bins * 2 - 1, the same instructions); next_ids[row * ids_stride] =
+ *     token (int64: the next call's input ids);
+ *   - a row with no candidate writes token act_lo, bin 0 and status[row] |= 1.
+ * One workgroup of 256 threads per row, which reads the window only; no atomics, no workspace (the query returns 0), no communication
+ * between workgroups, fixed-order reductions: two launches give the same bits.  DB1_ERR_BAD_SHAPE before any launch: a NULL logits, ctr,
+ * bins, next_ids or status, an empty window or one outside [0, V), n_mask outside [0, act_hi - act_lo] or not matching mask, act_len
+ * outside 1 .. 64, num_bins < 1, M outside 1 .. 65535, and, when not greedy, a temperature that is not finite and positive, top_k < 0 or
+ * top_p outside (0, 1]; DB1_ERR_UNSUPPORTED: a window wider than 4096 columns (_supported); DB1_ERR_UNSUPPORTED_DTYPE.
+ * db1_obs_tokens: float observations x [M, obs_dim] -> ids[row * ids_stride + j] = bin_base + the observation branch of db1_mulaw_discretize
+ * on x[row, j] (the same device function: the same ids) for j < obs_dim, and ids[row * ids_stride + obs_dim] = sep_id (int64; ids_stride >=
+ * obs_dim + 1): the observation call's input ids of every environment in one launch.  Nothing else is written. */
+int db1_select_actions_supported(int V, int64_t ld, int dt, int act_lo, int act_hi);
+int64_t db1_select_actions_workspace_bytes(int M, int V, int dt);
+int db1_select_actions(const void* logits, int M, int V, int64_t ld, int dt, int act_lo, int act_hi, const uint8_t* mask, int n_mask,
+                       float temperature, int top_k, float top_p, int greedy, uint32_t seed_lo, uint32_t seed_hi, int step_base,
+                       const int32_t* ctr, const int32_t* stream_id, int act_len, int num_bins, int32_t* bins, float* values,
+                       int64_t* next_ids, int64_t ids_stride, int32_t* status, void* stream);
+int db1_obs_tokens(const float* x, int M, int obs_dim, int64_t* ids, int64_t ids_stride, int bin_base, int sep_id, int num_bins, float mu,
+                   float M_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
